@@ -245,6 +245,70 @@ def multi_gpu_probe(args):
             "kernel_ms_per_rank": line["roofline"]["kernel_ms_per_rank"]}
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6    # --dump-outputs: all files together, headers included
+DUMP_SEED = 20240601                # the fixed particle sample of a run too large to dump whole
+
+
+def npy_bytes(n):
+    """Size of the .npy file np.save writes for n float64 values: its header and the data."""
+    import io
+    head = io.BytesIO()
+    np.lib.format.write_array_header_1_0(head, {"descr": np.lib.format.dtype_to_descr(np.dtype(np.float64)),
+                                               "fortran_order": False, "shape": (int(n),)})
+    return len(head.getvalue()) + 8 * int(n)
+
+
+def dump_outputs(out_dir, workload, atm, grid):
+    """--dump-outputs: what the timed path handed back in its last step -- the particle arrays (time, lon, lat, p and
+    every quantity, in the caller's order) and the gridded output of that step as mphip_grid_sums returns it (per
+    cell: the count, the sum of each quantity and the sum of its square) -- as <out_dir>/<name>.npy, float64.
+    Should the particle arrays not fit in DUMP_LIMIT_BYTES next to the grid, a fixed seeded sample of particle
+    indices is written (`particle_index`, ascending; the same for every run with the same particle count).  The
+    size of the whole set is settled before the first file is written."""
+    quantities = WORKLOADS[workload][3]
+    cnt, sums, sumsq = grid
+    arrays = {"grid_count": cnt}
+    for iq, name in enumerate(quantities):
+        arrays[f"grid_sum_{name}"] = sums[iq]
+        arrays[f"grid_sumsq_{name}"] = sumsq[iq]
+    particle_names = ["particle_index", "time", "lon", "lat", "p"] + [f"q_{name}" for name in quantities]
+    n = len(atm["time"])
+    grid_bytes = sum(npy_bytes(a.size) for a in arrays.values())
+    # the most particles whose files fit beside the grid (a header never shrinks as the count grows)
+    fit = n
+    if grid_bytes + len(particle_names) * npy_bytes(n) > DUMP_LIMIT_BYTES:
+        lo, hi = 0, n
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            if grid_bytes + len(particle_names) * npy_bytes(mid) <= DUMP_LIMIT_BYTES:
+                lo = mid
+            else:
+                hi = mid - 1
+        fit = lo
+    if fit >= n:
+        idx = np.arange(n)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=fit, replace=False))
+    arrays["particle_index"] = idx
+    for k in ("time", "lon", "lat", "p"):
+        arrays[k] = atm[k][idx]
+    for iq, name in enumerate(quantities):
+        arrays[f"q_{name}"] = atm["q"][iq][idx]
+    total = sum(npy_bytes(a.size) for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: the gridded output alone takes {grid_bytes} bytes, over the "
+                         f"{DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    written = 0
+    for name, a in arrays.items():
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, np.ascontiguousarray(a, dtype=np.float64))
+        written += os.path.getsize(path)
+    assert written == total, (written, total)
+    return {"dir": out_dir, "files": len(arrays), "bytes": written, "particles": int(len(idx)),
+            "particles_sampled": bool(len(idx) < n)}
+
+
 def build_id():
     """Hash of the kernel sources: ties the committed PMC profile (profiles/pmc_traffic.json) to the build it
     was taken from."""
@@ -298,6 +362,11 @@ def main():
     ap.add_argument("--no-multi-gpu-probe", action="store_true",
                     help="N = 1 on a box with several GPUs: do not append the short run over min(8, visible GPUs) RCCL "
                          "ranks (`multi_gpu_probe` in the line; outside the timed region, a separate launch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what their last step computed (particle arrays; the gridded "
+                         "output's counts, sums and sums of squares per cell) to DIR/<name>.npy, float64, at most "
+                         "64 MB (a fixed seeded sample of the particles beyond that); rank 0's particles on N > 1.  "
+                         "The one-launch-per-step kernel time is then not measured (the download idles the device)")
     ap.add_argument("--no-kernel-events", action="store_true",
                     help="(diagnostic) do not bracket the step kernel with HIP events; roofline is then not reported")
     args = ap.parse_args()
@@ -448,9 +517,15 @@ def main():
         per_rank_kernel_ms = [float(x) for x in km.tolist()]
         kernel_ms_per_step = max(per_rank_kernel_ms)
 
-    # outside the timed region: the step kernel with one launch per time step (what --multi-step off times)
+    # what the last timed step handed back, downloaded before the steps below move the particles on
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, args.workload, sim.get_atm(), (cnt, mean, _sig))
+
+    # outside the timed region: the step kernel with one launch per time step (what --multi-step off times); not
+    # after a dump, which leaves the device idle long enough for its clocks to drop (profiles/r03_clock_ramp.txt)
     single_ms = None
-    if not args.no_kernel_events:
+    if not args.no_kernel_events and not args.dump_outputs:
         sim.set_option("multi_step", 0)
         sim.profile_begin()
         for _ in range(min(10, args.steps)):
@@ -556,6 +631,8 @@ def main():
                          "alu": alu_roof(args.workload, n_local, kernel_ms_per_step) if not args.particles else None},
             "parity": PARITY_PINS,
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         dropin = os.path.join(ROOT, "profiles", "trac_dropin.json")
         if world == 1 and args.workload == "C3" and not args.particles and os.path.exists(dropin):
             out["dropin_trac"] = json.load(open(dropin))      # (a recorded measurement of the C driver at this size, labelled as such)

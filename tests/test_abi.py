@@ -10,6 +10,8 @@ import pytest
 from mptrac_amd import hip
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# a checkout of the reference MPTRAC sources (its src/mptrac.h), for the two checks of the integration glue
+REFERENCE = os.environ.get("MPTRAC_REFERENCE", "")
 
 
 def declared_symbols():
@@ -93,13 +95,13 @@ def test_product_never_imports_the_oracle():
 def test_integration_glue_names_only_members_the_reference_has():
     """integration/mptrac_hip_glue.c (route A of INTEGRATION.md) is written against the reference's own
     structs; every ctl_t / met_t / clim_t / cache_t / atm_t member it names must exist in the reference's
-    src/mptrac.h and every member of mphip_ctl_t must be filled.  Runs where the reference tree is present."""
+    src/mptrac.h and every member of mphip_ctl_t must be filled.  Runs where MPTRAC_REFERENCE names the reference tree."""
     import subprocess
     import sys
-    if not os.path.exists("/root/reference/src/mptrac.h"):
-        pytest.skip("reference tree not present on this machine")
+    if not os.path.exists(os.path.join(REFERENCE, "src", "mptrac.h")):
+        pytest.skip("no reference tree: set MPTRAC_REFERENCE to a checkout of the reference sources")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "integration", "check_glue_fields.py")],
+    r = subprocess.run([sys.executable, os.path.join(root, "integration", "check_glue_fields.py"), REFERENCE],
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
     assert r.returncode == 0, r.stdout.decode()
 
@@ -108,12 +110,12 @@ def test_integration_glue_type_checks_against_the_reference_header():
     """Route A is more than a claim: integration/mptrac_hip_glue.c compiles (gcc -fsyntax-only) in one unit with
     the reference's own src/mptrac.h -- every member access, argument and pointer type is checked by the
     compiler.  integration/typecheck_glue.py explains the empty stand-ins for the absent GSL / netCDF headers
-    (nothing is built).  Runs where the reference tree is present."""
+    (nothing is built).  Runs where MPTRAC_REFERENCE names the reference tree."""
     import subprocess
     import sys
-    if not os.path.exists("/root/reference/src/mptrac.h"):
-        pytest.skip("reference tree not present on this machine")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "integration", "typecheck_glue.py")],
+    if not os.path.exists(os.path.join(REFERENCE, "src", "mptrac.h")):
+        pytest.skip("no reference tree: set MPTRAC_REFERENCE to a checkout of the reference sources")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "integration", "typecheck_glue.py"), REFERENCE],
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
     assert r.returncode == 0, r.stdout.decode()
 
