@@ -95,7 +95,8 @@ enum {
   MPHIP_MOD_MIXING     = 1 << 17,  /* module_mixing      mptrac.c:5169 (own kernels) */
   MPHIP_MOD_BOUND_COND = 1 << 18,  /* module_bound_cond  mptrac.c:3789, first call (mptrac.c:7929) */
   MPHIP_MOD_BOUND_COND2 = 1 << 19, /* module_bound_cond, second call (mptrac.c:8000) */
-  MPHIP_MOD_ISOSURF_INIT = 1 << 20 /* module_isosurf_init mptrac.c:4886, modes 1-3 (not guarded by dt) */
+  MPHIP_MOD_ISOSURF_INIT = 1 << 20, /* module_isosurf_init mptrac.c:4886, modes 1-3 (not guarded by dt) */
+  MPHIP_MOD_OH_CHEM    = 1 << 21   /* module_oh_chem     mptrac.c:5351-5434 (between module_mixing and module_wet_depo) */
 };
 
 /* Hot-path subset of ctl_t (mptrac.h:2494-3553); same field names, meaning
@@ -155,6 +156,12 @@ typedef struct {
    * (mphip_update_clim_ts; mptrac.c:3857-3875) */
   int qnt_tracer[MPHIP_NTR];
   int pad4;
+  /* module_oh_chem (OH_CHEM_REACTION, OH_CHEM[0..3] of mptrac_read_ctl; SPECIES presets, mptrac.c:7291-7383):
+   * reaction type 0 (off) ... 3, its rate constants, and ctl->qnt_mloss_oh (-1 = not present).  Appended: every
+   * earlier member keeps its offset. */
+  int oh_chem_reaction;
+  int qnt_mloss_oh;
+  double oh_chem[4];
 } mphip_ctl_t;
 
 /* View of one met_t snapshot (mptrac.h:3844-4014).  The arrays stay where the
@@ -204,6 +211,7 @@ int mphip_update_clim(mphip_ctx *ctx, int ntime, int nlat, const double *tropo_t
  * times [s since the start of the year], descending pressures [hPa], ascending latitudes [deg] and the volume
  * mixing ratios vmr[ntime][np][nlat] (the reference's index order, compact).  module_meteo needs the table of
  * every climatology quantity that is requested (hno3: also for tnat); ntime = 0 removes a table. */
+/* module_oh_chem needs the OH table as well. */
 int mphip_update_clim_zm(mphip_ctx *ctx, int which, int ntime, int np, int nlat, const double *time,
                          const double *p, const double *lat, const double *vmr);
 /* ... and one of its trace-gas time series (clim_ts_t, mptrac.h:3729-3743; `which` = MPHIP_TR_*): ascending times
@@ -280,7 +288,8 @@ int mphip_run_timestep(mphip_ctx *ctx, double t);
  * and a batch ends before it; module_meteo is deferred as in mphip_run_timestep, so a batch ends only behind a step that
  * schedules it when the next one does not.  module_isosurf and the boundary-layer closure (TURB_PBL_SCHEME 1) share
  * launches on pressure-level winds.  Single steps throughout: the first step (t == T_START), ADVECT 0, ISOSURF or
- * TURB_PBL_SCHEME 1 with winds from the model levels, the option "generic_kernel". */
+ * TURB_PBL_SCHEME 1 with winds from the model levels, the option "generic_kernel", module_oh_chem (OH_CHEM_REACTION
+ * != 0: a kernel of its own between module_mixing and module_wet_depo). */
 int mphip_run_timesteps(mphip_ctx *ctx, double t_first, int nsteps);
 /* One reference module_* on its own (same state hand-over through the device
  * copy of cache->dt); `modules` is one MPHIP_MOD_* bit or an OR of the

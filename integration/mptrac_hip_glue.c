@@ -58,7 +58,7 @@ static int hip_ts_on[MPHIP_NTR] = { 1, 1, 1, 1, 1 };   /* CLIM_*_TIMESERIES is n
   X(grid_z0) X(grid_z1) X(grid_lon0) X(grid_lon1) X(grid_lat0) X(grid_lat1) X(grid_nx) X(grid_ny)        \
   X(grid_nz) X(met_dt_out) X(isosurf) X(bound_pbl) X(bound_mass) X(bound_mass_trend) X(bound_vmr)        \
   X(bound_vmr_trend) X(bound_lat0) X(bound_lat1) X(bound_p0) X(bound_p1) X(bound_dps) X(bound_dzs)       \
-  X(bound_zetas) X(oh_chem_beta) X(met_utm_ref_lon)
+  X(bound_zetas) X(oh_chem_beta) X(met_utm_ref_lon) X(oh_chem_reaction) X(qnt_mloss_oh)
 
 /* module_meteo outputs: mphip_ctl_t::qnt_met[MPHIP_MQ_<X>] = ctl_t::qnt_<x> */
 #define HIP_CTL_METEO_QNT(X)                                                                             \
@@ -89,9 +89,11 @@ static void hip_ctl(const ctl_t *c, mphip_ctl_t *d) {
     d->wet_depo_ic_h[k] = c->wet_depo_ic_h[k];
     d->wet_depo_bc_h[k] = c->wet_depo_bc_h[k];
   }
+  for (int k = 0; k < 4; k++)   /* module_oh_chem: its OH table is clim->oh, uploaded with the zonal means below */
+    d->oh_chem[k] = c->oh_chem[k];
   /* what the device does not implement must not run silently on stale host data */
-  if (c->oh_chem_reaction != 0 || c->h2o2_chem_reaction != 0 || c->kpp_chem || c->tracer_chem || c->radio_decay)
-    ERRMSG("MPTRAC_HIP: chemistry and radioactive decay are not implemented on the device!");
+  if (c->h2o2_chem_reaction != 0 || c->kpp_chem || c->tracer_chem || c->radio_decay)
+    ERRMSG("MPTRAC_HIP: H2O2 chemistry, KPP, tracer chemistry and radioactive decay are not implemented on the device!");
   if (c->qnt_hno3 >= 0 || c->qnt_oh >= 0 || c->qnt_h2o2 >= 0 || c->qnt_ho2 >= 0 || c->qnt_o1d >= 0 || c->qnt_tnat >= 0
       || c->qnt_tsts >= 0)
     ERRMSG("MPTRAC_HIP: the climatology-based quantities of module_meteo are not implemented on the device!");

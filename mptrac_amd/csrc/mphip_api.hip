@@ -1068,6 +1068,40 @@ int check_meteo(mphip_ctx *ctx) {
   return 0;
 }
 
+// module_oh_chem (mptrac.c:5351-5434): its own kernel, on the dt the step's launch stored (oh_chem_kernel)
+int launch_oh(mphip_ctx *ctx) {
+  const mphip_ctl_t &c = ctx->ctl;
+  if (c.oh_chem_reaction < 1 || c.oh_chem_reaction > 3)
+    return fail(ctx, "module_oh_chem: OH_CHEM_REACTION must be 1, 2 or 3");
+  if (c.qnt_m < 0 && c.qnt_vmr < 0)
+    return fail(ctx, "Module needs quantity mass or volume mixing ratio!");
+  if (!ctx->d_zm[MPHIP_ZM_OH])
+    return fail(ctx, "module_oh_chem: the OH climatology was not uploaded");
+  if (ctx->np == 0)
+    return 0;
+  if (ensure_packed(ctx))
+    return 1;
+  const MetSlot &s0 = ctx->slot[0 ^ ctx->flip], &s1 = ctx->slot[1 ^ ctx->flip];
+  if (!s0.valid || !s1.valid || !s0.has3[MPHIP_T] || !s1.has3[MPHIP_T])
+    return fail(ctx, "module_oh_chem: meteo field t was not uploaded");
+  MeteoArgs G;
+  memset(&G, 0, sizeof(G));
+  G.ctl = c;
+  G.met = dev_met(ctx);
+  G.atm = dev_atm(ctx);
+  G.zm[MPHIP_ZM_OH] = ctx->zm[MPHIP_ZM_OH];
+  long long per_block = (ctx->np + ctx->step_blocks - 1) / ctx->step_blocks;
+  per_block = std::max<long long>(256, (per_block + 255) / 256 * 256);
+  int nb = (int) ((ctx->np + per_block - 1) / per_block);
+  nb = (nb + 7) & ~7;
+  G.nblocks_logical = nb;
+  G.per_block = per_block;
+  G.xcd_map = ctx->xcd_map;
+  hipLaunchKernelGGL(oh_chem_kernel, dim3(nb), dim3(256), axes_lds_bytes(ctx), ctx->stream, G);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 int launch_meteo(mphip_ctx *ctx) {
   const mphip_ctl_t &c = ctx->ctl;
   if (ctx->np == 0 || !meteo_requested(c))
@@ -2297,12 +2331,14 @@ int mphip_update_ctl(mphip_ctx *ctx, const mphip_ctl_t *ctl) {
     return fail(ctx, "Set ADVECT_VERT_COORD to 0, 1, 2, or 3!");
   if (!(ctl->advect == 0 || ctl->advect == 1 || ctl->advect == 2 || ctl->advect == 4))
     return fail(ctx, "Set ADVECT to 1, 2, or 4!");
+  if (ctl->oh_chem_reaction < 0 || ctl->oh_chem_reaction > 3)   // (the reference would compute NaN masses)
+    return fail(ctx, "Set OH_CHEM_REACTION to 0, 1, 2, or 3!");
   // module_meteo runs after the loss / mixing / deposition modules here and is evaluated lazily: none of the
   // quantities it fills may be one those modules read or write
   for (int k = 0; k < MPHIP_NMQ; k++)
     if (ctl->qnt_met[k] >= 0)
       for (int other : { ctl->qnt_m, ctl->qnt_vmr, ctl->qnt_aoa, ctl->qnt_loss_rate, ctl->qnt_mloss_decay,
-                         ctl->qnt_mloss_wet, ctl->qnt_mloss_dry, ctl->qnt_rp, ctl->qnt_rhop, ctl->qnt_ens,
+                         ctl->qnt_mloss_wet, ctl->qnt_mloss_dry, ctl->qnt_mloss_oh, ctl->qnt_rp, ctl->qnt_rhop, ctl->qnt_ens,
                          ctl->qnt_zeta, ctl->qnt_eta, ctl->qnt_tracer[0], ctl->qnt_tracer[1], ctl->qnt_tracer[2],
                          ctl->qnt_tracer[3], ctl->qnt_tracer[4] })
         if (ctl->qnt_met[k] == other)
@@ -2989,15 +3025,27 @@ int mphip_run_timestep(mphip_ctx *ctx, double t) {
   const double t_next = t + c.direction * c.dt_mod;
   const bool sort_next = ctx->sort_ahead && ctx->np > 0 && ctx->ext_identity && c.sort_dt > 0
     && fmod(t_next, c.sort_dt) == 0 && c.direction * (t_next - c.t_stop) <= 0;
-  if (!mixing_now) {
+  // module_oh_chem (own kernel, launch_oh) sits between module_mixing and module_wet_depo: with it the step's launch
+  // stops before the deposition modules, which follow in a launch of their own
+  const bool oh = c.oh_chem_reaction != 0;
+  if (!mixing_now && !oh) {
     if (launch_step(ctx, mask | tail, t, ctr_turb, ctr_meso, ctr_conv, ctr_pbl))
       return 1;
     if (sort_next && ahead_launch(ctx, t_next))
       return 1;
     return meteo_now ? schedule_meteo(ctx) : 0;
   }
-  if (tail && (mask & MPHIP_MOD_TIMESTEPS))
+  if ((tail || oh) && (mask & MPHIP_MOD_TIMESTEPS))
     mask |= kStoreDt;
+  if (!mixing_now) {
+    if (launch_step(ctx, mask, t, ctr_turb, ctr_meso, ctr_conv, ctr_pbl))
+      return 1;
+    if (sort_next && ahead_launch(ctx, t_next))
+      return 1;
+    if (launch_oh(ctx) || (tail && launch_step(ctx, tail, t, 0, 0, 0, 0)))
+      return 1;
+    return meteo_now ? schedule_meteo(ctx) : 0;
+  }
   // the keys of the sort ahead, its module_timesteps and module_mixing's box index from the launch that moves the
   // particles (EmitKeys) instead of a kernel of their own behind it, where an instantiation for it exists
   EmitKeys ek;
@@ -3051,6 +3099,8 @@ int mphip_run_timestep(mphip_ctx *ctx, double t) {
   }
   if (do_mixing(ctx, t, cells_ready))
     return 1;
+  if (oh && launch_oh(ctx))
+    return 1;
   if (tail && launch_step(ctx, tail, t, 0, 0, 0, 0))
     return 1;
   return meteo_now ? schedule_meteo(ctx) : 0;
@@ -3093,7 +3143,8 @@ int mphip_run_timesteps(mphip_ctx *ctx, double t_first, int nsteps) {
     const bool quiet = ctx->multi_step && ctx->np > 0 && t != c.t_start && !scheduled(t)
       && c.advect > 0   // (every integrator has its multi-step instantiations; without module_advect: single steps)
       && !ctx->fused_perm
-      && !ctx->force_generic;
+      && !ctx->force_generic
+      && c.oh_chem_reaction == 0;   // (module_oh_chem is a launch of its own: single steps)
     if (quiet) {
       batch = nsteps - done;
       if (ctx->locality_interval > 0)
@@ -3226,8 +3277,10 @@ int mphip_module(mphip_ctx *ctx, unsigned modules, double t) {
     return do_mixing(ctx, t);
   if (modules == MPHIP_MOD_METEO)
     return launch_meteo(ctx);
+  if (modules == MPHIP_MOD_OH_CHEM)
+    return launch_oh(ctx);
   if (modules & ~kParticleBits)
-    return fail(ctx, "module_sort / module_mixing / module_meteo must be called on their own");
+    return fail(ctx, "module_sort / module_mixing / module_meteo / module_oh_chem must be called on their own");
   const uint64_t n = (uint64_t) ctx->np_total;
   uint64_t ctr_turb = 0, ctr_meso = 0, ctr_conv = 0, ctr_pbl = 0;
   if (modules & MPHIP_MOD_DIFF_TURB) {

@@ -68,6 +68,10 @@ __device__ __noinline__ double libm_pow(double x, double y) {
   return libm_pow(libm_tables(), x, y);
 }
 
+__device__ __noinline__ double libm_log10(double x) {   // glibc's log10 on top of libm_log (module_oh_chem)
+  return mphip_libm_log10(libm_tables(), x);
+}
+
 // sin and cos of the C library for |x| < 2.426 (mphip_libm.h; every latitude in radians, ZETA's argument); the device
 // library's beyond.  Calls: they serve the reference-rounding build (DX2DEG) and module_meteo, not the headline path.
 static __device__ const double g_sincos_tab[440] = { MPHIP_LIBM_SINCOS_TAB_INIT };
@@ -1205,6 +1209,28 @@ __device__ inline double clim_oh(const mphip_ctl_t &ctl, const DevZm &Z, double 
   const double csza = cos_sza(t, lon_ref, lat_ref);
   const double denom = (csza >= csza_thresh) ? csza : csza_thresh;
   return oh * libm_exp(-ctl.oh_chem_beta / denom);
+}
+
+// module_oh_chem, mptrac.c:5351-5434: the loss rate k [OH] M of the particle, from its temperature t (INTPOL_3D(t, 1))
+// and the OH table (clim_oh).  The "> 0 ?" guards of reaction 3 are the reference's (negative high-pressure exponents
+// give a constant ki).
+constexpr double kAvo = 6.02214e23;
+__device__ __forceinline__ double oh_chem_rate(const mphip_ctl_t &ctl, const DevZm &Z, double time, double p, double lon,
+                                               double lat, double t) {
+  const double M = fdiv(kAvo * 1e-6 * (p * 100), kRI * t);   // MOLEC_DENS
+  const double *c = ctl.oh_chem;
+  double k;
+  if (ctl.oh_chem_reaction == 1)
+    k = c[0];
+  else if (ctl.oh_chem_reaction == 2)
+    k = c[0] * libm_exp(fdiv(-c[1], t));
+  else {
+    const double k0 = c[0] * (c[1] > 0 ? libm_pow(fdiv(298., t), c[1]) : 1.);
+    const double ki = c[2] * (c[3] > 0 ? libm_pow(fdiv(298., t), c[3]) : 1.);
+    const double e = libm_log10(fdiv(k0 * M, ki));
+    k = fdiv(k0 * M, 1. + fdiv(k0 * M, ki)) * libm_pow(0.6, fdiv(1., 1. + e * e));
+  }
+  return k * clim_oh(ctl, Z, time, lon, lat, p) * M;
 }
 
 // nat_temperature, mptrac.c:8334-8355

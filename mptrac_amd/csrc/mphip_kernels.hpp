@@ -2702,6 +2702,34 @@ struct MeteoArgs {
 #ifndef MPHIP_METEO_WAVES_PER_SIMD
 #define MPHIP_METEO_WAVES_PER_SIMD 3
 #endif
+// module_oh_chem, mptrac.c:5351-5434: a launch of its own between the movers (and module_mixing) and the deposition
+// modules -- the clim_oh of its rate needs the device library's trigonometry, whose large-argument reduction is a call:
+// compiled into the step kernels it would give every instantiation a stack frame.  Every particle with dt != 0 (the
+// dt the step's launch stored): temperature at the particle (INTPOL_3D(t, 1)), k [OH] M, then the loss.
+__global__ __launch_bounds__(256, MPHIP_METEO_WAVES_PER_SIMD) void oh_chem_kernel(const MeteoArgs G) {
+  extern __shared__ double s_axes[];
+  const DevMet &M = G.met;
+  const DevAtm &a = G.atm;
+  const mphip_ctl_t &ctl = G.ctl;
+  const Axes A = load_axes(M, s_axes);
+  __syncthreads();
+  const int nb = G.nblocks_logical;
+  const int lb = G.xcd_map ? (int) (blockIdx.x % 8) * (nb / 8) + (int) (blockIdx.x / 8) : (int) blockIdx.x;
+  const long long first = (long long) lb * G.per_block;
+  long long last = first + G.per_block;
+  if (last > a.np)
+    last = a.np;
+  for (long long i = first + threadIdx.x; i < last; i += blockDim.x) {
+    const double dt = a.dt[i];
+    if (dt == 0)   // guard of PARTICLE_LOOP(..., check_dt = 1), mptrac.h:1759
+      continue;
+    const double tm = a.time[i], p = a.p[i], lon = a.lon[i], lat = a.lat[i];
+    const double t = temperature_at(M, A, tm, p, lon, lat);
+    const double rate = oh_chem_rate(ctl, G.zm[MPHIP_ZM_OH], tm, p, lon, lat, t);
+    apply_loss(ctl, a, i, libm_exp(-dt * rate), ctl.qnt_mloss_oh, rate);
+  }
+}
+
 __global__ __launch_bounds__(256, MPHIP_METEO_WAVES_PER_SIMD) void meteo_kernel(const MeteoArgs G) {
   extern __shared__ double s_axes[];
   const DevMet &M = G.met;

@@ -241,6 +241,41 @@ MPHIP_LIBM_FN double mphip_libm_log(const double *log_tab, double x) {
   return mphip_libm_log_away(log_tab, ix);
 }
 
+/* ---- log10 ---------------------------------------------------------------------------------------------------- */
+
+/* glibc 2.35's __ieee754_log10 (sysdeps/ieee754/dbl-64/e_log10.c, after fdlibm): the exponent k taken out (x scaled
+ * to [1, 2), or to [0.5, 1) with k + 1 for x < 1), then k log10(2) in two parts around ivln10 * log(mantissa).  That
+ * file has no FMA variant: its two products and sums stay unfused.  The log inside is the library's log, i.e. the one
+ * above.  Zero gives -inf, negatives and NaN a NaN, +inf itself. */
+MPHIP_LIBM_FN double mphip_libm_log10(const double *log_tab, double x) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+  const double ivln10 = 0x1.bcb7b1526e50ep-2, log10_2hi = 0x1.34413509f6000p-2, log10_2lo = 0x1.9fef311f12b36p-42;
+  uint64_t ix = mphip_libm_bits(x);
+  int32_t hx = (int32_t) (ix >> 32);
+  int32_t k = 0;
+  if (hx < 0x00100000) {   /* x < 2^-1022 */
+    if ((ix & 0x7fffffffffffffffull) == 0)
+      return -__builtin_inf();
+    if (hx < 0)
+      return __builtin_nan("");
+    k -= 54;
+    x *= 0x1p54;           /* subnormal: scale up */
+    ix = mphip_libm_bits(x);
+    hx = (int32_t) (ix >> 32);
+  }
+  if (hx >= 0x7ff00000)
+    return x + x;
+  k += (hx >> 20) - 1023;
+  const int32_t i = (int32_t) (((uint32_t) k & 0x80000000u) >> 31);
+  hx = (hx & 0x000fffff) | ((0x3ff - i) << 20);
+  const double y = (double) (k + i);
+  x = mphip_libm_from_words((uint32_t) hx, (uint32_t) ix);
+  const double z = y * log10_2lo + ivln10 * mphip_libm_log(log_tab, x);
+  return z + y * log10_2hi;
+}
+
 /* ---- pow ------------------------------------------------------------------------------------------------------ */
 
 /* 0: y is not an integer, 1: odd, 2: even */

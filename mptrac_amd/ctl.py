@@ -119,6 +119,15 @@ CTL_FIELDS = [
     ("pad4", C.c_int, 0),
 ]
 
+# Members of mphip_ctl_t behind the oracle's layout (the oracle's orc_ctl_t ends with pad4): module_oh_chem
+# (mptrac.c:5351-5434) -- OH_CHEM_REACTION, ctl->qnt_mloss_oh, OH_CHEM[0..3]
+HIP_CTL_FIELDS = [
+    ("oh_chem_reaction", C.c_int, 0),
+    ("qnt_mloss_oh", C.c_int, -1),
+    ("oh_chem", C.c_double * 4, (0.0,) * 4),
+]
+HIP_ONLY_KEYS = frozenset(n for n, _, _ in HIP_CTL_FIELDS)
+
 # quantities module_meteo fills, in the order of its SET_ATM list (mptrac.c:5091-5157) = MPHIP_MQ_*
 METEO_QUANTITIES = (
     "ps", "ts", "zs", "us", "vs", "ess", "nss", "shf", "lsm", "sst", "pbl", "pt", "tt", "zt", "h2ot", "zg", "p",
@@ -138,19 +147,23 @@ TRACERS = ("Cccl4", "Cccl3f", "Cccl2f2", "Cn2o", "Csf6")
 TRACER_SERIES = ("ccl4", "ccl3f", "ccl2f2", "n2o", "sf6")
 
 
-def make_ctl_struct(name):
+def make_ctl_struct(name, extra=()):
     """ctypes mirror of the C struct; one class per consumer so that the
-    library bindings do not share a type object."""
-    return type(name, (C.Structure,), {"_fields_": [(n, t) for n, t, _ in CTL_FIELDS]})
+    library bindings do not share a type object.  `extra`: fields appended
+    behind CTL_FIELDS (HIP_CTL_FIELDS for mphip_ctl_t)."""
+    return type(name, (C.Structure,), {"_fields_": [(n, t) for n, t, _ in list(CTL_FIELDS) + list(extra)]})
 
 
 def fill_ctl(struct, **kw):
-    """Set defaults (as mptrac_read_ctl would) and then the given keys."""
-    known = {n for n, _, _ in CTL_FIELDS}
+    """Set defaults (as mptrac_read_ctl would) and then the given keys.  Keys are judged by the struct filled: the
+    members of HIP_CTL_FIELDS are skipped for a struct without them (the oracle's: it has no module_oh_chem), any
+    other unknown key is an error."""
+    fields = [f for f in list(CTL_FIELDS) + HIP_CTL_FIELDS if f[0] in {n for n, _ in struct._fields_}]
+    known = {n for n, _, _ in fields}
     for k in kw:
-        if k not in known:
+        if k not in known and k not in HIP_ONLY_KEYS:
             raise KeyError(f"unknown control parameter {k!r}")
-    for n, t, d in CTL_FIELDS:
+    for n, t, d in fields:
         v = kw.get(n, d)
         if isinstance(d, tuple):
             arr = getattr(struct, n)
@@ -167,7 +180,7 @@ def ctl_from_quantities(names):
     table = {"m": "qnt_m", "vmr": "qnt_vmr", "rp": "qnt_rp", "rhop": "qnt_rhop", "ens": "qnt_ens",
              "loss_rate": "qnt_loss_rate", "mloss_decay": "qnt_mloss_decay",
              "mloss_wet": "qnt_mloss_wet", "mloss_dry": "qnt_mloss_dry", "zeta": "qnt_zeta", "eta": "qnt_eta",
-             "aoa": "qnt_aoa"}
+             "aoa": "qnt_aoa", "mloss_oh": "qnt_mloss_oh"}
     met = [-1] * len(METEO_QUANTITIES)
     tracer = [-1] * len(TRACERS)
     for i, n in enumerate(names):

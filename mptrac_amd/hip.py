@@ -14,7 +14,7 @@ import weakref
 import numpy as np
 
 from . import build as _build
-from .ctl import TRACER_SERIES, ZONAL_MEANS, fill_ctl, make_ctl_struct
+from .ctl import HIP_CTL_FIELDS, TRACER_SERIES, ZONAL_MEANS, fill_ctl, make_ctl_struct
 from .synth import FIELDS_2D, FIELDS_3D, FIELDS_ML
 
 NQ_MAX = 16
@@ -23,10 +23,10 @@ MOD = {
     "convection": 1 << 5, "sedi": 1 << 6, "position2": 1 << 7, "loss_zero": 1 << 8, "decay": 1 << 9,
     "wet_depo": 1 << 10, "dry_depo": 1 << 11, "advect_init": 1 << 12, "diff_pbl": 1 << 13, "meteo": 1 << 14,
     "isosurf": 1 << 15, "sort": 1 << 16, "mixing": 1 << 17, "bound_cond": 1 << 18, "bound_cond2": 1 << 19,
-    "isosurf_init": 1 << 20,
+    "isosurf_init": 1 << 20, "oh_chem": 1 << 21,
 }
 
-MphipCtl = make_ctl_struct("MphipCtl")
+MphipCtl = make_ctl_struct("MphipCtl", HIP_CTL_FIELDS)
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
 

@@ -132,7 +132,7 @@ static const struct {
   { "m", "mass", "kg" }, { "vmr", "volume mixing ratio", "ppv" }, { "rp", "particle radius", "microns" },
   { "rhop", "particle density", "kg/m^3" }, { "loss_rate", "total loss rate", "s^-1" },
   { "mloss_decay", "mass loss due to exponential decay", "kg" }, { "mloss_wet", "mass loss due to wet deposition", "kg" },
-  { "mloss_dry", "mass loss due to dry deposition", "kg" }, { "zeta", "zeta coordinate", "K" },
+  { "mloss_dry", "mass loss due to dry deposition", "kg" }, { "mloss_oh", "mass loss due to OH chemistry", "kg" }, { "zeta", "zeta coordinate", "K" },
   { "eta", "eta coordinate", "1" }, { "aoa", "age of air", "s" },
   { "ps", "surface pressure", "hPa" }, { "ts", "surface temperature", "K" }, { "zs", "surface height", "km" },
   { "us", "surface zonal wind", "m/s" }, { "vs", "surface meridional wind", "m/s" },
@@ -169,7 +169,7 @@ static const struct {
 static const char *unsupported_qnt[] = {
   /* quantities only the chemistry, radioactive-decay and domain-decomposition code of the reference fills or
    * mixes (SET_QNT table, mptrac.c:6905-6969): they would be carried along unchanged here */
-  "mloss_oh", "mloss_h2o2", "mloss_kpp", "Cx", "Ch2o", "Co3", "Cco", "Coh", "Ch", "Cho2", "Ch2o2", "Co1d", "Co3p",
+  "mloss_h2o2", "mloss_kpp", "Cx", "Ch2o", "Co3", "Cco", "Coh", "Ch", "Cho2", "Ch2o2", "Co1d", "Co3p",
   "Arn222", "Apb210", "Abe7", "Acs137", "Ai131", "Axe133",
   "current_subdomain", "target_subdomain", NULL
 };
@@ -335,7 +335,7 @@ void mptrac_read_ctl(const char *filename, int argc, char *argv[], ctl_t *ctl) {
 
   /* quantities, mptrac.c:6737-6971 */
   ctl->qnt_m = ctl->qnt_vmr = ctl->qnt_rp = ctl->qnt_rhop = ctl->qnt_ens = ctl->qnt_loss_rate = -1;
-  ctl->qnt_mloss_decay = ctl->qnt_mloss_wet = ctl->qnt_mloss_dry = ctl->qnt_zeta = ctl->qnt_eta = -1;
+  ctl->qnt_mloss_decay = ctl->qnt_mloss_wet = ctl->qnt_mloss_dry = ctl->qnt_mloss_oh = ctl->qnt_zeta = ctl->qnt_eta = -1;
   ctl->qnt_aoa = ctl->qnt_stat = -1;
   ctl->qnt_Cccl4 = ctl->qnt_Cccl3f = ctl->qnt_Cccl2f2 = ctl->qnt_Cn2o = ctl->qnt_Csf6 = -1;
 #define X(n, u) ctl->qnt_##n = -1;
@@ -374,6 +374,7 @@ void mptrac_read_ctl(const char *filename, int argc, char *argv[], ctl_t *ctl) {
     else if (!strcasecmp(n, "mloss_decay")) ctl->qnt_mloss_decay = iq;
     else if (!strcasecmp(n, "mloss_wet")) ctl->qnt_mloss_wet = iq;
     else if (!strcasecmp(n, "mloss_dry")) ctl->qnt_mloss_dry = iq;
+    else if (!strcasecmp(n, "mloss_oh")) ctl->qnt_mloss_oh = iq;
     else if (!strcasecmp(n, "zeta")) ctl->qnt_zeta = iq;
     else if (!strcasecmp(n, "eta")) ctl->qnt_eta = iq;
     else if (!strcasecmp(n, "aoa")) ctl->qnt_aoa = iq;
@@ -419,23 +420,28 @@ void mptrac_read_ctl(const char *filename, int argc, char *argv[], ctl_t *ctl) {
   REQUIRE(ctl->advect == 1 || ctl->advect == 2 || ctl->advect == 4, "Set ADVECT to 1, 2, or 4!");
   REQUIRE(ctl->turb_pbl_trans >= 0 && ctl->turb_pbl_trans <= 1, "TURB_PBL_TRANS must be in the range [0, 1]!");
   /* isosurface and boundary conditions (mptrac.c:7207-7209, 7266-7289) */
-  /* SPECIES presets (values: mptrac.c:7291-7383): molar mass and Henry's-law constants become the defaults of
-   * MOLMASS / WET_DEPO_*_H below; a species that also switches the OH chemistry on is only accepted with that
-   * chemistry explicitly off, because this build does not provide it */
+  /* SPECIES presets (values: mptrac.c:7291-7383): molar mass, Henry's-law constants and the OH reaction with its
+   * rate constants (JPL evaluation) become the defaults of MOLMASS / WET_DEPO_*_H / OH_CHEM_REACTION / OH_CHEM below */
   static const struct {
     const char *name;
     double molmass, henry_ref, henry_temp;
     int oh_reaction;
+    double oh_chem[4];
   } species[] = {
-    { "CF2Cl2", 120.907, 3e-5, 3500.0, 0 }, { "CFCl3", 137.359, 1.1e-4, 3300.0, 0 }, { "CH4", 16.043, 1.4e-5, 1600.0, 2 },
-    { "CO", 28.01, 9.7e-6, 1300.0, 3 }, { "CO2", 44.009, 3.3e-4, 2400.0, 0 }, { "H2O", 18.01528, 0, 0, 0 },
-    { "N2O", 44.013, 2.4e-4, 2600.0, 0 }, { "NH3", 17.031, 5.9e-1, 4200.0, 2 }, { "HNO3", 63.012, 2.1e3, 8700.0, 0 },
-    { "NO", 30.006, 1.9e-5, 1600.0, 3 }, { "NO2", 46.005, 1.2e-4, 2400.0, 3 }, { "O3", 47.997, 1e-4, 2800.0, 2 },
-    { "SF6", 146.048, 2.4e-6, 3100.0, 0 }, { "SO2", 64.066, 1.3e-2, 2900.0, 3 }, { NULL, 0, 0, 0, 0 }
+    { "CF2Cl2", 120.907, 3e-5, 3500.0, 0, { 0 } }, { "CFCl3", 137.359, 1.1e-4, 3300.0, 0, { 0 } },
+    { "CH4", 16.043, 1.4e-5, 1600.0, 2, { 2.45e-12, 1775, 0, 0 } },
+    { "CO", 28.01, 9.7e-6, 1300.0, 3, { 6.9e-33, 2.1, 1.1e-12, -1.3 } }, { "CO2", 44.009, 3.3e-4, 2400.0, 0, { 0 } },
+    { "H2O", 18.01528, 0, 0, 0, { 0 } }, { "N2O", 44.013, 2.4e-4, 2600.0, 0, { 0 } },
+    { "NH3", 17.031, 5.9e-1, 4200.0, 2, { 1.7e-12, 710, 0, 0 } }, { "HNO3", 63.012, 2.1e3, 8700.0, 0, { 0 } },
+    { "NO", 30.006, 1.9e-5, 1600.0, 3, { 7.1e-31, 2.6, 3.6e-11, 0.1 } },
+    { "NO2", 46.005, 1.2e-4, 2400.0, 3, { 1.8e-30, 3.0, 2.8e-11, 0.0 } },
+    { "O3", 47.997, 1e-4, 2800.0, 2, { 1.7e-12, 940, 0, 0 } }, { "SF6", 146.048, 2.4e-6, 3100.0, 0, { 0 } },
+    { "SO2", 64.066, 1.3e-2, 2900.0, 3, { 2.9e-31, 4.1, 1.7e-12, -0.2 } }, { NULL, 0, 0, 0, 0, { 0 } }
   };
   char defstr[LEN];
   double molmass_default = 0, henry_default[2] = { 0, 0 };   /* calloc'ed ctl_t of the reference */
   int oh_default = 0;
+  double oh_chem_default[4] = { 0, 0, 0, 0 };
   scan_ctl(filename, argc, argv, "SPECIES", -1, "-", ctl->species);
   for (int k = 0; species[k].name; k++)
     if (strcasecmp(ctl->species, species[k].name) == 0) {
@@ -443,13 +449,26 @@ void mptrac_read_ctl(const char *filename, int argc, char *argv[], ctl_t *ctl) {
       henry_default[0] = species[k].henry_ref;
       henry_default[1] = species[k].henry_temp;
       oh_default = species[k].oh_reaction;
+      for (int i = 0; i < 4; i++)
+        oh_chem_default[i] = species[k].oh_chem[i];
     }
   sprintf(defstr, "%g", molmass_default);
   ctl->molmass = scan_ctl(filename, argc, argv, "MOLMASS", -1, defstr, NULL);
+  /* module_oh_chem (mptrac.c:5351-5434) */
   sprintf(defstr, "%d", oh_default);
-  if ((int) scan_ctl(filename, argc, argv, "OH_CHEM_REACTION", -1, defstr, NULL) != 0)
-    ERRMSG("OH_CHEM_REACTION%s: the OH chemistry is not implemented in this build (set OH_CHEM_REACTION 0 to run "
-           "the species as a passive tracer with its deposition parameters)!", oh_default ? " (switched on by SPECIES)" : "");
+  ctl->oh_chem_reaction = (int) scan_ctl(filename, argc, argv, "OH_CHEM_REACTION", -1, defstr, NULL);
+  for (int i = 0; i < 4; i++) {
+    sprintf(defstr, "%g", oh_chem_default[i]);
+    ctl->oh_chem[i] = scan_ctl(filename, argc, argv, "OH_CHEM", i, defstr, NULL);
+  }
+  /* (any other reaction type would give NaN masses in the reference) */
+  REQUIRE(ctl->oh_chem_reaction >= 0 && ctl->oh_chem_reaction <= 3, "Set OH_CHEM_REACTION to 0, 1, 2, or 3!");
+  if (ctl->oh_chem_reaction != 0) {
+    if (ctl->qnt_m < 0 && ctl->qnt_vmr < 0)
+      ERRMSG("Module needs quantity mass or volume mixing ratio!");
+    LOG(1, "OH chemistry: reaction %d, OH_CHEM = %g, %g, %g, %g", ctl->oh_chem_reaction, ctl->oh_chem[0],
+        ctl->oh_chem[1], ctl->oh_chem[2], ctl->oh_chem[3]);
+  }
 
   /* wet / dry deposition, decay, mixing (mptrac.c:7425-7543): the species sets the defaults of the in-cloud
    * constants and of the below-cloud WET_DEPO_BC_H[0]; WET_DEPO_BC_H[1] is not a control parameter */
@@ -754,9 +773,9 @@ static int read_clim_ts(const char *filename, clim_ts_t *ts) {
   return 1;
 }
 
-/* mptrac.c:6663-6719: the tropopause climatology and the zonal means a requested module_meteo quantity needs
- * (the reference reads all its climatologies whatever the quantities; its photolysis rates and tracer time
- * series feed the chemistry modules, which are not part of this build) */
+/* mptrac.c:6663-6719: the tropopause climatology, the zonal means a requested module_meteo quantity needs and
+ * the OH table of module_oh_chem (the reference reads all its climatologies whatever the quantities; its photolysis
+ * rates feed the other chemistry modules, which are not part of this build) */
 void mptrac_read_clim(const ctl_t *ctl, clim_t *clim) {
   clim_tropo_init(clim);
   /* zonal means: read when a module_meteo quantity needs the table and a file is named */
@@ -766,7 +785,7 @@ void mptrac_read_clim(const ctl_t *ctl, clim_t *clim) {
     clim_zm_t *zm;
   } zonal[] = {
     { ctl->qnt_hno3 >= 0 || ctl->qnt_tnat >= 0, ctl->clim_hno3_filename, "HNO3", &clim->hno3 },
-    { ctl->qnt_oh >= 0, ctl->clim_oh_filename, "OH", &clim->oh },
+    { ctl->qnt_oh >= 0 || ctl->oh_chem_reaction != 0, ctl->clim_oh_filename, "OH", &clim->oh },
     { ctl->qnt_h2o2 >= 0, ctl->clim_h2o2_filename, "H2O2", &clim->h2o2 },
     { ctl->qnt_ho2 >= 0, ctl->clim_ho2_filename, "HO2", &clim->ho2 },
     { ctl->qnt_o1d >= 0, ctl->clim_o1d_filename, "O1D", &clim->o1d },
@@ -777,6 +796,9 @@ void mptrac_read_clim(const ctl_t *ctl, clim_t *clim) {
       if (zonal[k].zm == &clim->oh && ctl->oh_chem_beta > 0)
         clim_oh_diurnal_correction(ctl, clim);
     }
+  if (ctl->oh_chem_reaction != 0 && clim->oh.ntime <= 0)
+    ERRMSG("OH chemistry (OH_CHEM_REACTION %d) needs the OH climatology, which cannot be read from %s!",
+           ctl->oh_chem_reaction, ctl->clim_oh_filename);
   /* surface time series of the trace gases that are carried (module_bound_cond, mptrac.c:3857-3875) */
   const struct {
     int qnt;
@@ -1819,7 +1841,10 @@ static void to_device_ctl(const ctl_t *c, mphip_ctl_t *d) {
   TAKE(wet_depo_ic_ret_ratio); TAKE(wet_depo_bc_ret_ratio); TAKE(dry_depo_vdep); TAKE(dry_depo_dp);
   TAKE(grid_z0); TAKE(grid_z1); TAKE(grid_lon0); TAKE(grid_lon1); TAKE(grid_lat0); TAKE(grid_lat1);
   TAKE(grid_nx); TAKE(grid_ny); TAKE(grid_nz);
+  TAKE(oh_chem_reaction); TAKE(qnt_mloss_oh);
 #undef TAKE
+  for (int i = 0; i < 4; i++)
+    d->oh_chem[i] = c->oh_chem[i];
   d->qnt_zeta = c->qnt_zeta;
   d->qnt_eta = c->qnt_eta;
   d->met_dt_out = c->met_dt_out;

@@ -132,7 +132,7 @@ typedef struct {
   int nq;
   char qnt_name[NQ][LEN], qnt_longname[NQ][LEN], qnt_unit[NQ][LEN], qnt_format[NQ][LEN];
   int qnt_m, qnt_vmr, qnt_rp, qnt_rhop, qnt_ens, qnt_stat, qnt_loss_rate;
-  int qnt_mloss_decay, qnt_mloss_wet, qnt_mloss_dry, qnt_zeta, qnt_eta, qnt_aoa;
+  int qnt_mloss_decay, qnt_mloss_wet, qnt_mloss_dry, qnt_mloss_oh, qnt_zeta, qnt_eta, qnt_aoa;
   int qnt_Cccl4, qnt_Cccl3f, qnt_Cccl2f2, qnt_Cn2o, qnt_Csf6;   /* trace gases: boundary condition from a time series, mixing */
   /* module_meteo outputs: qnt_ps, qnt_ts, ..., qnt_tice (mptrac.h:2518-2740) */
 #define X(n, u) int qnt_##n;
@@ -146,6 +146,9 @@ typedef struct {
   char clim_hno3_filename[LEN], clim_oh_filename[LEN], clim_h2o2_filename[LEN], clim_ho2_filename[LEN],
     clim_o1d_filename[LEN];
   double oh_chem_beta;
+  /* module_oh_chem: reaction type (0 = off, 1 ... 3) and rate constants (OH_CHEM_REACTION, OH_CHEM[0..3]) */
+  int oh_chem_reaction;
+  double oh_chem[4];
   /* surface time series of the trace gases (mptrac.c:7471-7480) */
   char clim_ccl4_timeseries[LEN], clim_ccl3f_timeseries[LEN], clim_ccl2f2_timeseries[LEN], clim_n2o_timeseries[LEN],
     clim_sf6_timeseries[LEN];
