@@ -96,7 +96,9 @@ enum {
   MPHIP_MOD_BOUND_COND = 1 << 18,  /* module_bound_cond  mptrac.c:3789, first call (mptrac.c:7929) */
   MPHIP_MOD_BOUND_COND2 = 1 << 19, /* module_bound_cond, second call (mptrac.c:8000) */
   MPHIP_MOD_ISOSURF_INIT = 1 << 20, /* module_isosurf_init mptrac.c:4886, modes 1-3 (not guarded by dt) */
-  MPHIP_MOD_OH_CHEM    = 1 << 21   /* module_oh_chem     mptrac.c:5351-5434 (between module_mixing and module_wet_depo) */
+  MPHIP_MOD_OH_CHEM    = 1 << 21,  /* module_oh_chem     mptrac.c:5351-5434 (between module_mixing and module_wet_depo) */
+  MPHIP_MOD_CHEM_GRID  = 1 << 22,  /* module_chem_grid   (own kernels; between module_mixing and module_oh_chem) */
+  MPHIP_MOD_H2O2_CHEM  = 1 << 23   /* module_h2o2_chem   (own kernel; between module_oh_chem and module_wet_depo) */
 };
 
 /* Hot-path subset of ctl_t (mptrac.h:2494-3553); same field names, meaning
@@ -162,6 +164,15 @@ typedef struct {
   int oh_chem_reaction;
   int qnt_mloss_oh;
   double oh_chem[4];
+  /* module_h2o2_chem (H2O2_CHEM_REACTION: 0 off, else on; ctl->qnt_mloss_h2o2) and module_chem_grid (ctl->qnt_Cx,
+   * MOLMASS, CHEMGRID_*), which runs when either chemistry is on and both m and Cx are present.  Appended: every
+   * earlier member keeps its offset. */
+  int h2o2_chem_reaction;
+  int qnt_mloss_h2o2;
+  int qnt_Cx;
+  int chemgrid_nx, chemgrid_ny, chemgrid_nz;
+  double molmass;
+  double chemgrid_lon0, chemgrid_lon1, chemgrid_lat0, chemgrid_lat1, chemgrid_z0, chemgrid_z1;
 } mphip_ctl_t;
 
 /* View of one met_t snapshot (mptrac.h:3844-4014).  The arrays stay where the
@@ -211,7 +222,7 @@ int mphip_update_clim(mphip_ctx *ctx, int ntime, int nlat, const double *tropo_t
  * times [s since the start of the year], descending pressures [hPa], ascending latitudes [deg] and the volume
  * mixing ratios vmr[ntime][np][nlat] (the reference's index order, compact).  module_meteo needs the table of
  * every climatology quantity that is requested (hno3: also for tnat); ntime = 0 removes a table. */
-/* module_oh_chem needs the OH table as well. */
+/* module_oh_chem needs the OH table as well, module_h2o2_chem the H2O2 table. */
 int mphip_update_clim_zm(mphip_ctx *ctx, int which, int ntime, int np, int nlat, const double *time,
                          const double *p, const double *lat, const double *vmr);
 /* ... and one of its trace-gas time series (clim_ts_t, mptrac.h:3729-3743; `which` = MPHIP_TR_*): ascending times
@@ -289,7 +300,8 @@ int mphip_run_timestep(mphip_ctx *ctx, double t);
  * schedules it when the next one does not.  module_isosurf and the boundary-layer closure (TURB_PBL_SCHEME 1) share
  * launches on pressure-level winds.  Single steps throughout: the first step (t == T_START), ADVECT 0, ISOSURF or
  * TURB_PBL_SCHEME 1 with winds from the model levels, the option "generic_kernel", module_oh_chem (OH_CHEM_REACTION
- * != 0: a kernel of its own between module_mixing and module_wet_depo). */
+ * != 0: a kernel of its own between module_mixing and module_wet_depo), module_chem_grid and module_h2o2_chem (with
+ * either chemistry on: kernels of their own in the same place, in the order chem_grid, oh_chem, h2o2_chem). */
 int mphip_run_timesteps(mphip_ctx *ctx, double t_first, int nsteps);
 /* One reference module_* on its own (same state hand-over through the device
  * copy of cache->dt); `modules` is one MPHIP_MOD_* bit or an OR of the

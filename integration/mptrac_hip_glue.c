@@ -58,7 +58,10 @@ static int hip_ts_on[MPHIP_NTR] = { 1, 1, 1, 1, 1 };   /* CLIM_*_TIMESERIES is n
   X(grid_z0) X(grid_z1) X(grid_lon0) X(grid_lon1) X(grid_lat0) X(grid_lat1) X(grid_nx) X(grid_ny)        \
   X(grid_nz) X(met_dt_out) X(isosurf) X(bound_pbl) X(bound_mass) X(bound_mass_trend) X(bound_vmr)        \
   X(bound_vmr_trend) X(bound_lat0) X(bound_lat1) X(bound_p0) X(bound_p1) X(bound_dps) X(bound_dzs)       \
-  X(bound_zetas) X(oh_chem_beta) X(met_utm_ref_lon) X(oh_chem_reaction) X(qnt_mloss_oh)
+  X(bound_zetas) X(oh_chem_beta) X(met_utm_ref_lon) X(oh_chem_reaction) X(qnt_mloss_oh)                  \
+  X(h2o2_chem_reaction) X(qnt_mloss_h2o2) X(qnt_Cx) X(molmass) X(chemgrid_nx) X(chemgrid_ny)            \
+  X(chemgrid_nz) X(chemgrid_lon0) X(chemgrid_lon1) X(chemgrid_lat0) X(chemgrid_lat1) X(chemgrid_z0)      \
+  X(chemgrid_z1)
 
 /* module_meteo outputs: mphip_ctl_t::qnt_met[MPHIP_MQ_<X>] = ctl_t::qnt_<x> */
 #define HIP_CTL_METEO_QNT(X)                                                                             \
@@ -91,9 +94,11 @@ static void hip_ctl(const ctl_t *c, mphip_ctl_t *d) {
   }
   for (int k = 0; k < 4; k++)   /* module_oh_chem: its OH table is clim->oh, uploaded with the zonal means below */
     d->oh_chem[k] = c->oh_chem[k];
+  /* module_chem_grid and module_h2o2_chem (the H2O2 table: clim->h2o2) run inside mphip_run_timestep, where the
+   * reference calls them: chem_grid behind module_mixing, oh_chem, h2o2_chem before module_wet_depo */
   /* what the device does not implement must not run silently on stale host data */
-  if (c->h2o2_chem_reaction != 0 || c->kpp_chem || c->tracer_chem || c->radio_decay)
-    ERRMSG("MPTRAC_HIP: H2O2 chemistry, KPP, tracer chemistry and radioactive decay are not implemented on the device!");
+  if (c->kpp_chem || c->tracer_chem || c->radio_decay)
+    ERRMSG("MPTRAC_HIP: KPP, tracer chemistry and radioactive decay are not implemented on the device!");
   if (c->qnt_hno3 >= 0 || c->qnt_oh >= 0 || c->qnt_h2o2 >= 0 || c->qnt_ho2 >= 0 || c->qnt_o1d >= 0 || c->qnt_tnat >= 0
       || c->qnt_tsts >= 0)
     ERRMSG("MPTRAC_HIP: the climatology-based quantities of module_meteo are not implemented on the device!");

@@ -214,6 +214,11 @@ struct mphip_ctx {
   size_t sums_cap = 0;
 
   int *d_cnt = nullptr;               // particles per mixing cell (32-bit: the reference's `int count[]`)
+  // module_chem_grid: [press nz | area ny | lon nx | lat ny] of the chemistry grid, built by mphip_update_ctl with the
+  // C library's exp and cos when the grid is due and valid (chemgrid_ok)
+  double *d_chemgrid = nullptr;
+  bool chemgrid_ok = false;
+  double h2o2_low = 0;                // module_h2o2_chem: pow(1 / a, 1 / b) of the host's C library
   // exchange of the occupied levels only (exchange_occupied_levels): per-level occupancy, the dense band, what was found
   // option "mix_exchange_levels" (default 0): measured with a one-rank communicator, the band costs 0.14 ms per step (the
   // host reads the occupancy: the one synchronisation in the step path; pack / unpack) against a MODELLED saving of
@@ -1098,6 +1103,41 @@ int launch_oh(mphip_ctx *ctx) {
   G.per_block = per_block;
   G.xcd_map = ctx->xcd_map;
   hipLaunchKernelGGL(oh_chem_kernel, dim3(nb), dim3(256), axes_lds_bytes(ctx), ctx->stream, G);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// module_h2o2_chem: its own kernel behind module_oh_chem, on the dt the step's launch stored (h2o2_chem_kernel)
+int launch_h2o2(mphip_ctx *ctx) {
+  const mphip_ctl_t &c = ctx->ctl;
+  if (c.qnt_m < 0 && c.qnt_vmr < 0)
+    return fail(ctx, "Module needs quantity mass or volume mixing ratio!");
+  if (!ctx->d_zm[MPHIP_ZM_H2O2])
+    return fail(ctx, "module_h2o2_chem: the H2O2 climatology was not uploaded");
+  if (ctx->np == 0)
+    return 0;
+  if (ensure_packed(ctx))
+    return 1;
+  const MetSlot &s0 = ctx->slot[0 ^ ctx->flip], &s1 = ctx->slot[1 ^ ctx->flip];
+  bool have = s0.valid && s1.valid;
+  for (int f : { MPHIP_T, MPHIP_LWC, MPHIP_RWC })
+    have = have && s0.has3[f] && s1.has3[f];
+  if (!have)
+    return fail(ctx, "module_h2o2_chem: meteo fields t, lwc and rwc were not uploaded");
+  MeteoArgs G;
+  memset(&G, 0, sizeof(G));
+  G.ctl = c;
+  G.met = dev_met(ctx);
+  G.atm = dev_atm(ctx);
+  G.zm[MPHIP_ZM_H2O2] = ctx->zm[MPHIP_ZM_H2O2];
+  long long per_block = (ctx->np + ctx->step_blocks - 1) / ctx->step_blocks;
+  per_block = std::max<long long>(256, (per_block + 255) / 256 * 256);
+  int nb = (int) ((ctx->np + per_block - 1) / per_block);
+  nb = (nb + 7) & ~7;
+  G.nblocks_logical = nb;
+  G.per_block = per_block;
+  G.xcd_map = ctx->xcd_map;
+  hipLaunchKernelGGL(h2o2_chem_kernel, dim3(nb), dim3(256), axes_lds_bytes(ctx), ctx->stream, G, ctx->h2o2_low);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -2028,13 +2068,15 @@ int exchange_occupied_levels(mphip_ctx *ctx, int nq, size_t ntot, int nz) {
   return 0;
 }
 
-int mixing_sums(mphip_ctx *ctx, const MixPlan &P) {
+// (every_cell: every cell must read its sums and count afterwards, also the empty ones -- module_chem_grid's table)
+int mixing_sums(mphip_ctx *ctx, const MixPlan &P, bool every_cell = false) {
   const MixSet &mq = P.mq;
   const size_t ntot = P.ntot;
   if (ctx->deterministic_sums != 0) {
     MixVals vals = { mq };
     const bool exchanged = ctx->comm != nullptr || ctx->allreduce != nullptr;
-    if (ordered_cell_sums(ctx, vals, mq.n, ctx->ctl.mixing_nz, ntot, ctx->d_sums, ctx->d_cnt, (double *) nullptr, exchanged))
+    if (ordered_cell_sums(ctx, vals, mq.n, P.box.grid.nz, ntot, ctx->d_sums, ctx->d_cnt, (double *) nullptr,
+                          exchanged || every_cell))
       return 1;
   } else {
     HIPCHK(hipMemsetAsync(ctx->d_sums, 0, (size_t) mq.n * ntot * sizeof(double), ctx->stream));
@@ -2048,7 +2090,7 @@ int mixing_sums(mphip_ctx *ctx, const MixPlan &P) {
   }
   // one exchange per mixing step: the sums of every mixed quantity and the cell counts
   const bool exchange = ctx->comm != nullptr || ctx->allreduce != nullptr;
-  const int nz = ctx->ctl.mixing_nz;
+  const int nz = P.box.grid.nz;
   if (exchange && ctx->mix_exchange_levels && nz >= 8 && nz <= 256 && ntot >= ((size_t) 1 << 18))
     return exchange_occupied_levels(ctx, mq.n, ntot, nz);
   return run_allreduce(ctx, ctx->d_sums, (size_t) mq.n * ntot, ctx->d_cnt, ntot, ctx->d_sums + (size_t) mq.n * ntot);
@@ -2072,6 +2114,90 @@ int do_mixing(mphip_ctx *ctx, double t, bool cells_ready = false) {
   if (!active)
     return 0;
   return (!cells_ready && mixing_cells(ctx, P)) || mixing_sums(ctx, P) || mixing_relax(ctx, P);
+}
+
+// module_chem_grid: the mass per cell of the chemistry grid turned into a volume mixing ratio, written into quantity Cx
+// of every particle in the cell.  Reuses module_mixing's pieces: the box index (box_cell: time window
+// [t - DT_MOD / 2, t + DT_MOD / 2], inside the grid, ensemble offset), the cell sums of one value -- q[m] -- in the
+// serial order (atomics with deterministic_sums 0), the all-reduce of sums and counts over the ranks.  Then a table of
+// Cx over the occupied cells (the cell-centre temperature once per cell) and a gather per particle.
+bool chem_on(const mphip_ctl_t &c) {
+  return c.oh_chem_reaction != 0 || c.h2o2_chem_reaction != 0;
+}
+
+bool chemgrid_valid(const mphip_ctl_t &c) {
+  return c.chemgrid_nx >= 1 && c.chemgrid_ny >= 1 && c.chemgrid_nz >= 1 && c.chemgrid_lon0 < c.chemgrid_lon1
+    && c.chemgrid_lat0 < c.chemgrid_lat1 && c.chemgrid_z0 < c.chemgrid_z1;
+}
+
+int do_chem_grid(mphip_ctx *ctx, double t) {
+  const mphip_ctl_t &c = ctx->ctl;
+  if (c.qnt_m < 0 || c.qnt_Cx < 0)
+    return 0;
+  if (c.molmass <= 0)
+    return fail(ctx, "module_chem_grid: Molar mass is not defined!");
+  if (!chemgrid_valid(c) || !ctx->chemgrid_ok)
+    return fail(ctx, "module_chem_grid: invalid chemistry grid (CHEMGRID_NX / NY / NZ >= 1 and non-empty "
+                     "CHEMGRID_LON0 < LON1, LAT0 < LAT1, Z0 < Z1)");
+  if (ctx->np > 0) {
+    if (ensure_packed(ctx))
+      return 1;
+    const MetSlot &s0 = ctx->slot[0 ^ ctx->flip], &s1 = ctx->slot[1 ^ ctx->flip];
+    if (!s0.valid || !s1.valid || !s0.has3[MPHIP_T] || !s1.has3[MPHIP_T])
+      return fail(ctx, "module_chem_grid: meteo field t was not uploaded");
+  }
+  const long long ngrid = (long long) c.chemgrid_nx * c.chemgrid_ny * c.chemgrid_nz;
+  const int nens = c.nens > 0 ? c.nens : 1;
+  if (ngrid * nens >= 0x7fffffffLL)
+    return fail(ctx, "module_chem_grid: too many grid cells for 32-bit cell indices");
+  const size_t ntot = (size_t) ngrid * nens;
+  const DevAtm a = dev_atm(ctx);
+  MixPlan P;
+  memset(&P, 0, sizeof(P));
+  P.mq.q[0] = a.q[c.qnt_m];
+  P.mq.n = 1;
+  P.ntot = ntot;
+  P.box.grid = BoxGrid{ c.chemgrid_lon0, c.chemgrid_lon1, c.chemgrid_lat0, c.chemgrid_lat1, c.chemgrid_z0, c.chemgrid_z1,
+                        c.chemgrid_nx, c.chemgrid_ny, c.chemgrid_nz };
+  P.box.t0 = t - 0.5 * c.dt_mod;
+  P.box.t1 = t + 0.5 * c.dt_mod;
+  P.box.ens = (c.nens > 0 && c.qnt_ens >= 0) ? a.q[c.qnt_ens] : nullptr;
+  P.box.ngrid = (int) ngrid;
+  const bool hook = !ctx->comm && ctx->allreduce;
+  if (ensure_sums(ctx, (1 + (hook ? 1 : 0)) * ntot) || ensure_cell_counts(ctx, ntot))
+    return 1;
+  if (mixing_cells(ctx, P) || mixing_sums(ctx, P, true))
+    return 1;
+  ChemGridArgs C;
+  C.press = ctx->d_chemgrid;
+  C.area = C.press + c.chemgrid_nz;
+  C.lon = C.area + c.chemgrid_ny;
+  C.lat = C.lon + c.chemgrid_nx;
+  C.dz = (c.chemgrid_z1 - c.chemgrid_z0) / c.chemgrid_nz;
+  C.molmass = c.molmass;
+  C.tt = t;
+  C.nx = c.chemgrid_nx;
+  C.ny = c.chemgrid_ny;
+  C.nz = c.chemgrid_nz;
+  C.ngrid = (int) ngrid;
+  C.ntot = (long long) ntot;
+  C.val = ctx->d_sums;
+  C.cnt = ctx->d_cnt;
+  if (ctx->np == 0)   // (a rank without particles takes part in the all-reduce only)
+    return 0;
+  hipLaunchKernelGGL(chem_grid_table_kernel, dim3(grid_for((long long) ntot)), dim3(256), axes_lds_bytes(ctx), ctx->stream,
+                     dev_met(ctx), C);
+  hipLaunchKernelGGL(chem_grid_gather_kernel, dim3(grid_for(ctx->np)), dim3(256), 0, ctx->stream, a,
+                     (const int *) ctx->d_cell, (const double *) ctx->d_sums, c.qnt_Cx);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// the chemistry of a step, in the reference's order: module_chem_grid (with either chemistry; it does nothing without
+// m or Cx), module_oh_chem, module_h2o2_chem
+int launch_chem(mphip_ctx *ctx, double t) {
+  const mphip_ctl_t &c = ctx->ctl;
+  return do_chem_grid(ctx, t) || (c.oh_chem_reaction != 0 && launch_oh(ctx)) || (c.h2o2_chem_reaction != 0 && launch_h2o2(ctx));
 }
 
 void unpin_all(mphip_ctx *ctx, std::vector<std::pair<uintptr_t, uintptr_t>> &list) {
@@ -2296,6 +2422,7 @@ void mphip_destroy(mphip_ctx *ctx) {
   dev_free(ctx->d_prec);
   dev_free(ctx->d_cell);
   dev_free(ctx->d_sums);
+  dev_free(ctx->d_chemgrid);
   dev_free(ctx->d_cnt);
   dev_free(ctx->d_depo_busy);
   dev_free(ctx->d_occ);
@@ -2338,7 +2465,8 @@ int mphip_update_ctl(mphip_ctx *ctx, const mphip_ctl_t *ctl) {
   for (int k = 0; k < MPHIP_NMQ; k++)
     if (ctl->qnt_met[k] >= 0)
       for (int other : { ctl->qnt_m, ctl->qnt_vmr, ctl->qnt_aoa, ctl->qnt_loss_rate, ctl->qnt_mloss_decay,
-                         ctl->qnt_mloss_wet, ctl->qnt_mloss_dry, ctl->qnt_mloss_oh, ctl->qnt_rp, ctl->qnt_rhop, ctl->qnt_ens,
+                         ctl->qnt_mloss_wet, ctl->qnt_mloss_dry, ctl->qnt_mloss_oh, ctl->qnt_mloss_h2o2, ctl->qnt_Cx,
+                         ctl->qnt_rp, ctl->qnt_rhop, ctl->qnt_ens,
                          ctl->qnt_zeta, ctl->qnt_eta, ctl->qnt_tracer[0], ctl->qnt_tracer[1], ctl->qnt_tracer[2],
                          ctl->qnt_tracer[3], ctl->qnt_tracer[4] })
         if (ctl->qnt_met[k] == other)
@@ -2347,6 +2475,33 @@ int mphip_update_ctl(mphip_ctx *ctx, const mphip_ctl_t *ctl) {
     return 1;
   if (!ctx->have_ctl || ctx->ctl.advect_vert_coord != ctl->advect_vert_coord)
     ctx->packed_dirty = true;               // the model-level wind records carry zeta_dot or omega
+  // module_chem_grid's tables, with the C library's exp and cos as the reference computes them: pressures of the level
+  // centres P(z0 + dz (iz + 0.5)), the cell areas dlat dlon (RE pi / 180)^2 cos(lat), the cell centres; built when the
+  // grid will run and is valid (do_chem_grid refuses an invalid one)
+  ctx->chemgrid_ok = false;
+  if (chem_on(*ctl) && ctl->qnt_m >= 0 && ctl->qnt_Cx >= 0 && chemgrid_valid(*ctl)) {
+    const int nx = ctl->chemgrid_nx, ny = ctl->chemgrid_ny, nz = ctl->chemgrid_nz;
+    const double dz = (ctl->chemgrid_z1 - ctl->chemgrid_z0) / nz;
+    const double dlon = (ctl->chemgrid_lon1 - ctl->chemgrid_lon0) / nx;
+    const double dlat = (ctl->chemgrid_lat1 - ctl->chemgrid_lat0) / ny;
+    std::vector<double> tab((size_t) nz + 2 * (size_t) ny + nx);
+    double *press = tab.data(), *area = press + nz, *lon = area + ny, *lat = lon + nx;
+    for (int iz = 0; iz < nz; iz++)
+      press[iz] = kP0 * exp(-(ctl->chemgrid_z0 + dz * (iz + 0.5)) / kH0);
+    for (int ix = 0; ix < nx; ix++)
+      lon[ix] = ctl->chemgrid_lon0 + dlon * (ix + 0.5);
+    for (int iy = 0; iy < ny; iy++) {
+      lat[iy] = ctl->chemgrid_lat0 + dlat * (iy + 0.5);
+      area[iy] = dlat * dlon * ((kRE * M_PI / 180.) * (kRE * M_PI / 180.)) * cos(lat[iy] * M_PI / 180.);
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipStreamSynchronize(ctx->stream));   // (the old tables may still be read)
+    if (dev_alloc(ctx, &ctx->d_chemgrid, tab.size()))
+      return 1;
+    HIPCHK(hipMemcpy(ctx->d_chemgrid, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+    ctx->chemgrid_ok = true;
+  }
+  ctx->h2o2_low = pow(1. / kH2O2CorA, 1. / kH2O2CorB);
   ctx->ctl = *ctl;
   ctx->have_ctl = true;
   return 0;
@@ -3027,7 +3182,8 @@ int mphip_run_timestep(mphip_ctx *ctx, double t) {
     && fmod(t_next, c.sort_dt) == 0 && c.direction * (t_next - c.t_stop) <= 0;
   // module_oh_chem (own kernel, launch_oh) sits between module_mixing and module_wet_depo: with it the step's launch
   // stops before the deposition modules, which follow in a launch of their own
-  const bool oh = c.oh_chem_reaction != 0;
+  // module_chem_grid and module_h2o2_chem join it there (chem_grid, oh_chem, h2o2_chem: launch_chem)
+  const bool oh = chem_on(c);
   if (!mixing_now && !oh) {
     if (launch_step(ctx, mask | tail, t, ctr_turb, ctr_meso, ctr_conv, ctr_pbl))
       return 1;
@@ -3042,7 +3198,7 @@ int mphip_run_timestep(mphip_ctx *ctx, double t) {
       return 1;
     if (sort_next && ahead_launch(ctx, t_next))
       return 1;
-    if (launch_oh(ctx) || (tail && launch_step(ctx, tail, t, 0, 0, 0, 0)))
+    if (launch_chem(ctx, t) || (tail && launch_step(ctx, tail, t, 0, 0, 0, 0)))
       return 1;
     return meteo_now ? schedule_meteo(ctx) : 0;
   }
@@ -3099,7 +3255,7 @@ int mphip_run_timestep(mphip_ctx *ctx, double t) {
   }
   if (do_mixing(ctx, t, cells_ready))
     return 1;
-  if (oh && launch_oh(ctx))
+  if (oh && launch_chem(ctx, t))
     return 1;
   if (tail && launch_step(ctx, tail, t, 0, 0, 0, 0))
     return 1;
@@ -3144,7 +3300,7 @@ int mphip_run_timesteps(mphip_ctx *ctx, double t_first, int nsteps) {
       && c.advect > 0   // (every integrator has its multi-step instantiations; without module_advect: single steps)
       && !ctx->fused_perm
       && !ctx->force_generic
-      && c.oh_chem_reaction == 0;   // (module_oh_chem is a launch of its own: single steps)
+      && !chem_on(c);   // (module_chem_grid, module_oh_chem, module_h2o2_chem are launches of their own: single steps)
     if (quiet) {
       batch = nsteps - done;
       if (ctx->locality_interval > 0)
@@ -3279,8 +3435,13 @@ int mphip_module(mphip_ctx *ctx, unsigned modules, double t) {
     return launch_meteo(ctx);
   if (modules == MPHIP_MOD_OH_CHEM)
     return launch_oh(ctx);
+  if (modules == MPHIP_MOD_CHEM_GRID)
+    return do_chem_grid(ctx, t);
+  if (modules == MPHIP_MOD_H2O2_CHEM)
+    return launch_h2o2(ctx);
   if (modules & ~kParticleBits)
-    return fail(ctx, "module_sort / module_mixing / module_meteo / module_oh_chem must be called on their own");
+    return fail(ctx, "module_sort / module_mixing / module_meteo / module_chem_grid / module_oh_chem / module_h2o2_chem "
+                     "must be called on their own");
   const uint64_t n = (uint64_t) ctx->np_total;
   uint64_t ctr_turb = 0, ctr_meso = 0, ctr_conv = 0, ctr_pbl = 0;
   if (modules & MPHIP_MOD_DIFF_TURB) {

@@ -1233,6 +1233,26 @@ __device__ __forceinline__ double oh_chem_rate(const mphip_ctl_t &ctl, const Dev
   return k * clim_oh(ctl, Z, time, lon, lat, p) * M;
 }
 
+// module_h2o2_chem: the rate coefficient of the in-cloud oxidation of SO2 by H2O2 from the temperature t, the cloud
+// water lwc + rwc at the particle and the H2O2 table (clim_zm), in the reference's operation order.  The high-SO2
+// correction a Cx^b applies above `low` = pow(1 / a, 1 / b) (computed by the host's C library) when the particle
+// carries Cx (cx_on).
+constexpr double kH2O2CorA = 3.12541941e-06, kH2O2CorB = -5.72532259e-01;
+__device__ __forceinline__ double h2o2_chem_rate(const DevZm &Z, double time, double p, double lat, double t, double lwc,
+                                                 double rwc, bool cx_on, double cx, double low) {
+  const double M = fdiv(kAvo * 1e-6 * (p * 100), kRI * t);   // MOLEC_DENS
+  const double it = fdiv(1., t) - 1. / kTRef;                 // (1. / t - 1. / 298.15), the same in all four terms
+  const double k = 9.1e7 * libm_exp(-29700 / kRI * it);
+  const double H_SO2 = 1.3e-2 * libm_exp(2900 * it) * kRI * t;
+  const double K_1S = 1.23e-2 * libm_exp(2.01e3 * it);
+  const double H_h2o2 = 8.3e2 * libm_exp(7600 * it) * kRI * t;
+  const double cor = cx_on ? (cx > low ? kH2O2CorA * libm_pow(cx, kH2O2CorB) : 1) : 1;
+  const double h2o2 = fdiv(H_h2o2 * clim_zm(Z, time, lat, p) * M * cor * 1000., kAvo);
+  const double rho_air = fdiv(fdiv(p, kRI * t) * kMA, 10.);
+  const double CWC = fdiv((lwc + rwc) * rho_air, 1e3);
+  return k * K_1S * h2o2 * H_SO2 * CWC;
+}
+
 // nat_temperature, mptrac.c:8334-8355
 __device__ inline double nat_temperature(double p, double h2o, double hno3) {
   const double h2o_help = h2o > 0.1e-6 ? h2o : 0.1e-6;

@@ -2730,6 +2730,88 @@ __global__ __launch_bounds__(256, MPHIP_METEO_WAVES_PER_SIMD) void oh_chem_kerne
   }
 }
 
+// module_h2o2_chem: a launch of its own behind module_oh_chem and before the deposition modules, in the shape of
+// oh_chem_kernel.  Every particle with dt != 0: lwc, rwc and t at the particle from one stencil (the cloud quad and
+// the temperature pair of the packed records); outside clouds nothing happens, inside the loss.  `low`: the
+// threshold of the high-SO2 correction (h2o2_chem_rate).
+__global__ __launch_bounds__(256, MPHIP_METEO_WAVES_PER_SIMD) void h2o2_chem_kernel(const MeteoArgs G, double low) {
+  extern __shared__ double s_axes[];
+  const DevMet &M = G.met;
+  const DevAtm &a = G.atm;
+  const mphip_ctl_t &ctl = G.ctl;
+  const Axes A = load_axes(M, s_axes);
+  __syncthreads();
+  const int nb = G.nblocks_logical;
+  const int lb = G.xcd_map ? (int) (blockIdx.x % 8) * (nb / 8) + (int) (blockIdx.x / 8) : (int) blockIdx.x;
+  const long long first = (long long) lb * G.per_block;
+  long long last = first + G.per_block;
+  if (last > a.np)
+    last = a.np;
+  for (long long i = first + threadIdx.x; i < last; i += blockDim.x) {
+    const double dt = a.dt[i];
+    if (dt == 0)   // guard of PARTICLE_LOOP(..., check_dt = 1)
+      continue;
+    const double tm = a.time[i], p = a.p[i], lon = a.lon[i], lat = a.lat[i];
+    Stencil s;
+    stencil_3d(M, A, p, lon, lat, s);
+    const double wt = time_weight(M, tm);
+    CloudCorners cc;
+    load_cloud(M, s, cc);
+    const double lwc = cloud_time_3d(cc, s, wt, 0);
+    const double rwc = cloud_time_3d(cc, s, wt, 1);
+    if (!(lwc > 0 || rwc > 0))
+      continue;
+    const double t = temp_time_3d(M, s, wt);
+    const bool cx_on = ctl.qnt_Cx >= 0;
+    const double cx = cx_on ? a.q[ctl.qnt_Cx][i] : 0.0;
+    const double rate = h2o2_chem_rate(G.zm[MPHIP_ZM_H2O2], tm, p, lat, t, lwc, rwc, cx_on, cx, low);
+    apply_loss(ctl, a, i, libm_exp(-dt * rate), ctl.qnt_mloss_h2o2, rate);
+  }
+}
+
+// module_chem_grid: the tables of the chemistry grid (host-computed with the C library: press[nz] = P(z centre),
+// area[ny], the cell centres lon[nx] and lat[ny]) and the buffers of one pass.  `val` holds the mass per cell on entry
+// (cell sums, all-reduced) and the Cx value of every occupied cell on exit.
+struct ChemGridArgs {
+  const double *press, *area, *lon, *lat;
+  double dz, molmass, tt;
+  int nx, ny, nz, ngrid;
+  long long ntot;
+  double *val;
+  const int *cnt;
+};
+
+// module_chem_grid, per occupied cell (cnt > 0): the temperature at the cell centre at the step time (INTPOL_3D(t, 1)
+// at tt, press[iz], lon[ix], lat[iy]) and Cx = MA / molmass * mass / (1e9 RHO(press, t) area dz), once per cell
+// instead of once per particle.  Cell index as box_cell writes it: ens * ngrid + (ix * ny + iy) * nz + iz.
+__global__ __launch_bounds__(256) void chem_grid_table_kernel(const DevMet M, const ChemGridArgs C) {
+  extern __shared__ double s_axes[];
+  const Axes A = load_axes(M, s_axes);
+  __syncthreads();
+  for (long long c = blockIdx.x * (long long) blockDim.x + threadIdx.x; c < C.ntot;
+       c += (long long) gridDim.x * blockDim.x) {
+    if (C.cnt[c] == 0)
+      continue;
+    const int local = (int) (c % C.ngrid);
+    const int iz = local % C.nz, iy = (local / C.nz) % C.ny, ix = local / (C.nz * C.ny);
+    const double press = C.press[iz];
+    const double temp = temperature_at(M, A, C.tt, press, C.lon[ix], C.lat[iy]);
+    const double rho = fdiv(100. * press, kRA * temp);   // RHO
+    C.val[c] = fdiv(fdiv(kMA, C.molmass) * C.val[c], 1e9 * rho * C.area[iy] * C.dz);
+  }
+}
+
+// module_chem_grid, per particle: Cx from the table of its cell; particles outside the grid or the time window keep it
+__global__ __launch_bounds__(256) void chem_grid_gather_kernel(DevAtm a, const int *__restrict__ cell,
+                                                               const double *__restrict__ val, int qnt_Cx) {
+  for (long long i = blockIdx.x * (long long) blockDim.x + threadIdx.x; i < a.np;
+       i += (long long) gridDim.x * blockDim.x) {
+    const int c = cell[i];
+    if (c >= 0)
+      a.q[qnt_Cx][i] = val[c];
+  }
+}
+
 __global__ __launch_bounds__(256, MPHIP_METEO_WAVES_PER_SIMD) void meteo_kernel(const MeteoArgs G) {
   extern __shared__ double s_axes[];
   const DevMet &M = G.met;

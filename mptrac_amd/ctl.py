@@ -125,6 +125,20 @@ HIP_CTL_FIELDS = [
     ("oh_chem_reaction", C.c_int, 0),
     ("qnt_mloss_oh", C.c_int, -1),
     ("oh_chem", C.c_double * 4, (0.0,) * 4),
+    # module_h2o2_chem (H2O2_CHEM_REACTION, ctl->qnt_mloss_h2o2) and module_chem_grid (ctl->qnt_Cx, MOLMASS, CHEMGRID_*)
+    ("h2o2_chem_reaction", C.c_int, 0),
+    ("qnt_mloss_h2o2", C.c_int, -1),
+    ("qnt_Cx", C.c_int, -1),
+    ("chemgrid_nx", C.c_int, 360),
+    ("chemgrid_ny", C.c_int, 180),
+    ("chemgrid_nz", C.c_int, 1),
+    ("molmass", C.c_double, 0.0),
+    ("chemgrid_lon0", C.c_double, -180.0),
+    ("chemgrid_lon1", C.c_double, 180.0),
+    ("chemgrid_lat0", C.c_double, -90.0),
+    ("chemgrid_lat1", C.c_double, 90.0),
+    ("chemgrid_z0", C.c_double, -5.0),
+    ("chemgrid_z1", C.c_double, 85.0),
 ]
 HIP_ONLY_KEYS = frozenset(n for n, _, _ in HIP_CTL_FIELDS)
 
@@ -180,7 +194,7 @@ def ctl_from_quantities(names):
     table = {"m": "qnt_m", "vmr": "qnt_vmr", "rp": "qnt_rp", "rhop": "qnt_rhop", "ens": "qnt_ens",
              "loss_rate": "qnt_loss_rate", "mloss_decay": "qnt_mloss_decay",
              "mloss_wet": "qnt_mloss_wet", "mloss_dry": "qnt_mloss_dry", "zeta": "qnt_zeta", "eta": "qnt_eta",
-             "aoa": "qnt_aoa", "mloss_oh": "qnt_mloss_oh"}
+             "aoa": "qnt_aoa", "mloss_oh": "qnt_mloss_oh", "mloss_h2o2": "qnt_mloss_h2o2", "Cx": "qnt_Cx"}
     met = [-1] * len(METEO_QUANTITIES)
     tracer = [-1] * len(TRACERS)
     for i, n in enumerate(names):

@@ -23,7 +23,7 @@ MOD = {
     "convection": 1 << 5, "sedi": 1 << 6, "position2": 1 << 7, "loss_zero": 1 << 8, "decay": 1 << 9,
     "wet_depo": 1 << 10, "dry_depo": 1 << 11, "advect_init": 1 << 12, "diff_pbl": 1 << 13, "meteo": 1 << 14,
     "isosurf": 1 << 15, "sort": 1 << 16, "mixing": 1 << 17, "bound_cond": 1 << 18, "bound_cond2": 1 << 19,
-    "isosurf_init": 1 << 20, "oh_chem": 1 << 21,
+    "isosurf_init": 1 << 20, "oh_chem": 1 << 21, "chem_grid": 1 << 22, "h2o2_chem": 1 << 23,
 }
 
 MphipCtl = make_ctl_struct("MphipCtl", HIP_CTL_FIELDS)

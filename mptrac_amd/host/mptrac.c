@@ -163,13 +163,15 @@ static const struct {
   { "tsts", "STS existence temperature", "K" }, { "tnat", "NAT existence temperature", "K" },
   { "Cccl4", "CCl4 (CFC-10) volume mixing ratio", "ppv" }, { "Cccl3f", "CCl3F (CFC-11) volume mixing ratio", "ppv" },
   { "Cccl2f2", "CCl2F2 (CFC-12) volume mixing ratio", "ppv" }, { "Cn2o", "N2O volume mixing ratio", "ppv" },
-  { "Csf6", "SF6 volume mixing ratio", "ppv" },
+  { "Csf6", "SF6 volume mixing ratio", "ppv" }, { "Cx", "Trace species x volume mixing ratio", "ppv" },
 };
 
 static const char *unsupported_qnt[] = {
   /* quantities only the chemistry, radioactive-decay and domain-decomposition code of the reference fills or
-   * mixes (SET_QNT table, mptrac.c:6905-6969): they would be carried along unchanged here */
-  "mloss_h2o2", "mloss_kpp", "Cx", "Ch2o", "Co3", "Cco", "Coh", "Ch", "Cho2", "Ch2o2", "Co1d", "Co3p",
+   * mixes (SET_QNT table, mptrac.c:6905-6969): they would be carried along unchanged here.  Cx (module_chem_grid) is
+   * accepted with the OH chemistry and refused without it below; mloss_h2o2 stays here because this host layer
+   * refuses H2O2_CHEM_REACTION, so module_h2o2_chem never runs to fill it */
+  "mloss_h2o2", "mloss_kpp", "Ch2o", "Co3", "Cco", "Coh", "Ch", "Cho2", "Ch2o2", "Co1d", "Co3p",
   "Arn222", "Apb210", "Abe7", "Acs137", "Ai131", "Axe133",
   "current_subdomain", "target_subdomain", NULL
 };
@@ -279,6 +281,15 @@ static const char *unsupported_qnt[] = {
   D(grid_lat1, "GRID_LAT1", "90") \
   I(grid_ny, "GRID_NY", "180") \
   I(grid_type, "GRID_TYPE", "0") \
+  D(chemgrid_z0, "CHEMGRID_Z0", "-5") \
+  D(chemgrid_z1, "CHEMGRID_Z1", "85") \
+  I(chemgrid_nz, "CHEMGRID_NZ", "1") \
+  D(chemgrid_lon0, "CHEMGRID_LON0", "-180") \
+  D(chemgrid_lon1, "CHEMGRID_LON1", "180") \
+  I(chemgrid_nx, "CHEMGRID_NX", "360") \
+  D(chemgrid_lat0, "CHEMGRID_LAT0", "-90") \
+  D(chemgrid_lat1, "CHEMGRID_LAT1", "90") \
+  I(chemgrid_ny, "CHEMGRID_NY", "180") \
   I(obs_type, "OBS_TYPE", "0") \
   S(csi_basename, "CSI_BASENAME", "-") \
   S(csi_kernel, "CSI_KERNEL", "-") \
@@ -336,7 +347,7 @@ void mptrac_read_ctl(const char *filename, int argc, char *argv[], ctl_t *ctl) {
   /* quantities, mptrac.c:6737-6971 */
   ctl->qnt_m = ctl->qnt_vmr = ctl->qnt_rp = ctl->qnt_rhop = ctl->qnt_ens = ctl->qnt_loss_rate = -1;
   ctl->qnt_mloss_decay = ctl->qnt_mloss_wet = ctl->qnt_mloss_dry = ctl->qnt_mloss_oh = ctl->qnt_zeta = ctl->qnt_eta = -1;
-  ctl->qnt_aoa = ctl->qnt_stat = -1;
+  ctl->qnt_aoa = ctl->qnt_stat = ctl->qnt_Cx = ctl->qnt_mloss_h2o2 = -1;
   ctl->qnt_Cccl4 = ctl->qnt_Cccl3f = ctl->qnt_Cccl2f2 = ctl->qnt_Cn2o = ctl->qnt_Csf6 = -1;
 #define X(n, u) ctl->qnt_##n = -1;
   MPTRAC_METEO_QNT(X)
@@ -375,6 +386,7 @@ void mptrac_read_ctl(const char *filename, int argc, char *argv[], ctl_t *ctl) {
     else if (!strcasecmp(n, "mloss_wet")) ctl->qnt_mloss_wet = iq;
     else if (!strcasecmp(n, "mloss_dry")) ctl->qnt_mloss_dry = iq;
     else if (!strcasecmp(n, "mloss_oh")) ctl->qnt_mloss_oh = iq;
+    else if (!strcasecmp(n, "Cx")) ctl->qnt_Cx = iq;
     else if (!strcasecmp(n, "zeta")) ctl->qnt_zeta = iq;
     else if (!strcasecmp(n, "eta")) ctl->qnt_eta = iq;
     else if (!strcasecmp(n, "aoa")) ctl->qnt_aoa = iq;
@@ -468,6 +480,21 @@ void mptrac_read_ctl(const char *filename, int argc, char *argv[], ctl_t *ctl) {
       ERRMSG("Module needs quantity mass or volume mixing ratio!");
     LOG(1, "OH chemistry: reaction %d, OH_CHEM = %g, %g, %g, %g", ctl->oh_chem_reaction, ctl->oh_chem[0],
         ctl->oh_chem[1], ctl->oh_chem[2], ctl->oh_chem[3]);
+  }
+  /* module_h2o2_chem: H2O2_CHEM_REACTION is refused with the other unimplemented switches below */
+  ctl->h2o2_chem_reaction = 0;
+  /* module_chem_grid: runs with the OH or the H2O2 chemistry and needs m beside Cx; without a chemistry nothing
+   * fills Cx */
+  if (ctl->qnt_Cx >= 0) {
+    if (ctl->oh_chem_reaction == 0 && ctl->h2o2_chem_reaction == 0)
+      ERRMSG("Quantity Cx is filled by module_chem_grid, which runs only with the OH chemistry (OH_CHEM_REACTION); "
+             "without it this build does not provide Cx!");
+    if (ctl->qnt_m < 0)
+      ERRMSG("Quantity Cx needs quantity m: module_chem_grid computes Cx from the mass per grid cell!");
+    REQUIRE(ctl->molmass > 0, "Molar mass is not defined!");
+    REQUIRE(ctl->chemgrid_nx >= 1 && ctl->chemgrid_ny >= 1 && ctl->chemgrid_nz >= 1
+            && ctl->chemgrid_lon0 < ctl->chemgrid_lon1 && ctl->chemgrid_lat0 < ctl->chemgrid_lat1
+            && ctl->chemgrid_z0 < ctl->chemgrid_z1, "Invalid chemistry grid!");
   }
 
   /* wet / dry deposition, decay, mixing (mptrac.c:7425-7543): the species sets the defaults of the in-cloud
@@ -786,7 +813,7 @@ void mptrac_read_clim(const ctl_t *ctl, clim_t *clim) {
   } zonal[] = {
     { ctl->qnt_hno3 >= 0 || ctl->qnt_tnat >= 0, ctl->clim_hno3_filename, "HNO3", &clim->hno3 },
     { ctl->qnt_oh >= 0 || ctl->oh_chem_reaction != 0, ctl->clim_oh_filename, "OH", &clim->oh },
-    { ctl->qnt_h2o2 >= 0, ctl->clim_h2o2_filename, "H2O2", &clim->h2o2 },
+    { ctl->qnt_h2o2 >= 0 || ctl->h2o2_chem_reaction != 0, ctl->clim_h2o2_filename, "H2O2", &clim->h2o2 },
     { ctl->qnt_ho2 >= 0, ctl->clim_ho2_filename, "HO2", &clim->ho2 },
     { ctl->qnt_o1d >= 0, ctl->clim_o1d_filename, "O1D", &clim->o1d },
   };
@@ -799,6 +826,9 @@ void mptrac_read_clim(const ctl_t *ctl, clim_t *clim) {
   if (ctl->oh_chem_reaction != 0 && clim->oh.ntime <= 0)
     ERRMSG("OH chemistry (OH_CHEM_REACTION %d) needs the OH climatology, which cannot be read from %s!",
            ctl->oh_chem_reaction, ctl->clim_oh_filename);
+  if (ctl->h2o2_chem_reaction != 0 && clim->h2o2.ntime <= 0)
+    ERRMSG("H2O2 chemistry (H2O2_CHEM_REACTION %d) needs the H2O2 climatology, which cannot be read from %s!",
+           ctl->h2o2_chem_reaction, ctl->clim_h2o2_filename);
   /* surface time series of the trace gases that are carried (module_bound_cond, mptrac.c:3857-3875) */
   const struct {
     int qnt;
@@ -1842,6 +1872,9 @@ static void to_device_ctl(const ctl_t *c, mphip_ctl_t *d) {
   TAKE(grid_z0); TAKE(grid_z1); TAKE(grid_lon0); TAKE(grid_lon1); TAKE(grid_lat0); TAKE(grid_lat1);
   TAKE(grid_nx); TAKE(grid_ny); TAKE(grid_nz);
   TAKE(oh_chem_reaction); TAKE(qnt_mloss_oh);
+  TAKE(h2o2_chem_reaction); TAKE(qnt_mloss_h2o2); TAKE(qnt_Cx); TAKE(molmass);
+  TAKE(chemgrid_nx); TAKE(chemgrid_ny); TAKE(chemgrid_nz); TAKE(chemgrid_lon0); TAKE(chemgrid_lon1);
+  TAKE(chemgrid_lat0); TAKE(chemgrid_lat1); TAKE(chemgrid_z0); TAKE(chemgrid_z1);
 #undef TAKE
   for (int i = 0; i < 4; i++)
     d->oh_chem[i] = c->oh_chem[i];

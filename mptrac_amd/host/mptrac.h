@@ -133,6 +133,7 @@ typedef struct {
   char qnt_name[NQ][LEN], qnt_longname[NQ][LEN], qnt_unit[NQ][LEN], qnt_format[NQ][LEN];
   int qnt_m, qnt_vmr, qnt_rp, qnt_rhop, qnt_ens, qnt_stat, qnt_loss_rate;
   int qnt_mloss_decay, qnt_mloss_wet, qnt_mloss_dry, qnt_mloss_oh, qnt_zeta, qnt_eta, qnt_aoa;
+  int qnt_Cx, qnt_mloss_h2o2;   /* module_chem_grid's volume mixing ratio; module_h2o2_chem's mass loss (always -1 here) */
   int qnt_Cccl4, qnt_Cccl3f, qnt_Cccl2f2, qnt_Cn2o, qnt_Csf6;   /* trace gases: boundary condition from a time series, mixing */
   /* module_meteo outputs: qnt_ps, qnt_ts, ..., qnt_tice (mptrac.h:2518-2740) */
 #define X(n, u) int qnt_##n;
@@ -149,6 +150,11 @@ typedef struct {
   /* module_oh_chem: reaction type (0 = off, 1 ... 3) and rate constants (OH_CHEM_REACTION, OH_CHEM[0..3]) */
   int oh_chem_reaction;
   double oh_chem[4];
+  /* module_h2o2_chem (H2O2_CHEM_REACTION: refused by this host layer's reader, so always 0) and module_chem_grid
+   * (CHEMGRID_*: the grid Cx is computed on; MOLMASS) */
+  int h2o2_chem_reaction;
+  double chemgrid_z0, chemgrid_z1, chemgrid_lon0, chemgrid_lon1, chemgrid_lat0, chemgrid_lat1;
+  int chemgrid_nz, chemgrid_nx, chemgrid_ny;
   /* surface time series of the trace gases (mptrac.c:7471-7480) */
   char clim_ccl4_timeseries[LEN], clim_ccl3f_timeseries[LEN], clim_ccl2f2_timeseries[LEN], clim_n2o_timeseries[LEN],
     clim_sf6_timeseries[LEN];
