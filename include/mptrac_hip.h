@@ -98,7 +98,8 @@ enum {
   MPHIP_MOD_ISOSURF_INIT = 1 << 20, /* module_isosurf_init mptrac.c:4886, modes 1-3 (not guarded by dt) */
   MPHIP_MOD_OH_CHEM    = 1 << 21,  /* module_oh_chem     mptrac.c:5351-5434 (between module_mixing and module_wet_depo) */
   MPHIP_MOD_CHEM_GRID  = 1 << 22,  /* module_chem_grid   (own kernels; between module_mixing and module_oh_chem) */
-  MPHIP_MOD_H2O2_CHEM  = 1 << 23   /* module_h2o2_chem   (own kernel; between module_oh_chem and module_wet_depo) */
+  MPHIP_MOD_H2O2_CHEM  = 1 << 23,  /* module_h2o2_chem   (own kernel; between module_oh_chem and module_wet_depo) */
+  MPHIP_MOD_TRACER_CHEM = 1 << 24  /* module_tracer_chem (own kernel; between module_h2o2_chem and module_wet_depo) */
 };
 
 /* Hot-path subset of ctl_t (mptrac.h:2494-3553); same field names, meaning
@@ -173,6 +174,11 @@ typedef struct {
   int chemgrid_nx, chemgrid_ny, chemgrid_nz;
   double molmass;
   double chemgrid_lon0, chemgrid_lon1, chemgrid_lat0, chemgrid_lat1, chemgrid_z0, chemgrid_z1;
+  /* module_tracer_chem (TRACER_CHEM: 0 off, else on): loss of the quantities Cccl4, Cccl3f, Cccl2f2 and Cn2o of
+   * qnt_tracer by photolysis (mphip_update_clim_photo) and reaction with O(1D) (the O1D zonal mean); Csf6 is kept.
+   * Appended: every earlier member keeps its offset. */
+  int tracer_chem;
+  int pad5;
 } mphip_ctl_t;
 
 /* View of one met_t snapshot (mptrac.h:3844-4014).  The arrays stay where the
@@ -230,6 +236,14 @@ int mphip_update_clim_zm(mphip_ctx *ctx, int which, int ntime, int np, int nlat,
  * particle's time (constant beyond the ends of the series), ntime = 0 removes it -- the reference's
  * CLIM_*_TIMESERIES = "-". */
 int mphip_update_clim_ts(mphip_ctx *ctx, int which, int ntime, const double *time, const double *vmr);
+/* ... and its photolysis rates (clim_photo_t, the tables module_tracer_chem reads through clim_photo): descending
+ * pressures p[np] [hPa], ascending solar zenith angles sza[nsza] [rad] and total ozone columns o3c[no3c] [DU], and per
+ * trace gas (`rate` indexed by MPHIP_TR_*) the rates rate[k][np][nsza][no3c] [1/s] (the reference's index order,
+ * compact); NULL: that table is absent, rate[MPHIP_TR_SF6] must be NULL.  Every axis needs two nodes or more.
+ * np = 0 removes the tables.  module_tracer_chem needs the table of every present CFC / N2O quantity and the O1D
+ * zonal mean (mphip_update_clim_zm). */
+int mphip_update_clim_photo(mphip_ctx *ctx, int np, int nsza, int no3c, const double *p, const double *sza,
+                            const double *o3c, const double *const rate[MPHIP_NTR]);
 /* mptrac_update_device(..., met0, met1, ...), mptrac.c:8034-8048; slot 0 = met0,
  * slot 1 = met1. */
 int mphip_update_met(mphip_ctx *ctx, int slot, const mphip_met_t *met);
@@ -301,7 +315,8 @@ int mphip_run_timestep(mphip_ctx *ctx, double t);
  * launches on pressure-level winds.  Single steps throughout: the first step (t == T_START), ADVECT 0, ISOSURF or
  * TURB_PBL_SCHEME 1 with winds from the model levels, the option "generic_kernel", module_oh_chem (OH_CHEM_REACTION
  * != 0: a kernel of its own between module_mixing and module_wet_depo), module_chem_grid and module_h2o2_chem (with
- * either chemistry on: kernels of their own in the same place, in the order chem_grid, oh_chem, h2o2_chem). */
+ * either chemistry on: kernels of their own in the same place, in the order chem_grid, oh_chem, h2o2_chem),
+ * module_tracer_chem (TRACER_CHEM != 0: a kernel of its own behind them and before module_wet_depo). */
 int mphip_run_timesteps(mphip_ctx *ctx, double t_first, int nsteps);
 /* One reference module_* on its own (same state hand-over through the device
  * copy of cache->dt); `modules` is one MPHIP_MOD_* bit or an OR of the

@@ -61,7 +61,7 @@ static int hip_ts_on[MPHIP_NTR] = { 1, 1, 1, 1, 1 };   /* CLIM_*_TIMESERIES is n
   X(bound_zetas) X(oh_chem_beta) X(met_utm_ref_lon) X(oh_chem_reaction) X(qnt_mloss_oh)                  \
   X(h2o2_chem_reaction) X(qnt_mloss_h2o2) X(qnt_Cx) X(molmass) X(chemgrid_nx) X(chemgrid_ny)            \
   X(chemgrid_nz) X(chemgrid_lon0) X(chemgrid_lon1) X(chemgrid_lat0) X(chemgrid_lat1) X(chemgrid_z0)      \
-  X(chemgrid_z1)
+  X(chemgrid_z1) X(tracer_chem)
 
 /* module_meteo outputs: mphip_ctl_t::qnt_met[MPHIP_MQ_<X>] = ctl_t::qnt_<x> */
 #define HIP_CTL_METEO_QNT(X)                                                                             \
@@ -96,9 +96,11 @@ static void hip_ctl(const ctl_t *c, mphip_ctl_t *d) {
     d->oh_chem[k] = c->oh_chem[k];
   /* module_chem_grid and module_h2o2_chem (the H2O2 table: clim->h2o2) run inside mphip_run_timestep, where the
    * reference calls them: chem_grid behind module_mixing, oh_chem, h2o2_chem before module_wet_depo */
+  /* module_tracer_chem (the photolysis rates: clim->photo, uploaded below; O(1D): clim->o1d) runs behind
+   * module_h2o2_chem and before module_wet_depo */
   /* what the device does not implement must not run silently on stale host data */
-  if (c->kpp_chem || c->tracer_chem || c->radio_decay)
-    ERRMSG("MPTRAC_HIP: KPP, tracer chemistry and radioactive decay are not implemented on the device!");
+  if (c->kpp_chem || c->radio_decay)
+    ERRMSG("MPTRAC_HIP: KPP and radioactive decay are not implemented on the device!");
   if (c->qnt_hno3 >= 0 || c->qnt_oh >= 0 || c->qnt_h2o2 >= 0 || c->qnt_ho2 >= 0 || c->qnt_o1d >= 0 || c->qnt_tnat >= 0
       || c->qnt_tsts >= 0)
     ERRMSG("MPTRAC_HIP: the climatology-based quantities of module_meteo are not implemented on the device!");
@@ -206,6 +208,28 @@ void mptrac_hip_update_device(const ctl_t *ctl, const cache_t *cache, const clim
       HIPCALL(mphip_update_clim_zm(hip_ctx, k, zm[k]->ntime, zm[k]->np, zm[k]->nlat, zm[k]->time, zm[k]->p,
                                    zm[k]->lat, v));
       free(v);
+    }
+    /* the photolysis rates of module_tracer_chem: clim_photo_t holds rate[CP][CSZA][CO3], the back end takes compact
+     * tables (SF6 has none) */
+    {
+      const clim_photo_t *ph = &clim->photo;
+      double *r[MPHIP_NTR] = { NULL, NULL, NULL, NULL, NULL };
+      if (ph->np > 0) {
+        const size_t n = (size_t) ph->np * (size_t) ph->nsza * (size_t) ph->no3c;
+        const double (*tab[4])[CSZA][CO3] = { ph->ccl4, ph->ccl3f, ph->ccl2f2, ph->n2o };
+        for (int k = 0; k < 4; k++) {
+          size_t j = 0;
+          ALLOC(r[k], double, n);
+          for (int ip = 0; ip < ph->np; ip++)
+            for (int is = 0; is < ph->nsza; is++)
+              for (int io = 0; io < ph->no3c; io++)
+                r[k][j++] = tab[k][ip][is][io];
+        }
+      }
+      HIPCALL(mphip_update_clim_photo(hip_ctx, ph->np, ph->nsza, ph->no3c, ph->p, ph->sza, ph->o3c,
+                                      (const double *const *) r));
+      for (int k = 0; k < MPHIP_NTR; k++)
+        free(r[k]);
     }
     /* the surface time series of module_bound_cond's trace gases ("-" as file name: no boundary condition) */
     const clim_ts_t *ts[MPHIP_NTR] = { &clim->ccl4, &clim->ccl3f, &clim->ccl2f2, &clim->n2o, &clim->sf6 };

@@ -219,6 +219,11 @@ struct mphip_ctx {
   double *d_chemgrid = nullptr;
   bool chemgrid_ok = false;
   double h2o2_low = 0;                // module_h2o2_chem: pow(1 / a, 1 / b) of the host's C library
+  // module_tracer_chem: the photolysis rates, [p | sza | o3c | (pad) | PhotoRec rec[np][nsza][no3c]]
+  // (mphip_update_clim_photo); photo_have[k]: the table of trace gas k (MPHIP_TR_CCL4 ... MPHIP_TR_N2O) was given
+  double *d_photo = nullptr;
+  DevPhoto photo = {};
+  bool photo_have[4] = {};
   // exchange of the occupied levels only (exchange_occupied_levels): per-level occupancy, the dense band, what was found
   // option "mix_exchange_levels" (default 0): measured with a one-rank communicator, the band costs 0.14 ms per step (the
   // host reads the occupancy: the one synchronisation in the step path; pack / unpack) against a MODELLED saving of
@@ -1103,6 +1108,54 @@ int launch_oh(mphip_ctx *ctx) {
   G.per_block = per_block;
   G.xcd_map = ctx->xcd_map;
   hipLaunchKernelGGL(oh_chem_kernel, dim3(nb), dim3(256), axes_lds_bytes(ctx), ctx->stream, G);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// module_tracer_chem: its own kernel behind module_h2o2_chem, on the dt the step's launch stored (tracer_chem_kernel).
+// Without a present CFC or N2O quantity it does nothing (Csf6 has no reaction).
+int launch_tracer_chem(mphip_ctx *ctx) {
+  const mphip_ctl_t &c = ctx->ctl;
+  static const char *const names[4] = { "Cccl4", "Cccl3f", "Cccl2f2", "Cn2o" };
+  bool any = false;
+  for (int k = 0; k < 4; k++)
+    any = any || c.qnt_tracer[k] >= 0;
+  if (!any)
+    return 0;
+  if (c.met_coord_type != 0)
+    return fail(ctx, "module_tracer_chem: not implemented for MET_COORD_TYPE != 0 (the photolysis and O(1D) tables "
+                     "are on latitude and longitude)");
+  if (!ctx->d_zm[MPHIP_ZM_O1D])
+    return fail(ctx, "module_tracer_chem: the O1D climatology was not uploaded");
+  for (int k = 0; k < 4; k++)
+    if (c.qnt_tracer[k] >= 0 && !ctx->photo_have[k])
+      return fail(ctx, std::string("module_tracer_chem: the photolysis rates of quantity ") + names[k]
+                         + " were not uploaded");
+  if (ctx->np == 0)
+    return 0;
+  if (ensure_packed(ctx))
+    return 1;
+  const MetSlot &s0 = ctx->slot[0 ^ ctx->flip], &s1 = ctx->slot[1 ^ ctx->flip];
+  bool have = s0.valid && s1.valid && s0.has3[MPHIP_T] && s1.has3[MPHIP_T];
+  if (!have)
+    return fail(ctx, "module_tracer_chem: meteo field t was not uploaded");
+  have = s0.has2[MPHIP_O3C] && s1.has2[MPHIP_O3C];
+  if (!have)
+    return fail(ctx, "module_tracer_chem: meteo field o3c was not uploaded");
+  MeteoArgs G;
+  memset(&G, 0, sizeof(G));
+  G.ctl = c;
+  G.met = dev_met(ctx);
+  G.atm = dev_atm(ctx);
+  G.zm[MPHIP_ZM_O1D] = ctx->zm[MPHIP_ZM_O1D];
+  long long per_block = (ctx->np + ctx->step_blocks - 1) / ctx->step_blocks;
+  per_block = std::max<long long>(256, (per_block + 255) / 256 * 256);
+  int nb = (int) ((ctx->np + per_block - 1) / per_block);
+  nb = (nb + 7) & ~7;
+  G.nblocks_logical = nb;
+  G.per_block = per_block;
+  G.xcd_map = ctx->xcd_map;
+  hipLaunchKernelGGL(tracer_chem_kernel, dim3(nb), dim3(256), axes_lds_bytes(ctx), ctx->stream, G, ctx->photo);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -2193,11 +2246,20 @@ int do_chem_grid(mphip_ctx *ctx, double t) {
   return 0;
 }
 
+// chemistry in the step: the modules of chem_on, or module_tracer_chem (TRACER_CHEM; it alone does not run
+// module_chem_grid)
+bool step_chem_on(const mphip_ctl_t &c) {
+  return chem_on(c) || c.tracer_chem != 0;
+}
+
 // the chemistry of a step, in the reference's order: module_chem_grid (with either chemistry; it does nothing without
-// m or Cx), module_oh_chem, module_h2o2_chem
+// m or Cx), module_oh_chem, module_h2o2_chem, module_tracer_chem
 int launch_chem(mphip_ctx *ctx, double t) {
   const mphip_ctl_t &c = ctx->ctl;
-  return do_chem_grid(ctx, t) || (c.oh_chem_reaction != 0 && launch_oh(ctx)) || (c.h2o2_chem_reaction != 0 && launch_h2o2(ctx));
+  return (chem_on(c)
+          && (do_chem_grid(ctx, t) || (c.oh_chem_reaction != 0 && launch_oh(ctx))
+              || (c.h2o2_chem_reaction != 0 && launch_h2o2(ctx))))
+    || (c.tracer_chem != 0 && launch_tracer_chem(ctx));
 }
 
 void unpin_all(mphip_ctx *ctx, std::vector<std::pair<uintptr_t, uintptr_t>> &list) {
@@ -2423,6 +2485,7 @@ void mphip_destroy(mphip_ctx *ctx) {
   dev_free(ctx->d_cell);
   dev_free(ctx->d_sums);
   dev_free(ctx->d_chemgrid);
+  dev_free(ctx->d_photo);
   dev_free(ctx->d_cnt);
   dev_free(ctx->d_depo_busy);
   dev_free(ctx->d_occ);
@@ -2575,6 +2638,65 @@ int mphip_update_clim_zm(mphip_ctx *ctx, int which, int ntime, int np, int nlat,
   z.ntime = ntime;
   z.np = np;
   z.nlat = nlat;
+  return 0;
+}
+
+int mphip_update_clim_photo(mphip_ctx *ctx, int np, int nsza, int no3c, const double *p, const double *sza,
+                            const double *o3c, const double *const rate[MPHIP_NTR]) {
+  if (!ctx)
+    return 1;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (flush_meteo(ctx))
+    return 1;
+  HIPCHK(hipStreamSynchronize(ctx->stream));   // (kernels in flight may read the old tables)
+  dev_free(ctx->d_photo);
+  ctx->d_photo = nullptr;
+  memset(&ctx->photo, 0, sizeof(DevPhoto));
+  for (bool &h : ctx->photo_have)
+    h = false;
+  if (np == 0)
+    return 0;
+  if (!p || !sza || !o3c || !rate)
+    return fail(ctx, "null argument");
+  if (rate[MPHIP_TR_SF6])
+    return fail(ctx, "photolysis rates: SF6 has no table (rate[MPHIP_TR_SF6] must be NULL)");
+  if (np < 2 || nsza < 2 || no3c < 2 || np > 4096 || nsza > 4096 || no3c > 4096
+      || (size_t) np * (size_t) nsza * (size_t) no3c > ((size_t) 1 << 26))
+    return fail(ctx, "photolysis rates: dimensions out of range");
+  for (int i = 1; i < np; i++)        // (messages of the reference's reader)
+    if (!(p[i] < p[i - 1]))
+      return fail(ctx, "Pressure data are not descending!");
+  for (int i = 1; i < nsza; i++)
+    if (!(sza[i] > sza[i - 1]))
+      return fail(ctx, "Solar zenith angle data are not ascending!");
+  for (int i = 1; i < no3c; i++)
+    if (!(o3c[i] > o3c[i - 1]))
+      return fail(ctx, "Total column ozone data are not ascending!");
+  // [p | sza | o3c], padded to whole records, then the interleaved rates
+  const size_t nrec = (size_t) np * nsza * no3c, naxes = ((size_t) np + nsza + no3c + 3) / 4 * 4;
+  std::vector<double> h(naxes + 4 * nrec, 0.0);
+  std::copy(p, p + np, h.begin());
+  std::copy(sza, sza + nsza, h.begin() + np);
+  std::copy(o3c, o3c + no3c, h.begin() + np + nsza);
+  for (int k = 0; k < 4; k++)
+    if (rate[k])
+      for (size_t j = 0; j < nrec; j++)
+        h[naxes + 4 * j + k] = rate[k][j];
+  double *d = nullptr;
+  if (dev_alloc(ctx, &d, h.size()))
+    return 1;
+  ctx->d_photo = d;
+  HIPCHK(hipMemcpy(d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+  DevPhoto &ph = ctx->photo;
+  ph.p = d;
+  ph.sza = d + np;
+  ph.o3c = d + np + nsza;
+  ph.rec = (const PhotoRec *) (d + naxes);
+  ph.np = np;
+  ph.nsza = nsza;
+  ph.no3c = no3c;
+  for (int k = 0; k < 4; k++)
+    ctx->photo_have[k] = rate[k] != nullptr;
   return 0;
 }
 
@@ -3182,8 +3304,9 @@ int mphip_run_timestep(mphip_ctx *ctx, double t) {
     && fmod(t_next, c.sort_dt) == 0 && c.direction * (t_next - c.t_stop) <= 0;
   // module_oh_chem (own kernel, launch_oh) sits between module_mixing and module_wet_depo: with it the step's launch
   // stops before the deposition modules, which follow in a launch of their own
-  // module_chem_grid and module_h2o2_chem join it there (chem_grid, oh_chem, h2o2_chem: launch_chem)
-  const bool oh = chem_on(c);
+  // module_chem_grid, module_h2o2_chem and module_tracer_chem join it there (chem_grid, oh_chem, h2o2_chem,
+  // tracer_chem: launch_chem)
+  const bool oh = step_chem_on(c);
   if (!mixing_now && !oh) {
     if (launch_step(ctx, mask | tail, t, ctr_turb, ctr_meso, ctr_conv, ctr_pbl))
       return 1;
@@ -3300,7 +3423,8 @@ int mphip_run_timesteps(mphip_ctx *ctx, double t_first, int nsteps) {
       && c.advect > 0   // (every integrator has its multi-step instantiations; without module_advect: single steps)
       && !ctx->fused_perm
       && !ctx->force_generic
-      && !chem_on(c);   // (module_chem_grid, module_oh_chem, module_h2o2_chem are launches of their own: single steps)
+      && !step_chem_on(c);   // (module_chem_grid, module_oh_chem, module_h2o2_chem, module_tracer_chem are launches of
+                             // their own: single steps)
     if (quiet) {
       batch = nsteps - done;
       if (ctx->locality_interval > 0)
@@ -3439,9 +3563,11 @@ int mphip_module(mphip_ctx *ctx, unsigned modules, double t) {
     return do_chem_grid(ctx, t);
   if (modules == MPHIP_MOD_H2O2_CHEM)
     return launch_h2o2(ctx);
+  if (modules == MPHIP_MOD_TRACER_CHEM)
+    return launch_tracer_chem(ctx);
   if (modules & ~kParticleBits)
     return fail(ctx, "module_sort / module_mixing / module_meteo / module_chem_grid / module_oh_chem / module_h2o2_chem "
-                     "must be called on their own");
+                     "/ module_tracer_chem must be called on their own");
   const uint64_t n = (uint64_t) ctx->np_total;
   uint64_t ctr_turb = 0, ctr_meso = 0, ctr_conv = 0, ctr_pbl = 0;
   if (modules & MPHIP_MOD_DIFF_TURB) {

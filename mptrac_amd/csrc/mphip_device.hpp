@@ -1253,6 +1253,74 @@ __device__ __forceinline__ double h2o2_chem_rate(const DevZm &Z, double time, do
   return k * K_1S * h2o2 * H_SO2 * CWC;
 }
 
+// module_tracer_chem: the photolysis rates of clim_photo_t, packed on upload (mphip_update_clim_photo) as records
+// rec[ip][isza][io3] of the four reacting trace gases (MPHIP_TR_CCL4 ... MPHIP_TR_N2O; zeros for an absent table): a
+// corner of the interpolation is one 32-byte load for all four.  Axes: descending pressures [hPa], ascending solar
+// zenith angles [rad] and total ozone columns [DU].
+struct alignas(32) PhotoRec {
+  double r[4];
+};
+
+struct DevPhoto {
+  const double *p, *sza, *o3c;
+  const PhotoRec *rec;
+  int np, nsza, no3c, pad;
+};
+
+// clim_photo (the reference's LIN in pressure at the four (sza, o3c) corners, then in o3c, then in sza; MAX(aux, 0)) for
+// the four trace gases at once
+__device__ __forceinline__ void clim_photo4(const DevPhoto &P, double p, double sza, double o3c, double out[4]) {
+  double p_help = p;
+  if (p < P.p[P.np - 1])
+    p_help = P.p[P.np - 1];
+  else if (p > P.p[0])
+    p_help = P.p[0];
+  double sza_help = sza;
+  if (sza < P.sza[0])
+    sza_help = P.sza[0];
+  else if (sza > P.sza[P.nsza - 1])
+    sza_help = P.sza[P.nsza - 1];
+  double o3c_help = o3c;
+  if (o3c < P.o3c[0])
+    o3c_help = P.o3c[0];
+  else if (o3c > P.o3c[P.no3c - 1])
+    o3c_help = P.o3c[P.no3c - 1];
+  const int ip = locate_irr(P.p, P.np, p_help, 0);
+  const int isza = locate_reg(P.sza, P.nsza, sza_help);
+  const int io3 = locate_reg(P.o3c, P.no3c, o3c_help);
+  const double p0 = P.p[ip], p1 = P.p[ip + 1];
+  const double s0 = P.sza[isza], s1 = P.sza[isza + 1];
+  const double c0 = P.o3c[io3], c1 = P.o3c[io3 + 1];
+  // one interval per axis: the divisor of every LIN along it is the same (div_const: one reciprocal per particle)
+  const double dp = p1 - p0, ds = s1 - s0, dc = c1 - c0;
+  const double inv_dp = 1. / dp, inv_ds = 1. / ds, inv_dc = 1. / dc;
+  const size_t row = (size_t) P.nsza * P.no3c;
+  const PhotoRec *r0 = P.rec + (size_t) ip * row + (size_t) isza * P.no3c + io3;   // (ip, isza, io3)
+  const PhotoRec *r1 = r0 + row;                                                     // (ip + 1, isza, io3)
+  const PhotoRec a00 = r0[0], a01 = r0[1], a10 = r0[P.no3c], a11 = r0[P.no3c + 1];
+  const PhotoRec b00 = r1[0], b01 = r1[1], b10 = r1[P.no3c], b11 = r1[P.no3c + 1];
+  const double xp = p_help - p0, xc = o3c_help - c0, xs = sza_help - s0;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const double aux00 = a00.r[k] + div_const(b00.r[k] - a00.r[k], dp, inv_dp) * xp;
+    const double aux01 = a01.r[k] + div_const(b01.r[k] - a01.r[k], dp, inv_dp) * xp;
+    const double aux10 = a10.r[k] + div_const(b10.r[k] - a10.r[k], dp, inv_dp) * xp;
+    const double aux11 = a11.r[k] + div_const(b11.r[k] - a11.r[k], dp, inv_dp) * xp;
+    const double aux0 = aux00 + div_const(aux01 - aux00, dc, inv_dc) * xc;
+    const double aux1 = aux10 + div_const(aux11 - aux10, dc, inv_dc) * xc;
+    const double aux = aux0 + div_const(aux1 - aux0, ds, inv_ds) * xs;
+    out[k] = aux > 0 ? aux : 0;
+  }
+}
+
+// module_tracer_chem: ARRHENIUS(a, b, t) = a exp(-b / t) of the O(1D) reactions of CFC-10, CFC-11, CFC-12 and N2O
+// (k: MPHIP_TR_* order)
+__device__ __forceinline__ double tracer_o1d_arrhenius(int k, double t) {
+  const double a = k == 0 ? 3.30e-10 : k == 1 ? 2.30e-10 : k == 2 ? 1.40e-10 : 1.19e-10;
+  const double neg_b = k == 0 ? 0. : k == 1 ? 0. : k == 2 ? 25. : 20.;   // -b
+  return a * libm_exp(fdiv(neg_b, t));
+}
+
 // nat_temperature, mptrac.c:8334-8355
 __device__ inline double nat_temperature(double p, double h2o, double hno3) {
   const double h2o_help = h2o > 0.1e-6 ? h2o : 0.1e-6;

@@ -2769,6 +2769,53 @@ __global__ __launch_bounds__(256, MPHIP_METEO_WAVES_PER_SIMD) void h2o2_chem_ker
   }
 }
 
+// module_tracer_chem: a launch of its own behind module_h2o2_chem and before the deposition modules, in the shape of
+// oh_chem_kernel.  Every particle with dt != 0: temperature and total ozone column at the particle from one stencil
+// (INTPOL_3D(t, 1), INTPOL_2D(o3c, 1)), the solar zenith angle, the O(1D) zonal mean and the photolysis rates of the
+// four trace gases (clim_photo4), then for each present one q *= exp(-dt (K_hv + K_o1d)).  Csf6 has no reaction.
+__global__ __launch_bounds__(256, MPHIP_METEO_WAVES_PER_SIMD) void tracer_chem_kernel(const MeteoArgs G,
+                                                                                       const DevPhoto Ph) {
+  extern __shared__ double s_axes[];
+  const DevMet &M = G.met;
+  const DevAtm &a = G.atm;
+  const int *qt = G.ctl.qnt_tracer;
+  const Axes A = load_axes(M, s_axes);
+  __syncthreads();
+  const int nb = G.nblocks_logical;
+  const int lb = G.xcd_map ? (int) (blockIdx.x % 8) * (nb / 8) + (int) (blockIdx.x / 8) : (int) blockIdx.x;
+  const long long first = (long long) lb * G.per_block;
+  long long last = first + G.per_block;
+  if (last > a.np)
+    last = a.np;
+  const f32x4 *o3c_pairs = M.mx2 + (size_t) 6 * (size_t) M.nx * (size_t) M.ny;   // {o3c0, -, o3c1, -}
+  for (long long i = first + threadIdx.x; i < last; i += blockDim.x) {
+    const double dt = a.dt[i];
+    if (dt == 0)   // guard of PARTICLE_LOOP(..., check_dt = 1)
+      continue;
+    const double tm = a.time[i], p = a.p[i], lon = a.lon[i], lat = a.lat[i];
+    Stencil s;
+    stencil_3d(M, A, p, lon, lat, s);
+    const double wt = time_weight(M, tm);
+    const double t = temp_time_3d(M, s, wt);
+    SurfA c;
+    load_pair_2d(o3c_pairs, M, s, c);
+    const double o3c = sfa_time_2d(c, s, wt, 0);
+    const double Md = fdiv(kAvo * 1e-6 * (p * 100), kRI * t);   // MOLEC_DENS
+    const double sza = acos(cos_sza(tm, lon, lat));
+    const double o1d = clim_zm(G.zm[MPHIP_ZM_O1D], tm, lat, p);
+    double k_hv[4];
+    clim_photo4(Ph, p, sza, o3c, k_hv);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      if (qt[k] < 0)
+        continue;
+      const double k_o1d = tracer_o1d_arrhenius(k, t) * o1d * Md;
+      double *q = a.q[qt[k]];
+      q[i] *= libm_exp(-dt * (k_hv[k] + k_o1d));
+    }
+  }
+}
+
 // module_chem_grid: the tables of the chemistry grid (host-computed with the C library: press[nz] = P(z centre),
 // area[ny], the cell centres lon[nx] and lat[ny]) and the buffers of one pass.  `val` holds the mass per cell on entry
 // (cell sums, all-reduced) and the Cx value of every occupied cell on exit.

@@ -139,6 +139,9 @@ HIP_CTL_FIELDS = [
     ("chemgrid_lat1", C.c_double, 90.0),
     ("chemgrid_z0", C.c_double, -5.0),
     ("chemgrid_z1", C.c_double, 85.0),
+    # module_tracer_chem (TRACER_CHEM): loss of Cccl4, Cccl3f, Cccl2f2, Cn2o by photolysis and O(1D)
+    ("tracer_chem", C.c_int, 0),
+    ("pad5", C.c_int, 0),
 ]
 HIP_ONLY_KEYS = frozenset(n for n, _, _ in HIP_CTL_FIELDS)
 

@@ -24,6 +24,7 @@ MOD = {
     "wet_depo": 1 << 10, "dry_depo": 1 << 11, "advect_init": 1 << 12, "diff_pbl": 1 << 13, "meteo": 1 << 14,
     "isosurf": 1 << 15, "sort": 1 << 16, "mixing": 1 << 17, "bound_cond": 1 << 18, "bound_cond2": 1 << 19,
     "isosurf_init": 1 << 20, "oh_chem": 1 << 21, "chem_grid": 1 << 22, "h2o2_chem": 1 << 23,
+    "tracer_chem": 1 << 24,
 }
 
 MphipCtl = make_ctl_struct("MphipCtl", HIP_CTL_FIELDS)
@@ -88,6 +89,7 @@ def load(build=True):
     L.mphip_update_clim.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int]
     L.mphip_update_clim_zm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]
     L.mphip_update_clim_ts.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp]
+    L.mphip_update_clim_photo.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.POINTER(_dp)]
     L.mphip_update_met.argtypes = [C.c_void_p, C.c_int, C.POINTER(MphipMet)]
     L.mphip_swap_met.argtypes = [C.c_void_p]
     L.mphip_prefetch_met.argtypes = [C.c_void_p, C.POINTER(MphipMet)]
@@ -165,9 +167,11 @@ class Simulation:
                                            _ptr(np.ascontiguousarray(lat, dtype=np.float64), _dp),
                                            _ptr(tropo, _dp), tropo.shape[1]))
         # zonal-mean climatologies: optional fourth element {name: (time, p, lat, vmr[ntime][np][nlat])}
-        # ... and trace-gas time series {name: (time, vmr)}
+        # ... and trace-gas time series {name: (time, vmr)}, and the photolysis rates {"photo": (p, sza, o3c, rates)}
         for name, tab in (clim[3] if len(clim) > 3 else {}).items():
-            if name in TRACER_SERIES:
+            if name == "photo":
+                self.update_clim_photo(*tab)
+            elif name in TRACER_SERIES:
                 self.update_clim_ts(name, *tab)
             else:
                 self.update_clim_zm(name, *tab)
@@ -198,6 +202,22 @@ class Simulation:
         time, vmr = (np.ascontiguousarray(a, dtype=np.float64) for a in (time, vmr))
         assert time.shape == vmr.shape
         self._chk(self.L.mphip_update_clim_ts(self.h, TRACER_SERIES.index(name), len(time), _ptr(time, _dp), _ptr(vmr, _dp)))
+
+    def update_clim_photo(self, p=(), sza=(), o3c=(), rates=None):
+        """Photolysis rates of clim_t for module_tracer_chem: descending pressures [hPa], ascending solar zenith
+        angles [rad] and total ozone columns [DU], and {name: rate[np][nsza][no3c]} for some of ccl4, ccl3f, ccl2f2,
+        n2o (TRACER_SERIES names; sf6 has none).  No pressures: removed."""
+        p, sza, o3c = (np.ascontiguousarray(a, dtype=np.float64) for a in (p, sza, o3c))
+        rates = dict(rates or {})
+        keep = []
+        ptrs = (_dp * len(TRACER_SERIES))()
+        for name, tab in rates.items():
+            tab = np.ascontiguousarray(tab, dtype=np.float64)
+            assert tab.shape == (len(p), len(sza), len(o3c)), name
+            keep.append(tab)
+            ptrs[TRACER_SERIES.index(name)] = _ptr(tab, _dp)
+        self._chk(self.L.mphip_update_clim_photo(self.h, len(p), len(sza), len(o3c), _ptr(p, _dp), _ptr(sza, _dp),
+                                                 _ptr(o3c, _dp), ptrs))
 
     # -- plumbing -----------------------------------------------------------
     def _chk(self, rc):
