@@ -99,8 +99,14 @@ enum {
   MPHIP_MOD_OH_CHEM    = 1 << 21,  /* module_oh_chem     mptrac.c:5351-5434 (between module_mixing and module_wet_depo) */
   MPHIP_MOD_CHEM_GRID  = 1 << 22,  /* module_chem_grid   (own kernels; between module_mixing and module_oh_chem) */
   MPHIP_MOD_H2O2_CHEM  = 1 << 23,  /* module_h2o2_chem   (own kernel; between module_oh_chem and module_wet_depo) */
-  MPHIP_MOD_TRACER_CHEM = 1 << 24  /* module_tracer_chem (own kernel; between module_h2o2_chem and module_wet_depo) */
+  MPHIP_MOD_TRACER_CHEM = 1 << 24, /* module_tracer_chem (own kernel; between module_h2o2_chem and module_wet_depo) */
+  MPHIP_MOD_RADIO_DECAY = 1 << 25  /* module_radio_decay mptrac.c:5493-5572 (step kernel's tail; between
+                                      module_tracer_chem and module_wet_depo; mphip_set_radio_decay) */
 };
+
+/* Radionuclide activities of module_radio_decay and module_mixing (quantities Arn222, Apb210, Abe7, Acs137, Ai131,
+ * Axe133 of the reference's SET_QNT table): slots of mphip_set_radio_decay's qnt[] */
+enum { MPHIP_RN_RN222 = 0, MPHIP_RN_PB210, MPHIP_RN_BE7, MPHIP_RN_CS137, MPHIP_RN_I131, MPHIP_RN_XE133, MPHIP_NRADIO };
 
 /* Hot-path subset of ctl_t (mptrac.h:2494-3553); same field names, meaning
  * and defaults as mptrac_read_ctl (mptrac.c:6723-7741).  A compact POD is
@@ -298,9 +304,10 @@ int mphip_get_iso(mphip_ctx *ctx, double *iso_var);
 
 /* mptrac_run_timestep, mptrac.c:7851-8001: the reference's module order and
  * gating, fused into as few launches as the order allows. */
-/* module_mixing (mptrac.c:5169-5347) mixes the quantities of the hot path -- mass, volume mixing ratio, age
- * of air (qnt_m, qnt_vmr, qnt_aoa) -- in one pass; the chemistry and radionuclide quantities of the
- * reference's list (mptrac.c:5223-5230) are not part of this back end and are left untouched. */
+/* module_mixing (mptrac.c:5169-5347) mixes the quantities of the hot path -- mass, volume mixing ratio, the trace
+ * gases, age of air (qnt_m, qnt_vmr, qnt_tracer, qnt_aoa) -- and the radionuclide activities registered with
+ * mphip_set_radio_decay, in one pass; each quantity mixes on its own.  The other quantities of the reference's list
+ * (mptrac.c:5223-5230) are left untouched. */
 int mphip_run_timestep(mphip_ctx *ctx, double t);
 /* The time loop of the reference's driver (trac.c:204-226: `for (t = t_start; ...; t += direction * dt_mod)
  * mptrac_run_timestep(...)`) for `nsteps` consecutive steps starting at t_first: same results as nsteps calls of
@@ -316,11 +323,12 @@ int mphip_run_timestep(mphip_ctx *ctx, double t);
  * TURB_PBL_SCHEME 1 with winds from the model levels, the option "generic_kernel", module_oh_chem (OH_CHEM_REACTION
  * != 0: a kernel of its own between module_mixing and module_wet_depo), module_chem_grid and module_h2o2_chem (with
  * either chemistry on: kernels of their own in the same place, in the order chem_grid, oh_chem, h2o2_chem),
- * module_tracer_chem (TRACER_CHEM != 0: a kernel of its own behind them and before module_wet_depo). */
+ * module_tracer_chem (TRACER_CHEM != 0: a kernel of its own behind them and before module_wet_depo).
+ * module_radio_decay (mphip_set_radio_decay) is no obstacle: it runs in the tail of the step kernel. */
 int mphip_run_timesteps(mphip_ctx *ctx, double t_first, int nsteps);
 /* One reference module_* on its own (same state hand-over through the device
  * copy of cache->dt); `modules` is one MPHIP_MOD_* bit or an OR of the
- * per-particle bits in reference order. */
+ * per-particle bits in reference order (MPHIP_MOD_RADIO_DECAY counts as one of them). */
 int mphip_module(mphip_ctx *ctx, unsigned modules, double t);
 /* Keys (as the reference's double keys) and permutation of the last
  * module_sort call, for order checks. */
@@ -336,6 +344,16 @@ int mphip_grid_sums(mphip_ctx *ctx, double t, int *cnt, double *mean, double *si
  * weight of one as read_kernel does); every summand of mphip_grid_sums is then kernel * q (and its square).
  * nk < 2 switches it off (weight one, the default). */
 int mphip_set_grid_kernel(mphip_ctx *ctx, int nk, const double *kz, const double *kw);
+/* module_radio_decay (RADIO_DECAY): qnt[MPHIP_RN_*] is the quantity index of each activity [Bq] (-1: absent).  The
+ * registered activities are mixed by module_mixing whether or not the module is on.  on != 0: mphip_run_timestep(s)
+ * decay them after module_decay, module_mixing and the chemistry and before module_wet_depo, in the step kernel's tail
+ * (steps with it still share multi-step launches); for every particle with dt != 0 and each present activity
+ * A *= exp(-lambda dt), and Pb-210 gains the ingrowth of the Rn-222 it had before the step (two-member Bateman solution;
+ * lambda = ln 2 / half-life).  mphip_module(ctx, MPHIP_MOD_RADIO_DECAY, t) runs it alone on the stored dt.  Refused:
+ * an index outside [0, nq), one index twice, an index that is m, vmr, a loss quantity, aoa, a trace gas, Cx or a
+ * module_meteo quantity (also when mphip_update_ctl later makes it one).  qnt may be NULL when on == 0: nothing
+ * registered. */
+int mphip_set_radio_decay(mphip_ctx *ctx, int on, const int qnt[MPHIP_NRADIO]);
 
 int mphip_set_allreduce(mphip_ctx *ctx, mphip_allreduce_fn fn, void *user);
 

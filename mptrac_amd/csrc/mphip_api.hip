@@ -224,6 +224,10 @@ struct mphip_ctx {
   double *d_photo = nullptr;
   DevPhoto photo = {};
   bool photo_have[4] = {};
+  // module_radio_decay (mphip_set_radio_decay): the activities (-1: absent; module_mixing mixes the present ones) and the
+  // switch of the time step
+  RadioQnt radio = { { -1, -1, -1, -1, -1, -1 } };
+  bool radio_on = false;
   // exchange of the occupied levels only (exchange_occupied_levels): per-level occupancy, the dense band, what was found
   // option "mix_exchange_levels" (default 0): measured with a one-rank communicator, the band costs 0.14 ms per step (the
   // host reads the occupancy: the one synchronisation in the step path; pack / unpack) against a MODELLED saving of
@@ -811,6 +815,7 @@ int launch_step(mphip_ctx *ctx, unsigned mask, double t, uint64_t ctr_turb, uint
   S.ctr_meso = ctr_meso;
   S.ctr_conv = ctr_conv;
   S.ctr_pbl = ctr_pbl;
+  S.radio = ctx->radio;
   S.nsteps = nsteps;
   S.t_stride = t_stride;
   S.ctr_stride = ctr_stride;
@@ -2031,6 +2036,9 @@ int mixing_plan(mphip_ctx *ctx, double t, MixPlan *P, bool *active) {
                   c.qnt_tracer[MPHIP_TR_N2O], c.qnt_tracer[MPHIP_TR_SF6], c.qnt_aoa })
     if (iq >= 0)
       mq.q[mq.n++] = a.q[iq];
+  for (int iq : ctx->radio.q)   // ... and the activities registered with mphip_set_radio_decay
+    if (iq >= 0)
+      mq.q[mq.n++] = a.q[iq];
   if (mq.n == 0)
     return 0;
   // [sums of quantity 0 | 1 | 2 | scratch for a doubles-only all-reduce hook]
@@ -2244,6 +2252,50 @@ int do_chem_grid(mphip_ctx *ctx, double t) {
                      (const int *) ctx->d_cell, (const double *) ctx->d_sums, c.qnt_Cx);
   HIPCHK(hipGetLastError());
   return 0;
+}
+
+// module_radio_decay: an activity is registered; the bit of the step kernel's tail when the module is on (nothing to do
+// without an activity: no bit)
+bool radio_any(const mphip_ctx *ctx) {
+  for (int iq : ctx->radio.q)
+    if (iq >= 0)
+      return true;
+  return false;
+}
+
+unsigned radio_step_bit(const mphip_ctx *ctx) {
+  return ctx->radio_on && radio_any(ctx) ? kRadioDecay : 0u;
+}
+
+// what mphip_set_radio_decay refuses for the activities q[] under the control parameters c ("" = nothing)
+std::string radio_conflict(const mphip_ctl_t &c, const int *q) {
+  static const char *const names[MPHIP_NRADIO] = { "Arn222", "Apb210", "Abe7", "Acs137", "Ai131", "Axe133" };
+  const struct {
+    int iq;
+    const char *what;
+  } taken[] = { { c.qnt_m, "m" }, { c.qnt_vmr, "vmr" }, { c.qnt_loss_rate, "loss_rate" },
+                { c.qnt_mloss_decay, "mloss_decay" }, { c.qnt_mloss_wet, "mloss_wet" }, { c.qnt_mloss_dry, "mloss_dry" },
+                { c.qnt_mloss_oh, "mloss_oh" }, { c.qnt_mloss_h2o2, "mloss_h2o2" }, { c.qnt_aoa, "aoa" },
+                { c.qnt_tracer[MPHIP_TR_CCL4], "Cccl4" }, { c.qnt_tracer[MPHIP_TR_CCL3F], "Cccl3f" },
+                { c.qnt_tracer[MPHIP_TR_CCL2F2], "Cccl2f2" }, { c.qnt_tracer[MPHIP_TR_N2O], "Cn2o" },
+                { c.qnt_tracer[MPHIP_TR_SF6], "Csf6" }, { c.qnt_Cx, "Cx" } };
+  for (int k = 0; k < MPHIP_NRADIO; k++) {
+    if (q[k] < 0)
+      continue;
+    const std::string who = std::string("module_radio_decay: activity ") + names[k] + " (quantity " + std::to_string(q[k]) + ")";
+    if (q[k] >= c.nq)
+      return who + " is outside [0, nq = " + std::to_string(c.nq) + ")";
+    for (int j = 0; j < k; j++)
+      if (q[j] == q[k])
+        return who + " is also activity " + names[j];
+    for (const auto &t : taken)
+      if (t.iq == q[k])
+        return who + " is already quantity " + t.what;
+    for (int m = 0; m < MPHIP_NMQ; m++)   // (module_meteo runs lazily, after the modules that write the activities)
+      if (c.qnt_met[m] == q[k])
+        return who + " is already a module_meteo quantity";
+  }
+  return "";
 }
 
 // chemistry in the step: the modules of chem_on, or module_tracer_chem (TRACER_CHEM; it alone does not run
@@ -2534,6 +2586,11 @@ int mphip_update_ctl(mphip_ctx *ctx, const mphip_ctl_t *ctl) {
                          ctl->qnt_tracer[3], ctl->qnt_tracer[4] })
         if (ctl->qnt_met[k] == other)
           return fail(ctx, "a module_meteo quantity shares its index with a mass / mixing-ratio / loss / particle quantity");
+  if (radio_any(ctx)) {   // the activities of mphip_set_radio_decay stay valid under the new parameters
+    const std::string why = radio_conflict(*ctl, ctx->radio.q);
+    if (!why.empty())
+      return fail(ctx, why);
+  }
   if (ctx->have_ctl && flush_meteo(ctx))   // a deferred module_meteo belongs to the old parameters
     return 1;
   if (!ctx->have_ctl || ctx->ctl.advect_vert_coord != ctl->advect_vert_coord)
@@ -3287,6 +3344,8 @@ int mphip_run_timestep(mphip_ctx *ctx, double t) {
   if (c.tdec_trop > 0 && c.tdec_strat > 0)
     mask |= MPHIP_MOD_DECAY;
   unsigned tail = 0;
+  // module_radio_decay sits behind module_mixing and the chemistry: in the launch of the deposition modules
+  tail |= radio_step_bit(ctx);
   if ((c.wet_depo_ic_a > 0 || c.wet_depo_ic_h[0] > 0) && (c.wet_depo_bc_a > 0 || c.wet_depo_bc_h[0] > 0))
     tail |= MPHIP_MOD_WET_DEPO;
   if (c.dry_depo_vdep > 0)
@@ -3506,6 +3565,7 @@ int mphip_run_timesteps(mphip_ctx *ctx, double t_first, int nsteps) {
       mask |= MPHIP_MOD_LOSS_ZERO;
     if (c.tdec_trop > 0 && c.tdec_strat > 0)
       mask |= MPHIP_MOD_DECAY;
+    mask |= radio_step_bit(ctx);   // (a run-time bit of the tail in every instantiation: batches stay batches)
     if ((c.wet_depo_ic_a > 0 || c.wet_depo_ic_h[0] > 0) && (c.wet_depo_bc_a > 0 || c.wet_depo_bc_h[0] > 0))
       mask |= MPHIP_MOD_WET_DEPO;
     if (c.dry_depo_vdep > 0)
@@ -3565,7 +3625,15 @@ int mphip_module(mphip_ctx *ctx, unsigned modules, double t) {
     return launch_h2o2(ctx);
   if (modules == MPHIP_MOD_TRACER_CHEM)
     return launch_tracer_chem(ctx);
-  if (modules & ~kParticleBits)
+  // module_radio_decay: the tail of a step-kernel launch (alone: on the stored dt), with whatever activities are registered
+  if (modules & MPHIP_MOD_RADIO_DECAY) {
+    modules &= ~(unsigned) MPHIP_MOD_RADIO_DECAY;
+    if (radio_any(ctx))
+      modules |= kRadioDecay;
+    else if (!modules)
+      return 0;
+  }
+  if (modules & ~(kParticleBits | kRadioDecay))
     return fail(ctx, "module_sort / module_mixing / module_meteo / module_chem_grid / module_oh_chem / module_h2o2_chem "
                      "/ module_tracer_chem must be called on their own");
   const uint64_t n = (uint64_t) ctx->np_total;
@@ -3692,6 +3760,30 @@ int mphip_grid_sums(mphip_ctx *ctx, double t, int *cnt, double *mean, double *si
     cnt[i] = (int) h[i];
   memcpy(mean, h + ncell, ncell * (size_t) ctx->nq * sizeof(double));
   memcpy(sigma, h + ncell * (size_t) (1 + ctx->nq), ncell * (size_t) ctx->nq * sizeof(double));
+  return 0;
+}
+
+int mphip_set_radio_decay(mphip_ctx *ctx, int on, const int qnt[MPHIP_NRADIO]) {
+  if (ctx && ahead_drop(ctx))
+    return 1;
+  if (!ctx)
+    return 1;
+  if (!ctx->have_ctl)
+    return fail(ctx, "control parameters were not uploaded");
+  if (!qnt && on)
+    return fail(ctx, "module_radio_decay: null quantity list");
+  RadioQnt r = { { -1, -1, -1, -1, -1, -1 } };
+  if (qnt)
+    for (int k = 0; k < MPHIP_NRADIO; k++)
+      r.q[k] = qnt[k] < 0 ? -1 : qnt[k];
+  const std::string why = radio_conflict(ctx->ctl, r.q);
+  if (!why.empty())
+    return fail(ctx, why);
+  HIPCHK(hipSetDevice(ctx->device));
+  if (flush_meteo(ctx))   // (a deferred module_meteo belongs to the steps before)
+    return 1;
+  ctx->radio = r;
+  ctx->radio_on = on != 0;
   return 0;
 }
 

@@ -29,7 +29,8 @@ struct BoxGrid {
   int nx, ny, nz;
 };
 
-constexpr int kMixMax = 8;   // mass, volume mixing ratio, five trace gases, age of air (of the reference's list, mptrac.c:5223-5230)
+constexpr int kMixMax = 8 + MPHIP_NRADIO;   // mass, volume mixing ratio, five trace gases, age of air, six activities (of the
+                                           // reference's list, mptrac.c:5223-5230)
 struct MixSet {
   double *q[kMixMax];
   int n;
@@ -135,6 +136,7 @@ struct StepParams {
   int xcd_map;            // 1: workgroup b -> logical block (b % 8) * (n / 8) + b / 8
   const unsigned char *depo_busy;   // depo_kernel: EmitKeys::depo_busy of the launch that moved the particles (NULL: none)
   uint64_t ctr_turb, ctr_meso, ctr_conv, ctr_pbl;   // base counters of the module_rng calls
+  RadioQnt radio;         // the activities of module_radio_decay (kRadioDecay)
   // several consecutive time steps in one launch (kMultiStep instantiations, mphip_run_timesteps): step s runs
   // with model time t + s t_stride (accumulated as the caller's loop would) and counters + s ctr_stride
   int nsteps;
@@ -195,7 +197,10 @@ constexpr unsigned kPblClosure = 1u << 29;
 constexpr unsigned kEmitKeys = 1u << 22;
 constexpr unsigned kTemplateFlags = kTwoStage | kGated | kMultiStep | kMLWinds | kBigGrid | kPblClosure | kEmitKeys;
 constexpr unsigned kOptionalModules = MPHIP_MOD_DIFF_TURB | MPHIP_MOD_DIFF_MESO | MPHIP_MOD_CONVECTION | MPHIP_MOD_SEDI;
-constexpr unsigned kTailModules = MPHIP_MOD_LOSS_ZERO | MPHIP_MOD_DECAY | MPHIP_MOD_WET_DEPO | MPHIP_MOD_DRY_DEPO;
+// module_radio_decay in a step-kernel mask: the public bit MPHIP_MOD_RADIO_DECAY (1 << 25) is kGated's, so the run-time
+// masks carry it as a bit of its own that aliases no template flag (the instantiation a step selects stays the same)
+constexpr unsigned kRadioDecay = 1u << 31;
+constexpr unsigned kTailModules = MPHIP_MOD_LOSS_ZERO | MPHIP_MOD_DECAY | kRadioDecay | MPHIP_MOD_WET_DEPO | MPHIP_MOD_DRY_DEPO;
 constexpr unsigned kMovers = MPHIP_MOD_POSITION | MPHIP_MOD_ADVECT | MPHIP_MOD_DIFF_TURB | MPHIP_MOD_DIFF_MESO | MPHIP_MOD_DIFF_PBL
   | MPHIP_MOD_CONVECTION | MPHIP_MOD_SEDI | MPHIP_MOD_ISOSURF | MPHIP_MOD_POSITION2;
 
@@ -902,6 +907,8 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
       const double aux = libm_exp(ltab, -P.dt / tdec);
       apply_loss(ctl, a, i, aux, ctl.qnt_mloss_decay, 1. / tdec);
     }
+    if (tmask & kRadioDecay)   // module_radio_decay, behind module_decay (and module_mixing and the chemistry, which run
+      radio_decay(S.radio, a, i, P.dt, ltab);   // between the launch that moves the particles and this one's tail)
     if (lean) {
       // (particles above every cloud top / surface layer of the two snapshots need no stencil at all)
       const bool wet = (tmask & MPHIP_MOD_WET_DEPO) && !above_every_cloud_top(M, P);

@@ -163,6 +163,9 @@ ZONAL_MEANS = ("hno3", "oh", "h2o2", "ho2", "o1d")
 TRACERS = ("Cccl4", "Cccl3f", "Cccl2f2", "Cn2o", "Csf6")
 TRACER_SERIES = ("ccl4", "ccl3f", "ccl2f2", "n2o", "sf6")
 
+# radionuclide activities of module_radio_decay (quantities of the reference's SET_QNT table) = MPHIP_RN_* slots
+RADIO_ACTIVITIES = ("Arn222", "Apb210", "Abe7", "Acs137", "Ai131", "Axe133")
+
 
 def make_ctl_struct(name, extra=()):
     """ctypes mirror of the C struct; one class per consumer so that the
@@ -212,3 +215,9 @@ def ctl_from_quantities(names):
     if any(v >= 0 for v in tracer):
         out["qnt_tracer"] = tuple(tracer)
     return out
+
+
+def radio_from_quantities(names):
+    """The activity slots of mphip_set_radio_decay (RADIO_ACTIVITIES order, -1 = absent) of the quantity names `names`;
+    a companion of ctl_from_quantities, which leaves them out of the control parameters."""
+    return tuple(names.index(n) if n in names else -1 for n in RADIO_ACTIVITIES)

@@ -14,7 +14,8 @@ import weakref
 import numpy as np
 
 from . import build as _build
-from .ctl import HIP_CTL_FIELDS, TRACER_SERIES, ZONAL_MEANS, fill_ctl, make_ctl_struct
+from .ctl import (HIP_CTL_FIELDS, RADIO_ACTIVITIES, TRACER_SERIES, ZONAL_MEANS, fill_ctl, make_ctl_struct,
+                  radio_from_quantities)
 from .synth import FIELDS_2D, FIELDS_3D, FIELDS_ML
 
 NQ_MAX = 16
@@ -24,7 +25,7 @@ MOD = {
     "wet_depo": 1 << 10, "dry_depo": 1 << 11, "advect_init": 1 << 12, "diff_pbl": 1 << 13, "meteo": 1 << 14,
     "isosurf": 1 << 15, "sort": 1 << 16, "mixing": 1 << 17, "bound_cond": 1 << 18, "bound_cond2": 1 << 19,
     "isosurf_init": 1 << 20, "oh_chem": 1 << 21, "chem_grid": 1 << 22, "h2o2_chem": 1 << 23,
-    "tracer_chem": 1 << 24,
+    "tracer_chem": 1 << 24, "radio_decay": 1 << 25,
 }
 
 MphipCtl = make_ctl_struct("MphipCtl", HIP_CTL_FIELDS)
@@ -110,6 +111,7 @@ def load(build=True):
     L.mphip_get_sort.argtypes = [C.c_void_p, _dp, C.POINTER(C.c_int)]
     L.mphip_grid_sums.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int), _dp, _dp]
     L.mphip_set_grid_kernel.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
+    L.mphip_set_radio_decay.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.mphip_set_allreduce.argtypes = [C.c_void_p, ALLREDUCE_FN, C.c_void_p]
     L.mphip_comm_unique_id.argtypes = [C.c_void_p]
     L.mphip_comm_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -418,6 +420,27 @@ class Simulation:
         kw = np.ascontiguousarray(kw, dtype=np.float64)
         assert kz.shape == kw.shape
         self._chk(self.L.mphip_set_grid_kernel(self.h, len(kz), _ptr(kz, _dp), _ptr(kw, _dp)))
+
+    def set_radio_decay(self, quantities, on=True):
+        """module_radio_decay (mphip_set_radio_decay).  `quantities`: the quantity names of the particles (in quantity
+        order, as given to ctl_from_quantities; the activities among them are found by name), {activity name: index},
+        or the MPHIP_NRADIO indices in RADIO_ACTIVITIES order (-1: absent).  on=False: the time step leaves the
+        activities alone (module_mixing still mixes them)."""
+        if isinstance(quantities, dict):
+            unknown = set(quantities) - set(RADIO_ACTIVITIES)
+            if unknown:
+                raise KeyError(f"not an activity: {sorted(unknown)}")
+            idx = [int(quantities.get(n, -1)) for n in RADIO_ACTIVITIES]
+        else:
+            quantities = list(quantities)
+            if any(isinstance(q, str) for q in quantities):
+                idx = list(radio_from_quantities(quantities))
+            else:
+                if len(quantities) != len(RADIO_ACTIVITIES):
+                    raise ValueError(f"{len(RADIO_ACTIVITIES)} activity indices expected, got {len(quantities)}")
+                idx = [int(q) for q in quantities]
+        arr = (C.c_int * len(RADIO_ACTIVITIES))(*idx)
+        self._chk(self.L.mphip_set_radio_decay(self.h, 1 if on else 0, arr))
 
     def synchronize(self):
         self._chk(self.L.mphip_synchronize(self.h))
