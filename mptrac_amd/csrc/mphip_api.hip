@@ -640,12 +640,16 @@ int ensure_packed(mphip_ctx *ctx) {
   return 0;
 }
 
-bool both_have3(const mphip_ctx *c, int f) {
-  return c->slot[0].has3[f] && c->slot[1].has3[f];
-}
-
-bool both_have2(const mphip_ctx *c, int f) {
-  return c->slot[0].has2[f] && c->slot[1].has2[f];
+// both snapshots of the current pair are uploaded and have every 3-D field of mask3 and every 2-D field of mask2
+// (bit f: field f)
+bool both_have(const mphip_ctx *c, unsigned mask3, unsigned mask2 = 0) {
+  const MetSlot &s0 = c->slot[0], &s1 = c->slot[1];
+  bool have = s0.valid && s1.valid;
+  for (int f = 0; f < MPHIP_N3D; f++)
+    have = have && (!((mask3 >> f) & 1u) || (s0.has3[f] && s1.has3[f]));
+  for (int f = 0; f < MPHIP_N2D; f++)
+    have = have && (!((mask2 >> f) & 1u) || (s0.has2[f] && s1.has2[f]));
+  return have;
 }
 
 // cache->iso_var lives on the device only while an isosurface mode needs it
@@ -663,10 +667,10 @@ int ensure_iso(mphip_ctx *ctx) {
 int check_fields(mphip_ctx *ctx, unsigned mask) {
   const mphip_ctl_t &c = ctx->ctl;
   auto need3 = [&](int f, const char *who) {
-    return both_have3(ctx, f) ? 0 : fail(ctx, std::string(who) + ": a required 3-D meteo field was not uploaded");
+    return both_have(ctx, 1u << f) ? 0 : fail(ctx, std::string(who) + ": a required 3-D meteo field was not uploaded");
   };
   auto need2 = [&](int f, const char *who) {
-    return both_have2(ctx, f) ? 0 : fail(ctx, std::string(who) + ": a required 2-D meteo field was not uploaded");
+    return both_have(ctx, 0, 1u << f) ? 0 : fail(ctx, std::string(who) + ": a required 2-D meteo field was not uploaded");
   };
   if (mask & (MPHIP_MOD_POSITION | MPHIP_MOD_POSITION2))
     if (need2(MPHIP_PS, "module_position"))
@@ -772,6 +776,20 @@ static bool fits32(const mphip_ctx *ctx) {
 static bool lean32_ok(const mphip_ctx *ctx) { return lean_grid(ctx) && fits32(ctx) && !ctx->big_grid; }
 static bool lean64_ok(const mphip_ctx *ctx) { return lean_grid(ctx) && (!fits32(ctx) || ctx->big_grid); }
 
+// the logical blocks of a per-particle launch with at most about `blocks` of them: per_block a multiple of 256,
+// nblocks_logical a multiple of 8 (the kernels' block_range)
+struct BlockGeom {
+  int nblocks_logical;
+  long long per_block;
+};
+
+BlockGeom block_geom(long long np, int blocks) {
+  long long per_block = (np + blocks - 1) / blocks;
+  per_block = std::max<long long>(256, (per_block + 255) / 256 * 256);
+  const int nb = (int) ((np + per_block - 1) / per_block);
+  return { (nb + 7) & ~7, per_block };
+}
+
 int launch_step(mphip_ctx *ctx, unsigned mask, double t, uint64_t ctr_turb, uint64_t ctr_meso, uint64_t ctr_conv,
                 uint64_t ctr_pbl = 0, int nsteps = 1, double t_stride = 0, uint64_t ctr_stride = 0,
                 const EmitKeys *emit = nullptr, bool *emitted = nullptr) {
@@ -803,11 +821,9 @@ int launch_step(mphip_ctx *ctx, unsigned mask, double t, uint64_t ctr_turb, uint
   // (multi-step launches: more, shorter blocks -- a thread that takes 20 steps per particle should not also walk
   // five particles; measured on C3, alternating in one process: 0.744-0.781 / 0.738-0.757 / 0.729-0.747 ms per step
   // with 8 192 / 16 384 / 32 768 logical blocks)
-  const int blocks = nsteps > 1 ? ctx->step_blocks_multi : ctx->step_blocks;
-  long long per_block = (ctx->np + blocks - 1) / blocks;
-  per_block = std::max<long long>(256, (per_block + 255) / 256 * 256);
-  int nb = (int) ((ctx->np + per_block - 1) / per_block);
-  nb = (nb + 7) & ~7;
+  const BlockGeom geom = block_geom(ctx->np, nsteps > 1 ? ctx->step_blocks_multi : ctx->step_blocks);
+  const int nb = geom.nblocks_logical;
+  const long long per_block = geom.per_block;
   S.nblocks_logical = nb;
   S.per_block = per_block;
   S.xcd_map = ctx->xcd_map;
@@ -1056,8 +1072,7 @@ int check_meteo(mphip_ctx *ctx) {
   for (int k = 0; k < MPHIP_NMQ; k++)
     if (c.qnt_met[k] >= c.nq)
       return fail(ctx, "module_meteo: quantity index out of range");
-  const MetSlot &s0 = ctx->slot[0 ^ ctx->flip], &s1 = ctx->slot[1 ^ ctx->flip];
-  if (!s0.valid || !s1.valid)
+  if (!both_have(ctx, 0))
     return fail(ctx, "meteo data for both met0 and met1 must be uploaded before stepping");
   static const char *const n3[MPHIP_N3D] = { "u", "v", "w", "t", "lwc", "rwc", "iwc", "swc", "pl", "ul", "vl", "zetal",
                                              "zeta_dotl", "h2o", "z", "pv", "o3", "cc", "wl" };
@@ -1075,11 +1090,49 @@ int check_meteo(mphip_ctx *ctx) {
     return fail(ctx, "Need T_ice and T_NAT to calculate T_STS!");
   const MeteoDeps d = meteo_deps(c);
   for (int f = 0; f < MPHIP_N3D; f++)
-    if (((d.need3 >> f) & 1u) && (!s0.has3[f] || !s1.has3[f]))
+    if (((d.need3 >> f) & 1u) && !both_have(ctx, 1u << f))
       return fail(ctx, std::string("module_meteo: meteo field ") + n3[f] + " was not uploaded");
   for (int f = 0; f < MPHIP_N2D; f++)
-    if (((d.need2 >> f) & 1u) && (!s0.has2[f] || !s1.has2[f]))
+    if (((d.need2 >> f) & 1u) && !both_have(ctx, 0, 1u << f))
       return fail(ctx, std::string("module_meteo: meteo field ") + n2[f] + " was not uploaded");
+  return 0;
+}
+
+// fields a MeteoArgs kernel needs on the current pair (masks as both_have's) and its refusal without them
+struct FieldNeed {
+  unsigned mask3, mask2;
+  const char *refusal;
+};
+
+// a kernel over MeteoArgs on every particle (meteo_kernel, the chemistry kernels): nothing without particles; else the
+// packed grids, the fields of `needs` in order, and the launch with the climatology tables of zm_mask (bit k: table k),
+// the fields the kernel interpolates (`reads`: MeteoArgs::need3 / need2) and `extra` behind MeteoArgs
+template <class Kernel, class... Extra>
+int launch_meteo_args(mphip_ctx *ctx, Kernel kernel, std::initializer_list<FieldNeed> needs, unsigned zm_mask,
+                      const MeteoDeps &reads, Extra... extra) {
+  if (ctx->np == 0)
+    return 0;
+  if (ensure_packed(ctx))
+    return 1;
+  for (const FieldNeed &n : needs)
+    if (!both_have(ctx, n.mask3, n.mask2))
+      return fail(ctx, n.refusal);
+  MeteoArgs G;
+  memset(&G, 0, sizeof(G));
+  G.ctl = ctx->ctl;
+  G.met = dev_met(ctx);
+  G.atm = dev_atm(ctx);
+  G.need3 = reads.need3;
+  G.need2 = reads.need2;
+  for (int k = 0; k < MPHIP_NZM; k++)
+    if ((zm_mask >> k) & 1u)
+      G.zm[k] = ctx->zm[k];
+  const BlockGeom geom = block_geom(ctx->np, ctx->step_blocks);
+  G.nblocks_logical = geom.nblocks_logical;
+  G.per_block = geom.per_block;
+  G.xcd_map = ctx->xcd_map;
+  hipLaunchKernelGGL(kernel, dim3(geom.nblocks_logical), dim3(256), axes_lds_bytes(ctx), ctx->stream, G, extra...);
+  HIPCHK(hipGetLastError());
   return 0;
 }
 
@@ -1092,29 +1145,8 @@ int launch_oh(mphip_ctx *ctx) {
     return fail(ctx, "Module needs quantity mass or volume mixing ratio!");
   if (!ctx->d_zm[MPHIP_ZM_OH])
     return fail(ctx, "module_oh_chem: the OH climatology was not uploaded");
-  if (ctx->np == 0)
-    return 0;
-  if (ensure_packed(ctx))
-    return 1;
-  const MetSlot &s0 = ctx->slot[0 ^ ctx->flip], &s1 = ctx->slot[1 ^ ctx->flip];
-  if (!s0.valid || !s1.valid || !s0.has3[MPHIP_T] || !s1.has3[MPHIP_T])
-    return fail(ctx, "module_oh_chem: meteo field t was not uploaded");
-  MeteoArgs G;
-  memset(&G, 0, sizeof(G));
-  G.ctl = c;
-  G.met = dev_met(ctx);
-  G.atm = dev_atm(ctx);
-  G.zm[MPHIP_ZM_OH] = ctx->zm[MPHIP_ZM_OH];
-  long long per_block = (ctx->np + ctx->step_blocks - 1) / ctx->step_blocks;
-  per_block = std::max<long long>(256, (per_block + 255) / 256 * 256);
-  int nb = (int) ((ctx->np + per_block - 1) / per_block);
-  nb = (nb + 7) & ~7;
-  G.nblocks_logical = nb;
-  G.per_block = per_block;
-  G.xcd_map = ctx->xcd_map;
-  hipLaunchKernelGGL(oh_chem_kernel, dim3(nb), dim3(256), axes_lds_bytes(ctx), ctx->stream, G);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return launch_meteo_args(ctx, oh_chem_kernel, { { 1u << MPHIP_T, 0, "module_oh_chem: meteo field t was not uploaded" } },
+                           1u << MPHIP_ZM_OH, MeteoDeps());
 }
 
 // module_tracer_chem: its own kernel behind module_h2o2_chem, on the dt the step's launch stored (tracer_chem_kernel).
@@ -1136,33 +1168,10 @@ int launch_tracer_chem(mphip_ctx *ctx) {
     if (c.qnt_tracer[k] >= 0 && !ctx->photo_have[k])
       return fail(ctx, std::string("module_tracer_chem: the photolysis rates of quantity ") + names[k]
                          + " were not uploaded");
-  if (ctx->np == 0)
-    return 0;
-  if (ensure_packed(ctx))
-    return 1;
-  const MetSlot &s0 = ctx->slot[0 ^ ctx->flip], &s1 = ctx->slot[1 ^ ctx->flip];
-  bool have = s0.valid && s1.valid && s0.has3[MPHIP_T] && s1.has3[MPHIP_T];
-  if (!have)
-    return fail(ctx, "module_tracer_chem: meteo field t was not uploaded");
-  have = s0.has2[MPHIP_O3C] && s1.has2[MPHIP_O3C];
-  if (!have)
-    return fail(ctx, "module_tracer_chem: meteo field o3c was not uploaded");
-  MeteoArgs G;
-  memset(&G, 0, sizeof(G));
-  G.ctl = c;
-  G.met = dev_met(ctx);
-  G.atm = dev_atm(ctx);
-  G.zm[MPHIP_ZM_O1D] = ctx->zm[MPHIP_ZM_O1D];
-  long long per_block = (ctx->np + ctx->step_blocks - 1) / ctx->step_blocks;
-  per_block = std::max<long long>(256, (per_block + 255) / 256 * 256);
-  int nb = (int) ((ctx->np + per_block - 1) / per_block);
-  nb = (nb + 7) & ~7;
-  G.nblocks_logical = nb;
-  G.per_block = per_block;
-  G.xcd_map = ctx->xcd_map;
-  hipLaunchKernelGGL(tracer_chem_kernel, dim3(nb), dim3(256), axes_lds_bytes(ctx), ctx->stream, G, ctx->photo);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return launch_meteo_args(ctx, tracer_chem_kernel,
+                           { { 1u << MPHIP_T, 0, "module_tracer_chem: meteo field t was not uploaded" },
+                             { 0, 1u << MPHIP_O3C, "module_tracer_chem: meteo field o3c was not uploaded" } },
+                           1u << MPHIP_ZM_O1D, MeteoDeps(), ctx->photo);
 }
 
 // module_h2o2_chem: its own kernel behind module_oh_chem, on the dt the step's launch stored (h2o2_chem_kernel)
@@ -1172,60 +1181,19 @@ int launch_h2o2(mphip_ctx *ctx) {
     return fail(ctx, "Module needs quantity mass or volume mixing ratio!");
   if (!ctx->d_zm[MPHIP_ZM_H2O2])
     return fail(ctx, "module_h2o2_chem: the H2O2 climatology was not uploaded");
-  if (ctx->np == 0)
-    return 0;
-  if (ensure_packed(ctx))
-    return 1;
-  const MetSlot &s0 = ctx->slot[0 ^ ctx->flip], &s1 = ctx->slot[1 ^ ctx->flip];
-  bool have = s0.valid && s1.valid;
-  for (int f : { MPHIP_T, MPHIP_LWC, MPHIP_RWC })
-    have = have && s0.has3[f] && s1.has3[f];
-  if (!have)
-    return fail(ctx, "module_h2o2_chem: meteo fields t, lwc and rwc were not uploaded");
-  MeteoArgs G;
-  memset(&G, 0, sizeof(G));
-  G.ctl = c;
-  G.met = dev_met(ctx);
-  G.atm = dev_atm(ctx);
-  G.zm[MPHIP_ZM_H2O2] = ctx->zm[MPHIP_ZM_H2O2];
-  long long per_block = (ctx->np + ctx->step_blocks - 1) / ctx->step_blocks;
-  per_block = std::max<long long>(256, (per_block + 255) / 256 * 256);
-  int nb = (int) ((ctx->np + per_block - 1) / per_block);
-  nb = (nb + 7) & ~7;
-  G.nblocks_logical = nb;
-  G.per_block = per_block;
-  G.xcd_map = ctx->xcd_map;
-  hipLaunchKernelGGL(h2o2_chem_kernel, dim3(nb), dim3(256), axes_lds_bytes(ctx), ctx->stream, G, ctx->h2o2_low);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return launch_meteo_args(ctx, h2o2_chem_kernel,
+                           { { 1u << MPHIP_T | 1u << MPHIP_LWC | 1u << MPHIP_RWC, 0,
+                               "module_h2o2_chem: meteo fields t, lwc and rwc were not uploaded" } },
+                           1u << MPHIP_ZM_H2O2, MeteoDeps(), ctx->h2o2_low);
 }
 
 int launch_meteo(mphip_ctx *ctx) {
   const mphip_ctl_t &c = ctx->ctl;
   if (ctx->np == 0 || !meteo_requested(c))
     return 0;   // nothing to set: every SET_ATM of the reference is a no-op
-  if (check_meteo(ctx) || ensure_packed(ctx))
+  if (check_meteo(ctx))
     return 1;
-  MeteoArgs G;
-  memset(&G, 0, sizeof(G));
-  const MeteoDeps d = meteo_deps(c);
-  G.ctl = c;
-  G.met = dev_met(ctx);
-  G.atm = dev_atm(ctx);
-  G.need3 = d.need3;
-  G.need2 = d.need2;
-  for (int k = 0; k < MPHIP_NZM; k++)
-    G.zm[k] = ctx->zm[k];
-  long long per_block = (ctx->np + ctx->step_blocks - 1) / ctx->step_blocks;
-  per_block = std::max<long long>(256, (per_block + 255) / 256 * 256);
-  int nb = (int) ((ctx->np + per_block - 1) / per_block);
-  nb = (nb + 7) & ~7;
-  G.nblocks_logical = nb;
-  G.per_block = per_block;
-  G.xcd_map = ctx->xcd_map;
-  hipLaunchKernelGGL(meteo_kernel, dim3(nb), dim3(256), axes_lds_bytes(ctx), ctx->stream, G);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return launch_meteo_args(ctx, meteo_kernel, {}, (1u << MPHIP_NZM) - 1, meteo_deps(c));
 }
 
 // module_meteo of mphip_run_timestep: checked now, run when its result can be seen (lazy_meteo)
@@ -2203,8 +2171,7 @@ int do_chem_grid(mphip_ctx *ctx, double t) {
   if (ctx->np > 0) {
     if (ensure_packed(ctx))
       return 1;
-    const MetSlot &s0 = ctx->slot[0 ^ ctx->flip], &s1 = ctx->slot[1 ^ ctx->flip];
-    if (!s0.valid || !s1.valid || !s0.has3[MPHIP_T] || !s1.has3[MPHIP_T])
+    if (!both_have(ctx, 1u << MPHIP_T))
       return fail(ctx, "module_chem_grid: meteo field t was not uploaded");
   }
   const long long ngrid = (long long) c.chemgrid_nx * c.chemgrid_ny * c.chemgrid_nz;
@@ -3361,19 +3328,18 @@ int mphip_run_timestep(mphip_ctx *ctx, double t) {
   const double t_next = t + c.direction * c.dt_mod;
   const bool sort_next = ctx->sort_ahead && ctx->np > 0 && ctx->ext_identity && c.sort_dt > 0
     && fmod(t_next, c.sort_dt) == 0 && c.direction * (t_next - c.t_stop) <= 0;
-  // module_oh_chem (own kernel, launch_oh) sits between module_mixing and module_wet_depo: with it the step's launch
-  // stops before the deposition modules, which follow in a launch of their own
-  // module_chem_grid, module_h2o2_chem and module_tracer_chem join it there (chem_grid, oh_chem, h2o2_chem,
-  // tracer_chem: launch_chem)
-  const bool oh = step_chem_on(c);
-  if (!mixing_now && !oh) {
+  // the chemistry (module_chem_grid, module_oh_chem, module_h2o2_chem, module_tracer_chem: launch_chem, own kernels)
+  // sits between module_mixing and module_wet_depo: with it the step's launch stops before the deposition modules,
+  // which follow in a launch of their own
+  const bool chem = step_chem_on(c);
+  if (!mixing_now && !chem) {
     if (launch_step(ctx, mask | tail, t, ctr_turb, ctr_meso, ctr_conv, ctr_pbl))
       return 1;
     if (sort_next && ahead_launch(ctx, t_next))
       return 1;
     return meteo_now ? schedule_meteo(ctx) : 0;
   }
-  if ((tail || oh) && (mask & MPHIP_MOD_TIMESTEPS))
+  if ((tail || chem) && (mask & MPHIP_MOD_TIMESTEPS))
     mask |= kStoreDt;
   if (!mixing_now) {
     if (launch_step(ctx, mask, t, ctr_turb, ctr_meso, ctr_conv, ctr_pbl))
@@ -3437,7 +3403,7 @@ int mphip_run_timestep(mphip_ctx *ctx, double t) {
   }
   if (do_mixing(ctx, t, cells_ready))
     return 1;
-  if (oh && launch_chem(ctx, t))
+  if (chem && launch_chem(ctx, t))
     return 1;
   if (tail && launch_step(ctx, tail, t, 0, 0, 0, 0))
     return 1;
@@ -3611,20 +3577,22 @@ int mphip_module(mphip_ctx *ctx, unsigned modules, double t) {
   HIPCHK(hipSetDevice(ctx->device));
   if (flush_meteo(ctx))
     return 1;
-  if (modules == MPHIP_MOD_SORT)
+  switch (modules) {
+  case MPHIP_MOD_SORT:
     return do_sort(ctx);
-  if (modules == MPHIP_MOD_MIXING)
+  case MPHIP_MOD_MIXING:
     return do_mixing(ctx, t);
-  if (modules == MPHIP_MOD_METEO)
+  case MPHIP_MOD_METEO:
     return launch_meteo(ctx);
-  if (modules == MPHIP_MOD_OH_CHEM)
+  case MPHIP_MOD_OH_CHEM:
     return launch_oh(ctx);
-  if (modules == MPHIP_MOD_CHEM_GRID)
+  case MPHIP_MOD_CHEM_GRID:
     return do_chem_grid(ctx, t);
-  if (modules == MPHIP_MOD_H2O2_CHEM)
+  case MPHIP_MOD_H2O2_CHEM:
     return launch_h2o2(ctx);
-  if (modules == MPHIP_MOD_TRACER_CHEM)
+  case MPHIP_MOD_TRACER_CHEM:
     return launch_tracer_chem(ctx);
+  }
   // module_radio_decay: the tail of a step-kernel launch (alone: on the stored dt), with whatever activities are registered
   if (modules & MPHIP_MOD_RADIO_DECAY) {
     modules &= ~(unsigned) MPHIP_MOD_RADIO_DECAY;
@@ -4107,12 +4075,10 @@ int mphip_test_piece(mphip_ctx *ctx, int piece, int reps, double *checksum) {
   S.tracers = ctx->d_tracers;
   S.t = 0;
   S.mask = 0;
-  long long per_block = (ctx->np + ctx->step_blocks - 1) / ctx->step_blocks;
-  per_block = std::max<long long>(256, (per_block + 255) / 256 * 256);
-  int nb = (int) ((ctx->np + per_block - 1) / per_block);
-  nb = (nb + 7) & ~7;
+  const BlockGeom geom = block_geom(ctx->np, ctx->step_blocks);
+  const int nb = geom.nblocks_logical;
   S.nblocks_logical = nb;
-  S.per_block = per_block;
+  S.per_block = geom.per_block;
   S.xcd_map = ctx->xcd_map;
   S.ctr_turb = 1000;
   S.ctr_meso = 5000;

@@ -144,6 +144,18 @@ struct StepParams {
   uint64_t ctr_stride;
 };
 
+// the running workgroup's particles [first, last) of a launch with StepParams' or MeteoArgs' partition
+// (nblocks_logical, per_block, xcd_map; the host's block_geom): a contiguous run of the locality order per logical block
+template <class Params>
+__device__ __forceinline__ void block_range(const Params &G, long long np, long long &first, long long &last) {
+  const int nb = G.nblocks_logical;
+  const int lb = G.xcd_map ? (int) (blockIdx.x % 8) * (nb / 8) + (int) (blockIdx.x / 8) : (int) blockIdx.x;
+  first = (long long) lb * G.per_block;
+  last = first + G.per_block;
+  if (last > np)
+    last = np;
+}
+
 constexpr unsigned kMaskGeneric = 0xffffffffu;     // every module, module set taken from StepParams::mask
 // module set from StepParams::mask too, but without the code of the rarely used modules (model-level
 // advection and its init, module_diff_pbl, module_isosurf, module_bound_cond): small enough to keep
@@ -648,13 +660,8 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
   }
   __syncthreads();
 
-  const int nb = S.nblocks_logical;
-  const int lb = S.xcd_map ? (int) (blockIdx.x % 8) * (nb / 8) + (int) (blockIdx.x / 8) : (int) blockIdx.x;
-  const long long per_block = S.per_block;
-  const long long first = (long long) lb * per_block;
-  long long last = first + per_block;
-  if (last > a.np)
-    last = a.np;
+  long long first, last;
+  block_range(S, a.np, first, last);
 
   for (long long i = first + threadIdx.x; i < last; i += blockDim.x) {
 #if MPHIP_PARAMS_RELOAD
@@ -955,12 +962,8 @@ __global__ __launch_bounds__(256, MPHIP_TILE_WAVES_PER_SIMD) void traj_tile_kern
   const mphip_ctl_t &ctl = S.ctl;
   const Axes A = load_axes(M, s_axes);
   float *s_tile = (float *) (s_axes + ((axes_doubles(M) * 8 + (size_t) M.lut_size * 2 + 15) & ~(size_t) 15) / 8);
-  const int nb = S.nblocks_logical;
-  const int lb = S.xcd_map ? (int) (blockIdx.x % 8) * (nb / 8) + (int) (blockIdx.x / 8) : (int) blockIdx.x;
-  const long long first = (long long) lb * S.per_block;
-  long long last = first + S.per_block;
-  if (last > a.np)
-    last = a.np;
+  long long first, last;
+  block_range(S, a.np, first, last);
   for (long long base = first; base < last; base += 256) {   // (block-uniform: every thread meets every barrier)
     const long long i = base + threadIdx.x;
     const bool live = i < last;
@@ -1073,12 +1076,8 @@ __global__ __launch_bounds__(256, MPHIP_DEPO_WAVES_PER_SIMD) void depo_kernel(co
     s_count = 0;
   __syncthreads();
   const unsigned tmask = S.mask;
-  const int nb = S.nblocks_logical;
-  const int lb = S.xcd_map ? (int) (blockIdx.x % 8) * (nb / 8) + (int) (blockIdx.x / 8) : (int) blockIdx.x;
-  const long long first = (long long) lb * S.per_block;
-  long long last = first + S.per_block;
-  if (last > a.np)
-    last = a.np;
+  long long first, last;
+  block_range(S, a.np, first, last);
   const int lane = threadIdx.x & 63;
   // which particles have anything to do: p, time and dt only
   for (long long i = first + threadIdx.x; i < first + S.per_block; i += 256) {   // (whole waves stay together)
@@ -2709,32 +2708,38 @@ struct MeteoArgs {
 #ifndef MPHIP_METEO_WAVES_PER_SIMD
 #define MPHIP_METEO_WAVES_PER_SIMD 3
 #endif
+
+// the particle loop of the chemistry kernels: the axes into LDS, the workgroup's range, and body(A, i, dt) for every
+// particle with dt != 0 (the dt the step's launch stored; guard of PARTICLE_LOOP(..., check_dt = 1), mptrac.h:1759)
+template <class Body>
+__device__ __forceinline__ void chem_particle_loop(const MeteoArgs &G, Body body) {
+  extern __shared__ double s_axes[];
+  const Axes A = load_axes(G.met, s_axes);
+  __syncthreads();
+  long long first, last;
+  block_range(G, G.atm.np, first, last);
+  for (long long i = first + threadIdx.x; i < last; i += blockDim.x) {
+    const double dt = G.atm.dt[i];
+    if (dt == 0)
+      continue;
+    body(A, i, dt);
+  }
+}
+
 // module_oh_chem, mptrac.c:5351-5434: a launch of its own between the movers (and module_mixing) and the deposition
 // modules -- the clim_oh of its rate needs the device library's trigonometry, whose large-argument reduction is a call:
 // compiled into the step kernels it would give every instantiation a stack frame.  Every particle with dt != 0 (the
 // dt the step's launch stored): temperature at the particle (INTPOL_3D(t, 1)), k [OH] M, then the loss.
 __global__ __launch_bounds__(256, MPHIP_METEO_WAVES_PER_SIMD) void oh_chem_kernel(const MeteoArgs G) {
-  extern __shared__ double s_axes[];
   const DevMet &M = G.met;
   const DevAtm &a = G.atm;
   const mphip_ctl_t &ctl = G.ctl;
-  const Axes A = load_axes(M, s_axes);
-  __syncthreads();
-  const int nb = G.nblocks_logical;
-  const int lb = G.xcd_map ? (int) (blockIdx.x % 8) * (nb / 8) + (int) (blockIdx.x / 8) : (int) blockIdx.x;
-  const long long first = (long long) lb * G.per_block;
-  long long last = first + G.per_block;
-  if (last > a.np)
-    last = a.np;
-  for (long long i = first + threadIdx.x; i < last; i += blockDim.x) {
-    const double dt = a.dt[i];
-    if (dt == 0)   // guard of PARTICLE_LOOP(..., check_dt = 1), mptrac.h:1759
-      continue;
+  chem_particle_loop(G, [&](const Axes &A, long long i, double dt) {
     const double tm = a.time[i], p = a.p[i], lon = a.lon[i], lat = a.lat[i];
     const double t = temperature_at(M, A, tm, p, lon, lat);
     const double rate = oh_chem_rate(ctl, G.zm[MPHIP_ZM_OH], tm, p, lon, lat, t);
     apply_loss(ctl, a, i, libm_exp(-dt * rate), ctl.qnt_mloss_oh, rate);
-  }
+  });
 }
 
 // module_h2o2_chem: a launch of its own behind module_oh_chem and before the deposition modules, in the shape of
@@ -2742,22 +2747,10 @@ __global__ __launch_bounds__(256, MPHIP_METEO_WAVES_PER_SIMD) void oh_chem_kerne
 // the temperature pair of the packed records); outside clouds nothing happens, inside the loss.  `low`: the
 // threshold of the high-SO2 correction (h2o2_chem_rate).
 __global__ __launch_bounds__(256, MPHIP_METEO_WAVES_PER_SIMD) void h2o2_chem_kernel(const MeteoArgs G, double low) {
-  extern __shared__ double s_axes[];
   const DevMet &M = G.met;
   const DevAtm &a = G.atm;
   const mphip_ctl_t &ctl = G.ctl;
-  const Axes A = load_axes(M, s_axes);
-  __syncthreads();
-  const int nb = G.nblocks_logical;
-  const int lb = G.xcd_map ? (int) (blockIdx.x % 8) * (nb / 8) + (int) (blockIdx.x / 8) : (int) blockIdx.x;
-  const long long first = (long long) lb * G.per_block;
-  long long last = first + G.per_block;
-  if (last > a.np)
-    last = a.np;
-  for (long long i = first + threadIdx.x; i < last; i += blockDim.x) {
-    const double dt = a.dt[i];
-    if (dt == 0)   // guard of PARTICLE_LOOP(..., check_dt = 1)
-      continue;
+  chem_particle_loop(G, [&](const Axes &A, long long i, double dt) {
     const double tm = a.time[i], p = a.p[i], lon = a.lon[i], lat = a.lat[i];
     Stencil s;
     stencil_3d(M, A, p, lon, lat, s);
@@ -2767,13 +2760,13 @@ __global__ __launch_bounds__(256, MPHIP_METEO_WAVES_PER_SIMD) void h2o2_chem_ker
     const double lwc = cloud_time_3d(cc, s, wt, 0);
     const double rwc = cloud_time_3d(cc, s, wt, 1);
     if (!(lwc > 0 || rwc > 0))
-      continue;
+      return;
     const double t = temp_time_3d(M, s, wt);
     const bool cx_on = ctl.qnt_Cx >= 0;
     const double cx = cx_on ? a.q[ctl.qnt_Cx][i] : 0.0;
     const double rate = h2o2_chem_rate(G.zm[MPHIP_ZM_H2O2], tm, p, lat, t, lwc, rwc, cx_on, cx, low);
     apply_loss(ctl, a, i, libm_exp(-dt * rate), ctl.qnt_mloss_h2o2, rate);
-  }
+  });
 }
 
 // module_tracer_chem: a launch of its own behind module_h2o2_chem and before the deposition modules, in the shape of
@@ -2782,23 +2775,11 @@ __global__ __launch_bounds__(256, MPHIP_METEO_WAVES_PER_SIMD) void h2o2_chem_ker
 // four trace gases (clim_photo4), then for each present one q *= exp(-dt (K_hv + K_o1d)).  Csf6 has no reaction.
 __global__ __launch_bounds__(256, MPHIP_METEO_WAVES_PER_SIMD) void tracer_chem_kernel(const MeteoArgs G,
                                                                                        const DevPhoto Ph) {
-  extern __shared__ double s_axes[];
   const DevMet &M = G.met;
   const DevAtm &a = G.atm;
   const int *qt = G.ctl.qnt_tracer;
-  const Axes A = load_axes(M, s_axes);
-  __syncthreads();
-  const int nb = G.nblocks_logical;
-  const int lb = G.xcd_map ? (int) (blockIdx.x % 8) * (nb / 8) + (int) (blockIdx.x / 8) : (int) blockIdx.x;
-  const long long first = (long long) lb * G.per_block;
-  long long last = first + G.per_block;
-  if (last > a.np)
-    last = a.np;
   const f32x4 *o3c_pairs = M.mx2 + (size_t) 6 * (size_t) M.nx * (size_t) M.ny;   // {o3c0, -, o3c1, -}
-  for (long long i = first + threadIdx.x; i < last; i += blockDim.x) {
-    const double dt = a.dt[i];
-    if (dt == 0)   // guard of PARTICLE_LOOP(..., check_dt = 1)
-      continue;
+  chem_particle_loop(G, [&](const Axes &A, long long i, double dt) {
     const double tm = a.time[i], p = a.p[i], lon = a.lon[i], lat = a.lat[i];
     Stencil s;
     stencil_3d(M, A, p, lon, lat, s);
@@ -2820,7 +2801,7 @@ __global__ __launch_bounds__(256, MPHIP_METEO_WAVES_PER_SIMD) void tracer_chem_k
       double *q = a.q[qt[k]];
       q[i] *= libm_exp(-dt * (k_hv[k] + k_o1d));
     }
-  }
+  });
 }
 
 // module_chem_grid: the tables of the chemistry grid (host-computed with the C library: press[nz] = P(z centre),
@@ -2874,12 +2855,8 @@ __global__ __launch_bounds__(256, MPHIP_METEO_WAVES_PER_SIMD) void meteo_kernel(
   const Axes A = load_axes(M, s_axes);
   __syncthreads();
   const unsigned n3 = G.need3, n2 = G.need2;
-  const int nb = G.nblocks_logical;
-  const int lb = G.xcd_map ? (int) (blockIdx.x % 8) * (nb / 8) + (int) (blockIdx.x / 8) : (int) blockIdx.x;
-  const long long first = (long long) lb * G.per_block;
-  long long last = first + G.per_block;
-  if (last > a.np)
-    last = a.np;
+  long long first, last;
+  block_range(G, a.np, first, last);
   auto bits = [](int lo, int hi) { return ((2u << hi) - 1u) & ~((1u << lo) - 1u); };   // bits lo ... hi
   const bool want_wind = n3 & bits(MPHIP_U, MPHIP_W);
   const bool want_cloud = n3 & bits(MPHIP_LWC, MPHIP_SWC);
@@ -3054,12 +3031,8 @@ __global__ __launch_bounds__(256, MPHIP_STEP_WAVES_PER_SIMD) void piece_kernel(c
   for (int i = threadIdx.x; i < kLibmLogExpDoubles; i += blockDim.x)
     ltab[i] = libm_tables()[i];
   __syncthreads();
-  const int nb = S.nblocks_logical;
-  const int lb = S.xcd_map ? (int) (blockIdx.x % 8) * (nb / 8) + (int) (blockIdx.x / 8) : (int) blockIdx.x;
-  const long long first = (long long) lb * S.per_block;
-  long long last = first + S.per_block;
-  if (last > a.np)
-    last = a.np;
+  long long first, last;
+  block_range(S, a.np, first, last);
   for (long long i = first + threadIdx.x; i < last; i += blockDim.x) {
     Particle P;
     P.time = a.time[i];
