@@ -30,8 +30,8 @@ constexpr unsigned kAdvDiffConvSedi = kAdvDiff | MPHIP_MOD_CONVECTION | MPHIP_MO
 constexpr unsigned kDiffConvSediOnly = MPHIP_MOD_TIMESTEPS | MPHIP_MOD_DIFF_TURB | MPHIP_MOD_DIFF_MESO | MPHIP_MOD_CONVECTION
   | MPHIP_MOD_SEDI | MPHIP_MOD_POSITION2;
 constexpr unsigned kTailOnly = MPHIP_MOD_TIMESTEPS;   // no mover: a launch of loss / decay / deposition modules only
-constexpr unsigned kParticleBits = 0x3fffu | MPHIP_MOD_ISOSURF | MPHIP_MOD_BOUND_COND | MPHIP_MOD_BOUND_COND2
-  | MPHIP_MOD_ISOSURF_INIT;
+constexpr unsigned kBound = MPHIP_MOD_BOUND_COND | MPHIP_MOD_BOUND_COND2;
+constexpr unsigned kParticleBits = 0x3fffu | MPHIP_MOD_ISOSURF | kBound | MPHIP_MOD_ISOSURF_INIT;
 
 struct MetSlot {
   bool valid = false;
@@ -739,7 +739,7 @@ int check_fields(mphip_ctx *ctx, unsigned mask) {
     if (c.isosurf <= 3 && ensure_iso(ctx))
       return 1;
   }
-  if (mask & (MPHIP_MOD_BOUND_COND | MPHIP_MOD_BOUND_COND2)) {
+  if (mask & kBound) {
     if ((c.bound_dps > 0 || c.bound_dzs > 0 || c.bound_zetas > 0 || c.bound_pbl) && need2(MPHIP_PS, "module_bound_cond"))
       return 1;
     if (c.bound_zetas > 0 && need3(MPHIP_T, "module_bound_cond"))
@@ -752,8 +752,6 @@ int check_fields(mphip_ctx *ctx, unsigned mask) {
   return 0;
 }
 
-// nsteps > 1: that many consecutive time steps in one launch (kMultiStep instantiations; the caller has checked that
-// one exists for this module set, multi_step_mask)
 // The lean instantiations need a lat/lon grid with the pressure look-up table; cell indices are built with 24-bit
 // multiplies (cell32: columns below 2^24, cells below 2^32).  lean32_ok: 32-bit byte offsets into the packed grids
 // (the largest record has 24 bytes); lean64_ok: a grid beyond that -- or the option "big_grid" -- takes the kBigGrid
@@ -761,9 +759,11 @@ int check_fields(mphip_ctx *ctx, unsigned mask) {
 // With winds from the model levels (ADVECT_VERT_COORD 1..3) the lean kernels index the model-level records -- nml
 // levels per column, which need not be the np pressure levels of the same file (met_t::npl vs met_t::np,
 // mptrac.h:3862) -- so every size test takes the larger of the two level counts.
+static bool ml_winds(const mphip_ctl_t &c) {   // winds from the model levels
+  return c.advect_vert_coord >= 1 && c.advect_vert_coord <= 3;
+}
 static unsigned long long guard_levels(const mphip_ctx *ctx) {
-  const bool ml = ctx->ctl.advect_vert_coord >= 1 && ctx->ctl.advect_vert_coord <= 3;
-  return (unsigned long long) (ml ? std::max(ctx->npl, ctx->nml) : ctx->npl);
+  return (unsigned long long) (ml_winds(ctx->ctl) ? std::max(ctx->npl, ctx->nml) : ctx->npl);
 }
 static bool lean_grid(const mphip_ctx *ctx) {
   const unsigned long long cols = (unsigned long long) ctx->nx * ctx->ny;
@@ -790,14 +790,114 @@ BlockGeom block_geom(long long np, int blocks) {
   return { (nb + 7) & ~7, per_block };
 }
 
-int launch_step(mphip_ctx *ctx, unsigned mask, double t, uint64_t ctr_turb, uint64_t ctr_meso, uint64_t ctr_conv,
-                uint64_t ctr_pbl = 0, int nsteps = 1, double t_stride = 0, uint64_t ctr_stride = 0,
-                const EmitKeys *emit = nullptr, bool *emitted = nullptr) {
+// the base counters of a launch's module_rng calls (StepParams::ctr_*; 0 for a module the launch does not run)
+struct RngCtr {
+  uint64_t turb = 0, pbl = 0, meso = 0, conv = 0;
+};
+
+// the module_rng calls of one time step of module set `mask`, counted from `base` in the reference's order:
+// module_diff_turb (mptrac.c:4600, 5812), module_diff_pbl (mptrac.c:4354) and module_diff_meso take 3 np + 1 counters
+// each (module_rng(..., 3 * np, 1)), module_convection np + 1 (module_rng(..., np, 0), mptrac.c:4113); *per_step: the
+// counters the step takes in all
+RngCtr rng_counters(unsigned mask, uint64_t np, uint64_t base, uint64_t *per_step) {
+  RngCtr r;
+  uint64_t next = base;
+  const uint64_t triple = 3 * np + 1;
+  auto take = [&](unsigned bit, uint64_t draws, uint64_t &ctr) {
+    if (mask & bit) {
+      ctr = next;
+      next += draws;
+    }
+  };
+  take(MPHIP_MOD_DIFF_TURB, triple, r.turb);
+  take(MPHIP_MOD_DIFF_PBL, triple, r.pbl);
+  take(MPHIP_MOD_DIFF_MESO, triple, r.meso);
+  take(MPHIP_MOD_CONVECTION, np + 1, r.conv);
+  *per_step = next - base;
+  return r;
+}
+
+constexpr unsigned kNoStepKernel = 0;   // (no step_kernel instantiation has the template mask 0)
+
+// The step_kernel instantiation of a launch of module set `mask` with nsteps time steps per particle: a lean template
+// mask (before launch_step's variants of it: depo_kernel, kEmitKeys, the LDS tile), one of the general masks, or
+// kNoStepKernel -- several steps per launch, and no instantiation for them.  No side effects; model-level winds read
+// the packed grids' ml_monotonic (ensure_packed first).
+unsigned step_kernel_mask(const mphip_ctx *ctx, unsigned mask, int nsteps) {
+  const bool ml = ml_winds(ctx->ctl), fg = ctx->force_generic;
+  // model levels: the fast path needs monotonic height columns and none of the rarely used modules; module_bound_cond
+  // is no obstacle where the gated lean model-level instantiation can run (it switches the module at run time, as
+  // every gated instantiation does)
+  const bool ml_cols = ml && ctx->pk.ml_monotonic && ctx->nml <= kLockstepMaxLevels && !fg;
+  const bool ml_fast = ml_cols && !(mask & (kRareModules & ~MPHIP_MOD_ADVECT_INIT));
+  const bool ml_fast_bound = ml_cols && !(mask & (kRareModules & ~MPHIP_MOD_ADVECT_INIT & ~kBound));
+  const unsigned rare_bits = mask & kRareModules & ~(ml_fast ? MPHIP_MOD_ADVECT_INIT : 0u);
+  // the lean instantiations run a lat/lon grid with a pressure look-up table, and take module_timesteps / the dt store
+  // from the run-time mask; they are keyed on the movers (loss / decay / deposition are run-time bits in all of them)
+  const bool lean_ok = !fg && lean32_ok(ctx), big_ok = !fg && lean64_ok(ctx);
+  const unsigned req = (mask | MPHIP_MOD_TIMESTEPS) & ~(kStoreDt | kTailModules | kBound);
+  const unsigned multi = nsteps > 1 ? kMultiStep : 0u;
+  // (ADVECT 2 and 1 -- midpoint, the reference's default, and Euler -- share the two-stage instantiations)
+  const unsigned scheme = (mask & MPHIP_MOD_ADVECT) && ctx->ctl.advect != 4 ? kTwoStage : 0u;
+  // An exact module set has its own lean instantiation.  Any other subset of {turbulent, mesoscale diffusion,
+  // convection, sedimentation} on top of the time step's movers, and every set with module_bound_cond, runs the
+  // largest one with those switched at run time (kGated; module_bound_cond also in the instantiation without
+  // movers).  Everything else (single-module calls, the other rarely used modules) takes a general instantiation.
+  constexpr unsigned kClosure = MPHIP_MOD_DIFF_PBL | MPHIP_MOD_ISOSURF;
+  unsigned sel = kNoStepKernel;
+  if (ml) {
+    // model-level winds: the headline module set has lean instantiations (its subsets the gated one); the rest
+    // stays with the general model-level kernels below
+    if (!(rare_bits & ~kBound) && (ml_fast || (ml_fast_bound && (mask & kBound))) && (lean_ok || big_ok)) {
+      if (req == kAdvDiffConvSedi && !(mask & kBound) && lean_ok)
+        sel = req | kMLWinds | multi;
+      else if ((req & ~kOptionalModules) == kAdv)   // (subsets, every set with module_bound_cond, and every set of a big grid)
+        sel = kAdvDiffConvSedi | kGated | kMLWinds | (big_ok ? kBigGrid : 0u) | multi;
+    }
+  } else if (mask & kClosure) {
+    // the closure inside the boundary layer (TURB_PBL_SCHEME 1) and module_isosurf: gated instantiations of their own
+    if (!(rare_bits & ~(kBound | kClosure)) && lean_ok && ((req & ~kClosure & ~kOptionalModules) == kAdv))
+      sel = kAdvDiffConvSedi | kGated | kPblClosure | scheme | multi;
+  } else if (!(rare_bits & ~kBound) && lean_ok) {
+    // (kAdvTurbConvSedi has a kernel of its own for single steps only: several steps per launch take the gated one)
+    const bool exact = req == kAdv || req == kAdvTurb || req == kAdvDiff || req == kAdvDiffConvSedi
+      || (req == kAdvTurbConvSedi && nsteps == 1);
+    if (req == kTailOnly)
+      sel = kTailOnly;
+    else if (req == kDiffConvSediOnly && !(mask & kBound))
+      sel = kDiffConvSediOnly;
+    else if (exact && !(mask & kBound))
+      sel = req | scheme | multi;
+    else if ((req & ~kOptionalModules) == kAdv)
+      sel = kAdvDiffConvSedi | kGated | scheme | multi;
+  } else if (!(rare_bits & ~kBound) && big_ok && (req & ~kOptionalModules) == kAdv) {
+    // a grid beyond 32-bit offsets: the gated instantiation with 64-bit ones serves every set of the time step's movers
+    sel = kAdvDiffConvSedi | kGated | kBigGrid | scheme | multi;
+  }
+#ifdef MPHIP_QUICK   // (a development build with the five instantiations the headline workloads launch -- the fifth is
+                     // kAdvDiffConvSedi's kEmitKeys variant; every other module set runs a general kernel)
+  if (sel != kAdvDiffConvSedi && sel != (kAdvDiffConvSedi | kMultiStep) && sel != (kAdvDiffConvSedi | kMLWinds | kMultiStep)
+      && sel != (kAdvDiffConvSedi | kGated | kPblClosure | kMultiStep))
+    sel = kNoStepKernel;
+#endif
+  if (sel != kNoStepKernel)
+    return sel;
+  if (ml_fast)
+    return nsteps > 1 ? kMaskGenericMLMulti : kMaskGenericML;
+  if (nsteps > 1)
+    return kNoStepKernel;
+  return ml || (mask & kRareModules) || fg ? kMaskGeneric : kMaskGenericPL;
+}
+
+// nsteps > 1: that many consecutive time steps in one launch, time and counters advancing by t_stride and ctr_stride
+// (kMultiStep instantiations: step_kernel_mask says whether one exists for the module set)
+int launch_step(mphip_ctx *ctx, unsigned mask, double t, const RngCtr &rng = {}, int nsteps = 1, double t_stride = 0,
+                uint64_t ctr_stride = 0, const EmitKeys *emit = nullptr, bool *emitted = nullptr) {
   if (ctx->np == 0)
     return 0;
   if (ensure_packed(ctx) || check_fields(ctx, mask))
     return 1;
-  if (ctx->ctl.advect_vert_coord >= 1 && ctx->ctl.advect_vert_coord <= 3 && !ctx->d_kz) {
+  if (ml_winds(ctx->ctl) && !ctx->d_kz) {
     const size_t n = (size_t) std::max<long long>(ctx->np, 1);
     if (dev_alloc(ctx, &ctx->d_kz, n) || dev_alloc(ctx, &ctx->d_kz_alt, n))
       return 1;
@@ -827,10 +927,10 @@ int launch_step(mphip_ctx *ctx, unsigned mask, double t, uint64_t ctr_turb, uint
   S.nblocks_logical = nb;
   S.per_block = per_block;
   S.xcd_map = ctx->xcd_map;
-  S.ctr_turb = ctr_turb;
-  S.ctr_meso = ctr_meso;
-  S.ctr_conv = ctr_conv;
-  S.ctr_pbl = ctr_pbl;
+  S.ctr_turb = rng.turb;
+  S.ctr_meso = rng.meso;
+  S.ctr_conv = rng.conv;
+  S.ctr_pbl = rng.pbl;
   S.radio = ctx->radio;
   S.nsteps = nsteps;
   S.t_stride = t_stride;
@@ -850,63 +950,7 @@ int launch_step(mphip_ctx *ctx, unsigned mask, double t, uint64_t ctr_turb, uint
     e1 = ctx->ev[ctx->ev_used++];
     HIPCHK(hipEventRecord(e0, ctx->stream));
   }
-  const bool ml_ = ctx->ctl.advect_vert_coord >= 1 && ctx->ctl.advect_vert_coord <= 3;   // winds from the model levels
-  // model levels: the fast path needs monotonic height columns and none of the rarely used modules
-  const bool ml_fast = ml_ && ctx->pk.ml_monotonic && ctx->nml <= kLockstepMaxLevels
-    && !(mask & (kRareModules & ~MPHIP_MOD_ADVECT_INIT)) && !ctx->force_generic;
-  // ... module_bound_cond is no obstacle where the gated lean model-level instantiation can run (it switches the module
-  // at run time, as every gated instantiation does)
-  constexpr unsigned kBoundBits = MPHIP_MOD_BOUND_COND | MPHIP_MOD_BOUND_COND2;
-  const bool ml_fast_bound = ml_ && ctx->pk.ml_monotonic && ctx->nml <= kLockstepMaxLevels
-    && !(mask & (kRareModules & ~MPHIP_MOD_ADVECT_INIT & ~kBoundBits)) && !ctx->force_generic;
-  const unsigned rare_bits = mask & kRareModules & ~(ml_fast ? MPHIP_MOD_ADVECT_INIT : 0u);
-  const bool rare = (ml_ && !ml_fast) || rare_bits;
-  // the specialised instantiations take module_timesteps / the dt store from the run-time mask
-  // ... and run the lean code: lat/lon grid with a pressure look-up table
-  const bool lean_ok = lean32_ok(ctx), big_ok = lean64_ok(ctx);
-  // (the lean instantiations are keyed on the movers; loss / decay / deposition are run-time bits in all of them)
-  // (ADVECT 2 and 1 -- midpoint, the reference's default, and Euler -- share the two-stage instantiations)
-  const unsigned scheme = (mask & MPHIP_MOD_ADVECT) && ctx->ctl.advect != 4 ? kTwoStage : 0u;
-  // An exact module set has its own lean instantiation.  Any other subset of {turbulent, mesoscale diffusion,
-  // convection, sedimentation} on top of the time step's movers, and every set with module_bound_cond, runs the
-  // largest one with those switched at run time (kGated; module_bound_cond also in the instantiation without
-  // movers).  Everything else (single-module calls, the other rarely used modules) takes a general instantiation.
-  constexpr unsigned kBound = MPHIP_MOD_BOUND_COND | MPHIP_MOD_BOUND_COND2;
-  unsigned sel = kMaskGeneric;
-  if (!(rare_bits & ~kBound) && (ml_fast || (ml_fast_bound && (mask & kBound))) && !ctx->force_generic && (lean_ok || big_ok)) {
-    // model-level winds: the headline module set has lean instantiations (its subsets the gated one); the rest
-    // stays with the general model-level kernels below
-    const unsigned req = (mask | MPHIP_MOD_TIMESTEPS) & ~(kStoreDt | kTailModules | kBound);
-    if (req == kAdvDiffConvSedi && !(mask & kBound) && lean_ok)
-      sel = req | kMLWinds | (nsteps > 1 ? kMultiStep : 0u);
-    else if ((req & ~kOptionalModules) == kAdv)   // (subsets, every set with module_bound_cond, and every set of a big grid)
-      sel = kAdvDiffConvSedi | kGated | kMLWinds | (big_ok ? kBigGrid : 0u) | (nsteps > 1 ? kMultiStep : 0u);
-  } else if (!(rare_bits & ~(kBound | MPHIP_MOD_DIFF_PBL | MPHIP_MOD_ISOSURF)) && (mask & (MPHIP_MOD_DIFF_PBL | MPHIP_MOD_ISOSURF)) && !ml_
-             && !ctx->force_generic && lean_ok) {
-    // the closure inside the boundary layer (TURB_PBL_SCHEME 1) and module_isosurf: gated instantiations of their own
-    const unsigned req = (mask | MPHIP_MOD_TIMESTEPS) & ~(kStoreDt | kTailModules | kBound | MPHIP_MOD_DIFF_PBL | MPHIP_MOD_ISOSURF);
-    if ((req & ~kOptionalModules) == kAdv)
-      sel = kAdvDiffConvSedi | kGated | kPblClosure | scheme | (nsteps > 1 ? kMultiStep : 0u);
-  } else if (!(rare_bits & ~kBound) && !ml_ && !ctx->force_generic && lean_ok) {
-    const unsigned req = (mask | MPHIP_MOD_TIMESTEPS) & ~(kStoreDt | kTailModules | kBound);
-    // (kAdvTurbConvSedi has a kernel of its own for single steps only: several steps per launch take the gated one)
-    const bool exact = req == kAdv || req == kAdvTurb || req == kAdvDiff || req == kAdvDiffConvSedi
-      || (req == kAdvTurbConvSedi && nsteps == 1);
-    if (req == kTailOnly)
-      sel = kTailOnly;
-    else if (req == kDiffConvSediOnly && !(mask & kBound))
-      sel = kDiffConvSediOnly;
-    else if (exact && !(mask & kBound))
-      sel = req | scheme | (nsteps > 1 ? kMultiStep : 0u);
-    else if ((req & ~kOptionalModules) == kAdv)
-      sel = kAdvDiffConvSedi | kGated | scheme | (nsteps > 1 ? kMultiStep : 0u);
-  }
-  if (sel == kMaskGeneric && !(rare_bits & ~kBound) && !ml_ && !ctx->force_generic && big_ok) {
-    // a grid beyond 32-bit offsets: the gated instantiation with 64-bit ones serves every set of the time step's movers
-    const unsigned req = (mask | MPHIP_MOD_TIMESTEPS) & ~(kStoreDt | kTailModules | kBound);
-    if ((req & ~kOptionalModules) == kAdv)
-      sel = kAdvDiffConvSedi | kGated | kBigGrid | scheme | (nsteps > 1 ? kMultiStep : 0u);
-  }
+  unsigned sel = step_kernel_mask(ctx, mask, nsteps);
   // module_wet_depo / module_dry_depo alone (the launch behind module_mixing): the kernel that packs the few
   // particles with anything to do into full waves
   constexpr unsigned kDepo = MPHIP_MOD_WET_DEPO | MPHIP_MOD_DRY_DEPO;
@@ -948,8 +992,7 @@ int launch_step(mphip_ctx *ctx, unsigned mask, double t, uint64_t ctr_turb, uint
   }
   if (sel < kMaskGenericMLMulti && (sel & kPblClosure))
     lds += (size_t) (kLibmDoubles - kLibmLogExpDoubles) * sizeof(double);
-  // (-DMPHIP_QUICK: a development build with the five instantiations the headline workloads launch; every other
-  // module set then runs a general kernel)
+  // (-DMPHIP_QUICK: only the instantiations step_kernel_mask selects in that build)
   switch (sel) {
 #define STEP_CASE(M)                                                                                  \
   case M:                                                                                             \
@@ -999,19 +1042,14 @@ int launch_step(mphip_ctx *ctx, unsigned mask, double t, uint64_t ctr_turb, uint
     STEP_CASE_REST(kAdvDiffConvSedi | kGated | kBigGrid | kTwoStage | kMultiStep)
     STEP_CASE_REST(kAdvDiffConvSedi | kGated | kBigGrid | kMLWinds)
     STEP_CASE_REST(kAdvDiffConvSedi | kGated | kBigGrid | kMLWinds | kMultiStep)
+    STEP_CASE(kMaskGeneric)
+    STEP_CASE(kMaskGenericMLMulti)
+    STEP_CASE(kMaskGenericML)
+    STEP_CASE(kMaskGenericPL)
 #undef STEP_CASE_REST
 #undef STEP_CASE
-  default:
-    if (nsteps > 1 && !(ml_fast && !rare && !ctx->force_generic))
-      return fail(ctx, "internal: no multi-step instantiation for this module set");
-    if (rare || ctx->force_generic)
-      hipLaunchKernelGGL(step_kernel<kMaskGeneric>, dim3(nb), dim3(256), lds, ctx->stream, S);
-    else if (ml_fast && nsteps > 1)
-      hipLaunchKernelGGL(step_kernel<kMaskGenericMLMulti>, dim3(nb), dim3(256), lds, ctx->stream, S);
-    else if (ml_fast)
-      hipLaunchKernelGGL(step_kernel<kMaskGenericML>, dim3(nb), dim3(256), lds, ctx->stream, S);
-    else
-      hipLaunchKernelGGL(step_kernel<kMaskGenericPL>, dim3(nb), dim3(256), lds, ctx->stream, S);
+  default:   // kNoStepKernel
+    return fail(ctx, "internal: no multi-step instantiation for this module set");
   }
   HIPCHK(hipGetLastError());
   ctx->fused_perm = nullptr;   // module_sort's gather, if one was pending, has happened in this launch
@@ -1596,8 +1634,7 @@ int locality_sort(mphip_ctx *ctx) {
     return 1;
   int cur = 0;
   // measured (tools/gpu_ablate.py tiles): 4 x 4 columns for the pressure-level kernels, 8 x 8 for the model-level ones
-  const bool ml_winds = ctx->have_ctl && ctx->ctl.advect_vert_coord >= 1 && ctx->ctl.advect_vert_coord <= 3;
-  const int tile = ctx->locality_tile > 0 ? ctx->locality_tile : (ml_winds ? 8 : 4);
+  const int tile = ctx->locality_tile > 0 ? ctx->locality_tile : (ctx->have_ctl && ml_winds(ctx->ctl) ? 8 : 4);
   if (sort_pairs(ctx, tile, &cur, nullptr))
     return 1;
   PermArgs g = perm_args(ctx, true);
@@ -2279,6 +2316,86 @@ int launch_chem(mphip_ctx *ctx, double t) {
           && (do_chem_grid(ctx, t) || (c.oh_chem_reaction != 0 && launch_oh(ctx))
               || (c.h2o2_chem_reaction != 0 && launch_h2o2(ctx))))
     || (c.tracer_chem != 0 && launch_tracer_chem(ctx));
+}
+
+// ---- the plan of a time step --------------------------------------------------
+
+// what is due at model time t: module_sort (SORT_DT), module_mixing (MIXING_DT), module_convection (CONV_DT; every step
+// without one) and module_meteo (MET_DT_OUT, mptrac.c:7921-7924)
+struct StepDue {
+  bool sort, mixing, conv, meteo;
+};
+
+StepDue due_at(const mphip_ctl_t &c, double t) {
+  StepDue d;
+  d.sort = c.sort_dt > 0 && fmod(t, c.sort_dt) == 0;
+  d.mixing = c.mixing_trop >= 0 && c.mixing_strat >= 0 && (c.mixing_dt <= 0 || fmod(t, c.mixing_dt) == 0);
+  d.conv = (c.conv_mix_pbl || c.conv_cape >= 0) && (c.conv_dt <= 0 || fmod(t, c.conv_dt) == 0);
+  d.meteo = c.met_dt_out > 0 && (c.met_dt_out < c.dt_mod || fmod(t, c.met_dt_out) == 0);
+  return d;
+}
+
+// the time step at t of mphip_run_timestep (mphip_run_timesteps takes the plan of a batch's first step for all of its
+// steps: nothing is due in any of them)
+struct StepPlan {
+  StepDue due;
+  unsigned mask;       // the launch that moves the particles
+  unsigned tail;       // behind module_mixing and the chemistry: module_radio_decay, the deposition modules and the
+                       // second call of module_bound_cond
+  RngCtr rng;          // the counters of mask's module_rng calls, from ctx->rng_ctr on
+  uint64_t per_step;   // ... and how far the step moves ctx->rng_ctr
+};
+
+StepPlan plan_step(const mphip_ctx *ctx, double t) {
+  const mphip_ctl_t &c = ctx->ctl;
+  StepPlan P;
+  P.due = due_at(c, t);
+  // (module_timesteps: do_sort's on a step that sorts)
+  unsigned m = (P.due.sort ? 0u : MPHIP_MOD_TIMESTEPS) | MPHIP_MOD_POSITION | MPHIP_MOD_POSITION2;
+  if (c.advect > 0)
+    m |= MPHIP_MOD_ADVECT;
+  if (c.diffusion
+      && (c.turb_dx_pbl > 0 || c.turb_dz_pbl > 0 || c.turb_dx_trop > 0 || c.turb_dz_trop > 0 || c.turb_dx_strat > 0
+          || c.turb_dz_strat > 0))
+    m |= MPHIP_MOD_DIFF_TURB;
+  if (c.diffusion && c.turb_pbl_scheme == 1)   // (between module_diff_turb and module_diff_meso, mptrac.c:7893-7901)
+    m |= MPHIP_MOD_DIFF_PBL;
+  if (c.diffusion && (c.turb_mesox > 0 || c.turb_mesoz > 0))
+    m |= MPHIP_MOD_DIFF_MESO;
+  if (P.due.conv)
+    m |= MPHIP_MOD_CONVECTION;
+  if (c.qnt_rp >= 0 && c.qnt_rhop >= 0)
+    m |= MPHIP_MOD_SEDI;
+  if (c.isosurf >= 1 && c.isosurf <= 4)
+    m |= MPHIP_MOD_ISOSURF;
+  const bool bound = c.bound_lat0 < c.bound_lat1 && c.bound_p0 > c.bound_p1;
+  if (bound)
+    m |= MPHIP_MOD_BOUND_COND;
+  if (c.qnt_loss_rate >= 0)
+    m |= MPHIP_MOD_LOSS_ZERO;
+  if (c.tdec_trop > 0 && c.tdec_strat > 0)
+    m |= MPHIP_MOD_DECAY;
+  // module_radio_decay sits behind module_mixing and the chemistry: in the launch of the deposition modules
+  unsigned tail = radio_step_bit(ctx);
+  if ((c.wet_depo_ic_a > 0 || c.wet_depo_ic_h[0] > 0) && (c.wet_depo_bc_a > 0 || c.wet_depo_bc_h[0] > 0))
+    tail |= MPHIP_MOD_WET_DEPO;
+  if (c.dry_depo_vdep > 0)
+    tail |= MPHIP_MOD_DRY_DEPO;
+  if (bound)
+    tail |= MPHIP_MOD_BOUND_COND2;
+  P.mask = m;
+  P.tail = tail;
+  P.rng = rng_counters(m, (uint64_t) ctx->np_total, ctx->rng_ctr, &P.per_step);
+  return P;
+}
+
+// a deferred module_meteo of the step before, at the start of a step: dropped if this step runs module_meteo again
+// (nobody saw its values), evaluated now -- before the particles move -- otherwise
+int settle_meteo(mphip_ctx *ctx, bool meteo_due) {
+  if (!meteo_due)
+    return flush_meteo(ctx);
+  ctx->meteo_pending = false;
+  return 0;
 }
 
 void unpin_all(mphip_ctx *ctx, std::vector<std::pair<uintptr_t, uintptr_t>> &list) {
@@ -3235,17 +3352,9 @@ int mphip_run_timestep(mphip_ctx *ctx, double t) {
     return fail(ctx, "control parameters were not uploaded");
   HIPCHK(hipSetDevice(ctx->device));
   const mphip_ctl_t &c = ctx->ctl;
-  const uint64_t n = (uint64_t) ctx->np_total;
-  unsigned mask = MPHIP_MOD_TIMESTEPS;
-  // a deferred module_meteo of the previous step: dropped if this step runs module_meteo again (nobody
-  // saw its values), evaluated now -- before the particles move -- otherwise
-  {
-    const bool again = c.met_dt_out > 0 && (c.met_dt_out < c.dt_mod || fmod(t, c.met_dt_out) == 0);
-    if (again)
-      ctx->meteo_pending = false;
-    else if (flush_meteo(ctx))
-      return 1;
-  }
+  const StepPlan P = plan_step(ctx, t);
+  if (settle_meteo(ctx, P.due.meteo))
+    return 1;
 
   // module_isosurf_init and module_advect_init at the first call (mptrac.c:7863-7870)
   if (t == c.t_start) {
@@ -3254,76 +3363,28 @@ int mphip_run_timestep(mphip_ctx *ctx, double t) {
       init |= MPHIP_MOD_ISOSURF_INIT;
     if (c.advect_vert_coord == 1)
       init |= MPHIP_MOD_ADVECT_INIT;
-    if (init && launch_step(ctx, init, t, 0, 0, 0))
+    if (init && launch_step(ctx, init, t))
       return 1;
   }
 
   // module_timesteps + module_sort (mptrac.c:7877-7881).  The reference
   // permutes atm but not cache->dt, so on sort steps dt is computed per slot
   // before the sort and read back per slot afterwards.
-  if (c.sort_dt > 0 && fmod(t, c.sort_dt) == 0) {
+  if (P.due.sort) {
     if (restore_external_order(ctx) || do_sort(ctx, &t))
       return 1;
-    mask = 0;
   } else if (ctx->locality_interval > 0 && ctx->steps_since_resort >= ctx->locality_interval) {
     if (locality_sort(ctx))
       return 1;
   }
   if (ctx->steps_since_resort < (1 << 29))
     ctx->steps_since_resort++;
-  mask |= MPHIP_MOD_POSITION;
-  if (c.advect > 0)
-    mask |= MPHIP_MOD_ADVECT;
-  uint64_t ctr_turb = 0, ctr_meso = 0, ctr_conv = 0;
-  if (c.diffusion
-      && (c.turb_dx_pbl > 0 || c.turb_dz_pbl > 0 || c.turb_dx_trop > 0 || c.turb_dz_trop > 0 || c.turb_dx_strat > 0
-          || c.turb_dz_strat > 0)) {
-    mask |= MPHIP_MOD_DIFF_TURB;
-    ctr_turb = ctx->rng_ctr;
-    ctx->rng_ctr += 3 * n + 1;   // module_rng(..., 3 * np, 1), mptrac.c:4600, 5812
-  }
-  uint64_t ctr_pbl = 0;
-  if (c.diffusion && c.turb_pbl_scheme == 1) {
-    mask |= MPHIP_MOD_DIFF_PBL;
-    ctr_pbl = ctx->rng_ctr;
-    ctx->rng_ctr += 3 * n + 1;   // module_rng(..., 3 * np, 1), mptrac.c:4354
-  }
-  if (c.diffusion && (c.turb_mesox > 0 || c.turb_mesoz > 0)) {
-    mask |= MPHIP_MOD_DIFF_MESO;
-    ctr_meso = ctx->rng_ctr;
-    ctx->rng_ctr += 3 * n + 1;
-  }
-  if ((c.conv_mix_pbl || c.conv_cape >= 0) && (c.conv_dt <= 0 || fmod(t, c.conv_dt) == 0)) {
-    mask |= MPHIP_MOD_CONVECTION;
-    ctr_conv = ctx->rng_ctr;
-    ctx->rng_ctr += n + 1;       // module_rng(..., np, 0), mptrac.c:4113
-  }
-  if (c.qnt_rp >= 0 && c.qnt_rhop >= 0)
-    mask |= MPHIP_MOD_SEDI;
-  if (c.isosurf >= 1 && c.isosurf <= 4)
-    mask |= MPHIP_MOD_ISOSURF;
-  mask |= MPHIP_MOD_POSITION2;
-  const bool bound = c.bound_lat0 < c.bound_lat1 && c.bound_p0 > c.bound_p1;
-  if (bound)
-    mask |= MPHIP_MOD_BOUND_COND;
-  if (c.qnt_loss_rate >= 0)
-    mask |= MPHIP_MOD_LOSS_ZERO;
-  if (c.tdec_trop > 0 && c.tdec_strat > 0)
-    mask |= MPHIP_MOD_DECAY;
-  unsigned tail = 0;
-  // module_radio_decay sits behind module_mixing and the chemistry: in the launch of the deposition modules
-  tail |= radio_step_bit(ctx);
-  if ((c.wet_depo_ic_a > 0 || c.wet_depo_ic_h[0] > 0) && (c.wet_depo_bc_a > 0 || c.wet_depo_bc_h[0] > 0))
-    tail |= MPHIP_MOD_WET_DEPO;
-  if (c.dry_depo_vdep > 0)
-    tail |= MPHIP_MOD_DRY_DEPO;
-  if (bound)
-    tail |= MPHIP_MOD_BOUND_COND2;
+  ctx->rng_ctr += P.per_step;
+  unsigned mask = P.mask;
+  const unsigned tail = P.tail;
   // module_meteo (mptrac.c:7921-7924) sits between the final module_position and the loss / decay /
   // mixing / deposition modules; those neither move particles nor touch a quantity it sets, so it
   // runs after them here (own kernel, every particle)
-  const bool meteo_now = c.met_dt_out > 0 && (c.met_dt_out < c.dt_mod || fmod(t, c.met_dt_out) == 0);
-  const bool mixing_now = c.mixing_trop >= 0 && c.mixing_strat >= 0 && (c.mixing_dt <= 0 || fmod(t, c.mixing_dt) == 0);
   // module_sort of the next step can start as soon as this step's particles have moved (sort_ahead)
   const double t_next = t + c.direction * c.dt_mod;
   const bool sort_next = ctx->sort_ahead && ctx->np > 0 && ctx->ext_identity && c.sort_dt > 0
@@ -3332,23 +3393,23 @@ int mphip_run_timestep(mphip_ctx *ctx, double t) {
   // sits between module_mixing and module_wet_depo: with it the step's launch stops before the deposition modules,
   // which follow in a launch of their own
   const bool chem = step_chem_on(c);
-  if (!mixing_now && !chem) {
-    if (launch_step(ctx, mask | tail, t, ctr_turb, ctr_meso, ctr_conv, ctr_pbl))
+  if (!P.due.mixing && !chem) {
+    if (launch_step(ctx, mask | tail, t, P.rng))
       return 1;
     if (sort_next && ahead_launch(ctx, t_next))
       return 1;
-    return meteo_now ? schedule_meteo(ctx) : 0;
+    return P.due.meteo ? schedule_meteo(ctx) : 0;
   }
   if ((tail || chem) && (mask & MPHIP_MOD_TIMESTEPS))
     mask |= kStoreDt;
-  if (!mixing_now) {
-    if (launch_step(ctx, mask, t, ctr_turb, ctr_meso, ctr_conv, ctr_pbl))
+  if (!P.due.mixing) {
+    if (launch_step(ctx, mask, t, P.rng))
       return 1;
     if (sort_next && ahead_launch(ctx, t_next))
       return 1;
-    if (launch_chem(ctx, t) || (tail && launch_step(ctx, tail, t, 0, 0, 0, 0)))
+    if (launch_chem(ctx, t) || (tail && launch_step(ctx, tail, t)))
       return 1;
-    return meteo_now ? schedule_meteo(ctx) : 0;
+    return P.due.meteo ? schedule_meteo(ctx) : 0;
   }
   // the keys of the sort ahead, its module_timesteps and module_mixing's box index from the launch that moves the
   // particles (EmitKeys) instead of a kernel of their own behind it, where an instantiation for it exists
@@ -3388,7 +3449,7 @@ int mphip_run_timestep(mphip_ctx *ctx, double t) {
       }
     }
   }
-  if (launch_step(ctx, mask, t, ctr_turb, ctr_meso, ctr_conv, ctr_pbl, 1, 0, 0, &ek, &emitted))
+  if (launch_step(ctx, mask, t, P.rng, 1, 0, 0, &ek, &emitted))
     return 1;
   bool cells_ready = false;
   if (sort_next) {   // ... beside module_mixing and the deposition launch
@@ -3405,9 +3466,9 @@ int mphip_run_timestep(mphip_ctx *ctx, double t) {
     return 1;
   if (chem && launch_chem(ctx, t))
     return 1;
-  if (tail && launch_step(ctx, tail, t, 0, 0, 0, 0))
+  if (tail && launch_step(ctx, tail, t))
     return 1;
-  return meteo_now ? schedule_meteo(ctx) : 0;
+  return P.due.meteo ? schedule_meteo(ctx) : 0;
 }
 
 // mphip_run_timesteps: n calls of mphip_run_timestep at t_first, t_first + stride, ... (stride = direction * DT_MOD,
@@ -3433,16 +3494,14 @@ int mphip_run_timesteps(mphip_ctx *ctx, double t_first, int nsteps) {
     // module_meteo (lazy: evaluated when its values can be seen, dropped when the next step schedules it again --
     // mphip_run_timestep) lets a batch run on, except that it must be evaluated between a step that schedules it and a
     // step that does not: a batch ends behind such a step.  (module_meteo without a quantity to fill does nothing.)
-    const bool meteo = meteo_requested(c) && c.met_dt_out > 0;
-    auto meteo_at = [&](double tt) { return meteo && (c.met_dt_out < c.dt_mod || fmod(tt, c.met_dt_out) == 0); };
+    const bool meteo = meteo_requested(c);
+    auto meteo_at = [&](double tt) { return meteo && due_at(c, tt).meteo; };
     // module_sort and module_mixing run at multiples of SORT_DT / MIXING_DT: such a step takes the single-step path
     // (which sorts, or splits its launch around the mixing), the steps between two of them can share launches
     // (module_convection with CONV_DT > 0 likewise: due steps on their own, the steps between without it)
-    const bool conv_on = c.conv_mix_pbl || c.conv_cape >= 0;
     auto scheduled = [&](double tt) {
-      return (c.sort_dt > 0 && fmod(tt, c.sort_dt) == 0)
-        || (c.mixing_trop >= 0 && c.mixing_strat >= 0 && (c.mixing_dt <= 0 || fmod(tt, c.mixing_dt) == 0))
-        || (conv_on && c.conv_dt > 0 && fmod(tt, c.conv_dt) == 0);
+      const StepDue d = due_at(c, tt);
+      return d.sort || d.mixing || (d.conv && c.conv_dt > 0);
     };
     const bool quiet = ctx->multi_step && ctx->np > 0 && t != c.t_start && !scheduled(t)
       && c.advect > 0   // (every integrator has its multi-step instantiations; without module_advect: single steps)
@@ -3469,6 +3528,17 @@ int mphip_run_timesteps(mphip_ctx *ctx, double t_first, int nsteps) {
         tt = tn;
       }
     }
+    // the plan of mphip_run_timestep for the first step serves all `batch` steps, if an instantiation takes them
+    // (model-level winds: only once a single-step launch has allocated and seeded the search hints, d_kz)
+    StepPlan P{};
+    if (batch > 1) {
+      HIPCHK(hipSetDevice(ctx->device));
+      if (ensure_packed(ctx))
+        return 1;
+      P = plan_step(ctx, t);
+      if (step_kernel_mask(ctx, P.mask | P.tail, batch) == kNoStepKernel || (ml_winds(c) && !ctx->d_kz))
+        batch = 1;
+    }
     if (batch < 2) {
       if (mphip_run_timestep(ctx, t))
         return 1;
@@ -3476,83 +3546,11 @@ int mphip_run_timesteps(mphip_ctx *ctx, double t_first, int nsteps) {
       done++;
       continue;
     }
-    // the module set and the counters of mphip_run_timestep, for `batch` steps at once
-    HIPCHK(hipSetDevice(ctx->device));
-    const uint64_t n = (uint64_t) ctx->np_total;
-    unsigned mask = MPHIP_MOD_TIMESTEPS | MPHIP_MOD_POSITION | MPHIP_MOD_ADVECT | MPHIP_MOD_POSITION2;
-    uint64_t per_step = 0, off_turb = 0, off_meso = 0, off_conv = 0, off_pbl = 0;
-    if (c.diffusion
-        && (c.turb_dx_pbl > 0 || c.turb_dz_pbl > 0 || c.turb_dx_trop > 0 || c.turb_dz_trop > 0 || c.turb_dx_strat > 0
-            || c.turb_dz_strat > 0)) {
-      mask |= MPHIP_MOD_DIFF_TURB;
-      off_turb = per_step;
-      per_step += 3 * n + 1;
-    }
-    const bool pbl_closure = c.diffusion && c.turb_pbl_scheme == 1;
-    if (pbl_closure) {     // (between module_diff_turb and module_diff_meso, mptrac.c:7893-7901)
-      off_pbl = per_step;
-      per_step += 3 * n + 1;
-    }
-    if (c.diffusion && (c.turb_mesox > 0 || c.turb_mesoz > 0)) {
-      mask |= MPHIP_MOD_DIFF_MESO;
-      off_meso = per_step;
-      per_step += 3 * n + 1;
-    }
-    if (conv_on && !(c.conv_dt > 0)) {   // (CONV_DT > 0: the steps of a batch are the ones without convection)
-      mask |= MPHIP_MOD_CONVECTION;
-      off_conv = per_step;
-      per_step += n + 1;
-    }
-    if (c.qnt_rp >= 0 && c.qnt_rhop >= 0)
-      mask |= MPHIP_MOD_SEDI;
-    const unsigned movers = mask;
-    // winds from the model levels: the model-level instantiation (any of these module sets), if the height columns
-    // are monotonic; pressure levels: the exact lean instantiations
-    const bool ml_winds = c.advect_vert_coord >= 1 && c.advect_vert_coord <= 3;
-    if (ml_winds && ensure_packed(ctx))
+    if (settle_meteo(ctx, meteo_at(t)))
       return 1;
-    const bool lean_ok = lean32_ok(ctx) || lean64_ok(ctx);   // (launch_step's conditions; 64-bit offsets: the gated instantiations)
-    // module_bound_cond (per particle: its own time, the tracer series on the device) is switched at run time in the
-    // gated instantiations (pressure and model levels)
-    const bool bound = c.bound_lat0 < c.bound_lat1 && c.bound_p0 > c.bound_p1;
-    const bool exact = ml_winds ? ctx->pk.ml_monotonic && ctx->nml <= kLockstepMaxLevels && ctx->d_kz != nullptr && (!bound || lean_ok)
-                                : lean_ok && (movers & ~kOptionalModules) == kAdv;   // (exact sets: their own kernels; subsets: the gated one)
-    // the closure inside the boundary layer has lean instantiations for pressure-level winds on grids within 32-bit
-    // offsets; anything else with it takes the general kernel, one step per launch
-    const bool isosurf = c.isosurf >= 1 && c.isosurf <= 4;     // (module_isosurf: the same instantiations)
-    const bool closure_ok = !(pbl_closure || isosurf) || (!ml_winds && lean32_ok(ctx));
-    if (pbl_closure)
-      mask |= MPHIP_MOD_DIFF_PBL;
-    if (isosurf)
-      mask |= MPHIP_MOD_ISOSURF;
-    if (bound)
-      mask |= MPHIP_MOD_BOUND_COND | MPHIP_MOD_BOUND_COND2;
-    if (c.qnt_loss_rate >= 0)
-      mask |= MPHIP_MOD_LOSS_ZERO;
-    if (c.tdec_trop > 0 && c.tdec_strat > 0)
-      mask |= MPHIP_MOD_DECAY;
-    mask |= radio_step_bit(ctx);   // (a run-time bit of the tail in every instantiation: batches stay batches)
-    if ((c.wet_depo_ic_a > 0 || c.wet_depo_ic_h[0] > 0) && (c.wet_depo_bc_a > 0 || c.wet_depo_bc_h[0] > 0))
-      mask |= MPHIP_MOD_WET_DEPO;
-    if (c.dry_depo_vdep > 0)
-      mask |= MPHIP_MOD_DRY_DEPO;
-    if (!exact || !closure_ok) {     // no multi-step instantiation of this module set
-      if (mphip_run_timestep(ctx, t))
-        return 1;
-      t += stride;
-      done++;
-      continue;
-    }
-    // a deferred module_meteo of the step before: dropped if the first step of the batch schedules it again,
-    // evaluated now -- before the particles move -- otherwise (as mphip_run_timestep)
-    if (meteo_at(t))
-      ctx->meteo_pending = false;
-    else if (flush_meteo(ctx))
+    if (launch_step(ctx, P.mask | P.tail, t, P.rng, batch, stride, P.per_step))
       return 1;
-    if (launch_step(ctx, mask, t, ctx->rng_ctr + off_turb, ctx->rng_ctr + off_meso, ctx->rng_ctr + off_conv,
-                    ctx->rng_ctr + off_pbl, batch, stride, per_step))
-      return 1;
-    ctx->rng_ctr += per_step * (uint64_t) batch;
+    ctx->rng_ctr += P.per_step * (uint64_t) batch;
     if (ctx->steps_since_resort < (1 << 29))
       ctx->steps_since_resort += batch;
     double t_last = t;
@@ -3604,27 +3602,12 @@ int mphip_module(mphip_ctx *ctx, unsigned modules, double t) {
   if (modules & ~(kParticleBits | kRadioDecay))
     return fail(ctx, "module_sort / module_mixing / module_meteo / module_chem_grid / module_oh_chem / module_h2o2_chem "
                      "/ module_tracer_chem must be called on their own");
-  const uint64_t n = (uint64_t) ctx->np_total;
-  uint64_t ctr_turb = 0, ctr_meso = 0, ctr_conv = 0, ctr_pbl = 0;
-  if (modules & MPHIP_MOD_DIFF_TURB) {
-    ctr_turb = ctx->rng_ctr;
-    ctx->rng_ctr += 3 * n + 1;
-  }
-  if (modules & MPHIP_MOD_DIFF_PBL) {
-    ctr_pbl = ctx->rng_ctr;
-    ctx->rng_ctr += 3 * n + 1;
-  }
-  if (modules & MPHIP_MOD_DIFF_MESO) {
-    ctr_meso = ctx->rng_ctr;
-    ctx->rng_ctr += 3 * n + 1;
-  }
-  if (modules & MPHIP_MOD_CONVECTION) {
-    ctr_conv = ctx->rng_ctr;
-    ctx->rng_ctr += n + 1;
-  }
+  uint64_t per_step = 0;
+  const RngCtr rng = rng_counters(modules, (uint64_t) ctx->np_total, ctx->rng_ctr, &per_step);
+  ctx->rng_ctr += per_step;
   if (modules & MPHIP_MOD_TIMESTEPS)
     modules |= kStoreDt;
-  return launch_step(ctx, modules, t, ctr_turb, ctr_meso, ctr_conv, ctr_pbl);
+  return launch_step(ctx, modules, t, rng);
 }
 
 int mphip_get_sort(mphip_ctx *ctx, double *keys, int *perm) {
