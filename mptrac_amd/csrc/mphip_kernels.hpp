@@ -199,7 +199,8 @@ constexpr unsigned kTwoStage = 1u << 24;
 constexpr unsigned kGated = 1u << 25;
 // template mask only: the particle loop runs StepParams::nsteps time steps per particle before it moves on (a run
 // of steps with nothing between them -- no module_sort, mixing, output -- at small particle counts, where a step is
-// shorter than a kernel launch).  The state goes through memory between the steps as it does between launches.
+// shorter than a kernel launch).  The state stays in registers between the steps; the lean pressure-level
+// instantiations store it once behind the last step (step_kernel: store_once).
 constexpr unsigned kMultiStep = 1u << 26;
 // template mask only, on the gated pressure-level instantiations: module_diff_pbl (TURB_PBL_SCHEME 1, the closure inside
 // the boundary layer) and module_isosurf are compiled in -- as function calls -- and switched by the run-time mask like
@@ -679,9 +680,12 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
     double t_now = S.t;
     uint64_t c_turb = S.ctr_turb, c_meso = S.ctr_meso, c_conv = S.ctr_conv, c_pbl = S.ctr_pbl;
     // multi-step instantiations: the particle, its mesoscale wind perturbations and the wind corners it used last
-    // stay in registers from one step to the next (the stores of every step remain; what a step would load is what
-    // the step before stored, and the meteo arrays do not change inside a launch) -- the first Runge-Kutta stage
-    // of a step then gathers only in the lanes that left their grid cell since module_diff_meso of the step before
+    // stay in registers from one step to the next (what a step would load is what the step before stored, and the
+    // meteo arrays do not change inside a launch) -- the first Runge-Kutta stage of a step then gathers only in the
+    // lanes that left their grid cell since module_diff_meso of the step before.  The lean pressure-level ones also
+    // store the state once, behind the last step: nothing inside the launch reads time, lon, lat, p, up, vp, wp from
+    // memory (the tail modules take them from P), and every step would overwrite the stores of the step before.
+    constexpr bool store_once = multi && !kRuntimeMask<CT> && !kModelLevels<CT>;
     Particle P;
     WindCache wc;
     float up = 0.f, vp = 0.f, wp = 0.f;
@@ -734,7 +738,7 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
     } else
       P.dt = a.dt[i];
     if (P.dt == 0) {   // guard of PARTICLE_LOOP(..., check_dt = 1), mptrac.h:1759
-      if (fused_sort) {
+      if (fused_sort && !store_once) {
         a.time[i] = P.time;
         a.lon[i] = P.lon;
         a.lat[i] = P.lat;
@@ -748,7 +752,8 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
       if constexpr (!kRuntimeMask<CT> && (CT & kPblClosure) != 0)
         if (S.mask & MPHIP_MOD_ISOSURF) {
           P.p = isosurf_call(&ctl, &M, A, &a, P.time, P.p, P.lon, P.lat, ctl.isosurf <= 3 ? a.iso[i] : 0.0);
-          a.p[i] = P.p;
+          if (!store_once)
+            a.p[i] = P.p;
         }
       continue;
     }
@@ -842,9 +847,11 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
         wind_cache_reset(wc, true);   // (the cached corners do not cross the call: module_diff_meso gathers its own)
       } else
         diff_pbl<false>(M, A, P, up, vp, wp, c_pbl, g, ltab);
-      st_state(&a.up[i], up);
-      st_state(&a.vp[i], vp);
-      st_state(&a.wp[i], wp);
+      if (!(store_once && held)) {
+        st_state(&a.up[i], up);
+        st_state(&a.vp[i], vp);
+        st_state(&a.wp[i], wp);
+      }
     }
     if (opt & MPHIP_MOD_DIFF_MESO) {
       if (!multi) {
@@ -858,9 +865,11 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
         diff_meso_fast<!(CT & MPHIP_MOD_ADVECT) || kLeanML<CT>, kBig<CT>>(ctl, M, A, P, up, vp, wp, c_meso, g, early ? pre.meso : nullptr, wc, ltab);
       else
         diff_meso(ctl, M, A, P, up, vp, wp, c_meso, g, early ? pre.meso : nullptr, wc, ltab);
-      st_state(&a.up[i], up);
-      st_state(&a.vp[i], vp);
-      st_state(&a.wp[i], wp);
+      if (!store_once) {
+        st_state(&a.up[i], up);
+        st_state(&a.vp[i], vp);
+        st_state(&a.wp[i], wp);
+      }
     }
     if (lean) {
       if (opt & (MPHIP_MOD_CONVECTION | MPHIP_MOD_SEDI)) {
@@ -886,12 +895,14 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
         position(M, A, P);
     }
 
-    if ((mask & MPHIP_MOD_ADVECT) || fused_sort)
-      st_state(&a.time[i], P.time);
-    if ((mask & kMovers) || fused_sort) {
-      st_state(&a.lon[i], P.lon);
-      st_state(&a.lat[i], P.lat);
-      st_state(&a.p[i], P.p);
+    if (!store_once) {
+      if ((mask & MPHIP_MOD_ADVECT) || fused_sort)
+        st_state(&a.time[i], P.time);
+      if ((mask & kMovers) || fused_sort) {
+        st_state(&a.lon[i], P.lon);
+        st_state(&a.lat[i], P.lat);
+        st_state(&a.p[i], P.p);
+      }
     }
     if constexpr (lean && (CT & kEmitKeys) != 0)
       if (S.emit.keys)
@@ -933,6 +944,20 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
     }
     if (bmask & MPHIP_MOD_BOUND_COND2)
       bound_cond(ctl, M, A, a, i, P, S.tracers);
+    }
+    // (every lean multi-step mask has the advection: time and position are always written; a particle that had
+    // dt = 0 in every step gets back what it was loaded with, or its fused_sort gather)
+    if constexpr (store_once) {
+      static_assert((CT & MPHIP_MOD_ADVECT) != 0, "a lean multi-step instantiation without the advection");
+      st_state(&a.time[i], P.time);
+      st_state(&a.lon[i], P.lon);
+      st_state(&a.lat[i], P.lat);
+      st_state(&a.p[i], P.p);
+      if (mask & MPHIP_MOD_DIFF_MESO) {
+        st_state(&a.up[i], up);
+        st_state(&a.vp[i], vp);
+        st_state(&a.wp[i], wp);
+      }
     }
   }
 }
