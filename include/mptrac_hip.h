@@ -344,6 +344,47 @@ int mphip_grid_sums(mphip_ctx *ctx, double t, int *cnt, double *mean, double *si
  * weight of one as read_kernel does); every summand of mphip_grid_sums is then kernel * q (and its square).
  * nk < 2 switches it off (weight one, the default). */
 int mphip_set_grid_kernel(mphip_ctx *ctx, int nk, const double *kz, const double *kw);
+/* The particle loops of the four analysis outputs that look at every particle in every time step, on the device (the
+ * reference's writers run them on the host behind mptrac_update_host, src/mptrac.c write_csi, write_prof, write_sample,
+ * write_station; here: mptrac_amd/host/output.c, whose loops these calls reproduce bit for bit -- same decisions, sums
+ * added in ascending particle index).  All three need MET_COORD_TYPE 0 and work on the resident particles in the
+ * caller's (external) index order whatever the internal storage order is.
+ *
+ * A regular longitude / latitude / log-pressure-height box grid (upper bounds exclusive). */
+typedef struct {
+  double lon0, lon1;
+  int nx;
+  double lat0, lat1;
+  int ny;
+  double z0, z1;
+  int nz;
+} mphip_box_t;
+/* write_csi's and write_prof's binning loops (output.c:377-387, 557-563): for every particle with
+ * t - dt_mod / 2 <= time <= t + dt_mod / 2 and member = (int) q[qnt_member] (0 when qnt_member < 0, which needs
+ * nmember == 1): a member outside [0, nmember) is an error ("Ensemble ID out of range!" with the particle's index;
+ * checked before the box test), else with c = box of (lon, lat, Z(p)): sum[member * ncell + c] += kernel_weight(p) *
+ * q[qnt], ncell = nx ny nz, the summands of a cell in ascending particle index.  nk nodes (kz ascending, kw) of the
+ * vertical weighting function as read_kernel leaves them; nk < 2: weight one.  sum[nmember * ncell] are raw sums, summed
+ * over the ranks through the communicator or the all-reduce hook like mphip_grid_sums. */
+int mphip_box_sums(mphip_ctx *ctx, const mphip_box_t *box, double t, int qnt, int nmember, int qnt_member, int nk,
+                   const double *kz, const double *kw, double *sum);
+/* write_sample's inner loop (output.c:640-652) for the nobs observations of a time step: count[i] = particles with
+ * t0 <= time <= t1, fabs(obs_lat[i] - lat) <= dx 180 / (pi RE), dist2(geo2cart(observation), geo2cart(particle)) <= dx^2
+ * and -- when dz > 0 -- P(obs_z[i] + dz) <= p <= P(obs_z[i] - dz); mass[i] = sum of kernel_weight(p) * q[qnt_m] over them
+ * in ascending particle index (zeros without a quantity m; mass may be NULL).  dx [km], dz [km], the kernel as in
+ * mphip_box_sums.  Counts and masses are summed over the ranks like the box sums. */
+int mphip_sample_obs(mphip_ctx *ctx, double t0, double t1, int nobs, const double *obs_lon, const double *obs_lat,
+                     const double *obs_z, double dx, double dz, int nk, const double *kz, const double *kw, int *count,
+                     double *mass);
+/* write_station's loop (output.c:696-714): the particles with time inside the time step around t and inside
+ * [stat_t0, stat_t1], within r [km] of the station at (lon, lat) -- dist2 of the Cartesian positions against r^2 --, in
+ * ascending particle index: *nhit of them, index[k] and rows[k][4 + nq] = time, p, lon, lat, q[0 .. nq).  qnt_stat >= 0:
+ * particles whose flag (int) q[qnt_stat] is set are skipped, and the flag of the listed ones is set to 1 on the device
+ * (rows show it as 1) -- no mphip_update_quantity afterwards.  *nhit > cap: nothing else is returned and no flag has
+ * changed; call again with larger buffers.  One process only (the reference's write_station runs on rank 0 with all
+ * particles): refused with a communicator or an index range that is not the whole simulation. */
+int mphip_station_hits(mphip_ctx *ctx, double t, double lon, double lat, double r, double stat_t0, double stat_t1,
+                       int qnt_stat, int cap, int *nhit, int *index, double *rows);
 /* module_radio_decay (RADIO_DECAY): qnt[MPHIP_RN_*] is the quantity index of each activity [Bq] (-1: absent).  The
  * registered activities are mixed by module_mixing whether or not the module is on.  on != 0: mphip_run_timestep(s)
  * decay them after module_decay, module_mixing and the chemistry and before module_wet_depo, in the step kernel's tail
@@ -455,8 +496,9 @@ int mphip_test_rng(mphip_ctx *ctx, uint64_t ctr, long long n, int method, double
 /* out[i] = exp(x[i]) (op 0), log(x[i]) (1), pow(x[i], y[i]) (2), sqrt(x[i]) (3), cos(x[i]) (4), sin(x[i]) (5) as the
  * kernels evaluate them: the restatement of the C library's exp / log / pow the reference's CPU build links
  * (src/mptrac.c:4531-4546, 5822; csrc/mphip_libm.h), the square root of the Box-Muller radius, and the library's
- * cos / sin of DX2DEG / ZETA (mptrac.h:904, 2293; the reference-rounding build and module_meteo); op + 16 reads the
- * exp / log / pow tables from an LDS copy.
+ * cos / sin of DX2DEG / ZETA (mptrac.h:904, 2293; the reference-rounding build and module_meteo), op 6 / 7: the cos / sin
+ * of geo2cart in the analysis outputs (the library's bits for |x| < 105414350); op + 16 reads the exp / log / pow tables
+ * from an LDS copy.
  * x, y, out are host arrays of n doubles. */
 int mphip_test_libm(mphip_ctx *ctx, int op, const double *x, const double *y, long long n, double *out);
 /* Profiling aid: run building block `piece` of the step kernel (stencil set-up, one Runge-Kutta stage's

@@ -151,6 +151,14 @@ struct mphip_ctx {
   double *h_sums = nullptr;           // page-locked staging of mphip_grid_sums
   size_t h_sums_cap = 0;
   double *d_grid_kernel = nullptr;    // GRID_KERNEL: kz[nk] | kw[nk] (mphip_set_grid_kernel)
+  // analysis outputs (mphip_box_sums, mphip_sample_obs, mphip_station_hits)
+  double *d_ana_kernel = nullptr;     // the call's weighting function: kz[nk] | kw[nk]
+  size_t ana_kernel_cap = 0;
+  uint32_t *d_marks = nullptr;        // counts per external index (np + 1), then their scan; chunk offsets behind them
+  size_t marks_cap = 0;
+  int *d_slot_of = nullptr;           // station: where the particle of an external index is stored
+  size_t slot_of_cap = 0;
+  uint32_t *d_ana_flags = nullptr;    // [bad member | records (scan) | records (64-bit sum, 2 words)]
   int grid_nk = 0;
   bool locality_zorder = false;       // tiles of the locality key numbered along a Z-order curve instead of row by row
   int locality_tile = 0;              // horizontal tile edge of the locality key (columns); 0 = 4, or 8 with model-level winds
@@ -2631,6 +2639,10 @@ void mphip_destroy(mphip_ctx *ctx) {
     (void) hipHostFree(ctx->h_occ);
   dev_free(ctx->d_lists);
   dev_free(ctx->d_grid_kernel);
+  dev_free(ctx->d_ana_kernel);
+  dev_free(ctx->d_marks);
+  dev_free(ctx->d_slot_of);
+  dev_free(ctx->d_ana_flags);
   dev_free(ctx->d_rec);
   if (ctx->h_sums)
     (void) hipHostFree(ctx->h_sums);
@@ -3714,6 +3726,334 @@ int mphip_grid_sums(mphip_ctx *ctx, double t, int *cnt, double *mean, double *si
   return 0;
 }
 
+// ---- analysis outputs: write_csi / write_prof / write_sample / write_station particle loops ---------------------------
+
+namespace {
+
+int ana_common(mphip_ctx *ctx, const char *what) {
+  if (!ctx->have_ctl)
+    return fail(ctx, "control parameters were not uploaded");
+  if (ctx->ctl.met_coord_type != 0)
+    return fail(ctx, std::string(what) + ": Only lat/lon grid supported");
+  if (!ctx->d_ana_flags && dev_alloc(ctx, &ctx->d_ana_flags, 8))
+    return 1;
+  return 0;
+}
+
+bool is_meteo_quantity(const mphip_ctx *ctx, int iq) {
+  for (int k = 0; k < MPHIP_NMQ; k++)
+    if (iq >= 0 && ctx->ctl.qnt_met[k] == iq)
+      return true;
+  return false;
+}
+
+// the call's weighting function on the device (nk < 2: none)
+int ana_kernel_fn(mphip_ctx *ctx, int nk, const double *kz, const double *kw, KernelFn *K) {
+  K->kz = K->kw = nullptr;
+  K->nk = 0;
+  if (nk < 2)
+    return 0;
+  if (!kz || !kw)
+    return fail(ctx, "bad kernel function");
+  for (int k = 1; k < nk; k++)
+    if (kz[k] < kz[k - 1])
+      return fail(ctx, "height levels of the kernel function must be ascending");
+  if (2 * (size_t) nk > ctx->ana_kernel_cap) {
+    if (dev_alloc(ctx, &ctx->d_ana_kernel, 2 * (size_t) nk))
+      return 1;
+    ctx->ana_kernel_cap = 2 * (size_t) nk;
+  }
+  HIPCHK(hipMemcpyAsync(ctx->d_ana_kernel, kz, (size_t) nk * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(ctx->d_ana_kernel + nk, kw, (size_t) nk * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  K->kz = ctx->d_ana_kernel;
+  K->kw = ctx->d_ana_kernel + nk;
+  K->nk = nk;
+  return 0;
+}
+
+// a value per stored particle / per record (shares the record buffer of mphip_grid_sums)
+int ensure_rec(mphip_ctx *ctx, size_t need) {
+  if (need > ctx->rec_cap) {
+    ctx->rec_cap = 0;
+    if (dev_alloc(ctx, &ctx->d_rec, need))
+      return 1;
+    ctx->rec_cap = need;
+  }
+  return 0;
+}
+
+int ensure_h_sums(mphip_ctx *ctx, size_t total) {
+  if (total > ctx->h_sums_cap) {
+    if (ctx->h_sums)
+      (void) hipHostFree(ctx->h_sums);
+    ctx->h_sums = nullptr;
+    ctx->h_sums_cap = 0;
+    HIPCHK(hipHostMalloc((void **) &ctx->h_sums, total * sizeof(double), hipHostMallocDefault));
+    ctx->h_sums_cap = total;
+  }
+  return 0;
+}
+
+// Exclusive scan of the np + 1 counts in ctx->d_marks (the last one is zero): offset of element e afterwards =
+// d_marks[e] + chunk_off[e >> shift]; the total (offset of element np) goes to d_ana_flags[1].
+struct MarkScan {
+  uint32_t *chunk_off;
+  int shift;
+};
+
+int ensure_marks(mphip_ctx *ctx, MarkScan *M) {
+  const size_t m = (size_t) ctx->np + 1;
+  if (m + kScanThreads > ctx->marks_cap) {
+    if (dev_alloc(ctx, &ctx->d_marks, m + kScanThreads))
+      return 1;
+    ctx->marks_cap = m + kScanThreads;
+  }
+  M->chunk_off = ctx->d_marks + m;
+  M->shift = m <= (size_t) kScanThreads * kScanPerLarge * kScanThreads ? 14 : 16;
+  if (((m + ((size_t) 1 << M->shift) - 1) >> M->shift) > (size_t) kScanThreads)
+    return fail(ctx, "too many particles for the scan of the analysis outputs");
+  return 0;
+}
+
+int scan_marks(mphip_ctx *ctx, const MarkScan &M) {
+  const size_t m = (size_t) ctx->np + 1;
+  const int nchunks = (int) ((m + ((size_t) 1 << M.shift) - 1) >> M.shift);
+  if (M.shift == 14)
+    hipLaunchKernelGGL(sort_scan_local_kernel<kScanPerLarge>, dim3(nchunks), dim3(kScanThreads), 0, ctx->stream, ctx->d_marks,
+                       m, M.chunk_off, (const uint32_t *) nullptr, 0);
+  else
+    hipLaunchKernelGGL(sort_scan_local_kernel<64>, dim3(nchunks), dim3(kScanThreads), 0, ctx->stream, ctx->d_marks, m,
+                       M.chunk_off, (const uint32_t *) nullptr, 0);
+  hipLaunchKernelGGL(sort_scan_chunks_kernel, dim3(1), dim3(kScanThreads), 0, ctx->stream, M.chunk_off, nchunks);
+  hipLaunchKernelGGL(scan_total_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->d_marks, M.chunk_off, M.shift, ctx->np,
+                     ctx->d_ana_flags + 1);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// geo2cart(0, lon, lat, x) of output.c with the host's C library
+void geo2cart_host(double lon, double lat, double *x) {
+  const double r = 6367.421 + 0.0, phi = lat * (M_PI / 180.0), lam = lon * (M_PI / 180.0);
+  x[0] = r * cos(phi) * cos(lam);
+  x[1] = r * cos(phi) * sin(lam);
+  x[2] = r * sin(phi);
+}
+
+}   // namespace
+
+int mphip_box_sums(mphip_ctx *ctx, const mphip_box_t *box, double t, int qnt, int nmember, int qnt_member, int nk,
+                   const double *kz, const double *kw, double *sum) {
+  if (!ctx || !box || !sum)
+    return fail(ctx, "null argument");
+  HIPCHK(hipSetDevice(ctx->device));
+  if (ana_common(ctx, "mphip_box_sums"))
+    return 1;
+  if (box->nx < 1 || box->ny < 1 || box->nz < 1)
+    return fail(ctx, "mphip_box_sums: empty grid");
+  if (qnt < 0 || qnt >= ctx->nq)
+    return fail(ctx, "mphip_box_sums: no such quantity");
+  if (nmember < 1 || qnt_member >= ctx->nq || (qnt_member < 0 && nmember != 1))
+    return fail(ctx, "mphip_box_sums: bad ensemble members");
+  if ((is_meteo_quantity(ctx, qnt) || is_meteo_quantity(ctx, qnt_member)) && flush_meteo(ctx))
+    return 1;
+  const size_t ncell = (size_t) box->nx * (size_t) box->ny * (size_t) box->nz, ntot = ncell * (size_t) nmember;
+  if (ntot >= 0x7fffffffULL)
+    return fail(ctx, "too many grid cells for 32-bit cell indices");
+  BoxSumArgs B;
+  memset(&B, 0, sizeof(B));
+  B.G = BoxGrid{ box->lon0, box->lon1, box->lat0, box->lat1, box->z0, box->z1, box->nx, box->ny, box->nz };
+  B.t0 = t - 0.5 * ctx->ctl.dt_mod;
+  B.t1 = t + 0.5 * ctx->ctl.dt_mod;
+  B.qnt = qnt;
+  B.qnt_member = qnt_member;
+  B.nmember = nmember;
+  B.ncell = (int) ncell;
+  if (ana_kernel_fn(ctx, nk, kz, kw, &B.K) || ensure_sums(ctx, ntot) || ensure_rec(ctx, (size_t) std::max<long long>(ctx->np, 1)))
+    return 1;
+  int *bad = (int *) ctx->d_ana_flags;
+  HIPCHK(hipMemsetAsync(bad, 0x7f, sizeof(int), ctx->stream));   // 0x7f7f7f7f: above every index
+  hipLaunchKernelGGL(box_member_cell_kernel, dim3(grid_for(ctx->np)), dim3(256), 0, ctx->stream, dev_atm(ctx), B, ctx->d_cell,
+                     ctx->d_rec, bad);
+  HIPCHK(hipGetLastError());
+  int h_bad = 0;
+  HIPCHK(hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (h_bad != 0x7f7f7f7f)
+    return fail(ctx, "Ensemble ID out of range! (particle " + std::to_string(ctx->ip0 + h_bad) + ")");
+  const ArrayVals vals = { ctx->d_rec };
+  if (ordered_cell_sums(ctx, vals, 1, box->nz, ntot, ctx->d_sums, (int *) nullptr, (double *) nullptr, true))
+    return 1;
+  if (run_allreduce(ctx, ctx->d_sums, ntot) || ensure_h_sums(ctx, ntot))
+    return 1;
+  HIPCHK(hipMemcpyAsync(ctx->h_sums, ctx->d_sums, ntot * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  memcpy(sum, ctx->h_sums, ntot * sizeof(double));
+  return 0;
+}
+
+int mphip_sample_obs(mphip_ctx *ctx, double t0, double t1, int nobs, const double *obs_lon, const double *obs_lat,
+                     const double *obs_z, double dx, double dz, int nk, const double *kz, const double *kw, int *count,
+                     double *mass) {
+  if (!ctx || nobs < 0 || (nobs > 0 && (!obs_lon || !obs_lat || !obs_z || !count)))
+    return fail(ctx, "null argument");
+  HIPCHK(hipSetDevice(ctx->device));
+  if (ana_common(ctx, "mphip_sample_obs"))
+    return 1;
+  if (nobs == 0)
+    return 0;
+  const int qnt_m = ctx->ctl.qnt_m >= 0 && ctx->ctl.qnt_m < ctx->nq ? ctx->ctl.qnt_m : -1;
+  if (is_meteo_quantity(ctx, qnt_m) && flush_meteo(ctx))
+    return 1;
+  SampleArgs S;
+  memset(&S, 0, sizeof(S));
+  S.t0 = t0;
+  S.t1 = t1;
+  S.reach_lat = dx * 180. / (M_PI * 6367.421);
+  S.reach2 = dx * dx;
+  S.dz = dz;
+  S.nobs = nobs;
+  S.qnt_m = qnt_m;
+  MarkScan M;
+  if (ana_kernel_fn(ctx, nk, kz, kw, &S.K) || ensure_sums(ctx, (size_t) (kObsFields + 2) * (size_t) nobs) || ensure_marks(ctx, &M))
+    return 1;
+  // the observations as the kernel stages them: centre, latitude, pressures of the top and the bottom of the layer
+  std::vector<double> h_obs((size_t) kObsFields * (size_t) nobs);
+  for (int i = 0; i < nobs; i++) {
+    double *o = &h_obs[(size_t) kObsFields * (size_t) i];
+    geo2cart_host(obs_lon[i], obs_lat[i], o);
+    o[3] = obs_lat[i];
+    o[4] = 1013.25 * exp(-(obs_z[i] + dz) / 7.0);
+    o[5] = 1013.25 * exp(-(obs_z[i] - dz) / 7.0);
+  }
+  double *d_obs = ctx->d_sums, *d_out = ctx->d_sums + (size_t) kObsFields * (size_t) nobs;
+  HIPCHK(hipMemcpyAsync(d_obs, h_obs.data(), h_obs.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemsetAsync(d_out, 0, 2 * (size_t) nobs * sizeof(double), ctx->stream));
+  uint32_t nrec = 0;
+  if (ctx->np > 0) {
+    const DevAtm a = dev_atm(ctx);
+    const int blocks = grid_for(ctx->np);
+    hipLaunchKernelGGL(sample_hits_kernel<false>, dim3(blocks), dim3(256), 0, ctx->stream, a, S, d_obs, ctx->d_marks,
+                       (const uint32_t *) nullptr, 0, (uint32_t *) nullptr, (double *) nullptr);
+    HIPCHK(hipGetLastError());
+    // the number of records: every particle's count is at most nobs, so 64 bits hold their sum; the scan works in 32
+    HIPCHK(hipMemsetAsync(ctx->d_ana_flags + 2, 0, 2 * sizeof(uint32_t), ctx->stream));
+    hipLaunchKernelGGL(count_total_kernel, dim3(grid_for(ctx->np)), dim3(256), 0, ctx->stream,
+                       (const uint32_t *) ctx->d_marks, ctx->np, (unsigned long long *) (ctx->d_ana_flags + 2));
+    if (scan_marks(ctx, M))
+      return 1;
+    uint32_t h_flags[4] = { 0, 0, 0, 0 };
+    HIPCHK(hipMemcpyAsync(h_flags, ctx->d_ana_flags, sizeof(h_flags), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    const unsigned long long total = ((unsigned long long) h_flags[3] << 32) | h_flags[2];
+    if (total > 0x7fffffffULL || total != h_flags[1])
+      return fail(ctx, "mphip_sample_obs: more than 2^31 (observation, particle) pairs in one time step");
+    nrec = h_flags[1];
+    if (nrec > 0) {
+      const size_t words32 = 4 * (size_t) nrec;
+      if ((words32 + 1) / 2 > ctx->lists_cap) {
+        if (dev_alloc(ctx, &ctx->d_lists, (words32 + 1) / 2))
+          return 1;
+        ctx->lists_cap = (words32 + 1) / 2;
+      }
+      if (ensure_rec(ctx, nrec))
+        return 1;
+      uint32_t *base = (uint32_t *) ctx->d_lists;
+      uint32_t *keys[2] = { base, base + 2 * (size_t) nrec };
+      int *ids[2] = { (int *) (base + (size_t) nrec), (int *) (base + 3 * (size_t) nrec) };
+      hipLaunchKernelGGL(sample_hits_kernel<true>, dim3(blocks), dim3(256), 0, ctx->stream, a, S, d_obs, ctx->d_marks,
+                         (const uint32_t *) M.chunk_off, M.shift, keys[0], ctx->d_rec);
+      HIPCHK(hipGetLastError());
+      int cur = 0;
+      if (radix_passes(ctx, keys, ids, nrec, bits_for((unsigned long long) (nobs - 1)), &cur, nullptr, true))
+        return 1;
+      hipLaunchKernelGGL(sample_sum_kernel, dim3(grid_for((long long) nobs * 64)), dim3(256), 0, ctx->stream, keys[cur],
+                         ids[cur], ctx->d_rec, nrec, nobs, d_out);
+      HIPCHK(hipGetLastError());
+    }
+  }
+  if (run_allreduce(ctx, d_out, 2 * (size_t) nobs) || ensure_h_sums(ctx, 2 * (size_t) nobs))
+    return 1;
+  HIPCHK(hipMemcpyAsync(ctx->h_sums, d_out, 2 * (size_t) nobs * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  for (int i = 0; i < nobs; i++) {
+    count[i] = (int) ctx->h_sums[(size_t) nobs + (size_t) i];
+    if (mass)
+      mass[i] = ctx->h_sums[i];
+  }
+  return 0;
+}
+
+int mphip_station_hits(mphip_ctx *ctx, double t, double lon, double lat, double r, double stat_t0, double stat_t1,
+                       int qnt_stat, int cap, int *nhit, int *index, double *rows) {
+  if (!ctx || !nhit || cap < 0 || (cap > 0 && (!index || !rows)))
+    return fail(ctx, "null argument");
+  HIPCHK(hipSetDevice(ctx->device));
+  *nhit = 0;
+  if (ana_common(ctx, "mphip_station_hits"))
+    return 1;
+  if (ctx->comm || ctx->np != ctx->np_total)
+    return fail(ctx, "mphip_station_hits: the station output needs all particles in one process");
+  if (qnt_stat >= ctx->nq)
+    return fail(ctx, "mphip_station_hits: no such quantity");
+  if (flush_meteo(ctx))   // (the rows deliver every quantity)
+    return 1;
+  if (ctx->np == 0)
+    return 0;
+  StationArgs S;
+  memset(&S, 0, sizeof(S));
+  S.t0 = t - 0.5 * ctx->ctl.dt_mod;
+  S.t1 = t + 0.5 * ctx->ctl.dt_mod;
+  S.s0 = stat_t0;
+  S.s1 = stat_t1;
+  S.reach2 = r * r;
+  geo2cart_host(lon, lat, S.centre);
+  S.qnt_stat = qnt_stat < 0 ? -1 : qnt_stat;
+  MarkScan M;
+  if (ensure_marks(ctx, &M) || ensure_rec(ctx, (size_t) ctx->np))
+    return 1;
+  if ((size_t) ctx->np > ctx->slot_of_cap) {
+    if (dev_alloc(ctx, &ctx->d_slot_of, (size_t) ctx->np))
+      return 1;
+    ctx->slot_of_cap = (size_t) ctx->np;
+  }
+  const DevAtm a = dev_atm(ctx);
+  hipLaunchKernelGGL(station_mark_kernel, dim3(grid_for(ctx->np)), dim3(256), 0, ctx->stream, a, S, ctx->d_marks, ctx->d_slot_of,
+                     ctx->d_rec);
+  HIPCHK(hipGetLastError());
+  if (scan_marks(ctx, M))
+    return 1;
+  uint32_t total = 0;
+  HIPCHK(hipMemcpyAsync(&total, ctx->d_ana_flags + 1, sizeof(total), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  *nhit = (int) total;
+  if (total == 0)
+    return 0;
+  if (total > (uint32_t) cap) {   // the caller comes back with a larger buffer: nothing may have changed
+    if (S.qnt_stat >= 0) {
+      hipLaunchKernelGGL(station_restore_kernel, dim3(grid_for(ctx->np)), dim3(256), 0, ctx->stream, a, S.qnt_stat,
+                         (const uint32_t *) ctx->d_marks, (const uint32_t *) M.chunk_off, M.shift, (const int *) ctx->d_slot_of,
+                         (const double *) ctx->d_rec);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipStreamSynchronize(ctx->stream));
+    }
+    return 0;
+  }
+  const size_t width = 5 + (size_t) ctx->nq, words = (size_t) total * width;
+  if (ensure_sums(ctx, words) || ensure_h_sums(ctx, words))
+    return 1;
+  hipLaunchKernelGGL(station_rows_kernel, dim3(grid_for(ctx->np)), dim3(256), 0, ctx->stream, a, ctx->nq,
+                     (const uint32_t *) ctx->d_marks, (const uint32_t *) M.chunk_off, M.shift, (const int *) ctx->d_slot_of,
+                     ctx->d_sums);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(ctx->h_sums, ctx->d_sums, words * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  for (size_t k = 0; k < total; k++) {
+    index[k] = (int) ctx->h_sums[k * width];
+    memcpy(rows + k * (width - 1), ctx->h_sums + k * width + 1, (width - 1) * sizeof(double));
+  }
+  return 0;
+}
+
 int mphip_set_radio_decay(mphip_ctx *ctx, int on, const int qnt[MPHIP_NRADIO]) {
   if (ctx && ahead_drop(ctx))
     return 1;
@@ -4017,7 +4357,7 @@ int mphip_test_sincosf(mphip_ctx *ctx, uint32_t bits_first, uint32_t count, floa
 }
 
 int mphip_test_libm(mphip_ctx *ctx, int op, const double *x, const double *y, long long n, double *out) {
-  if (!ctx || !x || !out || n < 0 || ((op & 15) == 2 && !y) || (op & ~31) || (op & 15) > 5)
+  if (!ctx || !x || !out || n < 0 || ((op & 15) == 2 && !y) || (op & ~31) || (op & 15) > 7)
     return 1;
   HIPCHK(hipSetDevice(ctx->device));
   const size_t bytes = (size_t) std::max<long long>(n, 1) * sizeof(double);

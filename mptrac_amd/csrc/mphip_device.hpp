@@ -88,6 +88,21 @@ __device__ __noinline__ double libm_sin(double x) {
   return handled ? r : sin(x);
 }
 
+// ... and up to |x| < 105414350 (mphip_libm_cos_wide / _sin_wide: the library's reduce_sincos branch) -- geo2cart's
+// cos / sin of a longitude in radians in the analysis outputs (write_sample, write_station).  Inlined: their call sites
+// are kernels of their own, not the step kernels.
+__device__ __forceinline__ double libm_cos_wide(double x) {
+  int handled;
+  const double r = mphip_libm_cos_wide(g_sincos_tab, x, &handled);
+  return handled ? r : cos(x);
+}
+
+__device__ __forceinline__ double libm_sin_wide(double x) {
+  int handled;
+  const double r = mphip_libm_sin_wide(g_sincos_tab, x, &handled);
+  return handled ? r : sin(x);
+}
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ---- constants (mptrac.h:255-345, 430-460, 535) ---------------------------

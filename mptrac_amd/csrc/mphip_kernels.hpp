@@ -3024,6 +3024,347 @@ __global__ __launch_bounds__(256, MPHIP_METEO_WAVES_PER_SIMD) void meteo_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// Analysis outputs that look at every particle in every time step: write_csi, write_prof (box sums), write_sample
+// (particles in a cylinder around each observation), write_station (particles that come near the station) -- the
+// particle loops of mptrac_amd/host/output.c.  Everything a loop decides by -- box index, latitude band, distance,
+// depth -- is computed in the loop's own operation order with IEEE divisions, the C library's log / cos / sin and no
+// contraction, in both builds of the library: counts, hit lists and flags are the host loop's, and every sum adds its
+// summands in ascending external index, so the sums are the loop's bits too.
+// ---------------------------------------------------------------------------
+
+// vertical weighting function (read_kernel / kernel_weight of output.c): the loop's bisection and interpolation
+struct KernelFn {
+  const double *kz, *kw;   // device arrays, nk nodes each
+  int nk;
+};
+
+__device__ __forceinline__ double kernel_weight_exact(const KernelFn &K, double z) {
+#pragma clang fp contract(off)
+  if (K.nk < 2)
+    return 1.0;
+  if (z < K.kz[0])
+    return K.kw[0];
+  if (z > K.kz[K.nk - 1])
+    return K.kw[K.nk - 1];
+  int lo = 0, hi = K.nk - 1;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) / 2;
+    if (K.kz[mid] > z)
+      hi = mid;
+    else
+      lo = mid;
+  }
+  const double slope = (K.kw[lo + 1] - K.kw[lo]) / (K.kz[lo + 1] - K.kz[lo]);
+  const double rise = slope * (z - K.kz[lo]);
+  return K.kw[lo] + rise;
+}
+
+// box_column / box_cell of output.c for a height z = Z(p): -1 outside, upper bounds exclusive
+__device__ __forceinline__ int box_cell_of_height(const BoxGrid &G, double lon, double lat, double z) {
+#pragma clang fp contract(off)
+  if (lon < G.lon0 || lon >= G.lon1 || lat < G.lat0 || lat >= G.lat1)
+    return -1;
+  const double dlon = (G.lon1 - G.lon0) / G.nx, dlat = (G.lat1 - G.lat0) / G.ny, dz = (G.z1 - G.z0) / G.nz;
+  const int ix = (int) ((lon - G.lon0) / dlon), iy = (int) ((lat - G.lat0) / dlat);
+  if (ix >= G.nx || iy >= G.ny)
+    return -1;
+  if (z < G.z0 || z >= G.z1)
+    return -1;
+  const int iz = (int) ((z - G.z0) / dz);
+  if (iz >= G.nz)
+    return -1;
+  return (ix * G.ny + iy) * G.nz + iz;
+}
+
+struct BoxSumArgs {
+  BoxGrid G;
+  double t0, t1;
+  int qnt, qnt_member, nmember, ncell;
+  KernelFn K;
+};
+
+// cell[i] = member * ncell + box of stored particle i (-1: not in the time step or outside the grid), val[i] =
+// kernel_weight * q[qnt]: the summand of write_csi's / write_prof's loop.  A member outside [0, nmember) leaves the
+// smallest external index of such a particle in *bad (the loop stops at the first one).
+__global__ __launch_bounds__(256) void box_member_cell_kernel(DevAtm a, BoxSumArgs B, int *__restrict__ cell,
+                                                              double *__restrict__ val, int *__restrict__ bad) {
+#pragma clang fp contract(off)
+  for (long long i = blockIdx.x * (long long) blockDim.x + threadIdx.x; i < a.np; i += (long long) gridDim.x * blockDim.x) {
+    int c = -1;
+    double v = 0.0;
+    const double time = a.time[i];
+    if (!(time < B.t0 || time > B.t1)) {
+      const int member = B.qnt_member >= 0 ? (int) a.q[B.qnt_member][i] : 0;
+      if (member < 0 || member >= B.nmember)
+        atomicMin(bad, a.ext ? a.ext[i] : (int) i);
+      else {
+        const double z = zfromp(a.p[i]);
+        const int b = box_cell_of_height(B.G, a.lon[i], a.lat[i], z);
+        if (b >= 0) {
+          c = member * B.ncell + b;
+          v = kernel_weight_exact(B.K, z) * a.q[B.qnt][i];
+        }
+      }
+    }
+    cell[i] = c;
+    val[i] = v;
+  }
+}
+
+struct ArrayVals {   // one value per stored particle, computed beforehand
+  const double *v;
+  __device__ __forceinline__ int count() const { return 1; }
+  __device__ __forceinline__ double get(int, long long i) const { return v[i]; }
+};
+
+// geo2cart(0, lon, lat, x) of output.c
+__device__ __forceinline__ void geo2cart_surface(double lon, double lat, double (&x)[3]) {
+#pragma clang fp contract(off)
+  const double r = kRE + 0.0, phi = deg2rad(lat), lam = deg2rad(lon);
+  const double rc = r * libm_cos_wide(phi);   // (below 2.426 the wide functions are mphip_libm_cos / _sin)
+  x[0] = rc * libm_cos_wide(lam);
+  x[1] = rc * libm_sin_wide(lam);
+  x[2] = r * libm_sin_wide(phi);
+}
+
+// dist2(a, b) of output.c: s = 0; s += (a[k] - b[k])^2, k = 0, 1, 2
+__device__ __forceinline__ double dist2_exact(const double *a, const double (&b)[3]) {
+#pragma clang fp contract(off)
+  const double d0 = a[0] - b[0], d1 = a[1] - b[1], d2 = a[2] - b[2];
+  double s = 0.0;
+  s = s + d0 * d0;
+  s = s + d1 * d1;
+  s = s + d2 * d2;
+  return s;
+}
+
+// ---- write_sample ------------------------------------------------------------------------------------------------------
+// One thread per particle: its Cartesian position once, in registers, then a walk over the observations of the time
+// step, which every workgroup stages in LDS kObsTile at a time -- {centre x, y, z, latitude, p_top, p_bottom}, 48 bytes
+// each (the host allows ~10^7 observations: tiles, not a fixed array).  Count, then fill: the first launch leaves the
+// number of observations every particle hits at the particle's EXTERNAL index; an exclusive scan of these turns them
+// into offsets, and the second launch writes (observation, weight * mass) records there -- so the records lie in
+// ascending external index, observations ascending within a particle, and nothing is ever truncated.  The stable radix
+// sort by observation then leaves every observation's records side by side in ascending external index, and one wave
+// per observation adds them in that order (sample_sum_kernel).
+constexpr int kObsTile = 256;
+constexpr int kObsFields = 6;
+
+struct SampleArgs {
+  double t0, t1;          // the time step, closed at both ends
+  double reach_lat;       // SAMPLE_DX in degrees of latitude
+  double reach2;          // SAMPLE_DX^2
+  double dz;              // SAMPLE_DZ (the depth test applies when > 0)
+  int nobs, qnt_m;
+  KernelFn K;
+};
+
+template <bool FILL>
+__global__ __launch_bounds__(256) void sample_hits_kernel(DevAtm a, SampleArgs S, const double *__restrict__ obs,
+                                                          uint32_t *__restrict__ cnt, const uint32_t *__restrict__ chunk_off,
+                                                          int chunk_shift, uint32_t *__restrict__ rec_obs,
+                                                          double *__restrict__ rec_val) {
+#pragma clang fp contract(off)
+  __shared__ double tile[kObsFields * kObsTile];
+  const long long nround = (a.np + 255) / 256 * 256;
+  for (long long base = blockIdx.x * 256LL; base < nround; base += (long long) gridDim.x * 256LL) {
+    const long long i = base + threadIdx.x;
+    bool live = false;
+    double x[3] = { 0.0, 0.0, 0.0 }, lat = 0.0, p = 0.0, wm = 0.0;
+    uint32_t pos = 0, end = 0, hits = 0, e = 0;
+    if (i < a.np) {
+      e = a.ext ? (uint32_t) a.ext[i] : (uint32_t) i;
+      const double time = a.time[i];
+      live = !(time < S.t0 || time > S.t1);
+      if (FILL) {   // cnt holds the scanned counts: a particle without hits has nothing to write
+        pos = cnt[e] + chunk_off[e >> chunk_shift];
+        end = cnt[e + 1] + chunk_off[(e + 1) >> chunk_shift];
+        live = live && end > pos;
+      }
+      if (live) {
+        lat = a.lat[i];
+        p = a.p[i];
+        geo2cart_surface(a.lon[i], lat, x);
+        if (FILL && S.qnt_m >= 0)
+          wm = kernel_weight_exact(S.K, S.K.nk < 2 ? 0.0 : zfromp(p)) * a.q[S.qnt_m][i];
+      }
+    }
+    if (__syncthreads_or(live)) {
+      for (int first = 0; first < S.nobs; first += kObsTile) {
+        const int m = S.nobs - first < kObsTile ? S.nobs - first : kObsTile;
+        __syncthreads();
+        for (int k = threadIdx.x; k < kObsFields * m; k += 256)
+          tile[k] = obs[(size_t) kObsFields * (size_t) first + (size_t) k];
+        __syncthreads();
+        if (live)
+          for (int o = 0; o < m; o++) {
+            const double *ob = tile + kObsFields * o;
+            if (fabs(ob[3] - lat) > S.reach_lat)
+              continue;
+            if (dist2_exact(ob, x) > S.reach2)
+              continue;
+            if (S.dz > 0 && (p > ob[5] || p < ob[4]))
+              continue;
+            if (FILL) {
+              if (pos < end) {
+                rec_obs[pos] = (uint32_t) (first + o);
+                rec_val[pos] = wm;
+              }
+              pos++;
+            } else
+              hits++;
+          }
+      }
+    }
+    if (!FILL && i < a.np) {
+      cnt[e] = hits;
+      if (i == 0)
+        cnt[a.np] = 0;   // (one element more: its offset is the number of records)
+    }
+  }
+}
+
+// out[o] = sum of the values of observation o's records in list order, out[nobs + o] = their number.  One wave per
+// observation: 64 records per round, loaded side by side (the next round is in flight while this one is added) and
+// added one after the other -- the serial order of the host loop.
+__global__ __launch_bounds__(256) void sample_sum_kernel(const uint32_t *__restrict__ sorted_obs, const int *__restrict__ ids,
+                                                         const double *__restrict__ rec_val, uint32_t nrec, int nobs,
+                                                         double *__restrict__ out) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & 63;
+  const long long wave = ((long long) blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((long long) gridDim.x * blockDim.x) >> 6;
+  for (long long o = wave; o < nobs; o += nwaves) {
+    uint32_t lo = 0, hi = nrec;   // first record with key >= o
+    while (lo < hi) {
+      const uint32_t mid = lo + (hi - lo) / 2;
+      if (sorted_obs[mid] < (uint32_t) o)
+        lo = mid + 1;
+      else
+        hi = mid;
+    }
+    const uint32_t b = lo;
+    hi = nrec;                     // first record with key > o
+    while (lo < hi) {
+      const uint32_t mid = lo + (hi - lo) / 2;
+      if (sorted_obs[mid] <= (uint32_t) o)
+        lo = mid + 1;
+      else
+        hi = mid;
+    }
+    const uint32_t e = lo;
+    double sum = 0.0;
+    double v = b + lane < e ? rec_val[ids[b + lane]] : 0.0;
+    for (uint32_t k = b; k < e; k += 64) {
+      const uint32_t kn = k + 64;
+      const double vn = kn < e && kn + lane < e ? rec_val[ids[kn + lane]] : 0.0;
+      const int m = e - k < 64 ? (int) (e - k) : 64;
+      for (int j = 0; j < m; j++)
+        sum = sum + __shfl(v, j);
+      v = vn;
+    }
+    if (lane == 0) {
+      out[o] = sum;
+      out[(size_t) nobs + (size_t) o] = (double) (e - b);
+    }
+  }
+}
+
+// ---- write_station -----------------------------------------------------------------------------------------------------
+// Filter, order-preserving compaction, gather.  station_mark_kernel decides for every stored particle and leaves 0 / 1 at
+// the particle's external index (and where the particle is stored); with a flag quantity it sets the flag in the same
+// launch, keeping the value it replaces.  The exclusive scan of the marks numbers the hits in ascending external index;
+// station_rows_kernel gathers their rows {external index, time, p, lon, lat, q[0 .. nq)}, or -- when the caller's buffer
+// is too small -- station_restore_kernel puts the flags back.
+struct StationArgs {
+  double t0, t1, s0, s1;   // the time step and [STAT_T0, STAT_T1]
+  double reach2;           // STAT_R^2
+  double centre[3];        // geo2cart of the station
+  int qnt_stat;
+};
+
+__global__ __launch_bounds__(256) void station_mark_kernel(DevAtm a, StationArgs S, uint32_t *__restrict__ mark,
+                                                           int *__restrict__ slot_of, double *__restrict__ old) {
+#pragma clang fp contract(off)
+  for (long long i = blockIdx.x * (long long) blockDim.x + threadIdx.x; i < a.np; i += (long long) gridDim.x * blockDim.x) {
+    const double tp = a.time[i];
+    bool hit = !(tp < S.t0 || tp > S.t1 || tp < S.s0 || tp > S.s1);
+    if (hit && S.qnt_stat >= 0 && (int) a.q[S.qnt_stat][i])
+      hit = false;
+    if (hit) {
+      double x[3];
+      geo2cart_surface(a.lon[i], a.lat[i], x);
+      hit = !(dist2_exact(S.centre, x) > S.reach2);
+    }
+    const long long e = a.ext ? (long long) a.ext[i] : i;
+    mark[e] = hit ? 1u : 0u;
+    if (hit) {
+      slot_of[e] = (int) i;
+      if (S.qnt_stat >= 0) {
+        old[i] = a.q[S.qnt_stat][i];
+        a.q[S.qnt_stat][i] = 1.0;
+      }
+    }
+    if (i == 0)
+      mark[a.np] = 0;
+  }
+}
+
+// (mark holds the scanned marks: external index e is a hit when its offset differs from the next one's)
+__global__ __launch_bounds__(256) void station_rows_kernel(DevAtm a, int nq, const uint32_t *__restrict__ mark,
+                                                           const uint32_t *__restrict__ chunk_off, int chunk_shift,
+                                                           const int *__restrict__ slot_of, double *__restrict__ rows) {
+  const int width = 5 + nq;
+  for (long long e = blockIdx.x * (long long) blockDim.x + threadIdx.x; e < a.np; e += (long long) gridDim.x * blockDim.x) {
+    const uint32_t at = mark[e] + chunk_off[e >> chunk_shift], next = mark[e + 1] + chunk_off[(e + 1) >> chunk_shift];
+    if (next == at)
+      continue;
+    const int i = slot_of[e];
+    double *row = rows + (size_t) at * (size_t) width;
+    row[0] = (double) e;
+    row[1] = a.time[i];
+    row[2] = a.p[i];
+    row[3] = a.lon[i];
+    row[4] = a.lat[i];
+    for (int iq = 0; iq < nq; iq++)
+      row[5 + iq] = a.q[iq][i];
+  }
+}
+
+__global__ __launch_bounds__(256) void station_restore_kernel(DevAtm a, int qnt_stat, const uint32_t *__restrict__ mark,
+                                                              const uint32_t *__restrict__ chunk_off, int chunk_shift,
+                                                              const int *__restrict__ slot_of, const double *__restrict__ old) {
+  for (long long e = blockIdx.x * (long long) blockDim.x + threadIdx.x; e < a.np; e += (long long) gridDim.x * blockDim.x) {
+    const uint32_t at = mark[e] + chunk_off[e >> chunk_shift], next = mark[e + 1] + chunk_off[(e + 1) >> chunk_shift];
+    if (next != at)
+      a.q[qnt_stat][slot_of[e]] = old[slot_of[e]];
+  }
+}
+
+// *total (64 bits, cleared by the caller) += the n counts: the check on the 32-bit scan
+__global__ __launch_bounds__(256) void count_total_kernel(const uint32_t *__restrict__ cnt, long long n,
+                                                          unsigned long long *__restrict__ total) {
+  __shared__ unsigned long long s_sum;
+  if (threadIdx.x == 0)
+    s_sum = 0;
+  __syncthreads();
+  unsigned long long mine = 0;
+  for (long long i = blockIdx.x * (long long) blockDim.x + threadIdx.x; i < n; i += (long long) gridDim.x * blockDim.x)
+    mine += cnt[i];
+  if (mine)
+    atomicAdd(&s_sum, mine);
+  __syncthreads();
+  if (threadIdx.x == 0 && s_sum)
+    atomicAdd(total, s_sum);
+}
+
+// total[0] = the scanned value of element n (the sum of all n counts)
+__global__ void scan_total_kernel(const uint32_t *__restrict__ scanned, const uint32_t *__restrict__ chunk_off, int chunk_shift,
+                                  long long n, uint32_t *__restrict__ total) {
+  if (blockIdx.x == 0 && threadIdx.x == 0)
+    total[0] = scanned[n] + chunk_off[n >> chunk_shift];
+}
+
+// ---------------------------------------------------------------------------
 // self-test kernels
 // ---------------------------------------------------------------------------
 
@@ -3223,8 +3564,8 @@ __global__ __launch_bounds__(256, MPHIP_STEP_WAVES_PER_SIMD) void piece_kernel(c
 }
 
 // out[i] = exp(x[i]) / log(x[i]) / pow(x[i], y[i]) / sqrt(x[i]) / cos(x[i]) / sin(x[i]) (op 0 .. 5) as the kernels
-// evaluate them: the C library's functions of mphip_libm.h and the square root of the Box-Muller radius; op + 16: exp /
-// log / pow tables copied to LDS first
+// evaluate them: the C library's functions of mphip_libm.h and the square root of the Box-Muller radius; op 6 / 7: cos /
+// sin of the analysis outputs (libm_cos_wide / libm_sin_wide); op + 16: exp / log / pow tables copied to LDS first
 __global__ __launch_bounds__(256) void test_libm_kernel(int op, const double *__restrict__ x, const double *__restrict__ y,
                                                          long long n, double *__restrict__ out) {
   __shared__ double s_tab[kLibmDoubles];
@@ -3242,6 +3583,8 @@ __global__ __launch_bounds__(256) void test_libm_kernel(int op, const double *__
     case 2: out[i] = libm_pow(lt, x[i], y[i]); break;
     case 4: out[i] = libm_cos(x[i]); break;
     case 5: out[i] = libm_sin(x[i]); break;
+    case 6: out[i] = libm_cos_wide(x[i]); break;
+    case 7: out[i] = libm_sin_wide(x[i]); break;
     default: out[i] = sqrt_rn(x[i]); break;
     }
   }

@@ -507,4 +507,68 @@ MPHIP_LIBM_FN double mphip_libm_sin(const double *sincos_tab, double x, int *han
   return mphip_libm_from_bits(0x7ff8000000000000ULL);
 }
 
+/* ---- sin and cos for 2.426265 <= |x| < 105414350 (high word below 0x419921fb: every longitude in radians) ----
+ * The next branch of s_sin.c: reduce_sincos takes the nearest multiple n of pi / 2 off the argument, pi / 2 in four
+ * parts (mp1, mp2, pp3, pp4), and leaves a + da; do_sincos is do_sin or do_cos of it by the parity of the quadrant
+ * (n for sin, n + 1 for cos), negated in the quadrants 2 and 3.  Fused operations of the two variants (glibc 2.35):
+ *   t = fma(x, hpinv, toint); xn = t - toint; n = low word of t;  y = fnma(xn, mp2, fnma(xn, mp1, x));
+ *   t2 = fnma(xn, pp3, y); db = fnma(xn, pp3, y - t2); b = fnma(xn, pp4, t2); db += fnma(xn, pp4, t2 - b)
+ * (both uses of each product xn pp3, xn pp4 are contracted, so neither product is ever rounded by itself).
+ * New functions, so that the call sites of mphip_libm_cos / _sin keep their code; below 2.426265 they are those. */
+#define MPHIP_SC_HPINV 0x1.45f306dc9c883p-1
+#define MPHIP_SC_TOINT 0x1.8000000000000p+52
+#define MPHIP_SC_MP1 0x1.921fb58000000p+0
+#define MPHIP_SC_MP2 (-0x1.dde973c000000p-27)
+#define MPHIP_SC_PP3 (-0x1.cb3b398000000p-55)
+#define MPHIP_SC_PP4 (-0x1.d747f23e32ed7p-83)
+
+MPHIP_LIBM_FN uint32_t mphip_libm_reduce_sincos(double x, double *a, double *da) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+  const double t = MPHIP_LIBM_FMA(x, MPHIP_SC_HPINV, MPHIP_SC_TOINT);
+  const double xn = t - MPHIP_SC_TOINT;
+  const double y = MPHIP_LIBM_FMA(-xn, MPHIP_SC_MP2, MPHIP_LIBM_FMA(-xn, MPHIP_SC_MP1, x));
+  const double t2 = MPHIP_LIBM_FMA(-xn, MPHIP_SC_PP3, y);
+  double db = MPHIP_LIBM_FMA(-xn, MPHIP_SC_PP3, y - t2);
+  const double b = MPHIP_LIBM_FMA(-xn, MPHIP_SC_PP4, t2);
+  db = db + MPHIP_LIBM_FMA(-xn, MPHIP_SC_PP4, t2 - b);
+  *a = b;
+  *da = db;
+  return (uint32_t) mphip_libm_bits(t) & 3u;
+}
+
+MPHIP_LIBM_FN double mphip_libm_do_sincos(const double *tab, double a, double da, uint32_t n) {
+  const double r = (n & 1u) ? mphip_libm_do_cos(tab, mphip_libm_fabs(a), a < 0.0 ? -da : da) : mphip_libm_do_sin(tab, a, da);
+  return (n & 2u) ? -r : r;
+}
+
+MPHIP_LIBM_FN double mphip_libm_cos_wide(const double *sincos_tab, double x, int *handled) {
+  const uint32_t k = (uint32_t) (mphip_libm_bits(x) >> 32) & 0x7fffffffu;
+  if (k < 0x400368fdu)
+    return mphip_libm_cos(sincos_tab, x, handled);
+  if (k < 0x419921fbu) {
+    double a, da;
+    const uint32_t n = mphip_libm_reduce_sincos(x, &a, &da);
+    *handled = 1;
+    return mphip_libm_do_sincos(sincos_tab, a, da, n + 1u);
+  }
+  *handled = 0;
+  return mphip_libm_from_bits(0x7ff8000000000000ULL);
+}
+
+MPHIP_LIBM_FN double mphip_libm_sin_wide(const double *sincos_tab, double x, int *handled) {
+  const uint32_t k = (uint32_t) (mphip_libm_bits(x) >> 32) & 0x7fffffffu;
+  if (k < 0x400368fdu)
+    return mphip_libm_sin(sincos_tab, x, handled);
+  if (k < 0x419921fbu) {
+    double a, da;
+    const uint32_t n = mphip_libm_reduce_sincos(x, &a, &da);
+    *handled = 1;
+    return mphip_libm_do_sincos(sincos_tab, a, da, n);
+  }
+  *handled = 0;
+  return mphip_libm_from_bits(0x7ff8000000000000ULL);
+}
+
 #endif

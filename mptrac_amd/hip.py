@@ -46,6 +46,12 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_void_p)
 _lib = None
 
 
+class MphipBox(C.Structure):
+    """mphip_box_t: a regular lon / lat / log-pressure-height box grid (CSI, profiles)."""
+    _fields_ = [("lon0", C.c_double), ("lon1", C.c_double), ("nx", C.c_int), ("lat0", C.c_double), ("lat1", C.c_double),
+                ("ny", C.c_int), ("z0", C.c_double), ("z1", C.c_double), ("nz", C.c_int)]
+
+
 class MphipError(RuntimeError):
     pass
 
@@ -111,6 +117,12 @@ def load(build=True):
     L.mphip_get_sort.argtypes = [C.c_void_p, _dp, C.POINTER(C.c_int)]
     L.mphip_grid_sums.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int), _dp, _dp]
     L.mphip_set_grid_kernel.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
+    _ip = C.POINTER(C.c_int)
+    L.mphip_box_sums.argtypes = [C.c_void_p, C.POINTER(MphipBox), C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp]
+    L.mphip_sample_obs.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, C.c_double, C.c_double,
+                                   C.c_int, _dp, _dp, _ip, _dp]
+    L.mphip_station_hits.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                     C.c_int, C.c_int, _ip, _ip, _dp]
     L.mphip_set_radio_decay.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.mphip_set_allreduce.argtypes = [C.c_void_p, ALLREDUCE_FN, C.c_void_p]
     L.mphip_comm_unique_id.argtypes = [C.c_void_p]
@@ -421,6 +433,47 @@ class Simulation:
         assert kz.shape == kw.shape
         self._chk(self.L.mphip_set_grid_kernel(self.h, len(kz), _ptr(kz, _dp), _ptr(kw, _dp)))
 
+    # -- the particle loops of write_csi / write_prof / write_sample / write_station -----------------------------
+    @staticmethod
+    def _kernel_fn(kernel):
+        kz, kw = (np.ascontiguousarray(a, dtype=np.float64) for a in (kernel if kernel is not None else ((), ())))
+        assert kz.shape == kw.shape
+        return kz, kw
+
+    def box_sums(self, box, t, qnt, nmember=1, qnt_member=-1, kernel=None):
+        """sum[nmember][nx * ny * nz] of kernel_weight * q[qnt] over the particles of the time step around t
+        (mphip_box_sums).  `box` = (lon0, lon1, nx, lat0, lat1, ny, z0, z1, nz), `kernel` = (kz, kw) or None."""
+        b = MphipBox(*box)
+        kz, kw = self._kernel_fn(kernel)
+        out = np.zeros((nmember, b.nx * b.ny * b.nz))
+        self._chk(self.L.mphip_box_sums(self.h, C.byref(b), t, qnt, nmember, qnt_member, len(kz), _ptr(kz, _dp), _ptr(kw, _dp),
+                                        _ptr(out, _dp)))
+        return out
+
+    def sample_obs(self, t0, t1, lon, lat, z, dx, dz=0.0, kernel=None):
+        """(count, mass) per observation: the particles inside the cylinder of radius dx [km] (half depth dz [km] if
+        positive) around it with t0 <= time <= t1, and their kernel-weighted mass (mphip_sample_obs)."""
+        lon, lat, z = (np.ascontiguousarray(a, dtype=np.float64) for a in (lon, lat, z))
+        assert lon.shape == lat.shape == z.shape
+        kz, kw = self._kernel_fn(kernel)
+        count = np.zeros(len(lon), dtype=np.int32)
+        mass = np.zeros(len(lon))
+        self._chk(self.L.mphip_sample_obs(self.h, t0, t1, len(lon), _ptr(lon, _dp), _ptr(lat, _dp), _ptr(z, _dp), dx, dz,
+                                          len(kz), _ptr(kz, _dp), _ptr(kw, _dp), _ptr(count, C.POINTER(C.c_int)), _ptr(mass, _dp)))
+        return count, mass
+
+    def station_hits(self, t, lon, lat, r, stat_t0, stat_t1, qnt_stat=-1, cap=1024):
+        """(nhit, index, rows[nhit][4 + nq]) of the particles write_station would list (mphip_station_hits); with
+        nhit > cap nothing was listed and no flag was set: (nhit, None, None)."""
+        n = C.c_int(0)
+        index = np.zeros(max(cap, 1), dtype=np.int32)
+        rows = np.zeros((max(cap, 1), 4 + self.nq))
+        self._chk(self.L.mphip_station_hits(self.h, t, lon, lat, r, stat_t0, stat_t1, qnt_stat, cap, C.byref(n),
+                                            _ptr(index, C.POINTER(C.c_int)), _ptr(rows, _dp)))
+        if n.value > cap:
+            return n.value, None, None
+        return n.value, index[:n.value].copy(), rows[:n.value].copy()
+
     def set_radio_decay(self, quantities, on=True):
         """module_radio_decay (mphip_set_radio_decay).  `quantities`: the quantity names of the particles (in quantity
         order, as given to ctl_from_quantities; the activities among them are found by name), {activity name: index},
@@ -515,7 +568,7 @@ class Simulation:
 
     def test_libm(self, fn, x, y=None, lds=False):
         """exp / log / pow / sqrt of the arrays as the kernels evaluate them (mphip_libm.h; tables from LDS if asked)."""
-        op = {"exp": 0, "log": 1, "pow": 2, "sqrt": 3, "cos": 4, "sin": 5}[fn] + (16 if lds else 0)
+        op = {"exp": 0, "log": 1, "pow": 2, "sqrt": 3, "cos": 4, "sin": 5, "cos_wide": 6, "sin_wide": 7}[fn] + (16 if lds else 0)
         x = np.ascontiguousarray(x, dtype=np.float64)
         if y is not None:
             y = np.ascontiguousarray(y, dtype=np.float64)

@@ -42,6 +42,7 @@ static int g_rank, g_world = 1;
 static int g_nq;                        /* ctl->nq of the last control upload */
 static int g_isosurf;                   /* ctl->isosurf of the last control upload */
 static int g_meteo_fields;              /* a module_meteo quantity is requested: upload the fields only it reads */
+static long g_output_downloads;         /* particle downloads of mptrac_write_output */
 
 /* Time steps handed over by mptrac_run_timestep wait here while they follow each other at the model's stride;
  * they go to the device as one mphip_run_timesteps call -- steps with nothing scheduled between them share a kernel
@@ -338,7 +339,8 @@ static const char *unsupported_qnt[] = {
   I(vtk_sphere, "VTK_SPHERE", "0") \
   I(hip_device, "HIP_DEVICE", "0") \
   I(hip_locality_interval, "HIP_LOCALITY_SORT_INTERVAL", "60") \
-  I(hip_met_prefetch, "HIP_MET_PREFETCH", "0")
+  I(hip_met_prefetch, "HIP_MET_PREFETCH", "0") \
+  I(hip_device_analysis, "HIP_DEVICE_ANALYSIS", "1")
 
 void mptrac_read_ctl(const char *filename, int argc, char *argv[], ctl_t *ctl) {
   LOG(1, "\nMassive-Parallel Trajectory Calculations (MPTRAC), MI355X build (%s)\n", mphip_version());
@@ -2605,6 +2607,35 @@ int mptrac_amd_world(void) {
   return g_world;
 }
 
+long mptrac_amd_output_downloads(void) {
+  return g_output_downloads;
+}
+
+/* the particle loops of the per-step analysis outputs on the device (output.c) */
+void mptrac_amd_device_box_sums(double lon0, double lon1, int nx, double lat0, double lat1, int ny, double z0, double z1,
+                                int nz, double t, int qnt, int nmember, int qnt_member, int nk, const double *kz,
+                                const double *kw, double *sum) {
+  const mphip_box_t box = { lon0, lon1, nx, lat0, lat1, ny, z0, z1, nz };
+  flush_steps();
+  if (mphip_box_sums(g_ctx, &box, t, qnt, nmember, qnt_member, nk, kz, kw, sum) != 0) {
+    if (strstr(mphip_last_error(g_ctx), "Ensemble ID out of range!"))
+      ERRMSG("Ensemble ID out of range!");
+    ERRMSG("HIP back end: %s", mphip_last_error(g_ctx));
+  }
+}
+
+void mptrac_amd_device_sample_obs(double t0, double t1, int nobs, const double *lon, const double *lat, const double *z,
+                                  double dx, double dz, int nk, const double *kz, const double *kw, int *count, double *mass) {
+  HIP(mphip_sample_obs(g_ctx, t0, t1, nobs, lon, lat, z, dx, dz, nk, kz, kw, count, mass));
+}
+
+int mptrac_amd_device_station_hits(double t, double lon, double lat, double r, double stat_t0, double stat_t1, int qnt_stat,
+                                   int cap, int *index, double *rows) {
+  int nhit = 0;
+  HIP(mphip_station_hits(g_ctx, t, lon, lat, r, stat_t0, stat_t1, qnt_stat, cap, &nhit, index, rows));
+  return nhit;
+}
+
 void mptrac_write_output(const char *dirname, const ctl_t *ctl, met_t *met0, met_t *met1, atm_t *atm,
                          depo_t *depo, const double t) {
   /* mptrac.c:8230-8330 without the radioactive deposition output */
@@ -2623,8 +2654,17 @@ void mptrac_write_output(const char *dirname, const ctl_t *ctl, met_t *met0, met
     || ctl->stat_basename[0] != '-';
   if ((ens_due || vtk_due || every_step) && g_world > 1)
     ERRMSG("CSI, ensemble, profile, sample, station and VTK output need all particles in one process!");
-  if (atm_due || ens_due || vtk_due || every_step)
+  /* ... run their particle loops on the device copy (HIP_DEVICE_ANALYSIS, the default): the host sees the particles
+   * only when the particle file, the ensemble or the VTK output is due, and `atm` is stale in between */
+  const int on_device = every_step && g_ctx != NULL && ctl->hip_device_analysis;
+  atm_t *const loop_atm = on_device ? NULL : atm;
+  if (t == ctl->t_start)
+    g_output_downloads = 0;
+  if (atm_due || ens_due || vtk_due || (every_step && !on_device)) {
     mptrac_update_host(NULL, NULL, NULL, NULL, NULL, atm);
+    if (g_ctx)
+      g_output_downloads++;
+  }
   if (atm_due) {
     sprintf(filename, "%s/%s_%s.%s", dirname, ctl->atm_basename, stamp,
             ctl->atm_type_out == 0 ? "tab" : ctl->atm_type_out == 1 ? "bin" : "nc");
@@ -2638,7 +2678,7 @@ void mptrac_write_output(const char *dirname, const ctl_t *ctl, met_t *met0, met
   }
   if (ctl->csi_basename[0] != '-') {
     sprintf(filename, "%s/%s.tab", dirname, ctl->csi_basename);
-    write_csi(filename, ctl, atm, t);
+    write_csi(filename, ctl, loop_atm, t);
   }
   if (ens_due) {
     sprintf(filename, "%s/%s_%s.tab", dirname, ctl->ens_basename, stamp);
@@ -2646,18 +2686,19 @@ void mptrac_write_output(const char *dirname, const ctl_t *ctl, met_t *met0, met
   }
   if (ctl->prof_basename[0] != '-') {
     sprintf(filename, "%s/%s.tab", dirname, ctl->prof_basename);
-    write_prof(filename, ctl, met0, met1, atm, t);
+    write_prof(filename, ctl, met0, met1, loop_atm, t);
   }
   if (ctl->sample_basename[0] != '-') {
     sprintf(filename, "%s/%s.tab", dirname, ctl->sample_basename);
-    write_sample(filename, ctl, met0, met1, atm, t);
+    write_sample(filename, ctl, met0, met1, loop_atm, t);
   }
   if (ctl->stat_basename[0] != '-') {
     sprintf(filename, "%s/%s.tab", dirname, ctl->stat_basename);
-    write_station(filename, ctl, atm, t);
+    write_station(filename, ctl, loop_atm, t);
     /* write_station marks the particles it has listed in the quantity "stat" of the host copy; on the
-     * reference's CPU path that is the model state, so the marks go back to the device */
-    if (ctl->qnt_stat >= 0)
+     * reference's CPU path that is the model state, so the marks go back to the device (its device form has set
+     * them there) */
+    if (ctl->qnt_stat >= 0 && !on_device)
       HIP(mphip_update_quantity(g_ctx, ctl->qnt_stat, atm->q[ctl->qnt_stat]));
   }
   if (vtk_due) {

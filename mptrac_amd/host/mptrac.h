@@ -212,6 +212,8 @@ typedef struct {
   int hip_device;
   int hip_locality_interval;
   int hip_met_prefetch;   /* HIP_MET_PREFETCH: read and upload the next meteo file beside the time steps */
+  int hip_device_analysis;   /* HIP_DEVICE_ANALYSIS (default 1): the particle loops of the CSI, profile, sample and station
+                                outputs run on the device; 0: on particles downloaded in every time step */
 } ctl_t;
 
 /* air parcels, as the reference (mptrac.h:3563-3583) */
@@ -365,6 +367,18 @@ void geo2cart(const double z, const double lon, const double lat, double *x);   
 void cart2geo(const double *x, double *z, double *lon, double *lat);            /* mptrac.c:74 */
 int mptrac_amd_read_obs_nc(const char *filename, double *rt, double *rz, double *rlon, double *rlat, double *robs);
 int mptrac_amd_world(void);   /* processes that share this run (1 without a launcher) */
+/* The particle loops of write_csi / write_prof, write_sample and write_station on the device copy of the particles
+ * (mphip_box_sums, mphip_sample_obs, mphip_station_hits; output.c calls them when it is given no host particles).
+ * Errors end the run with the message of the host loop they stand for. */
+void mptrac_amd_device_box_sums(double lon0, double lon1, int nx, double lat0, double lat1, int ny, double z0, double z1,
+                                int nz, double t, int qnt, int nmember, int qnt_member, int nk, const double *kz,
+                                const double *kw, double *sum);
+void mptrac_amd_device_sample_obs(double t0, double t1, int nobs, const double *lon, const double *lat, const double *z,
+                                  double dx, double dz, int nk, const double *kz, const double *kw, int *count, double *mass);
+int mptrac_amd_device_station_hits(double t, double lon, double lat, double r, double stat_t0, double stat_t1, int qnt_stat,
+                                   int cap, int *index, double *rows);
+/* particle downloads mptrac_write_output has made since the last mptrac_init (the driver's closing summary) */
+long mptrac_amd_output_downloads(void);
 /* a level field (selected by its offset in met_t) at a point, both snapshots blended in time: what
  * intpol_met_time_3d returns (mptrac.c:3112-3137) -- for the few profile / sample points of the writers */
 double mptrac_amd_intpol_3d(const met_t *met0, const met_t *met1, size_t field_offset, double ts, double p,

@@ -4,9 +4,13 @@
  * crossings and VTK point clouds (reference interface: src/mptrac.h write_csi ... write_vtk; file formats as
  * documented in docs/manual and the reference's tests/trac_test goldens).
  *
- * These run on the host, on the particle arrays mptrac_write_output has just downloaded -- as in the reference,
- * whose writers are host code behind mptrac_update_host.  They are output post-processing, not part of the
- * time-step loop; nothing here is called between two device kernels of a step.
+ * In the reference all of them are host code behind mptrac_update_host.  Here the four that look at the particles in
+ * EVERY time step -- write_csi, write_prof, write_sample, write_station -- have two forms of their particle loop:
+ * the host loop over downloaded particle arrays (atm != NULL; the reference for everything, and what runs with
+ * HIP_DEVICE_ANALYSIS 0), and the same loop on the device (atm == NULL: mphip_box_sums, mphip_sample_obs,
+ * mphip_station_hits through the mptrac_amd_device_* calls of mptrac.c), which returns the loop's bits without a
+ * download.  File handling, observation tables, box post-processing, statistics and the printed lines are shared.
+ * write_ens and write_vtk are periodic and run on downloaded particles only.
  *
  * The implementation is this repository's own: one regular lon / lat / z box grid type serves the CSI and
  * profile binning, one observation table type with a cursor serves the three observation-driven writers, and
@@ -303,7 +307,30 @@ static double spearman(const double *x, const double *y, int n) {
  * the scores derived from them, and error statistics of the (model, observation) pairs in which at least one
  * side is above its threshold.  Only the boxes of the call at an output time enter (the counters start from
  * zero in every call). */
-void write_csi(const char *filename, const ctl_t *ctl, const atm_t *atm, const double t) {
+/* the particle loop of write_csi on host particles: (kernel-weighted) mass per box and member */
+static void csi_loop_host(const ctl_t *ctl, const atm_t *atm, const box_grid *grid, const step_window *now, int members,
+                          const double *kz, const double *kw, int nk, double *model) {
+  const size_t ncell = (size_t) grid->nx * (size_t) grid->ny * (size_t) grid->nz;
+  for (int ip = 0; ip < atm->np; ip++) {
+    if (!inside(now, atm->time[ip]))
+      continue;
+    const int member = ctl->nens > 0 ? (int) atm->q[ctl->qnt_ens][ip] : 0;
+    if (member < 0 || member >= members)
+      ERRMSG("Ensemble ID out of range!");
+    const long c = box_cell(grid, atm->lon[ip], atm->lat[ip], Z(atm->p[ip]));
+    if (c >= 0)
+      model[(size_t) member * ncell + (size_t) c] += kernel_weight(kz, kw, nk, atm->p[ip]) * atm->q[ctl->qnt_m][ip];
+  }
+}
+
+/* ... and on the particles the device holds (mphip_box_sums) */
+static void csi_loop_device(const ctl_t *ctl, const box_grid *grid, double t, int members, const double *kz,
+                            const double *kw, int nk, double *model) {
+  mptrac_amd_device_box_sums(grid->lon0, grid->lon1, grid->nx, grid->lat0, grid->lat1, grid->ny, grid->z0, grid->z1, grid->nz, t,
+                             ctl->qnt_m, members, ctl->nens > 0 ? ctl->qnt_ens : -1, nk, kz, kw, model);
+}
+
+void write_csi(const char *filename, const ctl_t *ctl, const atm_t *atm, const double t) {   /* atm == NULL: on the device */
   static FILE *out;
   static obs_table obs;
   static box_grid grid;
@@ -375,16 +402,10 @@ void write_csi(const char *filename, const ctl_t *ctl, const atm_t *atm, const d
     }
 
   /* (kernel-weighted) mass per box and member -> column density [kg/m^2] */
-  for (int ip = 0; ip < atm->np; ip++) {
-    if (!inside(&now, atm->time[ip]))
-      continue;
-    const int member = ctl->nens > 0 ? (int) atm->q[ctl->qnt_ens][ip] : 0;
-    if (member < 0 || member >= members)
-      ERRMSG("Ensemble ID out of range!");
-    const long c = box_cell(&grid, atm->lon[ip], atm->lat[ip], Z(atm->p[ip]));
-    if (c >= 0)
-      model[(size_t) member * ncell + (size_t) c] += kernel_weight(kz, kw, nk, atm->p[ip]) * atm->q[ctl->qnt_m][ip];
-  }
+  if (atm)
+    csi_loop_host(ctl, atm, &grid, &now, members, kz, kw, nk, model);
+  else
+    csi_loop_device(ctl, &grid, t, members, kz, kw, nk, model);
 
   for (int e = 0; e < members; e++) {
     int boxes = 0, hits = 0, misses = 0, alarms = 0, n = 0;
@@ -512,6 +533,23 @@ void write_ens(const char *filename, const ctl_t *ctl, const atm_t *atm, const d
 /* For every column of the profile grid that holds observations of this time step and any particle mass: the
  * volume mixing ratio the mass of each box corresponds to, with the temperature, water vapour and ozone of the
  * meteo data at the box centres, next to the mean observation of the column. */
+/* the particle loop of write_prof on host particles: mass per box */
+static void prof_loop_host(const ctl_t *ctl, const atm_t *atm, const box_grid *grid, const step_window *now, double *mass) {
+  for (int ip = 0; ip < atm->np; ip++) {
+    if (!inside(now, atm->time[ip]))
+      continue;
+    const long c = box_cell(grid, atm->lon[ip], atm->lat[ip], Z(atm->p[ip]));
+    if (c >= 0)
+      mass[c] += atm->q[ctl->qnt_m][ip];
+  }
+}
+
+/* ... and on the particles the device holds (mphip_box_sums: one member, no weighting function) */
+static void prof_loop_device(const ctl_t *ctl, const box_grid *grid, double t, double *mass) {
+  mptrac_amd_device_box_sums(grid->lon0, grid->lon1, grid->nx, grid->lat0, grid->lat1, grid->ny, grid->z0, grid->z1, grid->nz, t,
+                             ctl->qnt_m, 1, -1, 0, NULL, NULL, mass);
+}
+
 void write_prof(const char *filename, const ctl_t *ctl, met_t *met0, met_t *met1, const atm_t *atm, const double t) {
   static FILE *out;
   static obs_table obs;
@@ -554,13 +592,10 @@ void write_prof(const char *filename, const ctl_t *ctl, met_t *met0, met_t *met1
       ocount[c]++;
     }
   }
-  for (int ip = 0; ip < atm->np; ip++) {
-    if (!inside(&now, atm->time[ip]))
-      continue;
-    const long c = box_cell(&grid, atm->lon[ip], atm->lat[ip], Z(atm->p[ip]));
-    if (c >= 0)
-      mass[c] += atm->q[ctl->qnt_m][ip];
-  }
+  if (atm)
+    prof_loop_host(ctl, atm, &grid, &now, mass);
+  else
+    prof_loop_device(ctl, &grid, t, mass);
   for (size_t c = 0; c < ncol; c++) {
     if (ocount[c] <= 0)
       continue;
@@ -601,6 +636,43 @@ void write_prof(const char *filename, const ctl_t *ctl, met_t *met0, met_t *met1
 /* For every observation of this time step: particles and (kernel-weighted) mass inside a cylinder of radius
  * SAMPLE_DX [km] (and half depth SAMPLE_DZ [km], if positive) around it -> column density, and the volume
  * mixing ratio it stands for when a molar mass and a depth are given. */
+/* the particle loop of write_sample around one observation on host particles: count and (kernel-weighted) mass */
+static void sample_loop_host(const ctl_t *ctl, const atm_t *atm, double t0, double t1, double obs_lat, const double *centre,
+                             double reach_lat, double reach2, double p_top, double p_bottom, const double *kz,
+                             const double *kw, int nk, int *count, double *mass) {
+  for (int ip = 0; ip < atm->np; ip++) {
+    if (atm->time[ip] < t0 || atm->time[ip] > t1 || fabs(obs_lat - atm->lat[ip]) > reach_lat)
+      continue;
+    double x[3];
+    geo2cart(0, atm->lon[ip], atm->lat[ip], x);
+    if (dist2(centre, x) > reach2)
+      continue;
+    if (ctl->sample_dz > 0 && (atm->p[ip] > p_bottom || atm->p[ip] < p_top))
+      continue;
+    if (ctl->qnt_m >= 0)
+      *mass += kernel_weight(kz, kw, nk, atm->p[ip]) * atm->q[ctl->qnt_m][ip];
+    (*count)++;
+  }
+}
+
+/* ... and around all observations [first, first + n) of the time step on the particles the device holds
+ * (mphip_sample_obs); the observations of a time step lie side by side in the table (ascending times) */
+static void sample_loop_device(const ctl_t *ctl, const obs_table *obs, double t0, double t1, const double *kz,
+                               const double *kw, int nk, int *first, int **count, double **mass) {
+  int n = 0;
+  *first = 0;
+  while (*first < obs->n && obs->t[*first] < t0)
+    (*first)++;
+  while (*first + n < obs->n && obs->t[*first + n] < t1)
+    n++;
+  if (n == 0)
+    return;
+  ALLOC(*count, int, n);
+  ALLOC(*mass, double, n);
+  mptrac_amd_device_sample_obs(t0, t1, n, obs->lon + *first, obs->lat + *first, obs->z + *first, ctl->sample_dx,
+                               ctl->sample_dz, nk, kz, kw, *count, *mass);
+}
+
 void write_sample(const char *filename, const ctl_t *ctl, met_t *met0, met_t *met1, const atm_t *atm, const double t) {
   static FILE *out;
   static obs_table obs;
@@ -629,6 +701,11 @@ void write_sample(const char *filename, const ctl_t *ctl, met_t *met0, met_t *me
   const double t0 = now.t0, t1 = now.t1;
   const double reach2 = SQR(ctl->sample_dx), area = M_PI * reach2;
   const double reach_lat = ctl->sample_dx * 180. / (M_PI * RE);   /* the radius in degrees of latitude */
+  /* on the device (atm == NULL): one call counts and weighs the particles around every observation of the step */
+  int first = 0, *dev_count = NULL;
+  double *dev_mass = NULL;
+  if (!atm)
+    sample_loop_device(ctl, &obs, t0, t1, kz, kw, nk, &first, &dev_count, &dev_mass);
   for (int i = 0; i < obs.n && obs.t[i] < t1; i++) {
     if (obs.t[i] < t0)
       continue;
@@ -637,18 +714,11 @@ void write_sample(const char *filename, const ctl_t *ctl, met_t *met0, met_t *me
     const double p_obs = P(obs.z[i]), p_top = P(obs.z[i] + ctl->sample_dz), p_bottom = P(obs.z[i] - ctl->sample_dz);
     double mass = 0;
     int count = 0;
-    for (int ip = 0; ip < atm->np; ip++) {
-      if (atm->time[ip] < t0 || atm->time[ip] > t1 || fabs(obs.lat[i] - atm->lat[ip]) > reach_lat)
-        continue;
-      double x[3];
-      geo2cart(0, atm->lon[ip], atm->lat[ip], x);
-      if (dist2(centre, x) > reach2)
-        continue;
-      if (ctl->sample_dz > 0 && (atm->p[ip] > p_bottom || atm->p[ip] < p_top))
-        continue;
-      if (ctl->qnt_m >= 0)
-        mass += kernel_weight(kz, kw, nk, atm->p[ip]) * atm->q[ctl->qnt_m][ip];
-      count++;
+    if (atm)
+      sample_loop_host(ctl, atm, t0, t1, obs.lat[i], centre, reach_lat, reach2, p_top, p_bottom, kz, kw, nk, &count, &mass);
+    else {
+      mass = dev_mass[i - first];
+      count = dev_count[i - first];
     }
     const double cd = mass / (1e6 * area);
     double vmr = NAN;
@@ -662,6 +732,8 @@ void write_sample(const char *filename, const ctl_t *ctl, met_t *met0, met_t *me
     fprintf(out, "%.2f %g %g %g %g %g %d %g %g %g\n", obs.t[i], obs.z[i], obs.lon[i], obs.lat[i], area, ctl->sample_dz,
             count, cd, vmr, obs.val[i]);
   }
+  free(dev_count);
+  free(dev_mass);
   if (t == ctl->t_stop) {
     fclose(out);
     out = NULL;
@@ -675,7 +747,58 @@ void write_sample(const char *filename, const ctl_t *ctl, met_t *met0, met_t *me
 
 /* Particles that come within STAT_R [km] of the station (horizontal distance) between STAT_T0 and STAT_T1 are
  * listed when they do; with a quantity "stat" each particle is listed once (the flag is set on the host copy:
- * mptrac_write_output hands the change back to the device). */
+ * mptrac_write_output hands the change back to the device -- or, with atm == NULL, on the device, which returns the
+ * rows to print). */
+static void station_row(FILE *out, const ctl_t *ctl, double tp, double p, double lon, double lat, const double *q, size_t stride) {
+  fprintf(out, "%.2f %g %g %g", tp, Z(p), lon, lat);
+  for (int iq = 0; iq < ctl->nq; iq++) {
+    fputc(' ', out);
+    fprintf(out, ctl->qnt_format[iq], q[(size_t) iq * stride]);
+  }
+  fputc('\n', out);
+}
+
+/* the particle loop of write_station on host particles: list, and flag, the particles that are at the station */
+static void station_loop_host(FILE *out, const ctl_t *ctl, atm_t *atm, const double *station, double t0, double t1, double reach2) {
+  for (int ip = 0; ip < atm->np; ip++) {
+    const double tp = atm->time[ip];
+    if (tp < t0 || tp > t1 || tp < ctl->stat_t0 || tp > ctl->stat_t1)
+      continue;
+    if (ctl->qnt_stat >= 0 && (int) atm->q[ctl->qnt_stat][ip])
+      continue;
+    double x[3];
+    geo2cart(0, atm->lon[ip], atm->lat[ip], x);
+    if (dist2(station, x) > reach2)
+      continue;
+    if (ctl->qnt_stat >= 0)
+      atm->q[ctl->qnt_stat][ip] = 1;
+    station_row(out, ctl, tp, atm->p[ip], atm->lon[ip], atm->lat[ip], &atm->q[0][ip], NP);
+  }
+}
+
+/* ... and on the particles the device holds (mphip_station_hits): the listed particles in ascending index, their flags
+ * set there */
+static void station_loop_device(FILE *out, const ctl_t *ctl, double t) {
+  static int cap = 1024;
+  for (;;) {
+    int *index;
+    double *rows;
+    ALLOC(index, int, cap);
+    ALLOC(rows, double, (size_t) cap * (size_t) (4 + ctl->nq));
+    const int nhit = mptrac_amd_device_station_hits(t, ctl->stat_lon, ctl->stat_lat, ctl->stat_r, ctl->stat_t0,
+                                                    ctl->stat_t1, ctl->qnt_stat, cap, index, rows);
+    for (int k = 0; k < nhit && nhit <= cap; k++) {
+      const double *row = rows + (size_t) k * (size_t) (4 + ctl->nq);
+      station_row(out, ctl, row[0], row[1], row[2], row[3], row + 4, 1);
+    }
+    free(index);
+    free(rows);
+    if (nhit <= cap)
+      break;
+    cap = nhit;   /* nothing was listed and no flag was set: once more with room for all */
+  }
+}
+
 void write_station(const char *filename, const ctl_t *ctl, atm_t *atm, const double t) {
   static FILE *out;
   static double station[3];
@@ -693,25 +816,10 @@ void write_station(const char *filename, const ctl_t *ctl, atm_t *atm, const dou
   if (!out)
     ERRMSG("write_station was not called at the start time of the run!");
   const double t0 = t - 0.5 * ctl->dt_mod, t1 = t + 0.5 * ctl->dt_mod, reach2 = SQR(ctl->stat_r);
-  for (int ip = 0; ip < atm->np; ip++) {
-    const double tp = atm->time[ip];
-    if (tp < t0 || tp > t1 || tp < ctl->stat_t0 || tp > ctl->stat_t1)
-      continue;
-    if (ctl->qnt_stat >= 0 && (int) atm->q[ctl->qnt_stat][ip])
-      continue;
-    double x[3];
-    geo2cart(0, atm->lon[ip], atm->lat[ip], x);
-    if (dist2(station, x) > reach2)
-      continue;
-    if (ctl->qnt_stat >= 0)
-      atm->q[ctl->qnt_stat][ip] = 1;
-    fprintf(out, "%.2f %g %g %g", tp, Z(atm->p[ip]), atm->lon[ip], atm->lat[ip]);
-    for (int iq = 0; iq < ctl->nq; iq++) {
-      fputc(' ', out);
-      fprintf(out, ctl->qnt_format[iq], atm->q[iq][ip]);
-    }
-    fputc('\n', out);
-  }
+  if (atm)
+    station_loop_host(out, ctl, atm, station, t0, t1, reach2);
+  else
+    station_loop_device(out, ctl, t);
   if (t == ctl->t_stop) {
     fclose(out);
     out = NULL;

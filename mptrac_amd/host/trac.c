@@ -117,6 +117,8 @@ int main(int argc, char *argv[]) {
     LOG(1, "TIMER_RUN_TIMESTEP = %.3f s", w_step);
     LOG(1, "TIMER_WRITE_OUTPUT = %.3f s", w_out);
     LOG(1, "TIMER_UPDATE_HOST = %.3f s    (rest of the queue + final download)", w1 - a4);
+    LOG(1, "PARTICLE_DOWNLOADS = %ld    (by mptrac_write_output in %ld calls; the final download not counted)",
+        mptrac_amd_output_downloads(), nsteps);
     LOG(1, "TIMER_WITHOUT_MET_AND_OUTPUT = %.3f s    (%.3e particle-steps/s)", w1 - w0 - w_met - w_out,
         nsteps > 1 && w1 - w0 - w_met - w_out > 0 ? (double) atm->np * (double) (nsteps - 1) / (w1 - w0 - w_met - w_out) : 0.0);
 

@@ -123,12 +123,16 @@ def locate(sections):
     return found
 
 
-# s_sin.c / usncs.h: sn3, sn5, cs2, cs4, cs6 (table path), s1..s5 (Taylor path), hp0 + hp1 = pi / 2, big = 1.5 x 2^45, 0.126
+# s_sin.c / usncs.h: sn3, sn5, cs2, cs4, cs6 (table path), s1..s5 (Taylor path), hp0 + hp1 = pi / 2, big = 1.5 x 2^45, 0.126,
+# and the constants of reduce_sincos
 SINCOS_K = [("sn3", "-0x1.5555555555515p-3"), ("sn5", "0x1.11110e829872fp-7"), ("cs2", "0x1.0000000000000p-1"),
             ("cs4", "-0x1.5555555555535p-5"), ("cs6", "0x1.6c16bedd9e239p-10"), ("s1", "-0x1.5555555555555p-3"),
             ("s2", "0x1.1111111110ecep-7"), ("s3", "-0x1.a01a019db08b8p-13"), ("s4", "0x1.71de27b9a7ed9p-19"),
             ("s5", "-0x1.addffc2fcdf59p-26"), ("hp0", "0x1.921fb54442d18p+0"), ("hp1", "0x1.1a62633145c07p-54"),
-            ("big", "0x1.8000000000000p+45"), ("taylor_below", "0x1.020c49ba5e354p-3")]
+            ("big", "0x1.8000000000000p+45"), ("taylor_below", "0x1.020c49ba5e354p-3"),
+            # reduce_sincos (2.426265 <= |x| < 105414350): 2 / pi, 1.5 x 2^52, pi / 2 in four parts
+            ("hpinv", "0x1.45f306dc9c883p-1"), ("toint", "0x1.8000000000000p+52"), ("mp1", "0x1.921fb58000000p+0"),
+            ("mp2", "-0x1.dde973c000000p-27"), ("pp3", "-0x1.cb3b398000000p-55"), ("pp4", "-0x1.d747f23e32ed7p-83")]
 
 
 def hexd(v):
@@ -169,7 +173,7 @@ def main():
         w("#define MPHIP_LIBM_POW_TAB_INIT \\\n")
         w(", \\\n".join("  %s, %s, %s" % (hexd(pw["tab"][4 * i]), hexd(pw["tab"][4 * i + 2]), hexd(pw["tab"][4 * i + 3])) for i in range(N)) + "\n\n")
         sc = f["sincos"]
-        w("/* sin / cos: sn3, sn5, cs2, cs4, cs6, s1..s5, hp0, hp1, big, 0.126 */\n")
+        w("/* sin / cos: sn3, sn5, cs2, cs4, cs6, s1..s5, hp0, hp1, big, 0.126, hpinv, toint, mp1, mp2, pp3, pp4 */\n")
         w("static const double mphip_libm_sincos_k[%d] = {\n  %s\n};\n" % (len(SINCOS_K), ",\n  ".join(v for _, v in SINCOS_K)))
         w("/* sin / cos: {sin, tail, cos, tail} of k / 128, k = 0 .. 109 */\n")
         w("#define MPHIP_LIBM_SINCOS_TAB_INIT \\\n")

@@ -8,10 +8,19 @@ the whole loop, hand-overs and outputs included -- next to the rate without outp
 rocprofv3 trace of the same command.  GPU box; files go to /tmp (8 GB), the report to gpurun_out/trac_dropin/.
 
   tools/gpu_trac_dropin.py [--particles 1e7] [--hours 3] [--no-trace]
+
+--analysis: instead, the same run with a CSI and a sample output in EVERY time step (CSI 360 x 180 x 1, --obs
+observations per step at particle positions, SAMPLE_DX 50 km) and no other output before T_STOP, once with the host loops
+over a download per step (HIP_DEVICE_ANALYSIS 0) and once with their particle loops on the device (1), in one process
+after the other; checks that csi.tab and sample.tab are the same files and writes the timers of both and their ratio to
+profiles/analysis_outputs_trac.json.
 """
 import argparse
 import csv
+import filecmp
 import glob
+import json
+import math
 import os
 import re
 import subprocess
@@ -30,11 +39,61 @@ from mptrac_amd.synth import synthetic_met, synthetic_particles  # noqa: E402
 T0 = 0.0
 
 
+def analysis_runs(args, trac, tmp, keys, atm, env):
+    """CSI + sample output in every step: host loops (key 0) against device loops (key 1)"""
+    n, nsteps = len(atm["time"]), 20 * args.hours + 1
+    with open(os.path.join(tmp, "obs.tab"), "w") as f:
+        for k in range(nsteps):
+            for ip in range(args.obs):      # where particles start; column: time, altitude, lon, lat, value
+                j = (k * args.obs + ip) * 7919 % n
+                f.write("%.2f %g %.6f %.6f %g\n" % (T0 + 180.0 * k, 7.0 * math.log(1013.25 / atm["p"][j]), atm["lon"][j], atm["lat"][j], ip % 2))
+    res = {"particles": n, "calls": nsteps, "observations_per_step": args.obs, "sample_dx_km": 50, "csi_grid": [360, 180, 1], "runs": {}}
+    for key in (0, 1):
+        out = os.path.join(tmp, "key%d" % key)
+        os.makedirs(out)
+        hf.write_ctl(os.path.join(out, "trac.ctl"), dict(
+            keys, ATM_DT_OUT=86400 * 365, ATM_BASENAME="atm", GRID_BASENAME="-", HIP_DEVICE_ANALYSIS=key,
+            CSI_BASENAME="csi", CSI_DT_OUT=3600, CSI_OBSFILE=os.path.join(tmp, "obs.tab"), CSI_NX=360, CSI_NY=180,
+            CSI_MODMIN=1e-12, CSI_OBSMIN=0.5, SAMPLE_BASENAME="sample", SAMPLE_OBSFILE=os.path.join(tmp, "obs.tab"),
+            SAMPLE_DX=50))
+        open(os.path.join(out, "dirlist"), "w").write(out + "\n")
+        os.symlink(os.path.join(tmp, "atm_in"), os.path.join(out, "atm_in"))
+        best = None
+        for rep in range(2):      # (the second run reads the meteo files from the page cache)
+            r = subprocess.run([trac, os.path.join(out, "dirlist"), "trac.ctl", "atm_in"], cwd=out, env=env,
+                               stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+            text = r.stdout.decode()
+            assert r.returncode == 0, text[-3000:]
+            row = {}
+            for name in ("TIMER_TIMESTEPS", "TIMER_GET_MET", "TIMER_WRITE_OUTPUT", "TIMER_UPDATE_HOST", "PARTICLE_DOWNLOADS"):
+                m = re.search(name + r" = ([0-9.eE+-]+)", text)
+                if m:
+                    row[name] = float(m.group(1))
+            print("HIP_DEVICE_ANALYSIS %d, run %d: %s" % (key, rep + 1, json.dumps(row)), flush=True)
+            if best is None or row["TIMER_TIMESTEPS"] < best["TIMER_TIMESTEPS"]:
+                best = row
+        res["runs"]["HIP_DEVICE_ANALYSIS %d" % key] = best
+    for name in ("csi.tab", "sample.tab"):
+        assert filecmp.cmp(os.path.join(tmp, "key0", name), os.path.join(tmp, "key1", name), shallow=False), name
+    res["files_identical"] = True
+    a, b = res["runs"]["HIP_DEVICE_ANALYSIS 0"], res["runs"]["HIP_DEVICE_ANALYSIS 1"]
+    res["ratio_timesteps_key0_over_key1"] = a["TIMER_TIMESTEPS"] / b["TIMER_TIMESTEPS"]
+    if "TIMER_WRITE_OUTPUT" in a and b.get("TIMER_WRITE_OUTPUT"):
+        res["ratio_write_output_key0_over_key1"] = a["TIMER_WRITE_OUTPUT"] / b["TIMER_WRITE_OUTPUT"]
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "analysis_outputs_trac.json"), "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--particles", type=float, default=1e7)
     ap.add_argument("--hours", type=int, default=3)
     ap.add_argument("--no-trace", action="store_true")
+    ap.add_argument("--analysis", action="store_true")
+    ap.add_argument("--obs", type=int, default=20)
     args = ap.parse_args()
     n = int(args.particles)
     out_root = os.path.join(ROOT, "gpurun_out", "trac_dropin")
@@ -58,6 +117,10 @@ def main():
     report = [f"tools/gpu_trac_dropin.py: {n} particles, {args.hours} h ({20 * args.hours + 1} calls of mptrac_run_timestep), "
               f"C3 meteorology 721 x 361 x 137 as MET_TYPE 1 files (inputs generated in {t_gen:.0f} s)"]
     env = dict(os.environ, TMPDIR="/tmp")
+    if args.analysis:
+        analysis_runs(args, trac, tmp, keys, atm, env)
+        subprocess.run(["rm", "-rf", tmp])
+        return
     for name, extra in (("outputs every hour (1 grid + 1 particle file per interval)", {}),
                         ("no outputs", {"ATM_BASENAME": "-", "GRID_BASENAME": "-"}),
                         ("no outputs, next meteo file read beside the time steps (HIP_MET_PREFETCH 1)",
