@@ -1000,6 +1000,8 @@ int launch_step(mphip_ctx *ctx, unsigned mask, double t, const RngCtr &rng = {},
   }
   if (sel < kMaskGenericMLMulti && (sel & kPblClosure))
     lds += (size_t) (kLibmDoubles - kLibmLogExpDoubles) * sizeof(double);
+  if (step_kernel_parks(sel))   // + the thread-private parking area in front of them (step_kernel: park_slot)
+    lds += kParkBytes;
   // (-DMPHIP_QUICK: only the instantiations step_kernel_mask selects in that build)
   switch (sel) {
 #define STEP_CASE(M)                                                                                  \

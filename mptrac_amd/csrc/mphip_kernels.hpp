@@ -625,12 +625,40 @@ struct RngEarly {
 #ifndef MPHIP_PBL_WAVES_PER_SIMD
 #define MPHIP_PBL_WAVES_PER_SIMD 4
 #endif
+// Thread-private parking area in LDS of the lean pressure-level multi-step instantiations: what a particle needs in
+// every step of the launch and no step changes -- its external index and, for the sedimentation, q[qnt_rp] and
+// q[qnt_rhop] -- is loaded once per particle and parked there, structure of arrays (slot[k][threadIdx.x]: a wave's
+// reads hit consecutive banks).  A slot belongs to one thread (no barrier); a thread that walks several particles
+// reuses it.  The area lies at the START of the dynamic LDS block, in front of the axes (the issue of a slot's address
+// is then a constant offset on the lane's), and the lane is taken from the particle index where a slot is used
+// (every block's range starts at a multiple of 256 -- block_geom --, so i & 255 == threadIdx.x): no register holds
+// an address across the steps.  No module that runs in these launches writes the two quantities: module_bound_cond
+// writes m, vmr, the trace gases and aoa, the decay and deposition modules m, vmr, loss_rate and mloss_*,
+// module_radio_decay its nuclides -- indices of other quantity names.  The instantiations with the boundary-layer
+// closure keep their per-step loads: with pow's tables their LDS has no room left under the 40 KiB that let four
+// workgroups share a CU.
+constexpr bool step_kernel_parks(unsigned ct) {
+  return ct < kMaskGenericMLMulti && (ct & kMultiStep) && !(ct & (kMLWinds | kPblClosure))
+    && (ct & (MPHIP_MOD_DIFF_TURB | MPHIP_MOD_DIFF_MESO | MPHIP_MOD_CONVECTION | MPHIP_MOD_SEDI));
+}
+constexpr int kParkDoubles = 256 * 2 + 128;   // rp[256], rhop[256], ext[256] (int)
+constexpr size_t kParkBytes = kParkDoubles * sizeof(double);
+enum { kParkRp = 0, kParkRhop = 256, kParkExt = 512 };   // (offsets in doubles)
+template <class T>
+__device__ __forceinline__ T *park_slot(double *area, int slot, long long i) {
+  unsigned lane = (unsigned) i & 255u;
+  asm volatile("" : "+v"(lane));   // (the address is formed here, not once in front of the step loop)
+  return (T *) (area + slot) + lane;
+}
+
 template <unsigned CT>
 __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRuntimeMask<CT> && (CT & kPblClosure) ? MPHIP_PBL_WAVES_PER_SIMD : !kRuntimeMask<CT> ? ((CT & kMultiStep) ? MPHIP_MULTI_WAVES_PER_SIMD
                                                         : (CT & MPHIP_MOD_ADVECT) || CT == MPHIP_MOD_TIMESTEPS ? MPHIP_LEAN_WAVES_PER_SIMD : MPHIP_SPLITB_WAVES_PER_SIMD)
                                    : (CT == kMaskGenericPL ? MPHIP_STEP_WAVES_PER_SIMD : MPHIP_GENERIC_WAVES_PER_SIMD)) void step_kernel(
   const StepParams S) {
-  extern __shared__ double s_axes[];
+  extern __shared__ double s_lds[];
+  constexpr bool park = step_kernel_parks(CT);
+  double *const s_axes = s_lds + (park ? kParkDoubles : 0);   // (the parking area in front)
   const unsigned mask = kRuntimeMask<CT> ? S.mask : (CT & ~kTemplateFlags);
   // column indices of the model-level fields: 32 bits in the lean instantiations (launch_step's size check)
   using MLCol = std::conditional_t<kLeanML<CT> && MPHIP_ML_OFF32 && !kBig<CT>, uint32_t, size_t>;
@@ -664,7 +692,7 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
   long long first, last;
   block_range(S, a.np, first, last);
 
-  for (long long i = first + threadIdx.x; i < last; i += blockDim.x) {
+  for (long long i = first + threadIdx.x; i < last; i += (park ? 256 : blockDim.x)) {   // (256: the launch's block size)
 #if MPHIP_PARAMS_RELOAD
     // re-read the launch parameters from the kernarg segment in every iteration (scalar loads at
     // the point of use) instead of keeping all of them live across the loop, which spills SGPRs
@@ -716,6 +744,14 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
         wp = ld_state(&a.wp[i]);
       }
     }
+    if constexpr (park) {   // (behind the gather of module_sort, which writes a.q[k][i])
+      if (a.ext)
+        *park_slot<int>(s_lds, kParkExt, i) = ld_state(&a.ext[i]);
+      if (((CT & kGated) ? mask & S.mask : mask) & MPHIP_MOD_SEDI) {
+        *park_slot<double>(s_lds, kParkRp, i) = ld_state(&a.q[ctl.qnt_rp][i]);
+        *park_slot<double>(s_lds, kParkRhop, i) = ld_state(&a.q[ctl.qnt_rhop][i]);
+      }
+    }
     }
     if (CT == kMaskGeneric && (mask & (MPHIP_MOD_ADVECT_INIT | MPHIP_MOD_ISOSURF_INIT))) {   // no dt guard (check_dt = 0)
       P.dt = 0;
@@ -758,7 +794,15 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
       continue;
     }
     // random numbers belong to the external slot (rs[3 * ip + k], mptrac.c:4645)
-    const uint64_t g = (uint64_t) (a.ip0 + (a.ext ? (long long) ld_state(&a.ext[i]) : i));
+    // (parking instantiations: every module that draws reads the index from the slot -- held from here it would
+    // occupy two registers through the advection)
+    const uint64_t g_held = park ? 0 : (uint64_t) (a.ip0 + (a.ext ? (long long) ld_state(&a.ext[i]) : i));
+    auto g_now = [&]() -> uint64_t {
+      if constexpr (park)
+        return (uint64_t) (a.ip0 + (a.ext ? (long long) *park_slot<int>(s_lds, kParkExt, i) : i));
+      else
+        return g_held;
+    };
 
     // specialised instantiations = RK4 on pressure levels (launch_step): 4 stages, all hooks run
     constexpr bool early = MPHIP_RNG_EARLY && !kRuntimeMask<CT> && (CT & MPHIP_MOD_ADVECT) && !(CT & kTwoStage) && !kLeanML<CT>;   // (the hooks belong to the four-stage integrator)
@@ -767,7 +811,7 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
     pre.ctr_turb = c_turb;
     pre.ctr_meso = c_meso;
     pre.ctr_conv = c_conv;
-    pre.g = g;
+    pre.g = early ? g_now() : 0;
     pre.ltab = ltab;
 
     // the specialised instantiations run the lean versions (lat/lon grid, pressure table: launch_step)
@@ -818,9 +862,9 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
     const unsigned opt = (lean && (CT & kGated)) ? (mask & S.mask & kOptionalModules) : (mask & kOptionalModules);
     if (opt & MPHIP_MOD_DIFF_TURB) {
       if (lean)
-        diff_turb_fast(ctl, M, A, *clim, P, c_turb, g, early ? pre.turb : nullptr, ltab);
+        diff_turb_fast(ctl, M, A, *clim, P, c_turb, g_now(), early ? pre.turb : nullptr, ltab);
       else
-        diff_turb(ctl, M, A, *clim, P, c_turb, g, early ? pre.turb : nullptr, ltab);
+        diff_turb(ctl, M, A, *clim, P, c_turb, g_now(), early ? pre.turb : nullptr, ltab);
     }
 #ifndef MPHIP_PBL_EMPTY
 #define MPHIP_PBL_EMPTY 0     // 1: experiment -- the kPblClosure instantiations without the closure's code
@@ -837,7 +881,7 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
       }
       if constexpr (lean_pbl) {   // a call: the kernel keeps the registers of the instantiation without the closure
         PblState st = { P.time, P.lon, P.lat, P.p, P.dt, up, vp, wp };
-        st = diff_pbl_call(&M, A, st, c_pbl, g, ltab);
+        st = diff_pbl_call(&M, A, st, c_pbl, g_now(), ltab);
         P.lon = st.lon;
         P.lat = st.lat;
         P.p = st.p;
@@ -846,7 +890,7 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
         wp = st.wp;
         wind_cache_reset(wc, true);   // (the cached corners do not cross the call: module_diff_meso gathers its own)
       } else
-        diff_pbl<false>(M, A, P, up, vp, wp, c_pbl, g, ltab);
+        diff_pbl<false>(M, A, P, up, vp, wp, c_pbl, g_now(), ltab);
       if (!(store_once && held)) {
         st_state(&a.up[i], up);
         st_state(&a.vp[i], vp);
@@ -862,9 +906,9 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
       if (kGenericML<CT>)
         wind_cache_reset(wc, true);
       if (lean)   // (without a pressure-level advection before it there are no cached corners: the streaming version)
-        diff_meso_fast<!(CT & MPHIP_MOD_ADVECT) || kLeanML<CT>, kBig<CT>>(ctl, M, A, P, up, vp, wp, c_meso, g, early ? pre.meso : nullptr, wc, ltab);
+        diff_meso_fast<!(CT & MPHIP_MOD_ADVECT) || kLeanML<CT>, kBig<CT>>(ctl, M, A, P, up, vp, wp, c_meso, g_now(), early ? pre.meso : nullptr, wc, ltab);
       else
-        diff_meso(ctl, M, A, P, up, vp, wp, c_meso, g, early ? pre.meso : nullptr, wc, ltab);
+        diff_meso(ctl, M, A, P, up, vp, wp, c_meso, g_now(), early ? pre.meso : nullptr, wc, ltab);
       if (!store_once) {
         st_state(&a.up[i], up);
         st_state(&a.vp[i], vp);
@@ -874,12 +918,13 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
     if (lean) {
       if (opt & (MPHIP_MOD_CONVECTION | MPHIP_MOD_SEDI)) {
         const bool sedi_on = (opt & MPHIP_MOD_SEDI) != 0;
-        conv_sedi_fast<kBig<CT>>(ctl, M, A, P, opt, c_conv, g, early ? &pre.conv : nullptr,
-                       sedi_on ? ld_state(&a.q[ctl.qnt_rp][i]) : 0.0, sedi_on ? ld_state(&a.q[ctl.qnt_rhop][i]) : 0.0, ltab);
+        conv_sedi_fast<kBig<CT>>(ctl, M, A, P, opt, c_conv, g_now(), early ? &pre.conv : nullptr,
+                       !sedi_on ? 0.0 : park ? *park_slot<double>(s_lds, kParkRp, i) : ld_state(&a.q[ctl.qnt_rp][i]),
+                       !sedi_on ? 0.0 : park ? *park_slot<double>(s_lds, kParkRhop, i) : ld_state(&a.q[ctl.qnt_rhop][i]), ltab);
       }
     } else {
       if (opt & MPHIP_MOD_CONVECTION)
-        convection(ctl, M, A, P, c_conv, g, early ? &pre.conv : nullptr);
+        convection(ctl, M, A, P, c_conv, g_now(), early ? &pre.conv : nullptr);
       if (opt & MPHIP_MOD_SEDI)
         sedimentation(M, A, P, a.q[ctl.qnt_rp][i], a.q[ctl.qnt_rhop][i]);
     }
