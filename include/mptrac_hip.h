@@ -100,8 +100,9 @@ enum {
   MPHIP_MOD_CHEM_GRID  = 1 << 22,  /* module_chem_grid   (own kernels; between module_mixing and module_oh_chem) */
   MPHIP_MOD_H2O2_CHEM  = 1 << 23,  /* module_h2o2_chem   (own kernel; between module_oh_chem and module_wet_depo) */
   MPHIP_MOD_TRACER_CHEM = 1 << 24, /* module_tracer_chem (own kernel; between module_h2o2_chem and module_wet_depo) */
-  MPHIP_MOD_RADIO_DECAY = 1 << 25  /* module_radio_decay mptrac.c:5493-5572 (step kernel's tail; between
+  MPHIP_MOD_RADIO_DECAY = 1 << 25, /* module_radio_decay mptrac.c:5493-5572 (step kernel's tail; between
                                       module_tracer_chem and module_wet_depo; mphip_set_radio_decay) */
+  MPHIP_MOD_RADIO_DEPO = 1 << 26   /* module_radio_depo (own kernels; behind the step's tail; mphip_set_radio_depo) */
 };
 
 /* Radionuclide activities of module_radio_decay and module_mixing (quantities Arn222, Apb210, Abe7, Acs137, Ai131,
@@ -324,7 +325,8 @@ int mphip_run_timestep(mphip_ctx *ctx, double t);
  * != 0: a kernel of its own between module_mixing and module_wet_depo), module_chem_grid and module_h2o2_chem (with
  * either chemistry on: kernels of their own in the same place, in the order chem_grid, oh_chem, h2o2_chem),
  * module_tracer_chem (TRACER_CHEM != 0: a kernel of its own behind them and before module_wet_depo).
- * module_radio_decay (mphip_set_radio_decay) is no obstacle: it runs in the tail of the step kernel. */
+ * module_radio_decay (mphip_set_radio_decay) is no obstacle: it runs in the tail of the step kernel.  module_radio_depo
+ * (mphip_set_radio_depo, on with a depositing activity and a deposition module): a launch of its own behind the tail. */
 int mphip_run_timesteps(mphip_ctx *ctx, double t_first, int nsteps);
 /* One reference module_* on its own (same state hand-over through the device
  * copy of cache->dt); `modules` is one MPHIP_MOD_* bit or an OR of the
@@ -395,6 +397,39 @@ int mphip_station_hits(mphip_ctx *ctx, double t, double lon, double lat, double 
  * module_meteo quantity (also when mphip_update_ctl later makes it one).  qnt may be NULL when on == 0: nothing
  * registered. */
 int mphip_set_radio_decay(mphip_ctx *ctx, int on, const int qnt[MPHIP_NRADIO]);
+/* module_radio_depo (RADIO_DEPO; the reference's depo_t): the activity module_wet_depo and module_dry_depo take out of the
+ * air, and a gridded inventory of where it lands.  The reference's source was not available (as for the half-lives of
+ * module_radio_decay): what follows is this project's own definition, restated in tests/refradiodepo.py.
+ *   The ground grid is the longitude / latitude part of `grid` (nz must be 1; z0, z1 are ignored), ncell = nx ny.  The
+ * inventory is inv[2][MPHIP_NRADIO][ncell + 1] [Bq]: kind 0 wet, 1 dry; nuclides in MPHIP_RN_* order; cell ix ny + iy with
+ * the arithmetic of mphip_box_sums' boxes (upper bounds exclusive); the last element of every plane collects the deposits
+ * outside the grid.  The aerosol-bound Apb210, Abe7, Acs137, Ai131 deposit; the noble gases Arn222 and Axe133 never do --
+ * their planes and those of absent activities stay zero.
+ *   on != 0: in a time step at t (mphip_run_timestep(s)) with a depositing activity registered (mphip_set_radio_decay) and
+ * module_wet_depo or module_dry_depo configured, a launch behind the step's tail (1) decays the inventory on the ground:
+ * every element of nuclide k times exp(-lambda_k (t - t_inv)), the C library's exp, then t_inv = t (the first step only
+ * sets t_inv; no ingrowth on the ground: Rn-222 is never deposited); (2) for every particle with dt != 0, at its final
+ * position, takes the factors aux_w, aux_d = exp(-dt lambda) of the two deposition modules as the tail applied them to m
+ * (same switches, early-outs and operands) and, for every depositing present activity, a1 = a0 aux_w, w = a0 - a1 if the
+ * wet module acts, then a2 = a1 aux_d, d = a1 - a2 if the dry module acts, A = a2 -- every product and difference rounded
+ * once in both libraries, so the deposit is the activity before minus the activity after bit for bit; (3) adds the w and d
+ * of all particles per cell in ascending external particle index (no floating-point atomics; the result does not depend
+ * on the stored order, which the locality re-sort changes; module_sort redefines the external order itself and with it the
+ * order of summation, so a cell with three or more deposits may round differently with SORT_DT set) and sets
+ * inv = inv f + step, two roundings.  m, vmr, the loss quantities, positions, cache and random-number
+ * counters are what they are without the module.  Such steps share no multi-step launch.
+ * mphip_module(ctx, MPHIP_MOD_RADIO_DEPO, t) runs the module alone on the stored dt.
+ *   mphip_set_radio_depo with a new grid allocates the inventory, zeroes it and forgets t_inv; with the same grid it keeps
+ * the inventory (on toggled).  grid may be NULL when on == 0.  Refused: nz != 1, an empty or inverted grid, ncell + 1
+ * beyond 32-bit cell indices; with on != 0 also DIRECTION != 1, MET_COORD_TYPE != 0, no depositing activity registered
+ * (and mphip_update_ctl / mphip_set_radio_decay refuse to create these conditions while it is on).  The launch needs the
+ * lean deposition code -- a regular longitude / latitude meteo grid whose packed records fit 32-bit offsets, option
+ * "generic_kernel" off -- and refuses the step otherwise.
+ *   mphip_get_radio_depo: t_inv (NaN before the first step) and the planes wet, dry [MPHIP_NRADIO][ncell + 1] (any
+ * pointer may be NULL), summed over the ranks through the communicator or the all-reduce hook like mphip_grid_sums (every
+ * rank keeps the deposits of its own particles: no exchange inside the step).  Refused before mphip_set_radio_depo. */
+int mphip_set_radio_depo(mphip_ctx *ctx, int on, const mphip_box_t *grid);
+int mphip_get_radio_depo(mphip_ctx *ctx, double *t_inv, double *wet, double *dry);
 
 int mphip_set_allreduce(mphip_ctx *ctx, mphip_allreduce_fn fn, void *user);
 

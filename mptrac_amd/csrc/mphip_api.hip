@@ -236,6 +236,17 @@ struct mphip_ctx {
   // switch of the time step
   RadioQnt radio = { { -1, -1, -1, -1, -1, -1 } };
   bool radio_on = false;
+  // module_radio_depo (mphip_set_radio_depo): the switch of the time step, the ground grid, this rank's part of the
+  // inventory [2][MPHIP_NRADIO][rdepo_ntot] (rdepo_ntot = nx ny + 1: the last element of a plane is the bin outside the
+  // grid) and the time it is valid for (rdepo_have_t: one is known)
+  bool rdepo_on = false;
+  mphip_box_t rdepo_grid = {};
+  double *d_rdepo_inv = nullptr;
+  size_t rdepo_ntot = 0;
+  bool rdepo_have_t = false;
+  double rdepo_t = 0;
+  const unsigned char *depo_busy_last = nullptr;   // EmitKeys::depo_busy as the step's deposition launch has just used it
+  unsigned depo_busy_last_mask = 0;                // ... and the deposition modules it was decided for
   // exchange of the occupied levels only (exchange_occupied_levels): per-level occupancy, the dense band, what was found
   // option "mix_exchange_levels" (default 0): measured with a one-rank communicator, the band costs 0.14 ms per step (the
   // host reads the occupancy: the one synchronisation in the step path; pack / unpack) against a MODELLED saving of
@@ -967,6 +978,8 @@ int launch_step(mphip_ctx *ctx, unsigned mask, double t, const RngCtr &rng = {},
       && depo_lds <= 64 * 1024) {
     S.depo_busy = ctx->depo_busy_valid ? ctx->d_depo_busy : nullptr;
     ctx->depo_busy_valid = false;
+    ctx->depo_busy_last = S.depo_busy;      // (module_radio_depo behind this launch looks at the same particles)
+    ctx->depo_busy_last_mask = mask;
     hipLaunchKernelGGL(depo_kernel, dim3(nb), dim3(256), depo_lds, ctx->stream, S);
     HIPCHK(hipGetLastError());
     ctx->fused_perm = nullptr;
@@ -976,6 +989,7 @@ int launch_step(mphip_ctx *ctx, unsigned mask, double t, const RngCtr &rng = {},
   }
   // the headline module set, one step per launch, and the caller wants the keys of the sort ahead from this launch
   ctx->depo_busy_valid = false;     // (any other launch: positions may move, the flags of an earlier one are void)
+  ctx->depo_busy_last = nullptr;
   if (emit && emit->keys && sel == kAdvDiffConvSedi && nsteps == 1) {
     sel |= kEmitKeys;
     S.emit = *emit;
@@ -2318,6 +2332,151 @@ bool step_chem_on(const mphip_ctl_t &c) {
   return chem_on(c) || c.tracer_chem != 0;
 }
 
+// ---- module_radio_depo ---------------------------------------------------------
+
+int ensure_rec(mphip_ctx *ctx, size_t need);   // (the record buffer of the analysis outputs, below)
+
+// the deposition modules the control parameters configure (the bits of the step's tail, plan_step)
+unsigned depo_bits(const mphip_ctl_t &c) {
+  unsigned m = 0;
+  if ((c.wet_depo_ic_a > 0 || c.wet_depo_ic_h[0] > 0) && (c.wet_depo_bc_a > 0 || c.wet_depo_bc_h[0] > 0))
+    m |= MPHIP_MOD_WET_DEPO;
+  if (c.dry_depo_vdep > 0)
+    m |= MPHIP_MOD_DRY_DEPO;
+  return m;
+}
+
+// the aerosol-bound activities: they deposit (the noble gases Rn-222 and Xe-133 never do)
+constexpr int kRadioDepositing[kRadioDepoMax] = { MPHIP_RN_PB210, MPHIP_RN_BE7, MPHIP_RN_CS137, MPHIP_RN_I131 };
+
+bool radio_depo_any(const RadioQnt &r) {
+  for (int k : kRadioDepositing)
+    if (r.q[k] >= 0)
+      return true;
+  return false;
+}
+
+// module_radio_depo in the step: the module is on, a depositing activity is registered and the wet or the dry module is
+// configured.  Such a step takes the split path (the launch runs behind the tail, on the stored dt) and shares no
+// multi-step launch.
+bool step_radio_depo_on(const mphip_ctx *ctx) {
+  return ctx->rdepo_on && radio_depo_any(ctx->radio) && depo_bits(ctx->ctl) != 0;
+}
+
+// what keeps module_radio_depo from being on under the control parameters c with the activities r ("" = nothing)
+std::string radio_depo_conflict(const mphip_ctl_t &c, const RadioQnt &r) {
+  if (c.direction != 1)
+    return "module_radio_depo: DIRECTION must be 1 (the inventory of a backward run is not defined)";
+  if (c.met_coord_type != 0)
+    return "module_radio_depo: MET_COORD_TYPE must be 0 (longitude / latitude ground grid)";
+  if (!radio_depo_any(r))
+    return "module_radio_depo: no depositing activity (Apb210, Abe7, Acs137, Ai131) is registered with mphip_set_radio_decay";
+  return "";
+}
+
+// One step of module_radio_depo at model time t: the ground decay of the inventory since its time, the particles'
+// deposits (radio_depo_kernel), their sums per cell in ascending particle index (ordered_cell_sums), inv = inv f + step.
+// busy: EmitKeys::depo_busy of the launch that moved the particles, if it holds for depo_bits' modules (NULL: the kernel
+// decides from p, time and dt itself).
+int launch_radio_depo(mphip_ctx *ctx, double t, const unsigned char *busy) {
+  if (!ctx->d_rdepo_inv)
+    return fail(ctx, "module_radio_depo: no ground grid (mphip_set_radio_depo)");
+  const std::string why = radio_depo_conflict(ctx->ctl, ctx->radio);
+  if (!why.empty())
+    return fail(ctx, why);
+  const mphip_ctl_t &c = ctx->ctl;
+  const unsigned depo = depo_bits(c);
+  const mphip_box_t &g = ctx->rdepo_grid;
+  const size_t ntot = ctx->rdepo_ntot;
+  RadioDepoArgs R;
+  memset(&R, 0, sizeof(R));
+  R.G = BoxGrid{ g.lon0, g.lon1, g.lat0, g.lat1, 0.0, 1.0, g.nx, g.ny, 1 };
+  R.ncell = (int) (ntot - 1);
+  RadioDepoAdd D;
+  memset(&D, 0, sizeof(D));
+  for (int k : kRadioDepositing)
+    if (ctx->radio.q[k] >= 0) {
+      R.q[R.ndep++] = ctx->radio.q[k];
+      D.plane[D.ndep] = k;
+      // (the C library's exp; first step: the inventory only gets its time)
+      D.f[D.ndep++] = ctx->rdepo_have_t ? exp(-kRadioLambda[k] * (t - ctx->rdepo_t)) : 1.0;
+    }
+  const int nv = 2 * R.ndep;
+  const double *step = nullptr;
+  if (ctx->np > 0 && depo) {
+    if (ctx->fused_perm)   // (never behind a step's tail: the launch that moved the particles has done the gather)
+      return fail(ctx, "module_radio_depo: module_sort's gather of the particle arrays is still pending");
+    if (ensure_packed(ctx) || check_fields(ctx, depo))
+      return 1;
+    if (ctx->force_generic || !lean32_ok(ctx))
+      return fail(ctx, "module_radio_depo: needs the lean deposition code (a regular longitude / latitude meteo grid with a "
+                       "pressure look-up table, packed records within 32-bit offsets, option generic_kernel off)");
+    if (ensure_rec(ctx, (size_t) ctx->np * (size_t) nv) || ensure_sums(ctx, (size_t) nv * ntot))
+      return 1;
+    R.cell = ctx->d_cell;
+    R.val = ctx->d_rec;
+    StepParams S;
+    memset(&S.emit, 0, sizeof(S.emit));
+    S.ctl = c;
+    S.met = dev_met(ctx);
+    S.atm = dev_atm(ctx);
+    S.clim = ctx->d_clim;
+    S.tracers = ctx->d_tracers;
+    S.t = t;
+    S.mask = depo;
+    // the partition of the deposition launch, with more blocks where the list of a block would not fit the LDS
+    int blocks = ctx->step_blocks;
+    BlockGeom geom = block_geom(ctx->np, blocks);
+    const size_t axes = (axes_lds_bytes(ctx) + 15) & ~(size_t) 15;
+    const size_t lds_max = 64 * 1024 - 8;   // (the kernel's own 8 B of static LDS come on top of the dynamic part)
+    while (axes + (size_t) geom.per_block * sizeof(int) > lds_max && geom.per_block > 256) {
+      blocks *= 2;
+      geom = block_geom(ctx->np, blocks);
+    }
+    const size_t lds = axes + (size_t) geom.per_block * sizeof(int);
+    if (lds > lds_max)
+      return fail(ctx, "module_radio_depo: the axes of the meteo grid do not fit the LDS");
+    S.nblocks_logical = geom.nblocks_logical;
+    S.per_block = geom.per_block;
+    S.xcd_map = ctx->xcd_map;
+    S.depo_busy = busy;
+    S.ctr_turb = S.ctr_meso = S.ctr_conv = S.ctr_pbl = 0;
+    S.radio = ctx->radio;
+    S.nsteps = 1;
+    S.t_stride = 0;
+    S.ctr_stride = 0;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (ctx->prof) {   // (mphip_profile_begin / _end: the kernel counts as a launch of the step)
+      if (ctx->ev_used + 2 > ctx->ev.size())
+        for (int k = 0; k < 2; k++) {
+          hipEvent_t e;
+          HIPCHK(hipEventCreate(&e));
+          ctx->ev.push_back(e);
+        }
+      e0 = ctx->ev[ctx->ev_used++];
+      e1 = ctx->ev[ctx->ev_used++];
+      HIPCHK(hipEventRecord(e0, ctx->stream));
+    }
+    hipLaunchKernelGGL(radio_depo_kernel, dim3(geom.nblocks_logical), dim3(256), lds, ctx->stream, S, R);
+    HIPCHK(hipGetLastError());
+    if (ctx->prof)
+      HIPCHK(hipEventRecord(e1, ctx->stream));
+    const RecordVals vals = { ctx->d_rec, nv };
+    if (ordered_cell_sums(ctx, vals, nv, 1, ntot, ctx->d_sums, (int *) nullptr, (double *) nullptr, true))
+      return 1;
+    step = ctx->d_sums;
+  }
+  // (behind the last refusal: a refused call leaves the inventory and its time as they were)
+  ctx->rdepo_t = t;
+  ctx->rdepo_have_t = true;
+  if (D.ndep > 0) {
+    hipLaunchKernelGGL(radio_depo_add_kernel, dim3(grid_for((long long) (2 * (size_t) D.ndep * ntot))), dim3(256), 0, ctx->stream,
+                       ctx->d_rdepo_inv, step, ntot, D);
+    HIPCHK(hipGetLastError());
+  }
+  return 0;
+}
+
 // the chemistry of a step, in the reference's order: module_chem_grid (with either chemistry; it does nothing without
 // m or Cx), module_oh_chem, module_h2o2_chem, module_tracer_chem
 int launch_chem(mphip_ctx *ctx, double t) {
@@ -2387,10 +2546,7 @@ StepPlan plan_step(const mphip_ctx *ctx, double t) {
     m |= MPHIP_MOD_DECAY;
   // module_radio_decay sits behind module_mixing and the chemistry: in the launch of the deposition modules
   unsigned tail = radio_step_bit(ctx);
-  if ((c.wet_depo_ic_a > 0 || c.wet_depo_ic_h[0] > 0) && (c.wet_depo_bc_a > 0 || c.wet_depo_bc_h[0] > 0))
-    tail |= MPHIP_MOD_WET_DEPO;
-  if (c.dry_depo_vdep > 0)
-    tail |= MPHIP_MOD_DRY_DEPO;
+  tail |= depo_bits(c);
   if (bound)
     tail |= MPHIP_MOD_BOUND_COND2;
   P.mask = m;
@@ -2634,6 +2790,7 @@ void mphip_destroy(mphip_ctx *ctx) {
   dev_free(ctx->d_photo);
   dev_free(ctx->d_cnt);
   dev_free(ctx->d_depo_busy);
+  dev_free(ctx->d_rdepo_inv);
   dev_free(ctx->d_occ);
   dev_free(ctx->d_band);
   dev_free(ctx->d_band_cnt);
@@ -2686,6 +2843,11 @@ int mphip_update_ctl(mphip_ctx *ctx, const mphip_ctl_t *ctl) {
           return fail(ctx, "a module_meteo quantity shares its index with a mass / mixing-ratio / loss / particle quantity");
   if (radio_any(ctx)) {   // the activities of mphip_set_radio_decay stay valid under the new parameters
     const std::string why = radio_conflict(*ctl, ctx->radio.q);
+    if (!why.empty())
+      return fail(ctx, why);
+  }
+  if (ctx->rdepo_on) {    // ... and so does a module_radio_depo that is on
+    const std::string why = radio_depo_conflict(*ctl, ctx->radio);
     if (!why.empty())
       return fail(ctx, why);
   }
@@ -3407,7 +3569,16 @@ int mphip_run_timestep(mphip_ctx *ctx, double t) {
   // sits between module_mixing and module_wet_depo: with it the step's launch stops before the deposition modules,
   // which follow in a launch of their own
   const bool chem = step_chem_on(c);
-  if (!P.due.mixing && !chem) {
+  // module_radio_depo (mphip_set_radio_depo) is a launch of its own behind the tail, on the stored dt: the split path too
+  const bool rdepo = step_radio_depo_on(ctx);
+  // (the busy list of the launch that moved the particles, where the step's deposition launch has just used it)
+  auto radio_depo_step = [&]() {
+    const bool listed = ctx->depo_busy_last && ctx->depo_busy_last_mask == depo_bits(c);
+    const unsigned char *busy = listed ? ctx->depo_busy_last : nullptr;
+    ctx->depo_busy_last = nullptr;
+    return launch_radio_depo(ctx, t, busy);
+  };
+  if (!P.due.mixing && !chem && !rdepo) {
     if (launch_step(ctx, mask | tail, t, P.rng))
       return 1;
     if (sort_next && ahead_launch(ctx, t_next))
@@ -3421,7 +3592,7 @@ int mphip_run_timestep(mphip_ctx *ctx, double t) {
       return 1;
     if (sort_next && ahead_launch(ctx, t_next))
       return 1;
-    if (launch_chem(ctx, t) || (tail && launch_step(ctx, tail, t)))
+    if ((chem && launch_chem(ctx, t)) || (tail && launch_step(ctx, tail, t)) || (rdepo && radio_depo_step()))
       return 1;
     return P.due.meteo ? schedule_meteo(ctx) : 0;
   }
@@ -3482,6 +3653,8 @@ int mphip_run_timestep(mphip_ctx *ctx, double t) {
     return 1;
   if (tail && launch_step(ctx, tail, t))
     return 1;
+  if (rdepo && radio_depo_step())
+    return 1;
   return P.due.meteo ? schedule_meteo(ctx) : 0;
 }
 
@@ -3521,8 +3694,9 @@ int mphip_run_timesteps(mphip_ctx *ctx, double t_first, int nsteps) {
       && c.advect > 0   // (every integrator has its multi-step instantiations; without module_advect: single steps)
       && !ctx->fused_perm
       && !ctx->force_generic
-      && !step_chem_on(c);   // (module_chem_grid, module_oh_chem, module_h2o2_chem, module_tracer_chem are launches of
+      && !step_chem_on(c)    // (module_chem_grid, module_oh_chem, module_h2o2_chem, module_tracer_chem are launches of
                              // their own: single steps)
+      && !step_radio_depo_on(ctx);   // (module_radio_depo likewise, behind the tail)
     if (quiet) {
       batch = nsteps - done;
       if (ctx->locality_interval > 0)
@@ -3604,6 +3778,8 @@ int mphip_module(mphip_ctx *ctx, unsigned modules, double t) {
     return launch_h2o2(ctx);
   case MPHIP_MOD_TRACER_CHEM:
     return launch_tracer_chem(ctx);
+  case MPHIP_MOD_RADIO_DEPO:   // alone, on the stored dt (whether or not the step's switch is on)
+    return launch_radio_depo(ctx, t, nullptr);
   }
   // module_radio_decay: the tail of a step-kernel launch (alone: on the stored dt), with whatever activities are registered
   if (modules & MPHIP_MOD_RADIO_DECAY) {
@@ -3615,7 +3791,7 @@ int mphip_module(mphip_ctx *ctx, unsigned modules, double t) {
   }
   if (modules & ~(kParticleBits | kRadioDecay))
     return fail(ctx, "module_sort / module_mixing / module_meteo / module_chem_grid / module_oh_chem / module_h2o2_chem "
-                     "/ module_tracer_chem must be called on their own");
+                     "/ module_tracer_chem / module_radio_depo must be called on their own");
   uint64_t per_step = 0;
   const RngCtr rng = rng_counters(modules, (uint64_t) ctx->np_total, ctx->rng_ctr, &per_step);
   ctx->rng_ctr += per_step;
@@ -4072,11 +4248,85 @@ int mphip_set_radio_decay(mphip_ctx *ctx, int on, const int qnt[MPHIP_NRADIO]) {
   const std::string why = radio_conflict(ctx->ctl, r.q);
   if (!why.empty())
     return fail(ctx, why);
+  if (ctx->rdepo_on) {    // (a module_radio_depo that is on keeps a depositing activity)
+    const std::string why_depo = radio_depo_conflict(ctx->ctl, r);
+    if (!why_depo.empty())
+      return fail(ctx, why_depo);
+  }
   HIPCHK(hipSetDevice(ctx->device));
   if (flush_meteo(ctx))   // (a deferred module_meteo belongs to the steps before)
     return 1;
   ctx->radio = r;
   ctx->radio_on = on != 0;
+  return 0;
+}
+
+int mphip_set_radio_depo(mphip_ctx *ctx, int on, const mphip_box_t *grid) {
+  if (ctx && ahead_drop(ctx))
+    return 1;
+  if (!ctx)
+    return 1;
+  if (!ctx->have_ctl)
+    return fail(ctx, "control parameters were not uploaded");
+  if (!grid && on)
+    return fail(ctx, "module_radio_depo: null ground grid");
+  size_t ntot = 0;
+  if (grid) {
+    if (grid->nz != 1)
+      return fail(ctx, "module_radio_depo: the ground grid has one level (nz = 1)");
+    if (grid->nx < 1 || grid->ny < 1 || !(grid->lon0 < grid->lon1) || !(grid->lat0 < grid->lat1))
+      return fail(ctx, "module_radio_depo: empty or inverted ground grid");
+    ntot = (size_t) grid->nx * (size_t) grid->ny + 1;
+    if (ntot >= 0x7fffffffULL)
+      return fail(ctx, "module_radio_depo: too many grid cells for 32-bit cell indices");
+  }
+  if (on) {
+    const std::string why = radio_depo_conflict(ctx->ctl, ctx->radio);
+    if (!why.empty())
+      return fail(ctx, why);
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  if (grid) {
+    const mphip_box_t &g = ctx->rdepo_grid;
+    const bool same = ctx->d_rdepo_inv && g.nx == grid->nx && g.ny == grid->ny && g.lon0 == grid->lon0 && g.lon1 == grid->lon1
+      && g.lat0 == grid->lat0 && g.lat1 == grid->lat1;
+    if (!same) {   // a new inventory: zero, no time yet
+      HIPCHK(hipStreamSynchronize(ctx->stream));
+      ctx->rdepo_ntot = 0;
+      if (dev_alloc(ctx, &ctx->d_rdepo_inv, 2 * (size_t) MPHIP_NRADIO * ntot))
+        return 1;
+      HIPCHK(hipMemsetAsync(ctx->d_rdepo_inv, 0, 2 * (size_t) MPHIP_NRADIO * ntot * sizeof(double), ctx->stream));
+      ctx->rdepo_grid = *grid;
+      ctx->rdepo_ntot = ntot;
+      ctx->rdepo_have_t = false;
+      ctx->rdepo_t = 0;
+    }
+  }
+  ctx->rdepo_on = on != 0;
+  return 0;
+}
+
+int mphip_get_radio_depo(mphip_ctx *ctx, double *t_inv, double *wet, double *dry) {
+  if (!ctx)
+    return 1;
+  if (!ctx->d_rdepo_inv)
+    return fail(ctx, "mphip_get_radio_depo: no inventory (mphip_set_radio_depo has not been called)");
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t plane = (size_t) MPHIP_NRADIO * ctx->rdepo_ntot, total = 2 * plane;
+  // this rank's part, summed over the ranks in a copy (the inventory itself stays this rank's)
+  if (ensure_sums(ctx, total) || ensure_h_sums(ctx, total))
+    return 1;
+  HIPCHK(hipMemcpyAsync(ctx->d_sums, ctx->d_rdepo_inv, total * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+  if (run_allreduce(ctx, ctx->d_sums, total))
+    return 1;
+  HIPCHK(hipMemcpyAsync(ctx->h_sums, ctx->d_sums, total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (t_inv)
+    *t_inv = ctx->rdepo_have_t ? ctx->rdepo_t : NAN;
+  if (wet)
+    memcpy(wet, ctx->h_sums, plane * sizeof(double));
+  if (dry)
+    memcpy(dry, ctx->h_sums + plane, plane * sizeof(double));
   return 0;
 }
 

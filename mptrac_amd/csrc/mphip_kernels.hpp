@@ -213,6 +213,8 @@ constexpr unsigned kOptionalModules = MPHIP_MOD_DIFF_TURB | MPHIP_MOD_DIFF_MESO 
 // module_radio_decay in a step-kernel mask: the public bit MPHIP_MOD_RADIO_DECAY (1 << 25) is kGated's, so the run-time
 // masks carry it as a bit of its own that aliases no template flag (the instantiation a step selects stays the same)
 constexpr unsigned kRadioDecay = 1u << 31;
+// (MPHIP_MOD_RADIO_DEPO, 1 << 26, is kMultiStep's bit: harmless, the module is a launch of its own and never enters a
+// step-kernel mask -- as MPHIP_MOD_CHEM_GRID shares kEmitKeys' bit and MPHIP_MOD_TRACER_CHEM kTwoStage's)
 constexpr unsigned kTailModules = MPHIP_MOD_LOSS_ZERO | MPHIP_MOD_DECAY | kRadioDecay | MPHIP_MOD_WET_DEPO | MPHIP_MOD_DRY_DEPO;
 constexpr unsigned kMovers = MPHIP_MOD_POSITION | MPHIP_MOD_ADVECT | MPHIP_MOD_DIFF_TURB | MPHIP_MOD_DIFF_MESO | MPHIP_MOD_DIFF_PBL
   | MPHIP_MOD_CONVECTION | MPHIP_MOD_SEDI | MPHIP_MOD_ISOSURF | MPHIP_MOD_POSITION2;
@@ -1185,6 +1187,133 @@ __global__ __launch_bounds__(256, MPHIP_DEPO_WAVES_PER_SIMD) void depo_kernel(co
     Stencil sd = stencil_zero();
     horiz_fast(M, A, P.lon, P.lat, sd);
     depo_pair_fast(ctl, M, A, a, ip, P, sd, wet, dry);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// module_radio_depo (mphip_set_radio_depo): the activities the deposition modules take out of the air, and where they
+// land.  A launch of its own behind the step's tail: the factors exp(-dt lambda) of module_wet_depo / module_dry_depo are
+// computed again at the particle's final position -- depo_pair_factor with sinks that keep them, so the same switches,
+// early-outs and operands as the tail used for m --, applied to the aerosol-bound activities (Pb-210, Be-7, Cs-137,
+// I-131; the noble gases Rn-222 and Xe-133 never deposit), and the removed activity of every particle is left with the
+// cell of the ground grid it is over, for the ordered cell sums (radio_depo_add_kernel folds them into the inventory).
+// Patterned on depo_kernel: busy particles into an LDS list first, full waves for the rest.  Lean configurations only
+// (a longitude / latitude meteo grid within 32-bit offsets: horiz_fast and the LDS axes); the host refuses the others.
+// ---------------------------------------------------------------------------
+constexpr int kRadioDepoMax = 4;   // Apb210, Abe7, Acs137, Ai131
+
+struct RadioDepoArgs {
+  BoxGrid G;              // the ground grid (nz = 1; z0, z1 unused)
+  int ncell;              // nx ny: the index of the bin for deposits outside the grid
+  int ndep;               // depositing activities that are present
+  int q[kRadioDepoMax];   // ... their quantities
+  int *cell;              // per stored particle: the cell it deposits into, -1: nothing deposited
+  double *val;            // per stored particle: [wet of activity 0 .. ndep - 1 | dry of activity 0 .. ndep - 1]
+};
+
+// box_cell_of_height's arithmetic on the two horizontal axes (upper bounds exclusive, no contraction); ncell outside
+__device__ __forceinline__ int ground_cell(const BoxGrid &G, int ncell, double lon, double lat) {
+#pragma clang fp contract(off)
+  if (lon < G.lon0 || lon >= G.lon1 || lat < G.lat0 || lat >= G.lat1)
+    return ncell;
+  const double dlon = (G.lon1 - G.lon0) / G.nx, dlat = (G.lat1 - G.lat0) / G.ny;
+  const int ix = (int) ((lon - G.lon0) / dlon), iy = (int) ((lat - G.lat0) / dlat);
+  if (ix >= G.nx || iy >= G.ny)
+    return ncell;
+  return ix * G.ny + iy;
+}
+
+// a0 -> a1 = a0 aux_w -> a2 = a1 aux_d; the deposits are the differences: every product and difference rounded once, so
+// that "deposit = activity before - activity after" holds bit for bit
+__device__ __forceinline__ void radio_depo_apply(const RadioDepoArgs &R, const DevAtm &a, long long i, bool wet, double aux_w,
+                                                 bool dry, double aux_d) {
+#pragma clang fp contract(off)
+  double *out = R.val + (size_t) i * (size_t) (2 * R.ndep);
+  for (int j = 0; j < R.ndep; j++) {
+    double *q = a.q[R.q[j]];
+    const double a0 = q[i];
+    double a1 = a0, w = 0.0, d = 0.0;
+    if (wet) {
+      a1 = a0 * aux_w;
+      w = a0 - a1;
+    }
+    double a2 = a1;
+    if (dry) {
+      a2 = a1 * aux_d;
+      d = a1 - a2;
+    }
+    q[i] = a2;
+    out[j] = w;
+    out[R.ndep + j] = d;
+  }
+}
+
+#ifndef MPHIP_RADIO_DEPO_WAVES_PER_SIMD
+#define MPHIP_RADIO_DEPO_WAVES_PER_SIMD 4
+#endif
+__global__ __launch_bounds__(256, MPHIP_RADIO_DEPO_WAVES_PER_SIMD) void radio_depo_kernel(const StepParams S,
+                                                                                           const RadioDepoArgs R) {
+  extern __shared__ double s_axes[];
+  __shared__ int s_count;
+  const DevMet &M = S.met;
+  const DevAtm &a = S.atm;
+  const mphip_ctl_t &ctl = S.ctl;
+  const Axes A = load_axes(M, s_axes);
+  // the list of the workgroup's busy particles behind the axes (per_block entries: the host sizes the LDS)
+  int *s_list = (int *) (s_axes + ((axes_doubles(M) * 8 + (size_t) M.lut_size * 2 + 15) & ~(size_t) 15) / 8);
+  if (threadIdx.x == 0)
+    s_count = 0;
+  __syncthreads();
+  const unsigned tmask = S.mask;
+  long long first, last;
+  block_range(S, a.np, first, last);
+  const int lane = threadIdx.x & 63;
+  // which particles have anything to do (p, time and dt only); the others deposit nothing
+  for (long long i = first + threadIdx.x; i < first + S.per_block; i += 256) {   // (whole waves stay together)
+    bool busy = false;
+    if (S.depo_busy)                  // decided by the launch that moved the particles (EmitKeys::depo_busy)
+      busy = i < last && S.depo_busy[i] != 0;
+    else if (i < last && a.dt[i] != 0) {   // guard of PARTICLE_LOOP(..., check_dt = 1), mptrac.h:1759
+      Particle P;
+      P.time = a.time[i];
+      P.p = a.p[i];
+      busy = ((tmask & MPHIP_MOD_WET_DEPO) && !above_every_cloud_top(M, P))
+        || ((tmask & MPHIP_MOD_DRY_DEPO) && !above_every_surface_layer(ctl, M, P));
+    }
+    if (i < last && !busy)
+      R.cell[i] = -1;
+    const unsigned long long mine = __ballot(busy);
+    int at = 0;
+    if (lane == 0 && mine)
+      at = atomicAdd(&s_count, __builtin_popcountll(mine));
+    at = __builtin_amdgcn_readfirstlane(at);
+    if (busy)
+      s_list[at + __builtin_popcountll(mine & ((1ull << lane) - 1))] = (int) (i - first);
+  }
+  __syncthreads();
+  const int total = s_count;
+  for (int t = threadIdx.x; t < total; t += 256) {
+    const long long ip = first + s_list[t];
+    Particle P;
+    P.time = a.time[ip];
+    P.lon = a.lon[ip];
+    P.lat = a.lat[ip];
+    P.p = a.p[ip];
+    P.dt = a.dt[ip];
+    const bool wet = (tmask & MPHIP_MOD_WET_DEPO) && !above_every_cloud_top(M, P);
+    const bool dry = (tmask & MPHIP_MOD_DRY_DEPO) && !above_every_surface_layer(ctl, M, P);
+    Stencil sd = stencil_zero();
+    horiz_fast(M, A, P.lon, P.lat, sd);
+    bool wet_acts = false, dry_acts = false;
+    double aux_w = 1.0, aux_d = 1.0;
+    depo_pair_factor(ctl, M, A, a, ip, P, sd, wet, dry,
+                     [&](double aux, double) { wet_acts = true; aux_w = aux; },
+                     [&](double aux, double) { dry_acts = true; aux_d = aux; });
+    if (wet_acts || dry_acts) {
+      radio_depo_apply(R, a, ip, wet_acts, aux_w, dry_acts, aux_d);
+      R.cell[ip] = ground_cell(R.G, R.ncell, P.lon, P.lat);
+    } else
+      R.cell[ip] = -1;
   }
 }
 
@@ -3161,6 +3290,35 @@ struct ArrayVals {   // one value per stored particle, computed beforehand
   __device__ __forceinline__ int count() const { return 1; }
   __device__ __forceinline__ double get(int, long long i) const { return v[i]; }
 };
+
+struct RecordVals {   // ArrayVals' sibling for several values: one record of nv doubles per stored particle
+  const double *rec;
+  int nv;
+  __device__ __forceinline__ int count() const { return nv; }
+  __device__ __forceinline__ double get(int k, long long i) const { return rec[(size_t) i * (size_t) nv + (size_t) k]; }
+};
+
+// module_radio_depo: inv = inv f + step for the planes of the depositing activities -- the ground decay since the
+// inventory's time, then this step's deposits, as two roundings.  inv is [2][MPHIP_NRADIO][ntot], step [2 ndep][ntot]
+// (wet planes first); plane[j] = nuclide of depositing activity j, f[j] = its exp(-lambda (t - t_inv)) from the host.
+struct RadioDepoAdd {
+  int ndep;
+  int plane[kRadioDepoMax];
+  double f[kRadioDepoMax];
+};
+
+__global__ __launch_bounds__(256) void radio_depo_add_kernel(double *__restrict__ inv, const double *__restrict__ step,
+                                                             size_t ntot, RadioDepoAdd D) {
+#pragma clang fp contract(off)
+  const size_t n = 2 * (size_t) D.ndep * ntot;
+  for (size_t e = blockIdx.x * (size_t) blockDim.x + threadIdx.x; e < n; e += (size_t) gridDim.x * blockDim.x) {
+    const size_t v = e / ntot, c = e - v * ntot;
+    const int kind = (int) (v / (size_t) D.ndep), j = (int) (v - (size_t) kind * (size_t) D.ndep);
+    double *at = inv + ((size_t) kind * MPHIP_NRADIO + (size_t) D.plane[j]) * ntot + c;
+    const double decayed = *at * D.f[j];
+    *at = decayed + (step ? step[e] : 0.0);
+  }
+}
 
 // geo2cart(0, lon, lat, x) of output.c
 __device__ __forceinline__ void geo2cart_surface(double lon, double lat, double (&x)[3]) {

@@ -25,7 +25,7 @@ MOD = {
     "wet_depo": 1 << 10, "dry_depo": 1 << 11, "advect_init": 1 << 12, "diff_pbl": 1 << 13, "meteo": 1 << 14,
     "isosurf": 1 << 15, "sort": 1 << 16, "mixing": 1 << 17, "bound_cond": 1 << 18, "bound_cond2": 1 << 19,
     "isosurf_init": 1 << 20, "oh_chem": 1 << 21, "chem_grid": 1 << 22, "h2o2_chem": 1 << 23,
-    "tracer_chem": 1 << 24, "radio_decay": 1 << 25,
+    "tracer_chem": 1 << 24, "radio_decay": 1 << 25, "radio_depo": 1 << 26,
 }
 
 MphipCtl = make_ctl_struct("MphipCtl", HIP_CTL_FIELDS)
@@ -124,6 +124,9 @@ def load(build=True):
     L.mphip_station_hits.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                      C.c_int, C.c_int, _ip, _ip, _dp]
     L.mphip_set_radio_decay.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    if hasattr(L, "mphip_set_radio_depo"):      # (absent from libraries built before module_radio_depo: A/B runs through MPHIP_LIB)
+        L.mphip_set_radio_depo.argtypes = [C.c_void_p, C.c_int, C.POINTER(MphipBox)]
+        L.mphip_get_radio_depo.argtypes = [C.c_void_p, _dp, _dp, _dp]
     L.mphip_set_allreduce.argtypes = [C.c_void_p, ALLREDUCE_FN, C.c_void_p]
     L.mphip_comm_unique_id.argtypes = [C.c_void_p]
     L.mphip_comm_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -494,6 +497,31 @@ class Simulation:
                 idx = [int(q) for q in quantities]
         arr = (C.c_int * len(RADIO_ACTIVITIES))(*idx)
         self._chk(self.L.mphip_set_radio_decay(self.h, 1 if on else 0, arr))
+
+    def set_radio_depo(self, grid, on=True):
+        """module_radio_depo (mphip_set_radio_depo): `grid` = (lon0, lon1, nx, lat0, lat1, ny) of the ground grid -- or the
+        nine numbers of a box as box_sums takes them, with nz = 1 --, None with on=False: only the switch.  A new grid
+        starts a new, empty inventory; the same grid keeps it."""
+        if grid is None:
+            self._chk(self.L.mphip_set_radio_depo(self.h, 1 if on else 0, None))
+            return
+        grid = tuple(grid)
+        if len(grid) == 6:
+            grid = grid + (0.0, 1.0, 1)
+        b = MphipBox(*grid)
+        self._chk(self.L.mphip_set_radio_depo(self.h, 1 if on else 0, C.byref(b)))
+        self._radio_depo_cells = b.nx * b.ny + 1
+
+    def radio_depo(self):
+        """(t_inv, wet, dry) of the ground inventory (mphip_get_radio_depo): wet, dry [activity in RADIO_ACTIVITIES order]
+        [nx * ny + 1] in Bq, cell ix * ny + iy, the last element of a row = deposited outside the grid; t_inv is NaN
+        before the first step.  Summed over the ranks."""
+        n = getattr(self, "_radio_depo_cells", 1)
+        wet = np.zeros((len(RADIO_ACTIVITIES), n))
+        dry = np.zeros((len(RADIO_ACTIVITIES), n))
+        t_inv = C.c_double(0.0)
+        self._chk(self.L.mphip_get_radio_depo(self.h, C.byref(t_inv), _ptr(wet, _dp), _ptr(dry, _dp)))
+        return t_inv.value, wet, dry
 
     def synchronize(self):
         self._chk(self.L.mphip_synchronize(self.h))
