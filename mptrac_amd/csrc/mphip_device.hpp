@@ -597,15 +597,28 @@ __device__ __forceinline__ int locate_reg(const double *xx, int n, double x) {  
   return i < 0 ? 0 : (i > n - 2 ? n - 2 : i);
 }
 
-// the same with the reciprocal of the (regular) spacing; may differ from
-// locate_reg when x is within an ulp of a grid line -- used for interpolation
-// stencils only, where both neighbours give the same value
+// Longitude index from the product with the reciprocal of the (regular) spacing; false where the product lands
+// within 1e-9 of a whole number.  There -- a longitude on or within a few ulp of a grid line -- the product and the
+// reference's quotient may truncate to neighbouring cells, and the cells do not give the same value everywhere: with
+// a corner that is not finite intpol_met_space_2d takes the nearest corner, and whether it does depends on the cell.
+// (Product and quotient differ by a few ulp of a number below 2^11: far inside the window.)
+__device__ __forceinline__ bool lon_index_fast(double x, double lon_first, double inv_dlon, int nx, int &ix) {
+  const double q = (x - lon_first) * inv_dlon;
+  const int i = (int) q;
+  const double f = q - (double) i;
+  ix = i < 0 ? 0 : (i > nx - 2 ? nx - 2 : i);
+  return (f > 1e-9) & (f < 1.0 - 1e-9);
+}
+
+// locate_reg's index: from the product, next to a grid line from the reference's division
 __device__ __forceinline__ int locate_lon(const DevMet &M, const Axes &A, double x) {
 #if MPHIP_EXACT_DIV
   return locate_reg(A.lon, M.nx, x);
 #else
-  const int i = (int) ((x - A.lon[0]) * A.inv_lon[0]);
-  return i < 0 ? 0 : (i > M.nx - 2 ? M.nx - 2 : i);
+  int i;
+  if (!lon_index_fast(x, A.lon[0], A.inv_lon[0], M.nx, i))
+    i = locate_reg(A.lon, M.nx, x);
+  return i;
 #endif
 }
 
@@ -2126,10 +2139,11 @@ __device__ __forceinline__ void stencil_4d_fast(const DevMet &M, const Axes &A, 
     lon2 = lon + (lon < M.lon_first ? 360.0 : (lon > M.lon_last ? -360.0 : 0.0));
 #if MPHIP_EXACT_DIV
     s.ix = locate_reg(A.lon, M.nx, lon2);
+    guessed = true;
 #else
-    s.ix = clamp0_s((int) ((lon2 - M.lon_first) * M.inv_dlon0), M.nx - 2);
+    guessed = lon_index_fast(lon2, M.lon_first, M.inv_dlon0, M.nx, s.ix);   // (next to a grid line: locate_lon below)
 #endif
-    guessed = (fabs(lon) < 360.0) & lat_fast(M, A, lat2, hy.i, hy.x1, hy.inv);
+    guessed &= (fabs(lon) < 360.0) & lat_fast(M, A, lat2, hy.i, hy.x1, hy.inv);
     hy.x0 = A.lat[hy.i];
   }
 #endif
@@ -2711,7 +2725,7 @@ __device__ __forceinline__ bool in_boundary_region(const mphip_ctl_t &ctl, const
 // Lean versions for the specialised kernels (RK4 on pressure levels, lat/lon grid with a pressure look-up
 // table -- launch_step checks that; everything else runs the general code above).  Same values as the
 // general functions: every stencil is set up in straight-line code from a first guess and checked as a
-// whole; a lane whose check fails (a coordinate exactly on a grid line, |lon| >= 360, two axis nodes in
+// whole; a lane whose check fails (a coordinate on or next to a grid line, |lon| >= 360, two axis nodes in
 // one table bin, NaN) recomputes it with the general function, so there is one rarely taken branch per
 // stencil instead of one per search step and per special case.  On gfx950 every VALU instruction -- a
 // move, a compare, an fp64 fma -- occupies the SIMD for the same four cycles, so what these versions save
@@ -2771,19 +2785,20 @@ __device__ __forceinline__ double weight_of(double num, double inv) {
 // ---- stencil set-up ---------------------------------------------------------
 
 // longitude part of intpol_check_lon_lat + locate_reg + weight (mptrac.c:2762-2770, 3004-3018); false if the
-// longitude needs FMOD (|lon| >= 360)
+// longitude needs FMOD (|lon| >= 360) or lies next to a grid line (lon_index_fast)
 __device__ __forceinline__ bool lon_fast(const DevMet &M, const Axes &A, double lon, int &ix, double &wx) {
   double lon2 = lon + (lon < M.lon_first ? 360.0 : (lon > M.lon_last ? -360.0 : 0.0));
 #if MPHIP_EXACT_DIV
   ix = locate_reg(A.lon, M.nx, lon2);
   const double lx1 = A.lon[ix + 1];
   wx = (lx1 - lon2) / (lx1 - A.lon[ix]);
+  return fabs(lon) < 360.0;
 #else
-  ix = clamp0_s((int) ((lon2 - M.lon_first) * M.inv_dlon0), M.nx - 2);
+  const bool ok = lon_index_fast(lon2, M.lon_first, M.inv_dlon0, M.nx, ix);
   const double lx1 = A.lon[ix + 1], linv = A.inv_lon[ix];
   wx = (lx1 - lon2) * linv;
+  return ok & (fabs(lon) < 360.0);
 #endif
-  return fabs(lon) < 360.0;
 }
 
 // index of the latitude interval (locate_irr semantics on either axis direction) for a latitude inside

@@ -573,6 +573,42 @@ class Ref:
         m = self.m0
         return ((locate_reg(m.lon, lon) * len(m.lat) + locate_irr(m.lat, lat)) * len(m.p) + locate_irr(m.p, p)).astype(np.float64)
 
+    # -- module_diff_meso (mptrac.c:4264-4339) --------------------------------------------------------------------
+    def diff_meso(self, lon, lat, p, dt, uvwp, rs):
+        """Returns (cell, uvwp, lon, lat, p); cell = (ix, iy, iz) of the raw position (mptrac.c:4283-4285: locate_reg on
+        the longitude as it is).  The wind statistics over the cell's corners in both snapshots are single precision,
+        summed in the loop order of the reference."""
+        c = self.c
+        f = np.float32
+        ix, iy, iz = locate_reg(self.m0.lon, lon), locate_irr(self.m0.lat, lat), locate_irr(self.m0.p, p)
+        sig = []
+        for name in ("u", "v", "w"):
+            mean, sq = np.zeros(len(lon), dtype=f), np.zeros(len(lon), dtype=f)
+            for i in (0, 1):
+                for j in (0, 1):
+                    for k in (0, 1):
+                        for met in (self.m0, self.m1):
+                            a = met.f3[name][ix + i, iy + j, iz + k]
+                            mean = mean + a
+                            sq = sq + a * a
+            h = mean / f(16.0)
+            var = sq / f(16.0) - h * h
+            sig.append(np.where(var > 0, np.sqrt(np.maximum(var, f(0.0))), f(0.0)).astype(f))
+        r = 1.0 - 2.0 * np.abs(dt) / c.dt_met
+        r2 = np.sqrt(1.0 - r * r)
+        uvwp = np.array(uvwp, dtype=f)
+        new_lon, new_lat, new_p = lon.copy(), lat.copy(), p.copy()
+        on = dt != 0
+        if c.turb_mesox > 0:
+            uvwp[:, 0] = np.where(on, (r * uvwp[:, 0] + r2 * rs[0::3] * c.turb_mesox * sig[0]).astype(f), uvwp[:, 0])
+            new_lon = np.where(on, lon + DX2DEG(uvwp[:, 0] * dt / 1000.0, lat), lon)
+            uvwp[:, 1] = np.where(on, (r * uvwp[:, 1] + r2 * rs[1::3] * c.turb_mesox * sig[1]).astype(f), uvwp[:, 1])
+            new_lat = np.where(on, lat + DY2DEG(uvwp[:, 1] * dt / 1000.0), lat)
+        if c.turb_mesoz > 0:
+            uvwp[:, 2] = np.where(on, (r * uvwp[:, 2] + r2 * rs[2::3] * c.turb_mesoz * sig[2]).astype(f), uvwp[:, 2])
+            new_p = np.where(on, p + uvwp[:, 2] * dt, p)
+        return (ix, iy, iz), uvwp, new_lon, new_lat, new_p
+
     # -- module_convection (mptrac.c:4102-4171) -----------------------------------------------------------------
     def convection(self, time, lon, lat, p, rs):
         c = self.c
