@@ -277,6 +277,85 @@ int mphip_prefetch_done(mphip_ctx *ctx);
 /* drop a prefetched snapshot that will not be used (waits for its copies) */
 int mphip_discard_prefetch(mphip_ctx *ctx);
 
+/* The derived fields of the reference's meteo preprocessing, from one snapshot "as stored" (what a netCDF file of
+ * MET_TYPE 0 carries): geopotential height z, total ozone column o3c, boundary-layer pressure pbl, the cloud layer pct /
+ * pcb / cl, and plcl / plfc / pel / cape / cin.  `in` is a host view exactly as for mphip_update_met (compact or
+ * [EX][EY][EP]-strided); `what` an OR of MPHIP_PREP_* bits; the arrays of `out` have the strides of `in`.  The call uploads
+ * the inputs it needs into scratch of its own (kept for the grid size of the last call, freed by mphip_destroy), runs its
+ * kernels on a stream of its own, copies the results into the caller's arrays and returns when they are there.  It touches
+ * no meteo slot, no prefetch state and no particle state and may be called from a file-reader thread while another thread
+ * steps (the contract of mphip_prefetch_met); calls from several threads are serialised.  Only the outputs of the
+ * requested bits are written; a refused call writes nothing.
+ *   Refused: np < 2; a pressure axis that is not strictly descending; a missing input -- GEOPOT: t, h2o, ps, zs; O3C: o3,
+ * ps; PBL with met_pbl 3: t, ps, ts; with met_pbl 2 additionally u, v, us, vs, zs, h2o and z, given in `in` or derived by
+ * GEOPOT in the same call (the smoothed field); CLOUD: lwc, iwc, ps (rwc / swc absent = 0); CAPE: t, h2o, ps and the
+ * tropopause climatology of mphip_update_clim (on a Cartesian grid also mphip_update_ctl: met_utm_ref_lat is the
+ * tropopause's latitude) --; a missing output array of a requested bit; met_pbl other than 2 or 3 with PBL; smoothing
+ * half-widths with sx - 1 > nx or whose tile exceeds 64 KB of LDS.
+ *
+ *   DEFINITIONS.  This project's own statement of the reference's algorithms -- the reference's source was not available,
+ * so no line of mptrac.c is cited --, restated independently in tests/refmetprep.py.  All arithmetic is in double from the
+ * float inputs, products and quotients taken from left to right as written; each output value is rounded to float once.
+ * exp / log / pow are the C library's.  Constants: RI = 8.3144598, MA = 28.9644, G0 = 9.80665, MO3 = 48.00, EPS =
+ * 18.01528 / MA, RA = 1e3 RI / MA, CPD = 1003.5, LV = 2501000.
+ *   LIN(x0,y0,x1,y1,x) = y0 + (y1-y0)/(x1-x0)*(x-x0).  P(z) = 1013.25 exp(-z/7).  THETA(p,t) = t pow(1000/p, 0.286).
+ *   TVIRT(t,h) = t (1 + (1-EPS) max(h,1e-7)).  PSAT(t) = 6.112 exp(17.62 (t-273.15) / (243.12 + t - 273.15)).
+ *   PW(p,h) = p max(h,1e-7) / (1 + (1-EPS) max(h,1e-7)).  SH(h) = EPS max(h,1e-7).  max(a,b) = a > b ? a : b.
+ *   lapse_rate(t,h) = 1e3 G0 (a + LV r t) / (CPD a + LV LV r EPS) with a = RA (t t), r = SH(h) / (1 - SH(h)).
+ *   loc(q) = the largest k in [0, np-2] with p[k] >= q, else 0.  env(f,q) = LIN(p[k],f[k],p[k+1],f[k+1],q), k = loc(q): it
+ *   extrapolates beyond the ends.
+ *   Geopotential (z, km).  Tv[k] = TVIRT(t[k],h2o[k]), lp[k] = log(p[k]), ZD(a,Ta,b,Tb) = RI/MA/G0 (0.5 (Ta+Tb)) (a-b).
+ * k0 = loc(ps); Ts = LIN(p[k0],Tv[k0],p[k0+1],Tv[k0+1],ps); z[k0+1] = zs + ZD(log ps,Ts,lp[k0+1],Tv[k0+1]); upwards z[k] =
+ * z[k-1] + ZD(lp[k-1],Tv[k-1],lp[k],Tv[k]); z[k0] = zs + ZD(log ps,Ts,lp[k0],Tv[k0]); downwards z[k] = z[k+1] +
+ * ZD(lp[k+1],Tv[k+1],lp[k],Tv[k]) (the recurrences in double).  Then the float field is smoothed horizontally, per level:
+ * half-widths sx, sy = met_geopot_sx, _sy; if either is negative both are automatic -- 3, 2 if |lon[1]-lon[0]| < 0.5, else 6,
+ * 4 --; if either is 0: no smoothing.  For ix2 = ix-sx+1 ... ix+sx-1 (outer loop; wrapped once by +-nx, on regional grids
+ * too) and iy2 = max(iy-sy+1,0) ... min(iy+sy-1,ny-1) (inner loop), over the finite values: float weight w = (1 -
+ * |ix-ix2|/sx) (1 - |iy-iy2|/sy), float sums of w z and of w in that order, never contracted; the result is the quotient, or
+ * NaN without a finite neighbour.
+ *   Ozone column (o3c, DU).  Sum over k = 1 ... np-1 with p[k-1] <= ps of 0.5 (o3[k-1]+o3[k]) MO3 / MA (p[k-1]-p[k]) 100 /
+ * G0, divided by 2.1415e-5.
+ *   Cloud.  pct = pcb = NaN, cl = 0.  For k = 0 ... np-2, skipping p[k] > ps and p[k] < P(20): if any of lwc, rwc, iwc,
+ * swc[k] > met_cloud_min: pct = 0.5 (p[k]+p[k+1]) and, if pcb is still NaN, pcb = 0.5 (p[k]+p[max(k-1,0)]); then (cloud or
+ * not) cl += 0.5 S 100 (p[k]-p[k+1]) / G0 with S = (lwc[k]+lwc[k+1]) + (rwc[k]+rwc[k+1]) + (iwc[k]+iwc[k+1]) +
+ * (swc[k]+swc[k+1]).
+ *   PBL 3.  th0 = THETA(ps,ts); k runs from np-2 down to 1 and stops at the first k with p[k] >= 300 and (p[k] > ps or
+ * THETA(p[k],t[k]) <= th0+2), it ends at 0 otherwise; pbl = LIN(th[k+1],p[k+1],th[k],p[k],th0+2), th[k] = THETA(p[k],t[k]).
+ * Clamps: pmin = ps exp(-met_pbl_min/7); if pbl is not finite or pbl > pmin or p[k] > ps: pbl = pmin; pmax = ps
+ * exp(-met_pbl_max/7); if pbl < pmax: pbl = pmax.
+ *   PBL 2.  pb = ps exp(-0.05/7); k = the first level >= 1 with p[k] < pb (np-1 if there is none); h2os =
+ * LIN(p[k-1],h2o[k-1],p[k],h2o[k],pb); tvs = TVIRT(THETA(pb,ts),h2os); pbl = pb, rib_old = 0; upwards from k: vh2 =
+ * max((u[k]-us)^2 + (v[k]-vs)^2, 25); rib = G0 1e3 (z[k]-zs) / tvs (TVIRT(THETA(p[k],t[k]),h2o[k]) - tvs) / vh2; at the first
+ * rib >= 0.25: pbl = min(LIN(rib_old,p[k-1],rib,p[k],0.25), pb) and stop (min(a,b) = a < b ? a : b), else rib_old = rib.
+ * Then the two clamps of PBL 3 (every p[k] visited lies above the surface: that term drops out).
+ *   CAPE.  pfac = 1.01439, dz0 = RI/MA/G0 log(pfac).  pbot = min(ps,p[0]); th, h = mean THETA(p[k],t[k]) and mean h2o[k]
+ * over the levels with pbot >= p[k] >= pbot-50 (stop at the first level below pbot-50 once one was taken); plcl = plfc = pel =
+ * cape = cin = NaN; if h <= 0 or no level was taken: done.  Lifted condensation level: ptop = P(20), pbot = ps; do { plcl =
+ * 0.5 (pbot+ptop); t = th / pow(1000/plcl, 0.286); if (100 PW(plcl,h) / PSAT(t) > 100) ptop = plcl; else pbot = plcl; }
+ * while (pbot - ptop > 0.1).  cape = cin = 0, p = ps; do { dz = dz0 TVIRT(t,h); p /= pfac; t = th / pow(1000/p, 0.286); Te =
+ * env(t,p), he = env(h2o,p); d = 1e3 G0 (TVIRT(t,h) - TVIRT(Te,he)) / TVIRT(Te,he) dz; if (d < 0) cin += |d|; } while (p >
+ * plcl).  d = 0, p = plcl, t = th / pow(1000/p, 0.286), ptop = 0.75 clim_tropo(time, lat) (the climatological tropopause of
+ * mphip_update_clim at the column's latitude, met_utm_ref_lat on a Cartesian grid); do { dz = dz0 TVIRT(t,h); p /= pfac; t -=
+ * lapse_rate(t,h) dz; e = PSAT(t); h = e / (p - (1-EPS) e); Te, he as above; d_old = d; d = the same expression; if (d > 0) {
+ * cape += d; if plfc is NaN: plfc = p; } else if (d_old > 0) pel = p; if (d < 0 and plfc is NaN) cin += |d|; } while (p >
+ * ptop).  If plfc is NaN: cin = NaN.  (An infinite ps is taken as NaN, so that every loop ends: p shrinks by pfac per pass
+ * and a NaN makes each condition false.)
+ *   Out of scope: potential vorticity and the dynamical tropopause, the WMO / cold-point tropopause (pt, tt, zt, h2ot: they
+ * need the reference's spline), MET_PBL 1, detrending, down-sampling, model-to-pressure-level regridding. */
+enum { MPHIP_PREP_GEOPOT = 1, MPHIP_PREP_O3C = 2, MPHIP_PREP_PBL = 4, MPHIP_PREP_CLOUD = 8, MPHIP_PREP_CAPE = 16 };
+typedef struct {
+  int met_pbl;                        /* 2: bulk Richardson number, 3: potential temperature */
+  double met_pbl_min, met_pbl_max;    /* km; reference defaults 0.1, 5.0 */
+  int met_geopot_sx, met_geopot_sy;   /* smoothing half-widths; < 0: automatic, 0: none */
+  double met_cloud_min;
+} mphip_prep_t;
+typedef struct {
+  float *f3[MPHIP_N3D];
+  float *f2[MPHIP_N2D];
+} mphip_met_out_t;   /* same strides as `in` */
+int mphip_derive_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const mphip_prep_t *opt,
+                     const mphip_met_out_t *out);
+
 /* mptrac_update_device(..., atm), mptrac.c:8050-8055.  This process owns the
  * particles [ip0, ip0 + np) of a simulation with np_total particles; random
  * numbers are drawn for the global index so results do not depend on the
@@ -512,7 +591,10 @@ int mphip_comm_query(mphip_ctx *ctx, int *nranks, int *rank);
  *     particles that changed their cell are sorted, then merged with the others) instead of sorting from scratch; same
  *     permutation
  *   "big_grid" (default 0): tests -- take the instantiations with 64-bit byte offsets into the packed meteo records (what a
- *     grid with more than 4 GB of wind records -- 178e6 cells -- takes by itself) on a grid that fits 32 bits too: same bits. */
+ *     grid with more than 4 GB of wind records -- 178e6 cells -- takes by itself) on a grid that fits 32 bits too: same bits.
+ *   "derive_profile_phase" (default 0; 1, 2): measurement -- what mphip_profile_begin / _end time of a mphip_derive_met
+ *     call: every kernel (0), the uploads (1) or the downloads (2), as event pairs on the call's own stream (a caller that
+ *     profiles does not step from another thread meanwhile). */
 int mphip_set_option(mphip_ctx *ctx, const char *name, double value);
 int mphip_synchronize(mphip_ctx *ctx);
 

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "mphip_kernels.hpp"
+#include "mphip_metprep.hpp"
 
 using namespace mphip;
 
@@ -266,6 +267,17 @@ struct mphip_ctx {
   void *allreduce_user = nullptr;
   void *comm = nullptr;               // RCCL communicator (ncclComm_t) of mphip_comm_init, NULL = single rank / hook
   int comm_ranks = 1, comm_rank = 0;
+
+  // mphip_derive_met: a stream and scratch of its own (inputs, outputs and axes of one snapshot, kept for the grid size
+  // of the last call), so that a file-reader thread may call it while another thread steps; prep_lock serialises callers
+  std::mutex prep_lock;
+  hipStream_t prep_stream = nullptr;
+  int prep_nx = 0, prep_ny = 0, prep_np = 0;
+  float *prep_in3[MPHIP_N3D] = {}, *prep_in2[MPHIP_N2D] = {};
+  float *prep_out2[MPHIP_N2D] = {};
+  float *prep_z[2] = {};              // geopotential height before and after the smoothing
+  double *prep_axes = nullptr;        // p[np] | lat[ny]
+  int prep_profile_phase = 0;         // option "derive_profile_phase": what mphip_profile_begin / _end time of a call
 
   // profiling of the fused step kernel
   bool prof = false;
@@ -2663,6 +2675,71 @@ int upload_fields(mphip_ctx *ctx, MetSlot &S, const mphip_met_t *met, bool new_g
   return 0;
 }
 
+// ---- mphip_derive_met: scratch and copies --------------------------------------------------------------------------
+void prep_release(mphip_ctx *ctx) {
+  for (auto &q : ctx->prep_in3) {
+    dev_free(q);
+    q = nullptr;
+  }
+  for (auto &q : ctx->prep_in2) {
+    dev_free(q);
+    q = nullptr;
+  }
+  for (auto &q : ctx->prep_out2) {
+    dev_free(q);
+    q = nullptr;
+  }
+  for (auto &q : ctx->prep_z) {
+    dev_free(q);
+    q = nullptr;
+  }
+  dev_free(ctx->prep_axes);
+  ctx->prep_axes = nullptr;
+  ctx->prep_nx = ctx->prep_ny = ctx->prep_np = 0;
+}
+
+// a level field between the caller's (possibly strided) array and a compact device array
+int prep_copy3(mphip_ctx *ctx, float *dev, const float *host, const mphip_met_t *m, bool to_device, hipStream_t stream) {
+  const size_t n3 = (size_t) m->nx * m->ny * m->np;
+  if (m->sy == m->np && m->sx == (long long) m->ny * m->np) {
+    if (to_device)
+      HIPCHK(hipMemcpyAsync(dev, host, n3 * sizeof(float), hipMemcpyHostToDevice, stream));
+    else
+      HIPCHK(hipMemcpyAsync((void *) host, dev, n3 * sizeof(float), hipMemcpyDeviceToHost, stream));
+    return 0;
+  }
+  hipMemcpy3DParms p;
+  memset(&p, 0, sizeof(p));
+  const hipPitchedPtr h = make_hipPitchedPtr((void *) host, (size_t) m->sy * sizeof(float), (size_t) m->np, (size_t) (m->sx / m->sy));
+  const hipPitchedPtr d = make_hipPitchedPtr(dev, (size_t) m->np * sizeof(float), (size_t) m->np, (size_t) m->ny);
+  p.srcPtr = to_device ? h : d;
+  p.dstPtr = to_device ? d : h;
+  p.extent = make_hipExtent((size_t) m->np * sizeof(float), (size_t) m->ny, (size_t) m->nx);
+  p.kind = to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+  HIPCHK(hipMemcpy3DAsync(&p, stream));
+  return 0;
+}
+
+int prep_copy2(mphip_ctx *ctx, float *dev, const float *host, const mphip_met_t *m, bool to_device, hipStream_t stream) {
+  const size_t row = (size_t) m->ny * sizeof(float), hrow = (size_t) m->sx2 * sizeof(float);
+  if (to_device)
+    HIPCHK(hipMemcpy2DAsync(dev, row, host, hrow, row, (size_t) m->nx, hipMemcpyHostToDevice, stream));
+  else
+    HIPCHK(hipMemcpy2DAsync((void *) host, hrow, dev, row, row, (size_t) m->nx, hipMemcpyDeviceToHost, stream));
+  return 0;
+}
+
+// columns per workgroup of a column kernel that stages nf fields: the largest power of two up to 64 within 64 KB of LDS
+int prep_columns(int np, int nf, size_t *lds) {
+  const int pitch = np | 1;
+  for (int cpb = kPrepLanes; cpb >= 1; cpb >>= 1) {
+    *lds = 2 * (size_t) np * sizeof(double) + (size_t) nf * cpb * pitch * sizeof(float);
+    if (*lds <= 64 * 1024)
+      return cpb;
+  }
+  return 0;
+}
+
 }   // namespace
 
 // ---------------------------------------------------------------------------
@@ -2736,6 +2813,9 @@ void mphip_destroy(mphip_ctx *ctx) {
     for (auto p : s->f2)
       dev_free(p);
   }
+  prep_release(ctx);
+  if (ctx->prep_stream)
+    (void) hipStreamDestroy(ctx->prep_stream);
   dev_free(ctx->d_clim);
   for (auto p : ctx->d_zm)
     dev_free(p);
@@ -3230,6 +3310,281 @@ int mphip_prefetch_met(mphip_ctx *ctx, const mphip_met_t *met) {
     ctx->uploader_rc = rc;
     ctx->uploader_done = true;
   });
+  return 0;
+}
+
+int mphip_derive_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const mphip_prep_t *opt, const mphip_met_out_t *out) {
+  if (!ctx || !in || !opt || !out)
+    return fail(ctx, "mphip_derive_met: null argument");
+  constexpr unsigned kAll = MPHIP_PREP_GEOPOT | MPHIP_PREP_O3C | MPHIP_PREP_PBL | MPHIP_PREP_CLOUD | MPHIP_PREP_CAPE;
+  if (!what || (what & ~kAll))
+    return fail(ctx, "mphip_derive_met: `what` must be an OR of MPHIP_PREP_* bits");
+  if (in->nx < 2 || in->ny < 2 || !in->lon || !in->lat || !in->p)
+    return fail(ctx, "mphip_derive_met: meteo grid dimensions out of range");
+  if (in->np < 2)
+    return fail(ctx, "mphip_derive_met: needs two pressure levels or more (np < 2)");
+  if ((long long) in->nx * in->ny >= (1LL << 24) || (long long) in->nx * in->ny * in->np >= (1LL << 31))
+    return fail(ctx, "mphip_derive_met: meteo grid too large for the device index arithmetic");
+  const bool compact = in->sy == in->np && in->sx == (long long) in->ny * in->np;
+  if ((!compact && (in->sy < in->np || in->sx < in->sy * in->ny || in->sx % in->sy != 0)) || in->sx2 < in->ny)
+    return fail(ctx, "mphip_derive_met: unsupported meteo strides");
+  for (int k = 1; k < in->np; k++)
+    if (!(in->p[k] < in->p[k - 1]))
+      return fail(ctx, "mphip_derive_met: the pressure axis must be strictly descending");
+  // inputs and outputs of the requested bits
+  bool need3[MPHIP_N3D] = {}, need2[MPHIP_N2D] = {}, give2[MPHIP_N2D] = {};
+  const bool geopot = what & MPHIP_PREP_GEOPOT;
+  auto missing = [&](const char *bit, const char *names) {
+    return fail(ctx, std::string("mphip_derive_met: ") + bit + " needs the fields " + names);
+  };
+  auto have3 = [&](std::initializer_list<int> f) {
+    bool ok = true;
+    for (int k : f) {
+      ok = ok && in->f3[k];
+      need3[k] = true;
+    }
+    return ok;
+  };
+  auto have2 = [&](std::initializer_list<int> f) {
+    bool ok = true;
+    for (int k : f) {
+      ok = ok && in->f2[k];
+      need2[k] = true;
+    }
+    return ok;
+  };
+  auto outputs = [&](std::initializer_list<int> f) {
+    bool ok = true;
+    for (int k : f) {
+      ok = ok && out->f2[k];
+      give2[k] = true;
+    }
+    return ok;
+  };
+  int sx = 0, sy = 0;
+  if (geopot) {
+    if (!(have3({ MPHIP_T, MPHIP_H2O }) & have2({ MPHIP_PS, MPHIP_ZS })))
+      return missing("MPHIP_PREP_GEOPOT", "t, h2o, ps, zs");
+    if (!out->f3[MPHIP_Z])
+      return fail(ctx, "mphip_derive_met: MPHIP_PREP_GEOPOT needs the output array z");
+    sx = opt->met_geopot_sx;
+    sy = opt->met_geopot_sy;
+    if (sx < 0 || sy < 0) {
+      const bool fine = fabs(in->lon[1] - in->lon[0]) < 0.5;
+      sx = fine ? 3 : 6;
+      sy = fine ? 2 : 4;
+    }
+    if (sx == 0 || sy == 0)
+      sx = sy = 0;
+    if (sx > 0 && (sx - 1 > in->nx
+                   || (size_t) (kSmTX + 2 * (sx - 1)) * (kSmTY + 2 * (sy - 1)) * kSmKC * sizeof(float) > 64 * 1024))
+      return fail(ctx, "mphip_derive_met: smoothing half-widths too large (met_geopot_sx - 1 <= nx, tile within 64 KB of LDS)");
+  }
+  if (what & MPHIP_PREP_O3C) {
+    if (!(have3({ MPHIP_O3 }) & have2({ MPHIP_PS })))
+      return missing("MPHIP_PREP_O3C", "o3, ps");
+    if (!outputs({ MPHIP_O3C }))
+      return fail(ctx, "mphip_derive_met: MPHIP_PREP_O3C needs the output array o3c");
+  }
+  if (what & MPHIP_PREP_PBL) {
+    if (opt->met_pbl != 2 && opt->met_pbl != 3)
+      return fail(ctx, "mphip_derive_met: met_pbl must be 2 (bulk Richardson number) or 3 (potential temperature)");
+    if (!(have3({ MPHIP_T }) & have2({ MPHIP_PS, MPHIP_TS })))
+      return missing("MPHIP_PREP_PBL", "t, ps, ts");
+    if (opt->met_pbl == 2) {
+      if (!(have3({ MPHIP_U, MPHIP_V, MPHIP_H2O }) & have2({ MPHIP_US, MPHIP_VS, MPHIP_ZS })) || (!geopot && !in->f3[MPHIP_Z]))
+        return missing("MPHIP_PREP_PBL with met_pbl 2", "t, h2o, u, v, ps, ts, us, vs, zs and z (given, or MPHIP_PREP_GEOPOT in the same call)");
+      if (!geopot)
+        need3[MPHIP_Z] = true;
+    }
+    if (!outputs({ MPHIP_PBL }))
+      return fail(ctx, "mphip_derive_met: MPHIP_PREP_PBL needs the output array pbl");
+  }
+  if (what & MPHIP_PREP_CLOUD) {
+    if (!(have3({ MPHIP_LWC, MPHIP_IWC }) & have2({ MPHIP_PS })))
+      return missing("MPHIP_PREP_CLOUD", "lwc, iwc, ps");
+    need3[MPHIP_RWC] = in->f3[MPHIP_RWC] != nullptr;
+    need3[MPHIP_SWC] = in->f3[MPHIP_SWC] != nullptr;
+    if (!outputs({ MPHIP_PCT, MPHIP_PCB, MPHIP_CL }))
+      return fail(ctx, "mphip_derive_met: MPHIP_PREP_CLOUD needs the output arrays pct, pcb, cl");
+  }
+  if (what & MPHIP_PREP_CAPE) {
+    if (!(have3({ MPHIP_T, MPHIP_H2O }) & have2({ MPHIP_PS })))
+      return missing("MPHIP_PREP_CAPE", "t, h2o, ps");
+    if (!ctx->have_clim)
+      return fail(ctx, "mphip_derive_met: MPHIP_PREP_CAPE needs the tropopause climatology (mphip_update_clim first)");
+    if (in->coord_type != 0 && !ctx->have_ctl)
+      return fail(ctx, "mphip_derive_met: MPHIP_PREP_CAPE on a Cartesian grid needs met_utm_ref_lat (mphip_update_ctl first)");
+    if (!outputs({ MPHIP_PLCL, MPHIP_PLFC, MPHIP_PEL, MPHIP_CAPE, MPHIP_CIN }))
+      return fail(ctx, "mphip_derive_met: MPHIP_PREP_CAPE needs the output arrays plcl, plfc, pel, cape, cin");
+  }
+  const int np = in->np;
+  size_t lds_geo = 0, lds_o3 = 0, lds_cloud = 0, lds_pbl = 0, lds_cape = 0;
+  const int c_geo = prep_columns(np, 3, &lds_geo), c_o3 = prep_columns(np, 1, &lds_o3), c_cloud = prep_columns(np, 4, &lds_cloud);
+  const int c_pbl = prep_columns(np, opt->met_pbl == 2 ? 5 : 1, &lds_pbl), c_cape = prep_columns(np, 2, &lds_cape);
+  if ((geopot && !c_geo) || ((what & MPHIP_PREP_O3C) && !c_o3) || ((what & MPHIP_PREP_CLOUD) && !c_cloud)
+      || ((what & MPHIP_PREP_PBL) && !c_pbl) || ((what & MPHIP_PREP_CAPE) && !c_cape))
+    return fail(ctx, "mphip_derive_met: too many pressure levels for one column in 64 KB of LDS");
+
+  std::lock_guard<std::mutex> guard(ctx->prep_lock);
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!ctx->prep_stream)
+    HIPCHK(hipStreamCreateWithFlags(&ctx->prep_stream, hipStreamNonBlocking));
+  hipStream_t st = ctx->prep_stream;
+  if (in->nx != ctx->prep_nx || in->ny != ctx->prep_ny || np != ctx->prep_np) {
+    prep_release(ctx);
+    ctx->prep_nx = in->nx;
+    ctx->prep_ny = in->ny;
+    ctx->prep_np = np;
+    if (dev_alloc(ctx, &ctx->prep_axes, (size_t) np + in->ny))
+      return 1;
+  }
+  const size_t ncol = (size_t) in->nx * in->ny, ncell = ncol * np;
+  // mphip_profile_begin / _end (tools/gpu_met_prep_cost.py; a caller that profiles does not step from another thread):
+  // event pairs around every kernel (phase 0), around the uploads (1) or around the downloads (2)
+  hipEvent_t ev_stop = nullptr;
+  auto mark_begin = [&](int phase) {
+    ev_stop = nullptr;
+    if (!ctx->prof || ctx->prep_profile_phase != phase)
+      return 0;
+    while (ctx->ev_used + 2 > ctx->ev.size()) {
+      hipEvent_t e;
+      HIPCHK(hipEventCreate(&e));
+      ctx->ev.push_back(e);
+    }
+    HIPCHK(hipEventRecord(ctx->ev[ctx->ev_used++], st));
+    ev_stop = ctx->ev[ctx->ev_used++];
+    return 0;
+  };
+  auto mark_end = [&]() {
+    if (ev_stop)
+      HIPCHK(hipEventRecord(ev_stop, st));
+    return 0;
+  };
+  if (mark_begin(1))
+    return 1;
+  HIPCHK(hipMemcpyAsync(ctx->prep_axes, in->p, (size_t) np * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(ctx->prep_axes + np, in->lat, (size_t) in->ny * sizeof(double), hipMemcpyHostToDevice, st));
+  for (int f = 0; f < MPHIP_N3D; f++)
+    if (need3[f]) {
+      if (!ctx->prep_in3[f] && dev_alloc(ctx, &ctx->prep_in3[f], ncell))
+        return 1;
+      if (prep_copy3(ctx, ctx->prep_in3[f], in->f3[f], in, true, st))
+        return 1;
+    }
+  for (int f = 0; f < MPHIP_N2D; f++) {
+    if (need2[f]) {
+      if (!ctx->prep_in2[f] && dev_alloc(ctx, &ctx->prep_in2[f], ncol))
+        return 1;
+      if (prep_copy2(ctx, ctx->prep_in2[f], in->f2[f], in, true, st))
+        return 1;
+    }
+    if (give2[f] && !ctx->prep_out2[f] && dev_alloc(ctx, &ctx->prep_out2[f], ncol))
+      return 1;
+  }
+  if (geopot)
+    for (auto &q : ctx->prep_z)
+      if (!q && dev_alloc(ctx, &q, ncell))
+        return 1;
+  if (mark_end())
+    return 1;
+
+  PrepGrid G;
+  G.nx = in->nx;
+  G.ny = in->ny;
+  G.np = np;
+  G.pitch = np | 1;
+  G.ncol = (int) ncol;
+  G.p = ctx->prep_axes;
+  G.lat = ctx->prep_axes + np;
+  PrepOpt O;
+  O.met_pbl = opt->met_pbl;
+  O.pbl_min = opt->met_pbl_min;
+  O.pbl_max = opt->met_pbl_max;
+  O.cloud_min = opt->met_cloud_min;
+  O.time = in->time;
+  O.coord_type = in->coord_type;
+  O.ref_lat = ctx->have_ctl ? ctx->ctl.met_utm_ref_lat : 0.0;
+  auto blocks = [&](int cpb) {
+    G.cpb = cpb;
+    return dim3((unsigned) ((ncol + cpb - 1) / cpb));
+  };
+  float *const *i3 = ctx->prep_in3, *const *i2 = ctx->prep_in2, *const *o2 = ctx->prep_out2;
+  const float *z_final = i3[MPHIP_Z];
+  if (geopot) {
+    const dim3 nb = blocks(c_geo);
+    if (mark_begin(0))
+      return 1;
+    hipLaunchKernelGGL(prep_geopot_kernel, nb, dim3(kPrepLanes), lds_geo, st, G, i3[MPHIP_T], i3[MPHIP_H2O], i2[MPHIP_PS],
+                       i2[MPHIP_ZS], ctx->prep_z[0]);
+    HIPCHK(hipGetLastError());
+    if (mark_end())
+      return 1;
+    z_final = ctx->prep_z[0];
+    if (sx > 0) {
+      const size_t lds = (size_t) (kSmTX + 2 * (sx - 1)) * (kSmTY + 2 * (sy - 1)) * kSmKC * sizeof(float);
+      const dim3 tiles((in->nx + kSmTX - 1) / kSmTX, (in->ny + kSmTY - 1) / kSmTY, (np + kSmKC - 1) / kSmKC);
+      if (mark_begin(0))
+        return 1;
+      hipLaunchKernelGGL(prep_smooth_kernel, tiles, dim3(256), lds, st, G, sx, sy, ctx->prep_z[0], ctx->prep_z[1]);
+      HIPCHK(hipGetLastError());
+      if (mark_end())
+        return 1;
+      z_final = ctx->prep_z[1];
+    }
+  }
+  if (what & MPHIP_PREP_O3C) {
+    const dim3 nb = blocks(c_o3);
+    if (mark_begin(0))
+      return 1;
+    hipLaunchKernelGGL(prep_o3c_kernel, nb, dim3(kPrepLanes), lds_o3, st, G, i3[MPHIP_O3], i2[MPHIP_PS], o2[MPHIP_O3C]);
+    HIPCHK(hipGetLastError());
+    if (mark_end())
+      return 1;
+  }
+  if (what & MPHIP_PREP_CLOUD) {
+    const dim3 nb = blocks(c_cloud);
+    if (mark_begin(0))
+      return 1;
+    hipLaunchKernelGGL(prep_cloud_kernel, nb, dim3(kPrepLanes), lds_cloud, st, G, O, i3[MPHIP_LWC],
+                       need3[MPHIP_RWC] ? i3[MPHIP_RWC] : nullptr, i3[MPHIP_IWC], need3[MPHIP_SWC] ? i3[MPHIP_SWC] : nullptr,
+                       i2[MPHIP_PS], o2[MPHIP_PCT], o2[MPHIP_PCB], o2[MPHIP_CL]);
+    HIPCHK(hipGetLastError());
+    if (mark_end())
+      return 1;
+  }
+  if (what & MPHIP_PREP_PBL) {
+    const dim3 nb = blocks(c_pbl);
+    const bool ri = opt->met_pbl == 2;
+    if (mark_begin(0))
+      return 1;
+    hipLaunchKernelGGL(prep_pbl_kernel, nb, dim3(kPrepLanes), lds_pbl, st, G, O, i3[MPHIP_T], ri ? i3[MPHIP_H2O] : nullptr,
+                       ri ? i3[MPHIP_U] : nullptr, ri ? i3[MPHIP_V] : nullptr, ri ? z_final : nullptr, i2[MPHIP_PS], i2[MPHIP_TS],
+                       ri ? i2[MPHIP_ZS] : nullptr, ri ? i2[MPHIP_US] : nullptr, ri ? i2[MPHIP_VS] : nullptr, o2[MPHIP_PBL]);
+    HIPCHK(hipGetLastError());
+    if (mark_end())
+      return 1;
+  }
+  if (what & MPHIP_PREP_CAPE) {
+    const dim3 nb = blocks(c_cape);
+    if (mark_begin(0))
+      return 1;
+    hipLaunchKernelGGL(prep_cape_kernel, nb, dim3(kPrepLanes), lds_cape, st, G, O, ctx->d_clim, i3[MPHIP_T], i3[MPHIP_H2O],
+                       i2[MPHIP_PS], o2[MPHIP_PLCL], o2[MPHIP_PLFC], o2[MPHIP_PEL], o2[MPHIP_CAPE], o2[MPHIP_CIN]);
+    HIPCHK(hipGetLastError());
+    if (mark_end())
+      return 1;
+  }
+  if (mark_begin(2))
+    return 1;
+  if (geopot && prep_copy3(ctx, const_cast<float *>(z_final), out->f3[MPHIP_Z], in, false, st))
+    return 1;
+  for (int f = 0; f < MPHIP_N2D; f++)
+    if (give2[f] && prep_copy2(ctx, ctx->prep_out2[f], out->f2[f], in, false, st))
+      return 1;
+  if (mark_end())
+    return 1;
+  HIPCHK(hipStreamSynchronize(st));
   return 0;
 }
 
@@ -4467,6 +4822,12 @@ int mphip_set_option(mphip_ctx *ctx, const char *name, double value) {
   }
   if (strcmp(name, "big_grid") == 0) {
     ctx->big_grid = value != 0;
+    return 0;
+  }
+  if (strcmp(name, "derive_profile_phase") == 0) {
+    if (value != 0 && value != 1 && value != 2)
+      return fail(ctx, "derive_profile_phase must be 0 (kernels), 1 (uploads) or 2 (downloads)");
+    ctx->prep_profile_phase = (int) value;
     return 0;
   }
   if (strcmp(name, "xcd_map") == 0) {

@@ -1,8 +1,11 @@
 /*
  * met_conv.c -- conversion between the meteo file formats, MI355X build: the reference's met_conv tool
  * (src/met_conv.c) on the host layer's readers and writers -- MET_TYPE 0 (netCDF: classic or netCDF-4 in, classic
- * out) and 1 (the reference's binary format).  No device involved; as in mptrac_read_met of this build, netCDF input
- * is taken as stored (no meteo preprocessing).
+ * out) and 1 (the reference's binary format).  As in mptrac_read_met of this build, netCDF input is taken as stored
+ * by default and no device is involved; with HIP_MET_PREP 1 the device derives the geopotential heights, the ozone
+ * column, the boundary-layer pressure, the cloud layer and CAPE / CIN with their levels from the file's fields
+ * (mphip_derive_met), and the output carries them: every plane of a MET_TYPE 1 file, the surface variables of a netCDF
+ * file.  The tropopause fields and potential vorticity are not derived.
  *
  *   met_conv <ctl> <met_in> <met_in_type> <met_out> <met_out_type> [KEY VALUE ...]
  */

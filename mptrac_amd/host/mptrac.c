@@ -22,6 +22,7 @@
 /* process-global device state; the reference's interface is not re-entrant
  * either (file-static RNG state, mptrac.c:32-40) */
 static mphip_ctx *g_ctx;
+static int g_prep_ready;               /* met_derive has set up this context (HIP_MET_PREP) */
 static const met_t *g_met_host[2];     /* host snapshots mirrored in device slots met0 / met1 */
 /* meteo read-ahead (HIP_MET_PREFETCH), see start_read_ahead() */
 static struct {
@@ -105,6 +106,7 @@ void mptrac_free(ctl_t *ctl, cache_t *cache, clim_t *clim, met_t *met0, met_t *m
     mphip_destroy(g_ctx);
     g_ctx = NULL;
   }
+  g_prep_ready = 0;
   free(g_ahead.met);
   g_ahead.met = NULL;
   g_met_host[0] = g_met_host[1] = NULL;
@@ -203,6 +205,11 @@ static const char *unsupported_qnt[] = {
   I(met_nc_scale, "MET_NC_SCALE", "1") \
   I(met_pbl, "MET_PBL", "3") \
   I(met_cape, "MET_CAPE", "1") \
+  D(met_pbl_min, "MET_PBL_MIN", "0.1") \
+  D(met_pbl_max, "MET_PBL_MAX", "5.0") \
+  I(met_geopot_sx, "MET_GEOPOT_SX", "-1") \
+  I(met_geopot_sy, "MET_GEOPOT_SY", "-1") \
+  D(met_cloud_min, "MET_CLOUD_MIN", "0") \
   D(sort_dt, "SORT_DT", "-999") \
   I(rng_type, "RNG_TYPE", "1") \
   I(advect, "ADVECT", "2") \
@@ -340,6 +347,7 @@ static const char *unsupported_qnt[] = {
   I(hip_device, "HIP_DEVICE", "0") \
   I(hip_locality_interval, "HIP_LOCALITY_SORT_INTERVAL", "60") \
   I(hip_met_prefetch, "HIP_MET_PREFETCH", "0") \
+  I(hip_met_prep, "HIP_MET_PREP", "0") \
   I(hip_device_analysis, "HIP_DEVICE_ANALYSIS", "1")
 
 void mptrac_read_ctl(const char *filename, int argc, char *argv[], ctl_t *ctl) {
@@ -1388,7 +1396,7 @@ static void met_bin_body(FILE *f, int write, met_t *met) {
   free(buf);
 }
 
-static int read_met_nc(const char *filename, const ctl_t *ctl, met_t *met);
+static int read_met_nc(const char *filename, const ctl_t *ctl, const clim_t *clim, met_t *met);
 
 static int extent_from_file(FILE *in, const int max, const char *what) {
   const int n = get_int(in);
@@ -1399,11 +1407,10 @@ static int extent_from_file(FILE *in, const int max, const char *what) {
 
 /* MET_TYPE 1: [1] [104] time nx ny np lon[] lat[] p[] fields [999] (reference: read_met_bin, write_met_bin) */
 int mptrac_read_met(const char *filename, const ctl_t *ctl, const clim_t *clim, met_t *met, dd_t *dd) {
-  (void) clim;
   (void) dd;
   LOG(1, "Read meteo data: %s", filename);
   if (ctl->met_type == 0)
-    return read_met_nc(filename, ctl, met);
+    return read_met_nc(filename, ctl, clim, met);
   if (ctl->met_type != 1)
     ERRMSG("This build reads MET_TYPE 0 (classic netCDF, grids without preprocessing) and 1 (raw binary) meteo files!");
   FILE *in = fopen(filename, "r");
@@ -1694,7 +1701,14 @@ static void met_periodic(met_t *met) {
     memcpy(f3[f][last], f3[f][0], sizeof(f3[f][0]));
 }
 
-static int read_met_nc(const char *filename, const ctl_t *ctl, met_t *met) {
+/* What the file gave, for met_derive */
+typedef struct {
+  int zs, ts, us, vs, h2o, o3, lwc, rwc, iwc, swc, pbl;
+} nc_have_t;
+
+static unsigned met_derive(const ctl_t *ctl, const clim_t *clim, met_t *met, const nc_have_t *have);
+
+static int read_met_nc(const char *filename, const ctl_t *ctl, const clim_t *clim, met_t *met) {
   char err[256];
   ncc_file *nc = ncc_open(filename, err, sizeof(err));
   if (!nc) {
@@ -1763,10 +1777,12 @@ static int read_met_nc(const char *filename, const ctl_t *ctl, met_t *met) {
     EACH_COLUMN(met, i, j)
       met->ps[i][j] = (float) met->p[0];
   }
-  (void) NC_2D(zs, (float) (1. / (1000. * 9.80665)), "z", "Z");
-  (void) NC_2D(ts, 1.0f, "t2m", "T2M", "2t", "2T", "t2", "T2");
-  (void) NC_2D(us, 1.0f, "u10m", "U10M", "10u", "10U", "u10", "U10");
-  (void) NC_2D(vs, 1.0f, "v10m", "V10M", "10v", "10V", "v10", "V10");
+  nc_have_t have;
+  memset(&have, 0, sizeof(have));
+  have.zs = NC_2D(zs, (float) (1. / (1000. * 9.80665)), "z", "Z");
+  have.ts = NC_2D(ts, 1.0f, "t2m", "T2M", "2t", "2T", "t2", "T2");
+  have.us = NC_2D(us, 1.0f, "u10m", "U10M", "10u", "10U", "u10", "U10");
+  have.vs = NC_2D(vs, 1.0f, "v10m", "V10M", "10v", "10V", "v10", "V10");
   (void) NC_2D(ess, 1.0f, "iews", "IEWS");
   (void) NC_2D(nss, 1.0f, "inss", "INSS");
   (void) NC_2D(shf, 1.0f, "ishf", "ISHF");
@@ -1781,12 +1797,15 @@ static int read_met_nc(const char *filename, const ctl_t *ctl, met_t *met) {
   REQUIRE(NC_3D(v, 1.0f, "v", "V"), "Cannot read meridional wind!");
   if (!NC_3D(w, 0.01f, "w", "W", "omega", "OMEGA"))   /* Pa/s -> hPa/s */
     WARN("Cannot read vertical velocity!");
-  if (!NC_3D(h2o, (float) (MA / MH2O), "q", "Q", "sh", "SH"))   /* mass -> volume mixing ratio */
+  if (!(have.h2o = NC_3D(h2o, (float) (MA / MH2O), "q", "Q", "sh", "SH")))   /* mass -> volume mixing ratio */
     WARN("Cannot read specific humidity!");
-  if (!NC_3D(o3, (float) (MA / MO3), "o3", "O3"))
+  if (!(have.o3 = NC_3D(o3, (float) (MA / MO3), "o3", "O3")))
     WARN("Cannot read ozone data!");
-  const int have_cloud = NC_3D(lwc, 1.0f, "clwc", "CLWC") & NC_3D(rwc, 1.0f, "crwc", "CRWC")
-    & NC_3D(iwc, 1.0f, "ciwc", "CIWC") & NC_3D(swc, 1.0f, "cswc", "CSWC");
+  have.lwc = NC_3D(lwc, 1.0f, "clwc", "CLWC");
+  have.rwc = NC_3D(rwc, 1.0f, "crwc", "CRWC");
+  have.iwc = NC_3D(iwc, 1.0f, "ciwc", "CIWC");
+  have.swc = NC_3D(swc, 1.0f, "cswc", "CSWC");
+  have.pbl = have_pbl;
   (void) NC_3D(cc, 1.0f, "cc", "CC");
   ncc_close(nc);
   for (int k = 1; k < met->np; k++)
@@ -1811,32 +1830,43 @@ static int read_met_nc(const char *filename, const ctl_t *ctl, met_t *met) {
     met_periodic(met);
   }
 
-  /* Fields the reference derives in its preprocessing.  The boundary-layer pressure enters module_diff_turb
-   * only through weights that multiply TURB_DX_PBL / TURB_DZ_PBL against TURB_DX_TROP / TURB_DZ_TROP: with
-   * equal values (the defaults) and none of the other consumers active any finite value below the
-   * tropopause gives the reference's result, and surface pressure - 100 hPa is used.  Everything else that
-   * would need a derived field is refused. */
-  if (!have_pbl) {
+  /* Fields the reference derives in its preprocessing: with HIP_MET_PREP 1 the device derives what the file's fields
+   * allow (met_derive); a configuration that needs a field that was not derived is refused.  The boundary-layer
+   * pressure enters module_diff_turb only through weights that multiply TURB_DX_PBL / TURB_DZ_PBL against
+   * TURB_DX_TROP / TURB_DZ_TROP: with equal values (the defaults) and none of the other consumers active any finite
+   * value below the tropopause gives the reference's result, and surface pressure - 100 hPa is used. */
+  const unsigned got = ctl->hip_met_prep ? met_derive(ctl, clim, met, &have) : 0;
+  if (!have_pbl && !(got & MPHIP_PREP_PBL)) {
     if ((ctl->diffusion && (ctl->turb_dx_pbl != ctl->turb_dx_trop || ctl->turb_dz_pbl != ctl->turb_dz_trop
                             || ctl->turb_pbl_scheme != 0))
         || ctl->conv_mix_pbl || ctl->bound_pbl || ctl->qnt_pbl >= 0)
       ERRMSG("This configuration uses the boundary-layer pressure, which the reference derives in its meteo "
-             "preprocessing (not provided): supply it in the file (MET_PBL 0, variable blp) or use MET_TYPE 1 files!");
+             "preprocessing (not provided): supply it in the file (MET_PBL 0, variable blp) or use MET_TYPE 1 files, "
+             "or let the device derive it (HIP_MET_PREP 1 with MET_PBL 2 or 3 and the fields it needs: t2m; for 2 also "
+             "u10m, v10m, z, q)!");
     EACH_COLUMN(met, i, j)
       met->pbl[i][j] = met->ps[i][j] - 100.f;
   }
-  (void) have_cloud;
-  if (ctl->conv_cape >= 0)
-    ERRMSG("CONV_CAPE needs the equilibrium level from the reference's meteo preprocessing (not provided)!");
-  if (ctl->wet_depo_ic_a > 0 || ctl->wet_depo_ic_h[0] > 0)
-    ERRMSG("Wet deposition needs the cloud diagnostics (pct, pcb, cl) of the reference's meteo preprocessing (not provided)!");
-  static const char *const derived[] = { "pt", "tt", "zt", "h2ot", "zg", "pv", "pct", "pcb", "cl", "plcl", "plfc", "pel",
-    "cape", "cin", "o3c", NULL };
+  if (ctl->conv_cape >= 0 && !(got & MPHIP_PREP_CAPE))
+    ERRMSG("CONV_CAPE needs the equilibrium level from the reference's meteo preprocessing (not provided; "
+           "HIP_MET_PREP 1 with MET_CAPE 1 derives it on the device from t and q)!");
+  if ((ctl->wet_depo_ic_a > 0 || ctl->wet_depo_ic_h[0] > 0) && !(got & MPHIP_PREP_CLOUD))
+    ERRMSG("Wet deposition needs the cloud diagnostics (pct, pcb, cl) of the reference's meteo preprocessing (not provided; "
+           "HIP_MET_PREP 1 derives them on the device from clwc and ciwc)!");
+  static const struct {
+    const char *name;
+    unsigned bit;     /* the MPHIP_PREP_* bit that derives it; 0: out of scope */
+  } derived[] = { { "pt", 0 }, { "tt", 0 }, { "zt", 0 }, { "h2ot", 0 }, { "pv", 0 }, { "zg", MPHIP_PREP_GEOPOT },
+    { "pct", MPHIP_PREP_CLOUD }, { "pcb", MPHIP_PREP_CLOUD }, { "cl", MPHIP_PREP_CLOUD }, { "plcl", MPHIP_PREP_CAPE },
+    { "plfc", MPHIP_PREP_CAPE }, { "pel", MPHIP_PREP_CAPE }, { "cape", MPHIP_PREP_CAPE }, { "cin", MPHIP_PREP_CAPE },
+    { "o3c", MPHIP_PREP_O3C }, { NULL, 0 } };
   for (int iq = 0; iq < ctl->nq; iq++)
-    for (int k = 0; derived[k]; k++)
-      if (strcasecmp(ctl->qnt_name[iq], derived[k]) == 0 && !(have_cape && (k == 12 || k == 13)))
-        ERRMSG("Quantity %s comes from the reference's meteo preprocessing, which netCDF input does not get here!",
-               ctl->qnt_name[iq]);
+    for (int k = 0; derived[k].name; k++)
+      if (strcasecmp(ctl->qnt_name[iq], derived[k].name) == 0 && !(got & derived[k].bit)
+          && !(have_cape && (!strcmp(derived[k].name, "cape") || !strcmp(derived[k].name, "cin"))))
+        ERRMSG("Quantity %s comes from the reference's meteo preprocessing, which netCDF input does not get here%s!",
+               ctl->qnt_name[iq], derived[k].bit ? " without HIP_MET_PREP 1 and the fields it is derived from" :
+               " (HIP_MET_PREP does not derive it either)");
   return 1;
 }
 
@@ -2018,6 +2048,76 @@ static void upload_met(met_t *met, int slot) {
   mphip_met_t m;
   describe_met(met, &m);
   HIP(mphip_update_met(g_ctx, slot, &m));
+}
+
+/* HIP_MET_PREP 1: the fields of the reference's meteo preprocessing that the file's own fields allow, derived on the
+ * device into the met_t (mphip_derive_met: a stream and scratch of its own, so the read-ahead thread of
+ * HIP_MET_PREFETCH may call it while the main thread steps).  Returns the MPHIP_PREP_* bits that were derived.  The
+ * context and the tropopause table CAPE needs are set up by the first call, which every driver makes from its main
+ * thread (the first two files of a run are read there). */
+static unsigned met_derive(const ctl_t *ctl, const clim_t *clim, met_t *met, const nc_have_t *have) {
+  unsigned what = 0;
+  if (have->h2o && have->zs)
+    what |= MPHIP_PREP_GEOPOT;
+  if (have->o3)
+    what |= MPHIP_PREP_O3C;
+  if (!have->pbl && have->ts
+      && (ctl->met_pbl == 3 || (ctl->met_pbl == 2 && have->us && have->vs && (what & MPHIP_PREP_GEOPOT))))
+    what |= MPHIP_PREP_PBL;
+  if (have->lwc && have->iwc)
+    what |= MPHIP_PREP_CLOUD;
+  if (ctl->met_cape == 1 && have->h2o && clim)
+    what |= MPHIP_PREP_CAPE;
+  if (!what)
+    return 0;
+  if (!g_prep_ready) {
+    need_ctx(ctl);
+    if (what & MPHIP_PREP_CAPE)
+      HIP(mphip_update_clim(g_ctx, clim->tropo_ntime, clim->tropo_nlat, clim->tropo_time, clim->tropo_lat,
+                            &clim->tropo[0][0], 73));
+    if (ctl->met_coord_type != 0) {   /* the tropopause of a Cartesian grid is taken at MET_UTM_REF_LAT */
+      mphip_ctl_t d;
+      to_device_ctl(ctl, &d);
+      HIP(mphip_update_ctl(g_ctx, &d));
+    }
+    g_prep_ready = 1;
+  }
+  mphip_met_t in;
+  describe_met(met, &in);
+  in.npl = 0;
+  in.f3[MPHIP_Z] = NULL;
+  in.f3[MPHIP_O3] = have->o3 ? &met->o3[0][0][0] : NULL;
+  in.f3[MPHIP_H2O] = have->h2o ? &met->h2o[0][0][0] : NULL;
+  in.f3[MPHIP_LWC] = have->lwc ? &met->lwc[0][0][0] : NULL;
+  in.f3[MPHIP_RWC] = have->rwc ? &met->rwc[0][0][0] : NULL;
+  in.f3[MPHIP_IWC] = have->iwc ? &met->iwc[0][0][0] : NULL;
+  in.f3[MPHIP_SWC] = have->swc ? &met->swc[0][0][0] : NULL;
+  in.f2[MPHIP_ZS] = have->zs ? &met->zs[0][0] : NULL;
+  in.f2[MPHIP_TS] = have->ts ? &met->ts[0][0] : NULL;
+  in.f2[MPHIP_US] = have->us ? &met->us[0][0] : NULL;
+  in.f2[MPHIP_VS] = have->vs ? &met->vs[0][0] : NULL;
+  mphip_met_out_t out;
+  memset(&out, 0, sizeof(out));
+  out.f3[MPHIP_Z] = &met->z[0][0][0];
+  out.f2[MPHIP_O3C] = &met->o3c[0][0];
+  out.f2[MPHIP_PBL] = &met->pbl[0][0];
+  out.f2[MPHIP_PCT] = &met->pct[0][0];
+  out.f2[MPHIP_PCB] = &met->pcb[0][0];
+  out.f2[MPHIP_CL] = &met->cl[0][0];
+  out.f2[MPHIP_PLCL] = &met->plcl[0][0];
+  out.f2[MPHIP_PLFC] = &met->plfc[0][0];
+  out.f2[MPHIP_PEL] = &met->pel[0][0];
+  out.f2[MPHIP_CAPE] = &met->cape[0][0];
+  out.f2[MPHIP_CIN] = &met->cin[0][0];
+  const mphip_prep_t opt = { ctl->met_pbl, ctl->met_pbl_min, ctl->met_pbl_max, ctl->met_geopot_sx, ctl->met_geopot_sy,
+    ctl->met_cloud_min };
+  /* (not through HIP(): that macro first submits the main thread's queued time steps) */
+  if (mphip_derive_met(g_ctx, &in, what, &opt, &out) != 0)
+    ERRMSG("HIP back end: %s", mphip_last_error(g_ctx));
+  LOG(2, "Derived on the device:%s%s%s%s%s", what & MPHIP_PREP_GEOPOT ? " geopotential heights" : "",
+      what & MPHIP_PREP_O3C ? " ozone column" : "", what & MPHIP_PREP_PBL ? " boundary layer" : "",
+      what & MPHIP_PREP_CLOUD ? " cloud layer" : "", what & MPHIP_PREP_CAPE ? " CAPE" : "");
+  return what;
 }
 
 /* Read-ahead of the next meteo file (HIP_MET_PREFETCH 1, forward runs): while the time steps of the current
