@@ -254,7 +254,10 @@ int mphip_update_clim_photo(mphip_ctx *ctx, int np, int nsza, int no3c, const do
 /* mptrac_update_device(..., met0, met1, ...), mptrac.c:8034-8048; slot 0 = met0,
  * slot 1 = met1. */
 int mphip_update_met(mphip_ctx *ctx, int slot, const mphip_met_t *met);
-/* the met0/met1 pointer swap in mptrac_get_met, mptrac.c:6488-6491 */
+/* the met0/met1 pointer swap in mptrac_get_met, mptrac.c:6488-6491.  The forward hand-over is the swap followed by
+ * mphip_update_met(ctx, 1, next file); the backward hand-over of mptrac_get_met (DIRECTION -1, t < met0->time) is
+ * the same swap followed by mphip_update_met(ctx, 0, earlier file): the old met0 becomes met1, and the sort and
+ * interpolation axes become those of the snapshot just uploaded into slot 0. */
 int mphip_swap_met(mphip_ctx *ctx);
 /* The same hand-over of mptrac_get_met (read the next file into the old met0
  * buffer, swap, mptrac.c:6479-6503) with the upload taken off the stepping
@@ -270,7 +273,9 @@ int mphip_swap_met(mphip_ctx *ctx);
  * be called from a second thread (a file reader) while another thread steps;
  * everything else, the commit included, belongs to the stepping thread (the
  * reference's interface is not re-entrant either).  Same grid dimensions as the resident snapshots
- * ("Meteo grid dimensions do not match!" otherwise, mptrac.c:6543-6546). */
+ * ("Meteo grid dimensions do not match!" otherwise, mptrac.c:6543-6546).  The pair is the FORWARD hand-over only
+ * (the prefetched snapshot always becomes met1); a backward run hands over with mphip_swap_met +
+ * mphip_update_met(ctx, 0, ...). */
 int mphip_prefetch_met(mphip_ctx *ctx, const mphip_met_t *met);
 int mphip_commit_met(mphip_ctx *ctx);
 int mphip_prefetch_done(mphip_ctx *ctx);

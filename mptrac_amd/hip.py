@@ -175,6 +175,24 @@ def shard_range(n, rank, world):
     return (n * rank) // world, (n * (rank + 1)) // world
 
 
+def timestep_range(direction, dt_mod, t_stop, tmin, tmax):
+    """(t_start, t_stop) of module_timesteps_init (src/mptrac.c:6046-6073) from the smallest / largest particle time:
+    the run starts at the first release in the direction of travel, rounded outwards to the DT_MOD raster (floor for a
+    forward, ceil for a backward run), and ends at the last one unless T_STOP was given (<= 1e99)."""
+    if direction == 1:
+        t_start = tmin
+        if t_stop > 1e99:
+            t_stop = tmax
+    else:
+        t_start = tmax
+        if t_stop > 1e99:
+            t_stop = tmin
+    if direction * (t_stop - t_start) <= 0:
+        raise MphipError("Nothing to do! Check T_STOP and DIRECTION!")
+    t_start = float((np.floor if direction == 1 else np.ceil)(t_start / dt_mod) * dt_mod)
+    return t_start, float(t_stop)
+
+
 class Simulation:
     """Host-side handle: one device context + the reference's call sequence.
 
@@ -347,6 +365,14 @@ class Simulation:
         self._mets[0] = self._mets[1]
         self.set_met(1, new_met1)
 
+    def swap_met_backward(self, new_met0):
+        """mptrac_get_met when a backward run moves before met0: pointer swap (the old met0 is the new met1), then
+        read the earlier snapshot into met0 -- mphip_swap_met + mphip_update_met on slot 0 of a running context; the
+        sort and interpolation axes become the uploaded snapshot's."""
+        self._chk(self.L.mphip_swap_met(self.h))
+        self._mets[1] = self._mets[0]
+        self.set_met(0, new_met0)
+
     def prefetch_met(self, next_met):
         """Start the upload of the snapshot after met1 beside the time steps
         (copy stream); its arrays must stay untouched until commit_met()."""
@@ -441,17 +467,7 @@ class Simulation:
         """module_timesteps_init (src/mptrac.c:6046-6073) -- host logic on the
         global minimum / maximum particle time."""
         c = self.ctl
-        if c.direction == 1:
-            c.t_start = tmin
-            if c.t_stop > 1e99:
-                c.t_stop = tmax
-        else:
-            c.t_start = tmax
-            if c.t_stop > 1e99:
-                c.t_stop = tmin
-        if c.direction * (c.t_stop - c.t_start) <= 0:
-            raise MphipError("Nothing to do! Check T_STOP and DIRECTION!")
-        c.t_start = float((np.floor if c.direction == 1 else np.ceil)(c.t_start / c.dt_mod) * c.dt_mod)
+        c.t_start, c.t_stop = timestep_range(c.direction, c.dt_mod, c.t_stop, tmin, tmax)
         self.update_ctl()
 
     def run_timestep(self, t):

@@ -218,6 +218,12 @@ class Oracle:
         self.set_met(0, old1)
         self.set_met(1, new_met1)
 
+    def swap_met_backward(self, new_met0):
+        """mptrac_get_met's backward branch (t < met0->time): pointer swap + the earlier snapshot as the new met0."""
+        old0 = self._mets[0]
+        self.set_met(1, old0)
+        self.set_met(0, new_met0)
+
     def timesteps_init(self):
         self.lib.orc_module_timesteps_init(C.byref(self.ctl), C.byref(self.atm))
 

@@ -13,6 +13,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import backward
 import cases
 from mptrac_amd import hip
 from mptrac_amd.ctl import ctl_from_quantities
@@ -34,6 +35,16 @@ def _pair(name, n=10000, grid="C1", **kw):
     cases.prepare(o)
     cases.prepare(s)
     return o, s
+
+
+def _case(name, n, direction=1, **kw):
+    """(ctl, clim, met0, met1, atm) of a named case; direction -1: the case reversed in time (tests/backward.py: from
+    3600 s down to T_STOP 0 on the same two snapshots, particle times mirrored).  The bodies below that take a
+    `direction` run backward from tests/test_gpu_backward.py."""
+    if direction == 1:
+        return cases.make_case(name, n=n, **kw)
+    ctl, clim, mets, atm = backward.backward_case(name, n, **kw)
+    return ctl, clim, mets[0], mets[1], atm
 
 
 def _compare(o, s, tol=TOL):
@@ -311,17 +322,21 @@ def test_fused_step_equals_module_sequence():
                               "sedimentation_only", "convection_sedimentation", "mesoscale_only"])
 @pytest.mark.parametrize("advect", [4, 2, 1], ids=["rk4", "midpoint", "euler"])
 def test_lean_instantiations_equal_the_general_code(over, advect):
+    lean_instantiations_equal_the_general_code(over, advect)
+
+
+def lean_instantiations_equal_the_general_code(over, advect, direction=1):
     """The specialised (lean) instantiations of the step kernel -- straight-line stencil set-up, packed corner
     differences, one reciprocal per latitude; four Runge-Kutta stages, or the two of the midpoint scheme (the
     reference's default) of which the Euler scheme runs the first -- and the general instantiation compute the
     same bits."""
-    ctl, clim, m0, m1, atm = cases.make_case("conv_sedi", n=6001)
+    ctl, clim, m0, m1, atm = _case("conv_sedi", 6001, direction)
     ctl.update(over, advect=advect)
     runs = []
     for generic in (0, 1):
         s = hip.Simulation(ctl, clim, m0, m1, atm)
         s.set_option("generic_kernel", generic)
-        s.timesteps_init(0.0, 0.0)
+        s.timesteps_init(atm["time"].min(), atm["time"].max())
         for t in cases.step_times(s.ctl)[:6]:
             s.run_timestep(t)
         runs.append(s.state())
@@ -386,17 +401,21 @@ def test_module_sort_by_order_repair_equals_the_sort_from_scratch(n):
 @pytest.mark.parametrize("advect", [4, 2, 1], ids=["rk4", "midpoint", "euler"])
 @pytest.mark.parametrize("tile", [1024, 96])
 def test_lds_tile_trajectories_equal_the_launches_without_a_tile(advect, tile):
+    lds_tile_trajectories_equal_the_launches_without_a_tile(advect, tile)
+
+
+def lds_tile_trajectories_equal_the_launches_without_a_tile(advect, tile, direction=1):
     """Option lds_tile (the wind grid staged through an LDS tile per workgroup, traj_tile_kernel): runs of
     pure trajectory steps read their corner records from the tile where the stencil lies inside it and from global memory
     otherwise -- the bits of the launches without a tile, and the oracle's positions; with particles across the date
     line and at the poles, some of them released later, a tile far too small for a workgroup's box (96 cells), and the
     internal re-sort in between."""
-    ctl, clim, m0, m1, atm = cases.make_case("advect", n=30011, fields=("u", "v", "w", "ps"), quantities=("m",))
+    ctl, clim, m0, m1, atm = _case("advect", 30011, direction, fields=("u", "v", "w", "ps"), quantities=("m",))
     ctl.update(advect=advect)
     atm["lon"][:2000] = np.linspace(-180.0, 179.99, 2000)
     atm["lat"][:1000] = 89.95
     atm["lat"][1000:2000] = -89.95
-    atm["time"][::11] = 540.0
+    atm["time"][::11] = 540.0 if direction == 1 else 3600.0 - 540.0
     o = B.Oracle(ctl, clim, m0, m1, atm)
     o.timesteps_init()
     times = cases.step_times(o.ctl)[:14]
@@ -1292,16 +1311,20 @@ def test_full_size_subsample_against_oracle_1e6():
 
 @pytest.mark.parametrize("case", ["conv_sedi", "full"])
 def test_locality_order_is_not_observable(case):
+    locality_order_is_not_observable(case)
+
+
+def locality_order_is_not_observable(case, direction=1):
     """The device stores particles in grid-cell order and re-sorts every few
     steps; random numbers follow the external slot and downloads restore the
     caller's order, so results are bit-identical with the feature off, on, and
     on with downloads in between."""
-    ctl, clim, m0, m1, atm = cases.make_case(case, n=6001)
+    ctl, clim, m0, m1, atm = _case(case, 6001, direction)
     runs = {}
     for name, interval, peek in (("off", 0, False), ("every3", 3, False), ("every1_peek", 1, True)):
         s = hip.Simulation(ctl, clim, m0, m1, atm)
         s.set_option("locality_sort_interval", interval)
-        s.timesteps_init(0.0, 0.0)
+        s.timesteps_init(atm["time"].min(), atm["time"].max())
         for k, t in enumerate(cases.step_times(s.ctl)[:9]):
             s.run_timestep(t)
             if peek and k % 4 == 1:
@@ -1651,22 +1674,41 @@ def test_ensemble_mixing(nens):
 
 @pytest.mark.parametrize("sort_dt", [180.0, 360.0])
 def test_sort_ahead_of_time_is_not_observable(sort_dt):
+    sort_ahead_of_time_is_not_observable(sort_dt)
+
+
+def sort_ahead_of_time_is_not_observable(sort_dt, direction=1):
     """module_sort of the next time step starts on a second stream as soon as this step's particles have moved
     (option sort_ahead, default on) and is taken over if the next call comes with the expected time: the same
     bits as sorting when the call arrives -- with a sort every step and every other step, a download in between,
-    a single-module call in between (drops the prepared sort) and a meteo hand-over."""
-    ctl, clim, m0, m1, atm = cases.make_case("full", n=30000)
-    ctl = dict(ctl, sort_dt=sort_dt, mixing_dt=180.0, t_stop=7200.0)
-    m2 = synthetic_met("C1", 7200.0, 1.5, fields=cases.PRESSURE_LEVEL_FIELDS)
+    a single-module call in between (drops the prepared sort) and a meteo hand-over.
+    direction -1: two hours backward with the release times of backward.staggered_times -- the time step of the NEXT
+    call, which the prepared sort computes one step early, then differs between particles (some are released by it,
+    one sits exactly at its time, others still wait) -- and mptrac_get_met's backward hand-over."""
+    if direction == 1:
+        ctl, clim, m0, m1, atm = cases.make_case("full", n=30000)
+        ctl = dict(ctl, sort_dt=sort_dt, mixing_dt=180.0, t_stop=7200.0)
+        m2 = synthetic_met("C1", 7200.0, 1.5, fields=cases.PRESSURE_LEVEL_FIELDS)
+    else:
+        ctl, clim, mets, atm = backward.backward_case("full", 30000, hours=2, staggered=True, sort_dt=sort_dt, mixing_dt=180.0)
+        m2, m0, m1 = mets
+        backward.assert_staggered(atm["time"], 7200.0, 0.0, 180.0, steps=30)
     runs = []
     for ahead in (1, 0):
         s = hip.Simulation(ctl, clim, m0, m1, atm)
         s.set_option("sort_ahead", ahead)
-        s.timesteps_init(0.0, 0.0)
+        if direction == 1:
+            s.timesteps_init(0.0, 0.0)
+        else:
+            backward.start(s, atm["time"], t_start=7200.0)
         seen = []
         for k, t in enumerate(cases.step_times(s.ctl)[:30]):
             if k == 21:
-                s.swap_met(m2)
+                if direction == 1:
+                    s.swap_met(m2)
+                else:
+                    assert t < m0.time
+                    s.swap_met_backward(m2)
             s.run_timestep(t)
             if k == 5:
                 seen.append(s.state())              # download between two steps
@@ -1678,34 +1720,52 @@ def test_sort_ahead_of_time_is_not_observable(sort_dt):
         seen.append(s.get_cache()["dt"])
         runs.append(seen)
         s.close()
+    # Forward: equal bits, and no NaN passes.  Backward only: with staggered releases and module_sort in every step the
+    # reference hands particles the time steps of other indices, times run away from the meteo
+    # data's range and its arithmetic ends in NaN for some of them -- on the oracle too, whatever the release pattern
+    # (measured there: with 1 % staggered particles, or all releases within four steps, it ends the same way) --, so
+    # there a NaN must be a NaN at the same place in both runs.
+    nan_ok = direction == -1
     for a, b in zip(*runs):
         if isinstance(a, dict):
             for key in ("time", "lon", "lat", "p", "q", "uvwp"):
-                assert np.array_equal(a[key], b[key]), key
+                assert np.array_equal(a[key], b[key], equal_nan=nan_ok), key
         elif isinstance(a, tuple):
             assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
         else:
-            assert np.array_equal(a, b)
+            assert np.array_equal(a, b, equal_nan=nan_ok)
 
 
 def test_keys_and_deposition_flags_from_the_step_kernel_are_not_observable():
+    keys_and_deposition_flags_from_the_step_kernel_are_not_observable()
+
+
+def keys_and_deposition_flags_from_the_step_kernel_are_not_observable(direction=1):
     """BASELINE configs[4]'s schedule (module_sort and module_mixing in every step, decay, both deposition modules): the
     launch that moves the particles also writes the keys of the next module_sort, its module_timesteps, module_mixing's
     box and -- round 6 -- which particles the deposition launch behind module_mixing has to look at (EmitKeys, option
     emit_keys, default on).  With the option off a key kernel and the deposition launch derive all of that again from
-    the stored state: the same bits, with particles released later (dt = 0 in the first steps), and the oracle's."""
-    ctl, clim, m0, m1, atm = cases.make_case("full", n=30011)
+    the stored state: the same bits, with particles released later (dt = 0 in the first steps), and the oracle's.
+    direction -1: backward with the release times of backward.staggered_times (the next call's time step, written one
+    step early, differs between particles)."""
+    if direction == 1:
+        ctl, clim, m0, m1, atm = cases.make_case("full", n=30011)
+        atm["time"][::7] = 540.0
+    else:
+        ctl, clim, (m0, m1), atm = backward.backward_case("full", 30011, staggered=True)
+        backward.assert_staggered(atm["time"], 3600.0, 0.0, 180.0, steps=9)
     ctl = dict(ctl, sort_dt=180.0, mixing_dt=180.0)
-    atm["time"][::7] = 540.0
     atm["p"][::5] = 1013.25 * np.exp(-np.linspace(0.01, 1.5, len(atm["p"][::5])) / 7.0)      # a fifth near the ground: both modules busy
     o = B.Oracle(ctl, clim, m0, m1, atm)
     o.timesteps_init()
+    if direction == -1:
+        o.ctl.t_start = 3600.0
     times = cases.step_times(o.ctl)[:9]
     runs = []
     for emit in (1, 0):
         s = hip.Simulation(ctl, clim, m0, m1, atm)
         s.set_option("emit_keys", emit)
-        s.timesteps_init(atm["time"].min(), atm["time"].max())
+        s.timesteps_init(atm["time"].min(), atm["time"].max() if direction == 1 else 3600.0)
         for t in times:
             s.run_timestep(t)
         runs.append(s.state())
@@ -1715,24 +1775,29 @@ def test_keys_and_deposition_flags_from_the_step_kernel_are_not_observable():
             _compare(o, s)
         s.close()
     for k in ("time", "lon", "lat", "p", "q", "uvwp"):
-        assert np.array_equal(runs[0][k], runs[1][k]), k
+        assert np.array_equal(runs[0][k], runs[1][k]), k      # (nine steps: every value is finite in either direction)
     wet, dry = (list(cases.QUANTITIES).index(k) for k in ("mloss_wet", "mloss_dry"))
-    assert runs[0]["q"][wet].max() > 0 and runs[0]["q"][dry].max() > 0
+    # (both modules were busy; a backward step has dt < 0, so its "losses" are negative)
+    assert (direction * runs[0]["q"][wet]).max() > 0 and (direction * runs[0]["q"][dry]).max() > 0
 
 
 def test_deposition_launch_with_packed_waves_equals_the_fused_tail():
+    deposition_launch_with_packed_waves_equals_the_fused_tail()
+
+
+def deposition_launch_with_packed_waves_equals_the_fused_tail(direction=1):
     """The deposition modules behind module_mixing run in a kernel of their own that first packs the particles
     with anything to do into full waves (option compact_depo, default on); with the option off they run as the
     tail of the fused kernel -- the same bits, for the exponential-law and the Henry-law wet deposition, as single
     modules and inside time steps."""
     for case in ("full", "wet_henry"):
-        ctl, clim, m0, m1, atm = cases.make_case(case, n=20011)
+        ctl, clim, m0, m1, atm = _case(case, 20011, direction)
         ctl = dict(ctl, mixing_dt=180.0, mixing_trop=1e-3, mixing_strat=1e-6)
         runs = []
         for compact in (1, 0):
             s = hip.Simulation(ctl, clim, m0, m1, atm)
             s.set_option("compact_depo", compact)
-            s.timesteps_init(0.0, 0.0)
+            s.timesteps_init(atm["time"].min(), atm["time"].max())
             ts = cases.step_times(s.ctl)
             for t in ts[:6]:
                 s.run_timestep(t)
@@ -1865,13 +1930,17 @@ _BATCH_OVERRIDES = {"gas": dict(qnt_rp=-1, qnt_rhop=-1), "gas2": dict(qnt_rp=-1,
 @pytest.mark.parametrize("case,variant", _BATCH_CASES,
                          ids=[c if v is None else f"{c}-{v if isinstance(v, str) else 'advect%d' % v}" for c, v in _BATCH_CASES])
 def test_run_timesteps_equals_the_step_by_step_loop(case, variant):
+    run_timesteps_equals_the_step_by_step_loop(case, variant)
+
+
+def run_timesteps_equals_the_step_by_step_loop(case, variant, direction=1):
     """mphip_run_timesteps (the reference's time loop, trac.c:204-226, as one call): runs of steps with nothing
     scheduled between them share a kernel launch in which every particle takes its steps one after the other;
     same bits as one mphip_run_timestep per step -- state, uvwp and the counter of the random numbers --,
     whether the batches are long, short, cut by the internal re-sort, or (module sets with module_sort / mixing:
     "full") not possible at all; winds from the model levels (zeta / pressure advection) share launches too, and so
     does every integrator (ADVECT 4, 2, 1).  Where sharing is possible it must happen: seven quiet steps, one launch."""
-    ctl, clim, m0, m1, atm = cases.make_case(case, n=5003)
+    ctl, clim, m0, m1, atm = _case(case, 5003, direction)
     if isinstance(variant, str):
         ctl = dict(ctl, **_BATCH_OVERRIDES[variant])
     elif variant is not None:
@@ -1887,7 +1956,11 @@ def test_run_timesteps_equals_the_step_by_step_loop(case, variant):
         s.set_option("locality_sort_interval", interval)
         if variant == "eager_third":
             s.set_option("lazy_meteo", 0)
-        s.timesteps_init(0.0, 0.0)
+        if direction == 1:
+            s.timesteps_init(0.0, 0.0)
+        else:
+            s.timesteps_init(atm["time"].min(), atm["time"].max())
+        assert s.ctl.t_start == o.ctl.t_start and s.ctl.direction == direction
         if multi is None:
             s.run_timestep(times[0])
             s.synchronize()

@@ -14,15 +14,34 @@ from oracle import binding as B
 
 N = 1000
 TOL = 1e-13
+DIRECTION = 1       # -1: every case below reversed in time (tests/test_backward_cpu.py runs this file's tests that way)
+
+
+def _make_case(name, n, seed):
+    if DIRECTION == 1:
+        return cases.make_case(name, n=n, seed=seed)
+    import backward
+    ctl, clim, mets, atm = backward.backward_case(name, n, seed=seed)
+    return ctl, clim, mets[0], mets[1], atm
+
+
+def _timesteps(o, t):
+    """module_timesteps for the call at time t -- and the inputs of the check that follows: the case runs in this
+    file's direction, the particles released before t take a step of that sign, the others none.  Returns who moves."""
+    o.module("timesteps", t)
+    assert o.ctl.direction == DIRECTION
+    released = DIRECTION * (o.time - t) < 0
+    assert released.any() and np.all(DIRECTION * o.dt[released] > 0) and np.all(o.dt[~released] == 0)
+    return released
 
 
 def _oracle(name, seed=4711, **over):
-    ctl, clim, m0, m1, atm = cases.make_case(name, n=N, seed=seed)
+    ctl, clim, m0, m1, atm = _make_case(name, N, seed)
     ctl.update(over)
     o = B.Oracle(ctl, clim, m0, m1, atm)
     o.timesteps_init()
     t = cases.step_times(o.ctl)[1]          # (the first call of the time loop has dt = 0)
-    o.module("timesteps", t)
+    assert _timesteps(o, t).all()
     return o, R.Ref(o.ctl, clim, m0, m1), t
 
 
@@ -171,13 +190,13 @@ def test_boundary_layer_closure(case, seed):
     """module_diff_pbl (TURB_PBL_SCHEME 1, mptrac.c:4343-4584) appears in no reference test and was "HIP vs oracle only":
     the numpy statement evaluates every particle through all three stability classes and selects as the reference's
     ladder does.  Positions to 1e-13; the single-precision perturbations the module stores must be the oracle's bits."""
-    ctl, clim, m0, m1, atm = cases.make_case(case, n=4000, seed=seed)
+    ctl, clim, m0, m1, atm = _make_case(case, 4000, seed)
     o = B.Oracle(ctl, clim, m0, m1, atm)
     o.timesteps_init()
     ts = cases.step_times(o.ctl)
     for t in ts[:3]:                       # a few full steps first: perturbations of every size and sign
         o.run_timestep(t)
-    o.module("timesteps", ts[3])
+    _timesteps(o, ts[3])
     s0 = (o.time.copy(), o.lon.copy(), o.lat.copy(), o.p.copy())
     uv0 = o.uvwp.copy()
     o.module("diff_pbl")
@@ -197,13 +216,13 @@ def test_advect_model_levels(case):
     """module_advect's zeta / eta branch (mptrac.c:3681-3757) with intpol_met_4d_zeta (2808-2981: the eight column
     searches of locate_vert, the walk to the level pair that brackets the height after the horizontal and time blend, the
     float difference of the two snapshots) -- no reference test runs it, and it was "HIP vs oracle only"."""
-    ctl, clim, m0, m1, atm = cases.make_case(case, n=3000, seed=4711)
+    ctl, clim, m0, m1, atm = _make_case(case, 3000, 4711)
     o = B.Oracle(ctl, clim, m0, m1, atm)
     o.timesteps_init()
     ts = cases.step_times(o.ctl)
     for t in ts[:2]:
         o.run_timestep(t)
-    o.module("timesteps", ts[2])
+    _timesteps(o, ts[2])
     s0 = (o.time.copy(), o.lon.copy(), o.lat.copy(), o.p.copy())
     o.module("advect")
     ref = R.Ref(o.ctl, clim, m0, m1)
@@ -219,12 +238,13 @@ def test_advect_model_levels(case):
 def test_isosurface_modes(case):
     """module_isosurf_init stores pressure / density / potential temperature, module_isosurf puts the particle back on
     that surface after the movers (mptrac.c:4886-5005); mode 4 follows a balloon's pressure record."""
-    ctl, clim, m0, m1, atm = cases.make_case(case, n=N, seed=11)
+    ctl, clim, m0, m1, atm = _make_case(case, N, 11)
     o = B.Oracle(ctl, clim, m0, m1, atm)
     cases.prepare(o)
     o.timesteps_init()
     ts = cases.step_times(o.ctl)
-    o.module("timesteps", ts[1])
+    released = _timesteps(o, ts[1])
+    assert not released[::7].any() and np.all(o.dt[::7] == 0) and released.sum() == N - len(o.dt[::7])   # the late release
     ref = R.Ref(o.ctl, clim, m0, m1)
     s0 = (o.time.copy(), o.lon.copy(), o.lat.copy(), o.p.copy())
     if o.ctl.isosurf != 4:
@@ -246,11 +266,11 @@ def test_isosurface_modes(case):
 def test_boundary_condition_region_and_values(case):
     """module_bound_cond (mptrac.c:3789-3881): latitude / pressure box, surface layer by pressure depth, height, zeta and
     boundary-layer top; mass and volume mixing ratio with their trends, age of air."""
-    ctl, clim, m0, m1, atm = cases.make_case(case, n=N, seed=5)
+    ctl, clim, m0, m1, atm = _make_case(case, N, 5)
     o = B.Oracle(ctl, clim, m0, m1, atm)
     o.timesteps_init()
     ts = cases.step_times(o.ctl)
-    o.module("timesteps", ts[1])
+    _timesteps(o, ts[1])
     ref = R.Ref(o.ctl, clim, m0, m1)
     o.p[::7] = ref.time_2d("ps", o.time, o.lon, o.lat)[::7] - np.linspace(0.0, 60.0, N)[::7]      # some next to the ground
     s0 = (o.time.copy(), o.lon.copy(), o.lat.copy(), o.p.copy())
