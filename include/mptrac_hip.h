@@ -558,6 +558,11 @@ int mphip_comm_query(mphip_ctx *ctx, int *nranks, int *rank);
  *   "fuse_sort" (default 1): inside mphip_run_timestep the gather of time, p,
  *   lon, lat that module_sort ends with (mptrac.c:5944-5949) happens in the step
  *   launch that follows; 0 = every array is re-ordered in module_sort's own pass;
+ *   "fold_resort" (default 1): inside mphip_run_timesteps, a re-sort of the internal locality order that falls due
+ *   with at least two steps to share a launch behind it (pressure-level winds, a lean multi-step kernel for the
+ *   module set, no module_isosurf) has no gather pass of its own: the launch reads the particles through the sort's
+ *   permutation and takes the due step with the others; 0 = the re-sort gathers in its own pass and its step is a
+ *   launch of its own, as in mphip_run_timestep.  Not observable;
  *   "pin_host_atm" (default 0): page-lock the caller's particle arrays handed to
  *   mphip_update_atm / mphip_get_atm with one registration spanning them (for
  *   a persistent atm_t whose arrays lie in one allocation);

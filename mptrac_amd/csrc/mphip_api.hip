@@ -84,6 +84,8 @@ struct mphip_ctx {
   const int *fused_perm = nullptr;    // set by do_sort, consumed by the next launch_step
   bool fuse_quantities = true;        // ... which then moves the quantity arrays too (option fuse_sort_quantities)
   bool fused_quantities = false;
+  const int *fold_perm = nullptr;     // the locality re-sort's permutation, handed to the multi-step launch that follows
+                                      // it inside one mphip_run_timesteps iteration (DevAtm::perm_all)
   bool lazy_meteo = true;
   bool meteo_pending = false;
   bool pin_host_atm = false;          // page-lock the caller's particle arrays (persistent atm_t of a C caller only)
@@ -171,6 +173,7 @@ struct mphip_ctx {
   void *d_prec = nullptr;             // ... their buffer
   size_t prec_cap = 0;
   int multi_step = 64;                // mphip_run_timesteps: most time steps per launch (0 = always one by one)
+  bool fold_resort = true;            // ... and a launch that follows the locality re-sort does its gather (0: a pass of its own)
   bool force_generic = false;
   bool compact_depo = true;           // deposition-only launches through depo_kernel (0: the fused kernel's tail)
   int sort_bits = 0;                  // digit width of the radix sort (0 = fewest passes; 8, 9, 10: tuning / tests)
@@ -346,12 +349,19 @@ DevAtm dev_atm(const mphip_ctx *c) {
   a.iso_ts = c->d_iso_ts;
   a.iso_ps = c->d_iso_ps;
   a.iso_n = c->iso_n;
-  a.perm = c->fused_perm;
+  a.perm = c->fold_perm ? c->fold_perm : c->fused_perm;
   a.s_time = c->d_alt[0];
   a.s_p = c->d_alt[1];
   a.s_lon = c->d_alt[2];
   a.s_lat = c->d_alt[3];
-  a.nq_perm = c->fused_perm && c->fused_quantities ? c->nq : 0;
+  a.nq_perm = c->fold_perm || (c->fused_perm && c->fused_quantities) ? c->nq : 0;
+  a.perm_all = c->fold_perm ? 1 : 0;   // (locality_sort_apply: the pre-sort arrays are the alternates)
+  a.s_up = c->d_uvwp_alt[0];
+  a.s_vp = c->d_uvwp_alt[1];
+  a.s_wp = c->d_uvwp_alt[2];
+  a.s_dt = c->d_dt_alt;
+  a.s_ext = c->d_ext_alt;
+  a.ext_out = c->d_ext;
   for (int iq = 0; iq < MPHIP_NQ_MAX; iq++)
     a.s_q[iq] = iq < c->nq ? c->d_alt[4 + iq] : nullptr;
   a.np = c->np;
@@ -1663,20 +1673,25 @@ int restore_external_order(mphip_ctx *ctx) {
 // internal locality order: store the particles sorted by the grid cell their
 // interpolation stencil starts in.  Nothing observable changes: random numbers
 // follow the external slot (d_ext) and downloads restore the external order.
-int locality_sort(mphip_ctx *ctx) {
-  if (ctx->np == 0)
-    return 0;
+// First half: keys and radix sort; *cur = the buffer pair that holds the sorted (key, slot) pairs.
+int locality_sort_keys(mphip_ctx *ctx, int *cur) {
   if (ahead_drop(ctx) || ensure_packed(ctx))
     return 1;
-  int cur = 0;
   // measured (tools/gpu_ablate.py tiles): 4 x 4 columns for the pressure-level kernels, 8 x 8 for the model-level ones
   const int tile = ctx->locality_tile > 0 ? ctx->locality_tile : (ctx->have_ctl && ml_winds(ctx->ctl) ? 8 : 4);
-  if (sort_pairs(ctx, tile, &cur, nullptr))
-    return 1;
+  return sort_pairs(ctx, tile, cur, nullptr);
+}
+
+// Second half: every per-particle array moves by the sorted slots.  fold: no pass of its own -- the caller's next
+// launch, a lean multi-step one, reads its per-launch loads through the permutation (ctx->fold_perm, DevAtm::perm_all;
+// a re-sort only: `ext` composes with the one in place) and the caller clears the hand-over behind that launch.
+int locality_sort_apply(mphip_ctx *ctx, int cur, bool fold) {
   PermArgs g = perm_args(ctx, true);
   g.ext_in = ctx->ext_identity ? nullptr : ctx->d_ext;
   g.ext_out = ctx->d_ext_alt;
-  if (ctx->ext_identity) {   // out of the caller's order: a random permutation
+  if (fold) {
+    ctx->fold_perm = ctx->d_vals[cur];
+  } else if (ctx->ext_identity) {   // out of the caller's order: a random permutation
     if (permute_random(ctx, g, ctx->d_vals[cur], ctx->np, false))
       return 1;
   } else {                   // a re-sort: most particles stay where they are, the gathers hit the caches
@@ -1690,6 +1705,13 @@ int locality_sort(mphip_ctx *ctx) {
   ctx->ext_identity = false;
   ctx->steps_since_resort = 0;
   return 0;
+}
+
+int locality_sort(mphip_ctx *ctx) {
+  if (ctx->np == 0)
+    return 0;
+  int cur = 0;
+  return locality_sort_keys(ctx, &cur) || locality_sort_apply(ctx, cur, false);
 }
 
 // module_sort, mptrac.c:5887-5957: observable re-ordering of atm (time, p, lon,
@@ -4052,10 +4074,19 @@ int mphip_run_timesteps(mphip_ctx *ctx, double t_first, int nsteps) {
       && !step_chem_on(c)    // (module_chem_grid, module_oh_chem, module_h2o2_chem, module_tracer_chem are launches of
                              // their own: single steps)
       && !step_radio_depo_on(ctx);   // (module_radio_depo likewise, behind the tail)
+    // the internal re-sort falls due at this step: the launch that takes the steps behind it can do its gather on the
+    // way (the pass over every array and the single-step launch saved), if it is a lean pressure-level multi-step one.
+    // The batch is then sized as behind the sort; whatever cannot take the fold goes the way of a batch of 0 --
+    // mphip_run_timestep, which sorts with a pass of its own.
+    // (model-level winds and the general kernels -- `quiet` excludes the option generic_kernel -- have no such
+    // instantiation: ruled out here, so that their due step goes to mphip_run_timestep without being planned twice)
+    const bool fold = quiet && ctx->fold_resort && ctx->locality_interval > 0
+      && ctx->steps_since_resort >= ctx->locality_interval && !ctx->ext_identity
+      && !ml_winds(c) && !ctx->d_iso && !ctx->d_kz && ctx->lds_tile <= 0;
     if (quiet) {
       batch = nsteps - done;
       if (ctx->locality_interval > 0)
-        batch = std::min(batch, ctx->locality_interval - ctx->steps_since_resort);
+        batch = std::min(batch, fold ? ctx->locality_interval : ctx->locality_interval - ctx->steps_since_resort);
       batch = std::min(batch, ctx->multi_step);
       double tt = t;
       for (int j = 0; j < batch; j++) {
@@ -4079,7 +4110,8 @@ int mphip_run_timesteps(mphip_ctx *ctx, double t_first, int nsteps) {
       if (ensure_packed(ctx))
         return 1;
       P = plan_step(ctx, t);
-      if (step_kernel_mask(ctx, P.mask | P.tail, batch) == kNoStepKernel || (ml_winds(c) && !ctx->d_kz))
+      const unsigned sel = step_kernel_mask(ctx, P.mask | P.tail, batch);
+      if (sel == kNoStepKernel || (ml_winds(c) && !ctx->d_kz) || (fold && !step_kernel_stores_once(sel)))
         batch = 1;
     }
     if (batch < 2) {
@@ -4091,7 +4123,15 @@ int mphip_run_timesteps(mphip_ctx *ctx, double t_first, int nsteps) {
     }
     if (settle_meteo(ctx, meteo_at(t)))
       return 1;
-    if (launch_step(ctx, P.mask | P.tail, t, P.rng, batch, stride, P.per_step))
+    if (fold) {   // (sort and launch in this iteration: nothing else sees the hand-over)
+      int cur = 0;
+      if (check_fields(ctx, P.mask | P.tail)   // (what launch_step could refuse, before the arrays change places)
+          || locality_sort_keys(ctx, &cur) || locality_sort_apply(ctx, cur, true))
+        return 1;
+    }
+    const int rc = launch_step(ctx, P.mask | P.tail, t, P.rng, batch, stride, P.per_step);
+    ctx->fold_perm = nullptr;
+    if (rc)
       return 1;
     ctx->rng_ctr += P.per_step * (uint64_t) batch;
     if (ctx->steps_since_resort < (1 << 29))
@@ -4810,6 +4850,10 @@ int mphip_set_option(mphip_ctx *ctx, const char *name, double value) {
     if (value < 0 || value > 4096)
       return fail(ctx, "multi_step must be in 0 ... 4096");
     ctx->multi_step = (int) value;
+    return 0;
+  }
+  if (strcmp(name, "fold_resort") == 0) {   // 0: the locality re-sort always gathers in a pass of its own
+    ctx->fold_resort = value != 0;
     return 0;
   }
   if (strcmp(name, "fuse_sort_quantities") == 0) {   // 0: module_sort moves the quantity arrays in a pass of its own

@@ -194,6 +194,13 @@ struct DevAtm {
   const double *s_time, *s_p, *s_lon, *s_lat;
   const double *s_q[MPHIP_NQ_MAX];   // ... and the quantity arrays (nq_perm of them: 0 = they were moved by a pass of their own)
   int nq_perm;
+  // the internal locality re-sort folded into a lean multi-step launch (mphip_run_timesteps): unlike module_sort it
+  // moves everything -- uvwp, dt and the external slot come from slot perm[i] of the arrays below as well
+  int perm_all;
+  const float *s_up, *s_vp, *s_wp;
+  const double *s_dt;
+  const int *s_ext;              // (NULL = identity)
+  int *ext_out;                  // the array `ext` points to, writable
   long long np;                  // particles owned by this context
   long long ip0;                 // global index of the first one
   long long np_total;            // particles of the whole simulation

@@ -643,6 +643,37 @@ constexpr bool step_kernel_parks(unsigned ct) {
   return ct < kMaskGenericMLMulti && (ct & kMultiStep) && !(ct & (kMLWinds | kPblClosure))
     && (ct & (MPHIP_MOD_DIFF_TURB | MPHIP_MOD_DIFF_MESO | MPHIP_MOD_CONVECTION | MPHIP_MOD_SEDI));
 }
+// What a folded locality re-sort (DevAtm::perm_all) moves besides time, position and the quantity rows: cache->dt and
+// the external slot go from slot src of the pre-sort arrays to slot i, the mesoscale perturbations are returned (and
+// stored where the launch has no module_diff_meso, whose store behind the last step would write them)
+struct PermRest {
+  float up, vp, wp;
+  int ext;
+};
+__device__ __forceinline__ PermRest perm_rest(const DevAtm &a, long long i, long long src, bool store_uvwp) {
+  PermRest r;
+  a.dt[i] = a.s_dt[src];
+  r.ext = a.s_ext ? a.s_ext[src] : (int) src;
+  a.ext_out[i] = r.ext;
+  r.up = a.s_up[src];
+  r.vp = a.s_vp[src];
+  r.wp = a.s_wp[src];
+  if (store_uvwp) {
+    a.up[i] = r.up;
+    a.vp[i] = r.vp;
+    a.wp[i] = r.wp;
+  }
+  return r;
+}
+__device__ __attribute__((noinline)) PermRest perm_rest_call(const DevAtm *a, long long i, long long src, bool store_uvwp) {
+  return perm_rest(*a, i, src, store_uvwp);
+}
+
+// The lean pressure-level multi-step instantiations (step_kernel: store_once), which load a particle once per launch
+// and store it once behind the last step -- the ones a locality re-sort can be folded into (DevAtm::perm_all).
+constexpr bool step_kernel_stores_once(unsigned ct) {
+  return ct != 0 && ct < kMaskGenericMLMulti && (ct & kMultiStep) && !(ct & kMLWinds);
+}
 constexpr int kParkDoubles = 256 * 2 + 128;   // rp[256], rhop[256], ext[256] (int)
 constexpr size_t kParkBytes = kParkDoubles * sizeof(double);
 enum { kParkRp = 0, kParkRhop = 256, kParkExt = 512 };   // (offsets in doubles)
@@ -716,6 +747,7 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
     // store the state once, behind the last step: nothing inside the launch reads time, lon, lat, p, up, vp, wp from
     // memory (the tail modules take them from P), and every step would overwrite the stores of the step before.
     constexpr bool store_once = multi && !kRuntimeMask<CT> && !kModelLevels<CT>;
+    static_assert(store_once == step_kernel_stores_once(CT), "step_kernel_stores_once");
     Particle P;
     WindCache wc;
     float up = 0.f, vp = 0.f, wp = 0.f;
@@ -723,14 +755,36 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
              c_conv += S.ctr_stride, c_pbl += S.ctr_stride) {
     const bool fused_sort = a.perm != nullptr;
     if (!multi || step == 0) {
+    // A folded locality re-sort (a.perm_all) moves uvwp, dt and the external slot too -- one move, perm_rest, taken in
+    // one of two ways.  perm_call: the instantiations with the closure make it a call in front of their own loads, which
+    // stores everything at slot i, and then read a.up[i], a.ext[i], a.dt[i] back as ever (inline, their register
+    // allocation moved: spills v4 -> v6).  The read-back is safe: the thread that stored slot i is the one that loads
+    // it, in program order, and the compiler cannot move a load across the opaque call.  perm_all: every other lean
+    // instantiation takes the values from the registers perm_rest returns and skips the loads of slot i below.
+    constexpr bool perm_call = store_once && (CT & kPblClosure) != 0;
+    const bool perm_all = store_once && !perm_call && fused_sort && a.perm_all;
     if (fused_sort) {   // the gather of module_sort_help (mptrac.c:5944-5949) for time, p, lon, lat
       const long long src = a.perm[i];
+      if constexpr (perm_call)
+        if (a.perm_all)
+          (void) perm_rest_call(&a, i, src, true);
       P.time = a.s_time[src];
       P.lon = a.s_lon[src];
       P.lat = a.s_lat[src];
       P.p = a.s_p[src];
       for (int k = 0; k < a.nq_perm; k++)   // the quantities move here too (what follows reads them at slot i)
         a.q[k][i] = a.s_q[k][src];
+      if constexpr (store_once && !perm_call) {
+        if (a.perm_all) {   // the locality re-sort (mphip_run_timesteps): uvwp, dt and the external slot move as well
+          // (with module_diff_meso the store behind the last step writes uvwp)
+          const PermRest r = perm_rest(a, i, src, !(mask & MPHIP_MOD_DIFF_MESO));
+          if constexpr (park)
+            *park_slot<int>(s_lds, kParkExt, i) = r.ext;
+          up = r.up;
+          vp = r.vp;
+          wp = r.wp;
+        }
+      }
     } else {
       P.time = ld_state(&a.time[i]);
       P.lon = ld_state(&a.lon[i]);
@@ -740,14 +794,14 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
     if (multi) {   // (before any step can leave early: dt = 0 ...)
       if (MPHIP_MULTI_KEEP_WIND)
         wind_cache_reset(wc, true);
-      if (mask & MPHIP_MOD_DIFF_MESO) {
+      if ((mask & MPHIP_MOD_DIFF_MESO) && !perm_all) {
         up = ld_state(&a.up[i]);
         vp = ld_state(&a.vp[i]);
         wp = ld_state(&a.wp[i]);
       }
     }
     if constexpr (park) {   // (behind the gather of module_sort, which writes a.q[k][i])
-      if (a.ext)
+      if (a.ext && !perm_all)
         *park_slot<int>(s_lds, kParkExt, i) = ld_state(&a.ext[i]);
       if (((CT & kGated) ? mask & S.mask : mask) & MPHIP_MOD_SEDI) {
         *park_slot<double>(s_lds, kParkRp, i) = ld_state(&a.q[ctl.qnt_rp][i]);
