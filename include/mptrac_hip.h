@@ -215,6 +215,7 @@ typedef int (*mphip_allreduce_fn)(void *device_buffer, size_t count, void *user)
 
 size_t mphip_sizeof_ctl(void);
 size_t mphip_sizeof_met(void);
+size_t mphip_sizeof_prep(void);   /* sizeof(mphip_prep_t), for mirrors of the structure in other languages */
 /* "mptrac_amd <version> (gfx950)" -- or "(gfx950, reference rounding)" from libmptrac_hip_exact.so, the build of the
  * same sources and the same ABI whose results are the CPU reference's bits ("Two libraries") */
 const char *mphip_version(void);
@@ -284,8 +285,9 @@ int mphip_discard_prefetch(mphip_ctx *ctx);
 
 /* The derived fields of the reference's meteo preprocessing, from one snapshot "as stored" (what a netCDF file of
  * MET_TYPE 0 carries): geopotential height z, total ozone column o3c, boundary-layer pressure pbl, the cloud layer pct /
- * pcb / cl, and plcl / plfc / pel / cape / cin.  `in` is a host view exactly as for mphip_update_met (compact or
- * [EX][EY][EP]-strided); `what` an OR of MPHIP_PREP_* bits; the arrays of `out` have the strides of `in`.  The call uploads
+ * pcb / cl, plcl / plfc / pel / cape / cin, potential vorticity pv and the tropopause pt / tt / zt / h2ot.  `in` is a host
+ * view exactly as for mphip_update_met (compact or [EX][EY][EP]-strided); `what` an OR of MPHIP_PREP_* bits; the arrays
+ * of `out` have the strides of `in`.  The call uploads
  * the inputs it needs into scratch of its own (kept for the grid size of the last call, freed by mphip_destroy), runs its
  * kernels on a stream of its own, copies the results into the caller's arrays and returns when they are there.  It touches
  * no meteo slot, no prefetch state and no particle state and may be called from a file-reader thread while another thread
@@ -296,10 +298,17 @@ int mphip_discard_prefetch(mphip_ctx *ctx);
  * GEOPOT in the same call (the smoothed field); CLOUD: lwc, iwc, ps (rwc / swc absent = 0); CAPE: t, h2o, ps and the
  * tropopause climatology of mphip_update_clim (on a Cartesian grid also mphip_update_ctl: met_utm_ref_lat is the
  * tropopause's latitude) --; a missing output array of a requested bit; met_pbl other than 2 or 3 with PBL; smoothing
- * half-widths with sx - 1 > nx or whose tile exceeds 64 KB of LDS.
+ * half-widths with sx - 1 > nx or whose tile exceeds 64 KB of LDS.  PV: t, u, v; a grid that is not longitude / latitude
+ * (coord_type != 0); nx < 2 or ny < 5.  TROPO (the members met_tropo ... met_tropo_spline of `opt` are read only with this
+ * bit): t, h2o and z, given in `in` or derived by GEOPOT in the same call (the smoothed field); with met_tropo 5 also pv,
+ * given in `in` or derived by PV in the same call; with met_tropo 1 the tropopause climatology (and met_utm_ref_lat on a
+ * Cartesian grid) as for CAPE; met_tropo outside 1 ... 5; met_tropo_spline outside 0 ... 1; np < 3 with met_tropo 2 ... 5; a
+ * pressure axis with too many levels for one column's profiles in 64 KB of LDS (as for every column kernel).  All four
+ * output arrays of TROPO are required.
  *
  *   DEFINITIONS.  This project's own statement of the reference's algorithms -- the reference's source was not available,
- * so no line of mptrac.c is cited --, restated independently in tests/refmetprep.py.  All arithmetic is in double from the
+ * so no line of mptrac.c is cited --, restated independently in tests/refmetprep.py and (pv, tropopause)
+ * tests/reftropo.py.  All arithmetic is in double from the
  * float inputs, products and quotients taken from left to right as written; each output value is rounded to float once.
  * exp / log / pow are the C library's.  Constants: RI = 8.3144598, MA = 28.9644, G0 = 9.80665, MO3 = 48.00, EPS =
  * 18.01528 / MA, RA = 1e3 RI / MA, CPD = 1003.5, LV = 2501000.
@@ -345,14 +354,50 @@ int mphip_discard_prefetch(mphip_ctx *ctx);
  * cape += d; if plfc is NaN: plfc = p; } else if (d_old > 0) pel = p; if (d < 0 and plfc is NaN) cin += |d|; } while (p >
  * ptop).  If plfc is NaN: cin = NaN.  (An infinite ps is taken as NaN, so that every loop ends: p shrinks by pfac per pass
  * and a NaN makes each condition false.)
- *   Out of scope: potential vorticity and the dynamical tropopause, the WMO / cold-point tropopause (pt, tt, zt, h2ot: they
- * need the reference's spline), MET_PBL 1, detrending, down-sampling, model-to-pressure-level regridding. */
-enum { MPHIP_PREP_GEOPOT = 1, MPHIP_PREP_O3C = 2, MPHIP_PREP_PBL = 4, MPHIP_PREP_CLOUD = 8, MPHIP_PREP_CAPE = 16 };
+ *   Further helpers (each a function: its value is formed before it enters the expression around it; cos and sin are the
+ * C library's).  RE = 6367.421.  RAD(x) = x (M_PI / 180.0).  DEG2DX(d,lat) = RE RAD(d) cos(RAD(lat)).  DEG2DY(d) = RE
+ * RAD(d).  Z(p) = 7 log(1013.25 / p).  LAPSE(p1,t1,p2,t2) = 1e3 G0 / RA (t2 - t1) / (t2 + t1) (p2 + p1) / (p2 - p1).
+ *   Potential vorticity (pv, PVU).  pows[k] = pow(1000/p[k], 0.286).  Per column (ix, iy): ix0 = max(ix-1,0), ix1 =
+ * min(ix+1,nx-1) (clamped, not wrapped), iy0, iy1 likewise; latr = 0.5 (lat[iy1] + lat[iy0]); dx = 1000
+ * DEG2DX(lon[ix1]-lon[ix0], latr); dy = 1000 DEG2DY(lat[iy1]-lat[iy0]); c0 = cos(RAD(lat[iy0])), c1 = cos(RAD(lat[iy1])),
+ * cr = cos(RAD(latr)); vort = 2 * 2 * M_PI / 86400. * sin(RAD(lat[iy])).  Per level k: dtdx = (t[ix1][iy][k] - t[ix0][iy][k])
+ * pows[k] / dx; dvdx = (v[ix1][iy][k] - v[ix0][iy][k]) / dx; dtdy = (t[ix][iy1][k] - t[ix][iy0][k]) pows[k] / dy; dudy =
+ * (u[ix][iy1][k] c1 - u[ix][iy0][k] c0) / dy; k0 = max(k-1,0), k1 = min(k+1,np-1), dp0 = 100 (p[k]-p[k0]), dp1 = 100
+ * (p[k1]-p[k]); for a column profile a, in the interior (k != k0 and k != k1) D(a) = (dp0 dp0 a[k1] - dp1 dp1 a[k0] + (dp1
+ * dp1 - dp0 dp0) a[k]) / (dp0 dp1 (dp0+dp1)), at the two end levels D(a) = (a[k1] - a[k0]) / (dp0 + dp1); dtdp = D(t pows)
+ * (a[k] = t[k] pows[k]), dudp = D(u), dvdp = D(v); pv = 1e6 G0 (-dtdp (dvdx - dudy / cr + vort) + dvdp dtdx - dudp dtdy).
+ * After all columns, for every ix and k and by index, for either latitude order: rows 0 and 1 take row 2's value, rows ny-1
+ * and ny-2 row ny-3's.
+ *   Tropopause (pt hPa, tt K, zt km, h2ot ppv).  zc[k] = Z(p[k]) (ascending); z2[i] = 4.5 + 0.1 i, p2[i] = P(z2[i]), i = 0
+ * ... 200.  spline(y)[i] for a column profile y on zc: y[0] if z2[i] <= zc[0]; y[np-1] if z2[i] >= zc[np-1]; otherwise, with
+ * k the largest index with zc[k] <= z2[i] and k <= np-2: met_tropo_spline 0: LIN(zc[k],y[k],zc[k+1],y[k+1],z2[i]);
+ * met_tropo_spline 1, the natural cubic spline: h[k] = zc[k+1]-zc[k]; c[0] = c[np-1] = 0; for i = 0 ... np-3: d[i] = 2
+ * (h[i]+h[i+1]), o[i] = h[i+1], g[i] = 3 ((y[i+2]-y[i+1]) / h[i+1] - (y[i+1]-y[i]) / h[i]); forward, for i = 1 ... np-3: w =
+ * o[i-1] / d[i-1]; d[i] -= w o[i-1]; g[i] -= w g[i-1]; back: c[np-2] = g[np-3] / d[np-3], then c[i+1] = (g[i] - o[i] c[i+2]) /
+ * d[i] for i = np-4 down to 0; value: h = h[k], b = (y[k+1]-y[k]) / h - h (c[k+1] + 2 c[k]) / 3, e = (c[k+1]-c[k]) / (3 h),
+ * dx = z2[i]-zc[k], result y[k] + dx (b + dx (c[k] + dx e)).  A NaN among the fine values a mode looks at makes pt NaN.
+ *   met_tropo 1: pt = clim_tropo(time, lat[iy]) (met_utm_ref_lat on a Cartesian grid).  2 (cold point): t2 = spline(t) on i
+ * = 0 ... 170; iz = the first index of the minimum; pt = p2[iz] if 0 < iz < 170, else NaN.  3 (WMO): t2 on i = 0 ... 200;
+ * B(iz): LAPSE(p2[iz],t2[iz],p2[j],t2[j]) <= 2.0 for every j = iz+1 ... iz+20; iz1 = the first iz in 0 ... 170 with B; pt =
+ * p2[iz1] if it exists and 0 < iz1 < 170, else NaN.  4 (WMO, second tropopause): iz1 as for 3, NaN if there is none; A(iz):
+ * LAPSE(...) >= 3.0 for every j = iz+1 ... iz+10; iza = the first iz in iz1 ... 170 with A; iz2 = the first iz in iza ... 170
+ * with B; pt = p2[iz2] if it exists and 0 < iz2 < 170, else NaN.  5 (dynamical): pv2 = spline(pv), th2 =
+ * spline(THETA(p[k],t[k])) on 0 ... 170; iz = the first index with fabs(pv2[iz]) >= met_tropo_pv or th2[iz] >=
+ * met_tropo_theta; pt = p2[iz] if it exists and 0 < iz < 170, else NaN.  Then tt = env(t,pt), zt = env(z,pt), h2ot =
+ * env(h2o,pt); all three NaN when pt is NaN.
+ *   Out of scope: MET_PBL 1, detrending, down-sampling, model-to-pressure-level regridding. */
+enum { MPHIP_PREP_GEOPOT = 1, MPHIP_PREP_O3C = 2, MPHIP_PREP_PBL = 4, MPHIP_PREP_CLOUD = 8, MPHIP_PREP_CAPE = 16,
+       MPHIP_PREP_PV = 32, MPHIP_PREP_TROPO = 64 };
 typedef struct {
   int met_pbl;                        /* 2: bulk Richardson number, 3: potential temperature */
   double met_pbl_min, met_pbl_max;    /* km; reference defaults 0.1, 5.0 */
   int met_geopot_sx, met_geopot_sy;   /* smoothing half-widths; < 0: automatic, 0: none */
   double met_cloud_min;
+  /* read only with MPHIP_PREP_TROPO (appended: the members above keep their offsets) */
+  int met_tropo;                      /* 1 climatology, 2 cold point, 3 WMO, 4 second WMO, 5 dynamical; reference default 3 */
+  double met_tropo_pv;                /* PVU; reference default 3.5 */
+  double met_tropo_theta;             /* K; reference default 380 */
+  int met_tropo_spline;               /* 1: cubic, 0: linear; reference default 1 */
 } mphip_prep_t;
 typedef struct {
   float *f3[MPHIP_N3D];

@@ -279,7 +279,8 @@ struct mphip_ctx {
   float *prep_in3[MPHIP_N3D] = {}, *prep_in2[MPHIP_N2D] = {};
   float *prep_out2[MPHIP_N2D] = {};
   float *prep_z[2] = {};              // geopotential height before and after the smoothing
-  double *prep_axes = nullptr;        // p[np] | lat[ny]
+  float *prep_pv = nullptr;           // potential vorticity (MPHIP_PREP_PV; what MPHIP_PREP_TROPO with met_tropo 5 reads)
+  double *prep_axes = nullptr;        // p[np] | lat[ny] | lon[nx] | the tropopause's tables (PrepTropo::tab)
   int prep_profile_phase = 0;         // option "derive_profile_phase": what mphip_profile_begin / _end time of a call
 
   // profiling of the fused step kernel
@@ -2715,6 +2716,8 @@ void prep_release(mphip_ctx *ctx) {
     dev_free(q);
     q = nullptr;
   }
+  dev_free(ctx->prep_pv);
+  ctx->prep_pv = nullptr;
   dev_free(ctx->prep_axes);
   ctx->prep_axes = nullptr;
   ctx->prep_nx = ctx->prep_ny = ctx->prep_np = 0;
@@ -2762,6 +2765,21 @@ int prep_columns(int np, int nf, size_t *lds) {
   return 0;
 }
 
+// the same for the tropopause kernel: the axis tables, per column c[np] and (met_tropo 3, 4) the fine profile in double, and
+// the staged profiles (t; t and pv with met_tropo 5)
+int prep_tropo_columns(int np, int mode, size_t *lds, int *nprof, int *fine) {
+  const int pitch = np | 1;
+  *nprof = mode == 1 ? 0 : (mode == 5 ? 2 : 1);
+  *fine = mode == 3 || mode == 4 ? kTropoFine : 0;
+  for (int cpb = kPrepLanes; cpb >= 1; cpb >>= 1) {
+    *lds = ((size_t) 6 * np + 2 * kTropoFine + (size_t) cpb * (np + *fine)) * sizeof(double)
+      + (size_t) *nprof * cpb * pitch * sizeof(float);
+    if (*lds <= 64 * 1024)
+      return cpb;
+  }
+  return 0;
+}
+
 }   // namespace
 
 // ---------------------------------------------------------------------------
@@ -2776,6 +2794,10 @@ size_t mphip_sizeof_ctl(void) {
 
 size_t mphip_sizeof_met(void) {
   return sizeof(mphip_met_t);
+}
+
+size_t mphip_sizeof_prep(void) {
+  return sizeof(mphip_prep_t);
 }
 
 const char *mphip_version(void) {
@@ -3338,7 +3360,8 @@ int mphip_prefetch_met(mphip_ctx *ctx, const mphip_met_t *met) {
 int mphip_derive_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const mphip_prep_t *opt, const mphip_met_out_t *out) {
   if (!ctx || !in || !opt || !out)
     return fail(ctx, "mphip_derive_met: null argument");
-  constexpr unsigned kAll = MPHIP_PREP_GEOPOT | MPHIP_PREP_O3C | MPHIP_PREP_PBL | MPHIP_PREP_CLOUD | MPHIP_PREP_CAPE;
+  constexpr unsigned kAll = MPHIP_PREP_GEOPOT | MPHIP_PREP_O3C | MPHIP_PREP_PBL | MPHIP_PREP_CLOUD | MPHIP_PREP_CAPE
+    | MPHIP_PREP_PV | MPHIP_PREP_TROPO;
   if (!what || (what & ~kAll))
     return fail(ctx, "mphip_derive_met: `what` must be an OR of MPHIP_PREP_* bits");
   if (in->nx < 2 || in->ny < 2 || !in->lon || !in->lat || !in->p)
@@ -3440,12 +3463,55 @@ int mphip_derive_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const
     if (!outputs({ MPHIP_PLCL, MPHIP_PLFC, MPHIP_PEL, MPHIP_CAPE, MPHIP_CIN }))
       return fail(ctx, "mphip_derive_met: MPHIP_PREP_CAPE needs the output arrays plcl, plfc, pel, cape, cin");
   }
+  const bool do_pv = what & MPHIP_PREP_PV, tropo = what & MPHIP_PREP_TROPO;
+  if (do_pv) {
+    if (!have3({ MPHIP_T, MPHIP_U, MPHIP_V }))
+      return missing("MPHIP_PREP_PV", "t, u, v");
+    if (!out->f3[MPHIP_PV])
+      return fail(ctx, "mphip_derive_met: MPHIP_PREP_PV needs the output array pv");
+    if (in->coord_type != 0)
+      return fail(ctx, "mphip_derive_met: MPHIP_PREP_PV needs a longitude / latitude grid (coord_type 0)");
+    if (in->ny < 5)
+      return fail(ctx, "mphip_derive_met: MPHIP_PREP_PV needs two columns and five rows or more (nx < 2 or ny < 5)");
+  }
+  size_t lds_tropo = 0;
+  int c_tropo = 0, tropo_nprof = 0, tropo_fine = 0;
+  if (tropo) {
+    const int mode = opt->met_tropo;
+    if (mode < 1 || mode > 5)
+      return fail(ctx, "mphip_derive_met: met_tropo must be 1 (climatology), 2 (cold point), 3 (WMO first), 4 (WMO second) "
+                  "or 5 (dynamical)");
+    if (opt->met_tropo_spline != 0 && opt->met_tropo_spline != 1)
+      return fail(ctx, "mphip_derive_met: met_tropo_spline must be 0 (linear) or 1 (cubic)");
+    if (mode != 1 && in->np < 3)
+      return fail(ctx, "mphip_derive_met: MPHIP_PREP_TROPO with met_tropo 2 to 5 needs three pressure levels or more "
+                  "(np < 3)");
+    if (!have3({ MPHIP_T, MPHIP_H2O }) || (!geopot && !in->f3[MPHIP_Z]))
+      return missing("MPHIP_PREP_TROPO", "t, h2o and z (given, or MPHIP_PREP_GEOPOT in the same call)");
+    if (!geopot)
+      need3[MPHIP_Z] = true;
+    if (mode == 5) {
+      if (!do_pv && !in->f3[MPHIP_PV])
+        return missing("MPHIP_PREP_TROPO with met_tropo 5", "pv (given, or MPHIP_PREP_PV in the same call)");
+      if (!do_pv)
+        need3[MPHIP_PV] = true;
+    }
+    if (mode == 1 && !ctx->have_clim)
+      return fail(ctx, "mphip_derive_met: MPHIP_PREP_TROPO with met_tropo 1 needs the tropopause climatology "
+                  "(mphip_update_clim first)");
+    if (mode == 1 && in->coord_type != 0 && !ctx->have_ctl)
+      return fail(ctx, "mphip_derive_met: MPHIP_PREP_TROPO with met_tropo 1 on a Cartesian grid needs met_utm_ref_lat "
+                  "(mphip_update_ctl first)");
+    if (!outputs({ MPHIP_PT, MPHIP_TT, MPHIP_ZT, MPHIP_H2OT }))
+      return fail(ctx, "mphip_derive_met: MPHIP_PREP_TROPO needs the output arrays pt, tt, zt, h2ot");
+    c_tropo = prep_tropo_columns(in->np, mode, &lds_tropo, &tropo_nprof, &tropo_fine);
+  }
   const int np = in->np;
   size_t lds_geo = 0, lds_o3 = 0, lds_cloud = 0, lds_pbl = 0, lds_cape = 0;
   const int c_geo = prep_columns(np, 3, &lds_geo), c_o3 = prep_columns(np, 1, &lds_o3), c_cloud = prep_columns(np, 4, &lds_cloud);
   const int c_pbl = prep_columns(np, opt->met_pbl == 2 ? 5 : 1, &lds_pbl), c_cape = prep_columns(np, 2, &lds_cape);
   if ((geopot && !c_geo) || ((what & MPHIP_PREP_O3C) && !c_o3) || ((what & MPHIP_PREP_CLOUD) && !c_cloud)
-      || ((what & MPHIP_PREP_PBL) && !c_pbl) || ((what & MPHIP_PREP_CAPE) && !c_cape))
+      || ((what & MPHIP_PREP_PBL) && !c_pbl) || ((what & MPHIP_PREP_CAPE) && !c_cape) || (tropo && !c_tropo))
     return fail(ctx, "mphip_derive_met: too many pressure levels for one column in 64 KB of LDS");
 
   std::lock_guard<std::mutex> guard(ctx->prep_lock);
@@ -3458,7 +3524,7 @@ int mphip_derive_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const
     ctx->prep_nx = in->nx;
     ctx->prep_ny = in->ny;
     ctx->prep_np = np;
-    if (dev_alloc(ctx, &ctx->prep_axes, (size_t) np + in->ny))
+    if (dev_alloc(ctx, &ctx->prep_axes, (size_t) np + in->ny + in->nx + 5 * (size_t) np + 2 * kTropoFine))
       return 1;
   }
   const size_t ncol = (size_t) in->nx * in->ny, ncell = ncol * np;
@@ -3487,6 +3553,39 @@ int mphip_derive_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const
     return 1;
   HIPCHK(hipMemcpyAsync(ctx->prep_axes, in->p, (size_t) np * sizeof(double), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(ctx->prep_axes + np, in->lat, (size_t) in->ny * sizeof(double), hipMemcpyHostToDevice, st));
+  double *const d_lon = ctx->prep_axes + np + in->ny, *const d_tab = d_lon + in->nx;
+  std::vector<double> tab;      // (alive until the stream is synchronised below)
+  if (do_pv || tropo) {
+    // what depends on the pressure axis alone, with the host's C library -- the one mphip_libm.h restates, so these are
+    // the values the device functions would give --: pows = pow(1000 / p, 0.286) and, for met_tropo 2 ... 5 only, zc =
+    // Z(p), the spline's interval widths h, elimination factors w and eliminated diagonal d, z2 and p2 = P(z2).  The
+    // recurrence of d must keep its two roundings (the definition's `d[i] -= w o[i-1]`): the product is rounded on its
+    // own line, whatever the host compiler may contract.
+    tab.assign(5 * (size_t) np + 2 * kTropoFine, 0.0);
+    double *zc = tab.data(), *h = zc + np, *w = h + np, *d = w + np, *pows = d + np, *z2 = pows + np, *p2 = z2 + kTropoFine;
+    for (int k = 0; k < np; k++)
+      pows[k] = pow(1000. / in->p[k], 0.286);
+    if (tropo && opt->met_tropo != 1) {
+      for (int k = 0; k < np; k++)
+        zc[k] = 7 * log(1013.25 / in->p[k]);
+      for (int k = 0; k + 1 < np; k++)
+        h[k] = zc[k + 1] - zc[k];
+      for (int i = 0; i + 3 <= np; i++) {
+        d[i] = 2 * (h[i] + h[i + 1]);
+        if (i > 0) {
+          w[i] = h[i] / d[i - 1];
+          volatile double wh = w[i] * h[i];
+          d[i] -= wh;
+        }
+      }
+      for (int i = 0; i < kTropoFine; i++) {
+        z2[i] = 4.5 + 0.1 * i;
+        p2[i] = 1013.25 * exp(-z2[i] / 7.);
+      }
+    }
+    HIPCHK(hipMemcpyAsync(d_lon, in->lon, (size_t) in->nx * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  }
   for (int f = 0; f < MPHIP_N3D; f++)
     if (need3[f]) {
       if (!ctx->prep_in3[f] && dev_alloc(ctx, &ctx->prep_in3[f], ncell))
@@ -3508,6 +3607,8 @@ int mphip_derive_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const
     for (auto &q : ctx->prep_z)
       if (!q && dev_alloc(ctx, &q, ncell))
         return 1;
+  if (do_pv && !ctx->prep_pv && dev_alloc(ctx, &ctx->prep_pv, ncell))
+    return 1;
   if (mark_end())
     return 1;
 
@@ -3597,7 +3698,43 @@ int mphip_derive_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const
     if (mark_end())
       return 1;
   }
+  const float *pv_final = i3[MPHIP_PV];
+  if (do_pv) {
+    const dim3 tiles((in->nx + kPvTX - 1) / kPvTX, (in->ny + kPvTY - 1) / kPvTY, (np + kPvKC - 1) / kPvKC);
+    if (mark_begin(0))
+      return 1;
+    hipLaunchKernelGGL(prep_pv_kernel, tiles, dim3(256), kPvLds, st, G, d_lon, d_tab + 4 * (size_t) np, i3[MPHIP_T],
+                       i3[MPHIP_U], i3[MPHIP_V], ctx->prep_pv);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(prep_pv_polar_kernel, dim3((unsigned) (((size_t) in->nx * np + 255) / 256)), dim3(256), 0, st, G,
+                       ctx->prep_pv);
+    HIPCHK(hipGetLastError());
+    if (mark_end())
+      return 1;
+    pv_final = ctx->prep_pv;
+  }
+  if (tropo) {
+    const dim3 nb = blocks(c_tropo);
+    PrepTropo T;
+    T.mode = opt->met_tropo;
+    T.spline = opt->met_tropo_spline;
+    T.pv_thr = opt->met_tropo_pv;
+    T.theta_thr = opt->met_tropo_theta;
+    T.nprof = tropo_nprof;
+    T.fine = tropo_fine;
+    T.tab = d_tab;
+    if (mark_begin(0))
+      return 1;
+    hipLaunchKernelGGL(prep_tropo_kernel, nb, dim3(kPrepLanes), lds_tropo, st, G, O, T, ctx->d_clim, i3[MPHIP_T],
+                       i3[MPHIP_H2O], z_final, T.mode == 5 ? pv_final : nullptr, o2[MPHIP_PT], o2[MPHIP_TT], o2[MPHIP_ZT],
+                       o2[MPHIP_H2OT]);
+    HIPCHK(hipGetLastError());
+    if (mark_end())
+      return 1;
+  }
   if (mark_begin(2))
+    return 1;
+  if (do_pv && prep_copy3(ctx, ctx->prep_pv, out->f3[MPHIP_PV], in, false, st))
     return 1;
   if (geopot && prep_copy3(ctx, const_cast<float *>(z_final), out->f3[MPHIP_Z], in, false, st))
     return 1;

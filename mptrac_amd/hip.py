@@ -44,7 +44,9 @@ class MphipMet(C.Structure):
 class MphipPrep(C.Structure):
     """mphip_prep_t: the options of mphip_derive_met."""
     _fields_ = [("met_pbl", C.c_int), ("met_pbl_min", C.c_double), ("met_pbl_max", C.c_double),
-                ("met_geopot_sx", C.c_int), ("met_geopot_sy", C.c_int), ("met_cloud_min", C.c_double)]
+                ("met_geopot_sx", C.c_int), ("met_geopot_sy", C.c_int), ("met_cloud_min", C.c_double),
+                ("met_tropo", C.c_int), ("met_tropo_pv", C.c_double), ("met_tropo_theta", C.c_double),
+                ("met_tropo_spline", C.c_int)]
 
 
 class MphipMetOut(C.Structure):
@@ -52,9 +54,9 @@ class MphipMetOut(C.Structure):
     _fields_ = [("f3", _fp * len(FIELDS_3D)), ("f2", _fp * len(FIELDS_2D))]
 
 
-PREP = {"geopot": 1, "o3c": 2, "pbl": 4, "cloud": 8, "cape": 16}
+PREP = {"geopot": 1, "o3c": 2, "pbl": 4, "cloud": 8, "cape": 16, "pv": 32, "tropo": 64}
 PREP_OUTPUTS = {"geopot": ("z",), "o3c": ("o3c",), "pbl": ("pbl",), "cloud": ("pct", "pcb", "cl"),
-                "cape": ("plcl", "plfc", "pel", "cape", "cin")}
+                "cape": ("plcl", "plfc", "pel", "cape", "cin"), "pv": ("pv",), "tropo": ("pt", "tt", "zt", "h2ot")}
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_void_p)
 
@@ -120,6 +122,10 @@ def load(build=True):
     L.mphip_discard_prefetch.argtypes = [C.c_void_p]
     if hasattr(L, "mphip_derive_met"):      # (absent from libraries built before the meteo preprocessing: A/B runs through MPHIP_LIB)
         L.mphip_derive_met.argtypes = [C.c_void_p, C.POINTER(MphipMet), C.c_uint, C.POINTER(MphipPrep), C.POINTER(MphipMetOut)]
+    if hasattr(L, "mphip_sizeof_prep"):     # (absent from libraries built before pv and the tropopause: they read the old members)
+        L.mphip_sizeof_prep.restype = C.c_size_t
+        if L.mphip_sizeof_prep() != C.sizeof(MphipPrep):
+            raise MphipError("mphip_prep_t layout mismatch between header and Python mirror")
     L.mphip_update_atm.argtypes = [C.c_void_p, C.c_longlong, C.c_longlong, C.c_longlong, C.c_int,
                                    _dp, _dp, _dp, _dp, C.POINTER(_dp)]
     L.mphip_get_atm.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, C.POINTER(_dp)]
@@ -314,15 +320,18 @@ class Simulation:
         """The derived fields of the meteo preprocessing (mphip_derive_met).  `met`: a snapshot as synthetic_met returns
         it, or a strided view -- any object with its attributes whose f3 / f2 arrays are NumPy views [nx][ny][np] /
         [nx][ny] into larger float32 arrays (last axis contiguous) and which names their strides in floats as
-        `strides` = (sx, sy, sx2).  `what`: names among geopot, o3c, pbl, cloud, cape (or the OR of their MPHIP_PREP_*
-        bits).  Options: met_pbl (3), met_pbl_min (0.1), met_pbl_max (5.0), met_geopot_sx, met_geopot_sy (-1: automatic),
-        met_cloud_min (0).  `out`: {name: float32 array with the strides of the input} to write into (tests); by default
-        new arrays.  Returns {name: array} of the fields of the requested bits."""
+        `strides` = (sx, sy, sx2).  `what`: names among geopot, o3c, pbl, cloud, cape, pv, tropo (or the OR of their
+        MPHIP_PREP_* bits).  Options: met_pbl (3), met_pbl_min (0.1), met_pbl_max (5.0), met_geopot_sx, met_geopot_sy (-1:
+        automatic), met_cloud_min (0), met_tropo (3), met_tropo_pv (3.5), met_tropo_theta (380), met_tropo_spline (1).
+        `out`: {name: float32 array with the strides of the input} to write into (tests); by default new arrays.  Returns
+        {name: array} of the fields of the requested bits."""
         if isinstance(what, str):
             what = (what,)
         bits = what if isinstance(what, int) else sum(PREP[w] for w in set(what))
         o = MphipPrep(int(opts.pop("met_pbl", 3)), float(opts.pop("met_pbl_min", 0.1)), float(opts.pop("met_pbl_max", 5.0)),
-                      int(opts.pop("met_geopot_sx", -1)), int(opts.pop("met_geopot_sy", -1)), float(opts.pop("met_cloud_min", 0.0)))
+                      int(opts.pop("met_geopot_sx", -1)), int(opts.pop("met_geopot_sy", -1)), float(opts.pop("met_cloud_min", 0.0)),
+                      int(opts.pop("met_tropo", 3)), float(opts.pop("met_tropo_pv", 3.5)), float(opts.pop("met_tropo_theta", 380.)),
+                      int(opts.pop("met_tropo_spline", 1)))
         if opts:
             raise TypeError(f"unknown options {sorted(opts)}")
         m = self._met_struct(met)
@@ -332,22 +341,23 @@ class Simulation:
         mo = MphipMetOut()
         for name, fields in PREP_OUTPUTS.items():
             for f in fields:
-                like = like3 if f == "z" else like2
+                three = f in FIELDS_3D
+                like = like3 if three else like2
                 if out is not None and f in out:        # (passed whether requested or not: the library must leave it alone)
                     a = out[f]
                 elif not bits & PREP[name] or like is None:
                     continue
                 elif like.flags["C_CONTIGUOUS"]:
                     a = np.empty_like(like)
-                elif f == "z":      # a strided view: allocate the enclosing extents, hand out the same view
+                elif three:      # a strided view: allocate the enclosing extents, hand out the same view
                     a = np.empty((met.nx, m.sx // m.sy, m.sy), dtype=np.float32)[:, :met.ny, :met.np]
                 else:
                     a = np.empty((met.nx, m.sx2), dtype=np.float32)[:, :met.ny]
                 assert a.dtype == np.float32 and a.strides == like.strides, f
                 if bits & PREP[name]:
                     res[f] = a
-                if f == "z":
-                    mo.f3[FIELDS_3D.index("z")] = _ptr(a, _fp)
+                if three:
+                    mo.f3[FIELDS_3D.index(f)] = _ptr(a, _fp)
                 else:
                     mo.f2[FIELDS_2D.index(f)] = _ptr(a, _fp)
         self._chk(self.L.mphip_derive_met(self.h, C.byref(m), bits, C.byref(o), C.byref(mo)))

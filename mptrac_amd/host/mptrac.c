@@ -210,6 +210,10 @@ static const char *unsupported_qnt[] = {
   I(met_geopot_sx, "MET_GEOPOT_SX", "-1") \
   I(met_geopot_sy, "MET_GEOPOT_SY", "-1") \
   D(met_cloud_min, "MET_CLOUD_MIN", "0") \
+  I(met_tropo, "MET_TROPO", "3") \
+  D(met_tropo_pv, "MET_TROPO_PV", "3.5") \
+  D(met_tropo_theta, "MET_TROPO_THETA", "380") \
+  I(met_tropo_spline, "MET_TROPO_SPLINE", "1") \
   D(sort_dt, "SORT_DT", "-999") \
   I(rng_type, "RNG_TYPE", "1") \
   I(advect, "ADVECT", "2") \
@@ -1835,6 +1839,7 @@ static int read_met_nc(const char *filename, const ctl_t *ctl, const clim_t *cli
    * pressure enters module_diff_turb only through weights that multiply TURB_DX_PBL / TURB_DZ_PBL against
    * TURB_DX_TROP / TURB_DZ_TROP: with equal values (the defaults) and none of the other consumers active any finite
    * value below the tropopause gives the reference's result, and surface pressure - 100 hPa is used. */
+  REQUIRE(ctl->hip_met_prep >= 0 && ctl->hip_met_prep <= 2, "HIP_MET_PREP must be 0, 1 or 2 (got %d)!", ctl->hip_met_prep);
   const unsigned got = ctl->hip_met_prep ? met_derive(ctl, clim, met, &have) : 0;
   if (!have_pbl && !(got & MPHIP_PREP_PBL)) {
     if ((ctl->diffusion && (ctl->turb_dx_pbl != ctl->turb_dx_trop || ctl->turb_dz_pbl != ctl->turb_dz_trop
@@ -1855,8 +1860,9 @@ static int read_met_nc(const char *filename, const ctl_t *ctl, const clim_t *cli
            "HIP_MET_PREP 1 derives them on the device from clwc and ciwc)!");
   static const struct {
     const char *name;
-    unsigned bit;     /* the MPHIP_PREP_* bit that derives it; 0: out of scope */
-  } derived[] = { { "pt", 0 }, { "tt", 0 }, { "zt", 0 }, { "h2ot", 0 }, { "pv", 0 }, { "zg", MPHIP_PREP_GEOPOT },
+    unsigned bit;     /* the MPHIP_PREP_* bit that derives it */
+  } derived[] = { { "pt", MPHIP_PREP_TROPO }, { "tt", MPHIP_PREP_TROPO }, { "zt", MPHIP_PREP_TROPO },
+    { "h2ot", MPHIP_PREP_TROPO }, { "pv", MPHIP_PREP_PV }, { "zg", MPHIP_PREP_GEOPOT },
     { "pct", MPHIP_PREP_CLOUD }, { "pcb", MPHIP_PREP_CLOUD }, { "cl", MPHIP_PREP_CLOUD }, { "plcl", MPHIP_PREP_CAPE },
     { "plfc", MPHIP_PREP_CAPE }, { "pel", MPHIP_PREP_CAPE }, { "cape", MPHIP_PREP_CAPE }, { "cin", MPHIP_PREP_CAPE },
     { "o3c", MPHIP_PREP_O3C }, { NULL, 0 } };
@@ -1865,8 +1871,9 @@ static int read_met_nc(const char *filename, const ctl_t *ctl, const clim_t *cli
       if (strcasecmp(ctl->qnt_name[iq], derived[k].name) == 0 && !(got & derived[k].bit)
           && !(have_cape && (!strcmp(derived[k].name, "cape") || !strcmp(derived[k].name, "cin"))))
         ERRMSG("Quantity %s comes from the reference's meteo preprocessing, which netCDF input does not get here%s!",
-               ctl->qnt_name[iq], derived[k].bit ? " without HIP_MET_PREP 1 and the fields it is derived from" :
-               " (HIP_MET_PREP does not derive it either)");
+               ctl->qnt_name[iq], derived[k].bit & (MPHIP_PREP_PV | MPHIP_PREP_TROPO) ?
+               " without HIP_MET_PREP 2 and the fields it is derived from" :
+               " without HIP_MET_PREP 1 and the fields it is derived from");
   return 1;
 }
 
@@ -2050,7 +2057,8 @@ static void upload_met(met_t *met, int slot) {
   HIP(mphip_update_met(g_ctx, slot, &m));
 }
 
-/* HIP_MET_PREP 1: the fields of the reference's meteo preprocessing that the file's own fields allow, derived on the
+/* HIP_MET_PREP 1 or 2: the fields of the reference's meteo preprocessing that the file's own fields allow (2: potential
+ * vorticity and the tropopause of MET_TROPO as well), derived on the
  * device into the met_t (mphip_derive_met: a stream and scratch of its own, so the read-ahead thread of
  * HIP_MET_PREFETCH may call it while the main thread steps).  Returns the MPHIP_PREP_* bits that were derived.  The
  * context and the tropopause table CAPE needs are set up by the first call, which every driver makes from its main
@@ -2068,11 +2076,18 @@ static unsigned met_derive(const ctl_t *ctl, const clim_t *clim, met_t *met, con
     what |= MPHIP_PREP_CLOUD;
   if (ctl->met_cape == 1 && have->h2o && clim)
     what |= MPHIP_PREP_CAPE;
+  if (ctl->hip_met_prep == 2) {
+    if (ctl->met_coord_type == 0 && met->nx >= 2 && met->ny >= 5)
+      what |= MPHIP_PREP_PV;
+    if (have->h2o && (what & MPHIP_PREP_GEOPOT) && met->np >= 3 && (ctl->met_tropo != 1 || clim)
+        && (ctl->met_tropo != 5 || (what & MPHIP_PREP_PV)))
+      what |= MPHIP_PREP_TROPO;
+  }
   if (!what)
     return 0;
   if (!g_prep_ready) {
     need_ctx(ctl);
-    if (what & MPHIP_PREP_CAPE)
+    if ((what & MPHIP_PREP_CAPE) || ((what & MPHIP_PREP_TROPO) && ctl->met_tropo == 1))
       HIP(mphip_update_clim(g_ctx, clim->tropo_ntime, clim->tropo_nlat, clim->tropo_time, clim->tropo_lat,
                             &clim->tropo[0][0], 73));
     if (ctl->met_coord_type != 0) {   /* the tropopause of a Cartesian grid is taken at MET_UTM_REF_LAT */
@@ -2086,6 +2101,7 @@ static unsigned met_derive(const ctl_t *ctl, const clim_t *clim, met_t *met, con
   describe_met(met, &in);
   in.npl = 0;
   in.f3[MPHIP_Z] = NULL;
+  in.f3[MPHIP_PV] = NULL;
   in.f3[MPHIP_O3] = have->o3 ? &met->o3[0][0][0] : NULL;
   in.f3[MPHIP_H2O] = have->h2o ? &met->h2o[0][0][0] : NULL;
   in.f3[MPHIP_LWC] = have->lwc ? &met->lwc[0][0][0] : NULL;
@@ -2109,14 +2125,20 @@ static unsigned met_derive(const ctl_t *ctl, const clim_t *clim, met_t *met, con
   out.f2[MPHIP_PEL] = &met->pel[0][0];
   out.f2[MPHIP_CAPE] = &met->cape[0][0];
   out.f2[MPHIP_CIN] = &met->cin[0][0];
+  out.f3[MPHIP_PV] = &met->pv[0][0][0];
+  out.f2[MPHIP_PT] = &met->pt[0][0];
+  out.f2[MPHIP_TT] = &met->tt[0][0];
+  out.f2[MPHIP_ZT] = &met->zt[0][0];
+  out.f2[MPHIP_H2OT] = &met->h2ot[0][0];
   const mphip_prep_t opt = { ctl->met_pbl, ctl->met_pbl_min, ctl->met_pbl_max, ctl->met_geopot_sx, ctl->met_geopot_sy,
-    ctl->met_cloud_min };
+    ctl->met_cloud_min, ctl->met_tropo, ctl->met_tropo_pv, ctl->met_tropo_theta, ctl->met_tropo_spline };
   /* (not through HIP(): that macro first submits the main thread's queued time steps) */
   if (mphip_derive_met(g_ctx, &in, what, &opt, &out) != 0)
     ERRMSG("HIP back end: %s", mphip_last_error(g_ctx));
-  LOG(2, "Derived on the device:%s%s%s%s%s", what & MPHIP_PREP_GEOPOT ? " geopotential heights" : "",
+  LOG(2, "Derived on the device:%s%s%s%s%s%s%s", what & MPHIP_PREP_GEOPOT ? " geopotential heights" : "",
       what & MPHIP_PREP_O3C ? " ozone column" : "", what & MPHIP_PREP_PBL ? " boundary layer" : "",
-      what & MPHIP_PREP_CLOUD ? " cloud layer" : "", what & MPHIP_PREP_CAPE ? " CAPE" : "");
+      what & MPHIP_PREP_CLOUD ? " cloud layer" : "", what & MPHIP_PREP_CAPE ? " CAPE" : "",
+      what & MPHIP_PREP_PV ? " potential vorticity" : "", what & MPHIP_PREP_TROPO ? " tropopause" : "");
   return what;
 }
 

@@ -145,6 +145,9 @@ typedef struct {
   /* the reference's parameters of the fields HIP_MET_PREP 1 derives from netCDF input (mphip_derive_met) */
   double met_pbl_min, met_pbl_max, met_cloud_min;
   int met_geopot_sx, met_geopot_sy;
+  /* ... and of HIP_MET_PREP 2: the tropopause definition (1 climatology, 2 cold point, 3 WMO, 4 second WMO, 5 dynamical) */
+  int met_tropo, met_tropo_spline;
+  double met_tropo_pv, met_tropo_theta;
   double t_start, t_stop, dt_mod, dt_met, met_utm_ref_lat, met_utm_ref_lon, met_dt_out;
   /* zonal-mean climatologies module_meteo samples (mptrac.c:7461-7470) and the diurnal scaling of OH (mptrac.c:7394) */
   char clim_hno3_filename[LEN], clim_oh_filename[LEN], clim_h2o2_filename[LEN], clim_ho2_filename[LEN],
@@ -215,8 +218,10 @@ typedef struct {
   int hip_device;
   int hip_locality_interval;
   int hip_met_prefetch;   /* HIP_MET_PREFETCH: read and upload the next meteo file beside the time steps */
-  int hip_met_prep;       /* HIP_MET_PREP (default 0): derive geopotential height, ozone column, boundary layer, cloud layer and
-                             CAPE of netCDF input (MET_TYPE 0) on the device, as the reference's meteo preprocessing does */
+  int hip_met_prep;       /* HIP_MET_PREP (default 0): 1: derive geopotential height, ozone column, boundary layer, cloud
+                             layer and CAPE of netCDF input (MET_TYPE 0) on the device, as the reference's meteo
+                             preprocessing does; 2: potential vorticity and the tropopause (MET_TROPO) as well; other
+                             values are refused */
   int hip_device_analysis;   /* HIP_DEVICE_ANALYSIS (default 1): the particle loops of the CSI, profile, sample and station
                                 outputs run on the device; 0: on particles downloaded in every time step */
 } ctl_t;

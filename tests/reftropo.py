@@ -1,0 +1,287 @@
+"""Potential vorticity and the tropopause of mphip_derive_met (MPHIP_PREP_PV, MPHIP_PREP_TROPO), restated in plain Python
+from the definitions of include/mptrac_hip.h -- not from the kernels.  As in refmetprep.py, `math` is the C library, Python
+contracts nothing, and every comparison between COMPUTED values is recorded in a Margin: each LAPSE against 2.0 and 3.0,
+|pv2| against met_tropo_pv, th2 against met_tropo_theta, the cold-point minimum against every other t2, and (through
+refmetprep.env) the pressure nodes next to pt.
+
+For the potential vorticity it also returns, per element, S = 1e6 G0 (|dtdp (dvdx - dudy/cr + vort)| + |dvdp dtdx| + |dudp
+dtdy|): the size of the three terms whose sum pv is, so that a comparison can allow the forward error of that sum.
+"""
+import functools
+import math
+
+import numpy as np
+
+import refmetprep as R
+from refmetprep import G0, RA, NAN, LIN, P, THETA, Margin, atmosphere, strided, clim_tropo, env      # noqa: F401
+
+RE = 6367.421
+NFINE, TOP = 201, 170
+TROPO_OUTPUTS = ("pt", "tt", "zt", "h2ot")
+
+
+def RAD(x):
+    return x * (math.pi / 180.0)
+
+
+def DEG2DX(d, lat):
+    return RE * RAD(d) * math.cos(RAD(lat))
+
+
+def DEG2DY(d):
+    return RE * RAD(d)
+
+
+def Z(p):
+    return 7 * math.log(1013.25 / p)
+
+
+def LAPSE(p1, t1, p2, t2):
+    return 1e3 * G0 / RA * (t2 - t1) / (t2 + t1) * (p2 + p1) / (p2 - p1)
+
+
+Z2 = [4.5 + 0.1 * i for i in range(NFINE)]
+P2 = [P(z) for z in Z2]
+
+
+# ---- potential vorticity -----------------------------------------------------------------------------------------------------
+
+def pv_field(lon, lat, p, t, u, v):
+    """(pv float32 [nx][ny][np], S float64 [nx][ny][np]); t, u, v nested lists of doubles."""
+    nx, ny, n = len(lon), len(lat), len(p)
+    pows = [math.pow(1000. / p[k], 0.286) for k in range(n)]
+    pv = np.empty((nx, ny, n), dtype=np.float32)
+    S = np.empty((nx, ny, n))
+
+    def D(a, k, k0, k1, dp0, dp1):
+        if k != k0 and k != k1:
+            return (dp0 * dp0 * a[k1] - dp1 * dp1 * a[k0] + (dp1 * dp1 - dp0 * dp0) * a[k]) / (dp0 * dp1 * (dp0 + dp1))
+        return (a[k1] - a[k0]) / (dp0 + dp1)
+    for ix in range(nx):
+        ix0, ix1 = max(ix - 1, 0), min(ix + 1, nx - 1)
+        for iy in range(ny):
+            iy0, iy1 = max(iy - 1, 0), min(iy + 1, ny - 1)
+            latr = 0.5 * (lat[iy1] + lat[iy0])
+            dx = 1000. * DEG2DX(lon[ix1] - lon[ix0], latr)
+            dy = 1000. * DEG2DY(lat[iy1] - lat[iy0])
+            c0, c1, cr = math.cos(RAD(lat[iy0])), math.cos(RAD(lat[iy1])), math.cos(RAD(latr))
+            vort = 2 * 2 * math.pi / 86400. * math.sin(RAD(lat[iy]))
+            tc, uc, vc = t[ix][iy], u[ix][iy], v[ix][iy]
+            tp = [tc[k] * pows[k] for k in range(n)]
+            for k in range(n):
+                dtdx = (t[ix1][iy][k] - t[ix0][iy][k]) * pows[k] / dx
+                dvdx = (v[ix1][iy][k] - v[ix0][iy][k]) / dx
+                dtdy = (t[ix][iy1][k] - t[ix][iy0][k]) * pows[k] / dy
+                dudy = (u[ix][iy1][k] * c1 - u[ix][iy0][k] * c0) / dy
+                k0, k1 = max(k - 1, 0), min(k + 1, n - 1)
+                dp0, dp1 = 100. * (p[k] - p[k0]), 100. * (p[k1] - p[k])
+                dtdp, dudp, dvdp = D(tp, k, k0, k1, dp0, dp1), D(uc, k, k0, k1, dp0, dp1), D(vc, k, k0, k1, dp0, dp1)
+                pv[ix, iy, k] = 1e6 * G0 * (-dtdp * (dvdx - dudy / cr + vort) + dvdp * dtdx - dudp * dtdy)
+                S[ix, iy, k] = 1e6 * G0 * (abs(dtdp * (dvdx - dudy / cr + vort)) + abs(dvdp * dtdx) + abs(dudp * dtdy))
+    for a in (pv, S):
+        a[:, 0] = a[:, 1] = a[:, 2]
+        a[:, ny - 1] = a[:, ny - 2] = a[:, ny - 3]
+    return pv, S
+
+
+# ---- the spline ------------------------------------------------------------------------------------------------------------------
+
+def spline_coeffs(zc, y):
+    """c[0 ... n-1] of the natural cubic spline through (zc, y)."""
+    n = len(zc)
+    h = [zc[k + 1] - zc[k] for k in range(n - 1)]
+    c = [0.] * n
+    d = [2 * (h[i] + h[i + 1]) for i in range(n - 2)]
+    o = [h[i + 1] for i in range(n - 2)]
+    g = [3 * ((y[i + 2] - y[i + 1]) / h[i + 1] - (y[i + 1] - y[i]) / h[i]) for i in range(n - 2)]
+    for i in range(1, n - 2):
+        w = o[i - 1] / d[i - 1]
+        d[i] -= w * o[i - 1]
+        g[i] -= w * g[i - 1]
+    c[n - 2] = g[n - 3] / d[n - 3]
+    for i in range(n - 4, -1, -1):
+        c[i + 1] = (g[i] - o[i] * c[i + 2]) / d[i]
+    return c
+
+
+def spline(zc, y, x2, method=1):
+    """The profile y on the ascending axis zc at the ascending points x2 (the definition's spline(y)[i])."""
+    n = len(zc)
+    c = spline_coeffs(zc, y) if method == 1 else None
+    out = []
+    k = 0
+    for x in x2:
+        if x <= zc[0]:
+            out.append(y[0])
+            continue
+        if x >= zc[n - 1]:
+            out.append(y[n - 1])
+            continue
+        while k < n - 2 and zc[k + 1] <= x:      # (k only grows: x2 ascends)
+            k += 1
+        if method == 0:
+            out.append(LIN(zc[k], y[k], zc[k + 1], y[k + 1], x))
+            continue
+        h = zc[k + 1] - zc[k]
+        b = (y[k + 1] - y[k]) / h - h * (c[k + 1] + 2 * c[k]) / 3
+        e = (c[k + 1] - c[k]) / (3 * h)
+        dx = x - zc[k]
+        out.append(y[k] + dx * (b + dx * (c[k] + dx * e)))
+    return out
+
+
+# ---- the tropopause of a column -------------------------------------------------------------------------------------------------------
+
+def _B(t2, iz, m):
+    for j in range(iz + 1, iz + 21):
+        g = LAPSE(P2[iz], t2[iz], P2[j], t2[j])
+        m.see(g, 2.0)
+        if not g <= 2.0:
+            return False
+    return True
+
+
+def _A(t2, iz, m):
+    for j in range(iz + 1, iz + 11):
+        g = LAPSE(P2[iz], t2[iz], P2[j], t2[j])
+        m.see(g, 3.0)
+        if not g >= 3.0:
+            return False
+    return True
+
+
+def _first(lo, test):
+    for iz in range(lo, TOP + 1):
+        if test(iz):
+            return iz
+    return None
+
+
+def _inside(iz):
+    return P2[iz] if iz is not None and 0 < iz < TOP else NAN
+
+
+def tropo_pt(mode, method, zc, p, t, pv, m, pv_thr=3.5, theta_thr=380., pclim=NAN):
+    """pt of one column (t, pv: lists of doubles)."""
+    if mode == 1:
+        return pclim
+    if mode == 2:
+        t2 = spline(zc, t, Z2[:TOP + 1], method)
+        if any(x != x for x in t2):
+            return NAN
+        iz = t2.index(min(t2))
+        for i, x in enumerate(t2):
+            if i != iz:
+                m.see(x, t2[iz])
+        return _inside(iz)
+    if mode in (3, 4):
+        t2 = spline(zc, t, Z2, method)
+        if any(x != x for x in t2):
+            return NAN
+        iz = _first(0, lambda i: _B(t2, i, m))
+        if mode == 4 and iz is not None:
+            iz = _first(iz, lambda i: _A(t2, i, m))
+            if iz is not None:
+                iz = _first(iz, lambda i: _B(t2, i, m))
+        return _inside(iz)
+    if mode == 5:
+        pv2 = spline(zc, pv, Z2[:TOP + 1], method)
+        th2 = spline(zc, [THETA(p[k], t[k]) for k in range(len(p))], Z2[:TOP + 1], method)
+        if any(x != x for x in pv2 + th2):
+            return NAN
+
+        def hit(i):
+            m.see(abs(pv2[i]), pv_thr)
+            m.see(th2[i], theta_thr)
+            return abs(pv2[i]) >= pv_thr or th2[i] >= theta_thr
+        return _inside(_first(0, hit))
+    raise ValueError(mode)
+
+
+# ---- whole snapshots -------------------------------------------------------------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def atmosphere2(key):
+    """atmosphere(*key) in which every second column (flat index even) resumes cooling at 6.5 K/km from 3 km above its
+    first isothermal level for 4 km, so that met_tropo 4 finds second tropopauses."""
+    from mptrac_amd.synth import Met
+    met = atmosphere(*key)
+    zlev = 7. * np.log(1013.25 / met.p)
+    t = met.f3["t"].astype(np.float64)
+    # the seeded tropopause height is not kept by atmosphere(): the first isothermal level is the first whose layer below
+    # cools by less than 2 K/km (the noise is 0.3 K on layers of 0.3 km and more ... 2.2 km)
+    for c in range(0, met.nx * met.ny, 2):
+        ix, iy = c // met.ny, c % met.ny
+        col = t[ix, iy]
+        k_iso = next((k for k in range(1, met.np) if zlev[k] > 8. and (col[k - 1] - col[k]) / (zlev[k] - zlev[k - 1]) < 2.), None)
+        if k_iso is None:
+            continue
+        z0 = zlev[k_iso] + 3.
+        col -= 6.5 * np.clip(zlev - z0, 0., 4.)
+    f3 = dict(met.f3, t=np.ascontiguousarray(t, dtype=np.float32))
+    f3["t"][-1] = f3["t"][0]
+    f3["t"].setflags(write=False)
+    out = Met(met.time, met.lon, met.lat, met.p, f3, dict(met.f2))
+    for d in (out.f3, out.f2):
+        for a in d.values():
+            a.setflags(write=False)
+    return out
+
+
+def snapshot(key, second=False):
+    return atmosphere2(key) if second else atmosphere(*key)
+
+
+@functools.lru_cache(maxsize=None)
+def z_field(key, second=False):
+    """The float geopotential-height field of the restatement (smoothing automatic): what the tests pass in as z."""
+    met = snapshot(key, second)
+    p = met.p.tolist()
+    t, h2o = R._f64(met, "t"), R._f64(met, "h2o")
+    ps, zs = R._f64(met, "ps", False), R._f64(met, "zs", False)
+    z = np.empty((met.nx, met.ny, met.np), dtype=np.float32)
+    for ix in range(met.nx):
+        for iy in range(met.ny):
+            z[ix, iy] = R.geopot_column(p, t[ix][iy], h2o[ix][iy], ps[ix][iy], zs[ix][iy])
+    z = R.smooth(z, met.lon, -1, -1)
+    z.setflags(write=False)
+    return z
+
+
+@functools.lru_cache(maxsize=None)
+def pv_reference(key, second=False):
+    """(pv float32, S) of the snapshot."""
+    met = snapshot(key, second)
+    pv, S = pv_field(met.lon.tolist(), met.lat.tolist(), met.p.tolist(), R._f64(met, "t"), R._f64(met, "u"), R._f64(met, "v"))
+    pv.setflags(write=False)
+    return pv, S
+
+
+@functools.lru_cache(maxsize=None)
+def tropo_reference(key, mode, method=1, second=False, pv_thr=3.5, theta_thr=380.):
+    """({pt, tt, zt, h2ot: float32 [nx][ny]}, margin [nx][ny]) with z = z_field and pv = pv_reference (both as floats)."""
+    if mode in (2, 3, 4) and len(key) > 4 and key[4]:
+        # nothing these modes read depends on the latitudes: the columns of the ascending snapshot
+        return tropo_reference(key[:4] + (False,) + key[5:], mode, method, second, pv_thr, theta_thr)
+    met = snapshot(key, second)
+    p = met.p.tolist()
+    zc = [Z(x) for x in p]
+    t, h2o = R._f64(met, "t"), R._f64(met, "h2o")
+    z = z_field(key, second).astype(np.float64).tolist()
+    pv = pv_reference(key, second)[0].astype(np.float64).tolist() if mode == 5 else None
+    clim = R.load_clim_tropo() if mode == 1 else None
+    out = {k: np.empty((met.nx, met.ny), dtype=np.float32) for k in TROPO_OUTPUTS}
+    margin = np.empty((met.nx, met.ny))
+    for ix in range(met.nx):
+        for iy in range(met.ny):
+            m = Margin()
+            pclim = clim_tropo(clim, met.time, met.lat[iy]) if mode == 1 else NAN
+            pt = tropo_pt(mode, method, zc, p, t[ix][iy], pv[ix][iy] if pv else None, m, pv_thr, theta_thr, pclim)
+            if pt == pt:
+                vals = (pt, env(p, t[ix][iy], pt, m), env(p, z[ix][iy], pt, m), env(p, h2o[ix][iy], pt, m))
+            else:
+                vals = (NAN,) * 4
+            for name, val in zip(TROPO_OUTPUTS, vals):
+                out[name][ix, iy] = val
+            margin[ix, iy] = m.value
+    return out, margin
