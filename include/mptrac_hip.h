@@ -352,8 +352,8 @@ int mphip_discard_prefetch(mphip_ctx *ctx);
  * mphip_update_clim at the column's latitude, met_utm_ref_lat on a Cartesian grid); do { dz = dz0 TVIRT(t,h); p /= pfac; t -=
  * lapse_rate(t,h) dz; e = PSAT(t); h = e / (p - (1-EPS) e); Te, he as above; d_old = d; d = the same expression; if (d > 0) {
  * cape += d; if plfc is NaN: plfc = p; } else if (d_old > 0) pel = p; if (d < 0 and plfc is NaN) cin += |d|; } while (p >
- * ptop).  If plfc is NaN: cin = NaN.  (An infinite ps is taken as NaN, so that every loop ends: p shrinks by pfac per pass
- * and a NaN makes each condition false.)
+ * ptop).  If plfc is NaN: cin = NaN.  (An infinite ps is taken as NaN, here and in the geopotential, so that every loop ends: p
+ * shrinks by pfac per pass and a NaN makes each condition false.)
  *   Further helpers (each a function: its value is formed before it enters the expression around it; cos and sin are the
  * C library's).  RE = 6367.421.  RAD(x) = x (M_PI / 180.0).  DEG2DX(d,lat) = RE RAD(d) cos(RAD(lat)).  DEG2DY(d) = RE
  * RAD(d).  Z(p) = 7 log(1013.25 / p).  LAPSE(p1,t1,p2,t2) = 1e3 G0 / RA (t2 - t1) / (t2 + t1) (p2 + p1) / (p2 - p1).
@@ -385,6 +385,21 @@ int mphip_discard_prefetch(mphip_ctx *ctx);
  * spline(THETA(p[k],t[k])) on 0 ... 170; iz = the first index with fabs(pv2[iz]) >= met_tropo_pv or th2[iz] >=
  * met_tropo_theta; pt = p2[iz] if it exists and 0 < iz < 170, else NaN.  Then tt = env(t,pt), zt = env(z,pt), h2ot =
  * env(h2o,pt); all three NaN when pt is NaN.
+ *   Values outside the physical range are not refused: the arithmetic above decides, by IEEE rules and with the C library's
+ * results (log 0 = -inf, log of a negative number NaN, 1000/0 = inf, pow(x, 0.286) NaN for x < 0 and 0 for x = -0), and
+ * every comparison with a NaN is false.  So max(h, 1e-7) takes a NaN h for 1e-7 -- TVIRT, PW and SH treat a NaN water
+ * vapour as the dry floor -- and min(ps, p[0]) a NaN ps for p[0]; loc(NaN) = 0, and loc(q) = np-2 for every q <= p[np-2], q
+ * <= 0 included.  The geopotential and CAPE take an infinite ps as NaN; the ozone column, the cloud layer and the boundary
+ * layer take it as it is.  The outcomes (tests/metprep_cases.py, `nonfinite`):
+ *   ps NaN: z NaN on every level; o3c = 0; no level is skipped by the cloud search; pbl NaN; the parcel is that of p[0],
+ * every loop of CAPE ends in its first pass: cape = 0, plcl = plfc = pel = cin = NaN.  ps = +inf: z and CAPE as for NaN;
+ * o3c and the cloud layer are those of the whole column; pbl = +inf.  ps = -inf: z and CAPE as for NaN; o3c = 0, pct = pcb =
+ * NaN, cl = 0; pbl = -inf.  ps = 0: z = -inf on every level (the smoothing skips it like a NaN: it sums finite values
+ * only); o3c = 0, pct = pcb = NaN, cl = 0; no level lies at or below the surface, so no parcel: the five CAPE outputs are
+ * NaN; pbl = 0.  ps < 0: as for 0, but z NaN (log ps) and pbl = ps exp(-met_pbl_max/7) (pmin < pmax there, and the second
+ * clamp is the last).  A NaN in t[k] makes z NaN on the levels from k away from the surface (on all levels if the surface's
+ * LIN reads it); an infinite h2o makes z NaN on every level; a NaN zs makes z NaN on every level; a NaN ts makes PBL 3's pbl
+ * pmin (it is not finite) and keeps PBL 2's criterion false, which is pmin as well.
  *   Out of scope: MET_PBL 1, detrending, down-sampling, model-to-pressure-level regridding. */
 enum { MPHIP_PREP_GEOPOT = 1, MPHIP_PREP_O3C = 2, MPHIP_PREP_PBL = 4, MPHIP_PREP_CLOUD = 8, MPHIP_PREP_CAPE = 16,
        MPHIP_PREP_PV = 32, MPHIP_PREP_TROPO = 64 };

@@ -7,9 +7,16 @@ It also builds the input (atmosphere) and, for every column, the smallest relati
 COMPUTED values from its threshold (Margin): a comparison decided by less than a few ulp may go the other way in the
 default library, whose divisions and contractions move a double by an ulp, and the GPU test would then compare different
 branches.  Comparisons between input values alone (a level against the surface pressure, a water content against the
-cloud threshold, an exact zero) come out the same in any arithmetic and are not recorded.
+cloud threshold, an exact zero) come out the same in any arithmetic and are not recorded in the Margin; where such a
+comparison is an EQUALITY -- a tie -- a Ties recorder counts it by name, so that a test can show that its inputs reach it.
+
+Where Python would raise -- the logarithm of a number that is not positive, a division by zero, an exp or pow that
+overflows -- the restatement returns what IEEE arithmetic and the C library return (_log, _exp, _pow, _div), so that it is
+defined on every float input, a NaN, an infinity or a surface pressure <= 0 included.  Every loop whose end depends on
+the arithmetic has a cap (CAP passes) and raises beyond it.
 """
 import bisect
+import collections
 import functools
 import math
 import os
@@ -31,6 +38,56 @@ OUTPUTS_2D = ("o3c", "pbl", "pct", "pcb", "cl", "plcl", "plfc", "pel", "cape", "
 DEFAULTS = dict(met_pbl_min=0.1, met_pbl_max=5.0, met_cloud_min=0.0)
 
 
+CAP = 20000       # passes of a bisection or an ascent: three orders above what any finite input takes
+
+
+def _log(x):
+    if x > 0:
+        return math.log(x)
+    return -math.inf if x == 0 else NAN
+
+
+def _exp(x):
+    try:
+        return math.exp(x)
+    except OverflowError:
+        return math.inf
+
+
+def _pow(x, y):
+    try:
+        return math.pow(x, y)
+    except OverflowError:
+        return math.inf
+    except ValueError:          # a zero to a negative power; a negative number to a power that is no integer
+        return math.inf if x == 0 else NAN
+
+
+def _div(a, b):
+    try:
+        return a / b
+    except ZeroDivisionError:
+        if a != a or a == 0:
+            return NAN
+        return math.copysign(math.inf, a) * math.copysign(1., b)
+
+
+class Ties:
+    """Counts, by name, the comparisons between input values that were equalities."""
+
+    def __init__(self):
+        self.count = collections.Counter()
+
+    def see(self, name, a, b):
+        if a == b:
+            self.count[name] += 1
+
+
+def _tie(ties, name, a, b):
+    if ties is not None:
+        ties.see(name, a, b)
+
+
 class Margin:
     """Smallest relative distance of a recorded comparison from equality."""
 
@@ -44,11 +101,11 @@ class Margin:
 
 
 def LIN(x0, y0, x1, y1, x):
-    return y0 + (y1 - y0) / (x1 - x0) * (x - x0)
+    return y0 + _div(y1 - y0, x1 - x0) * (x - x0)
 
 
 def P(z):
-    return 1013.25 * math.exp(-z / 7.)
+    return 1013.25 * _exp(-z / 7.)
 
 
 def fmax(a, b):
@@ -60,7 +117,7 @@ def fmin(a, b):
 
 
 def THETA(p, t):
-    return t * math.pow(1000. / p, KAPPA)
+    return t * _pow(_div(1000., p), KAPPA)
 
 
 def TVIRT(t, h):
@@ -68,11 +125,11 @@ def TVIRT(t, h):
 
 
 def PSAT(t):
-    return 6.112 * math.exp(17.62 * (t - T0) / (243.12 + t - T0))
+    return 6.112 * _exp(_div(17.62 * (t - T0), 243.12 + t - T0))
 
 
 def PW(p, h):
-    return p * fmax(h, 0.1e-6) / (1. + (1. - EPS) * fmax(h, 0.1e-6))
+    return _div(p * fmax(h, 0.1e-6), 1. + (1. - EPS) * fmax(h, 0.1e-6))
 
 
 def SH(h):
@@ -81,8 +138,8 @@ def SH(h):
 
 def lapse_rate(t, h):
     a = RA * (t * t)
-    r = SH(h) / (1. - SH(h))
-    return 1e3 * G0 * (a + LV * r * t) / (CPD * a + LV * LV * r * EPS)
+    r = _div(SH(h), 1. - SH(h))
+    return _div(1e3 * G0 * (a + LV * r * t), CPD * a + LV * LV * r * EPS)
 
 
 _NEGATED = {}
@@ -116,8 +173,12 @@ def clim_tropo(clim, t, lat):
     time, lats, tropo = clim[:3]
     year = 365.25 * 86400.
     sec = t - int(t / year) * year
-    while sec < 0:
+    for _ in range(CAP):
+        if not sec < 0:
+            break
         sec += year
+    else:
+        raise RuntimeError("the second of the year does not become positive")
     lo, hi = 0, len(time) - 1
     while hi > lo + 1:
         mid = (hi + lo) >> 1
@@ -133,18 +194,21 @@ def clim_tropo(clim, t, lat):
 
 # ---- the columns ---------------------------------------------------------------------------------------------------------
 
-def geopot_column(p, t, h2o, ps, zs):
-    """z[np] in km as doubles (the caller rounds to float once)."""
+def geopot_column(p, t, h2o, ps, zs, ties=None):
+    """z[np] in km as doubles (the caller rounds to float once).  An infinite ps is taken as NaN."""
     n = len(p)
+    if math.isinf(ps):
+        ps = NAN
     tv = [TVIRT(t[k], h2o[k]) for k in range(n)]
-    lp = [math.log(p[k]) for k in range(n)]
+    lp = [_log(p[k]) for k in range(n)]
     c = RI / MA / G0
 
     def ZD(a, ta, b, tb):
         return c * (0.5 * (ta + tb)) * (a - b)
     k0 = loc(p, ps)
+    _tie(ties, "loc", p[k0], ps)
     tsurf = LIN(p[k0], tv[k0], p[k0 + 1], tv[k0 + 1], ps)
-    lps = math.log(ps)
+    lps = _log(ps)
     z = [NAN] * n
     z[k0 + 1] = zs + ZD(lps, tsurf, lp[k0 + 1], tv[k0 + 1])
     for k in range(k0 + 2, n):
@@ -187,21 +251,25 @@ def smooth(z, lon, sx, sy):
         return np.where(ws > 0, (wz / ws).astype(f32), f32(NAN)).astype(f32)
 
 
-def o3c_column(p, o3, ps):
+def o3c_column(p, o3, ps, ties=None):
     cd = 0.
     for k in range(1, len(p)):
+        _tie(ties, "o3c", p[k - 1], ps)
         if p[k - 1] <= ps:
             cd += 0.5 * (o3[k - 1] + o3[k]) * MO3 / MA * (p[k - 1] - p[k]) * 100. / G0
     return cd / 2.1415e-5
 
 
-def cloud_column(p, lwc, rwc, iwc, swc, ps, cloud_min):
+def cloud_column(p, lwc, rwc, iwc, swc, ps, cloud_min, ties=None):
     pct = pcb = NAN
     cl = 0.
     p20 = P(20.)
     for k in range(len(p) - 1):
+        _tie(ties, "cloud_ps", p[k], ps)
         if p[k] > ps or p[k] < p20:     # (P(20) lies between levels by construction of the axes: checked by the CPU test)
             continue
+        for w in (lwc[k], rwc[k], iwc[k], swc[k]):
+            _tie(ties, "cloud_min", w, cloud_min)
         if lwc[k] > cloud_min or rwc[k] > cloud_min or iwc[k] > cloud_min or swc[k] > cloud_min:
             pct = 0.5 * (p[k] + p[k + 1])
             if pcb != pcb:
@@ -212,8 +280,8 @@ def cloud_column(p, lwc, rwc, iwc, swc, ps, cloud_min):
 
 
 def pbl_clamp(ps, pbl, below, pbl_min, pbl_max, m):
-    pmin = ps * math.exp(-pbl_min / 7.)
-    pmax = ps * math.exp(-pbl_max / 7.)
+    pmin = ps * _exp(-pbl_min / 7.)
+    pmax = ps * _exp(-pbl_max / 7.)
     m.see(pbl, pmin)
     if not math.isfinite(pbl) or pbl > pmin or below:
         pbl = pmin
@@ -223,16 +291,18 @@ def pbl_clamp(ps, pbl, below, pbl_min, pbl_max, m):
     return pbl
 
 
-def pbl3_column(p, t, ps, ts, pbl_min, pbl_max, m):
+def pbl3_column(p, t, ps, ts, pbl_min, pbl_max, m, ties=None):
     th0 = THETA(ps, ts)
     k = len(p) - 2
     while k > 0:
         if p[k] >= 300.:
+            _tie(ties, "pbl3_ps", p[k], ps)
             if p[k] > ps:
                 break
             th = THETA(p[k], t[k])
             m.see(th, th0 + 2.)
             if th <= th0 + 2.:
+                _tie(ties, "pbl3_300", p[k], 300.)      # the 300 hPa level itself ends the search
                 break
         k -= 1
     pbl = LIN(THETA(p[k + 1], t[k + 1]), p[k + 1], THETA(p[k], t[k]), p[k], th0 + 2.)
@@ -241,7 +311,7 @@ def pbl3_column(p, t, ps, ts, pbl_min, pbl_max, m):
 
 def pbl2_column(p, t, h2o, u, v, z, ps, ts, zs, us, vs, pbl_min, pbl_max, m):
     n = len(p)
-    pb = ps * math.exp(-0.05 / 7.)
+    pb = ps * _exp(-0.05 / 7.)
     k = 1
     while k < n - 1:
         m.see(p[k], pb)
@@ -256,7 +326,7 @@ def pbl2_column(p, t, h2o, u, v, z, ps, ts, zs, us, vs, pbl_min, pbl_max, m):
         du, dv = u[k] - us, v[k] - vs
         vh2 = fmax(du * du + dv * dv, 25.)
         m.see(du * du + dv * dv, 25.)
-        rib = G0 * 1e3 * (z[k] - zs) / tvs * (TVIRT(THETA(p[k], t[k]), h2o[k]) - tvs) / vh2
+        rib = _div(_div(G0 * 1e3 * (z[k] - zs), tvs) * (TVIRT(THETA(p[k], t[k]), h2o[k]) - tvs), vh2)
         m.see(rib, 0.25)
         if rib >= 0.25:
             cand = LIN(rib_old, p[k - 1], rib, p[k], 0.25)
@@ -268,13 +338,17 @@ def pbl2_column(p, t, h2o, u, v, z, ps, ts, zs, us, vs, pbl_min, pbl_max, m):
     return pbl_clamp(ps, pbl, False, pbl_min, pbl_max, m)
 
 
-def cape_column(p, t, h2o, ps, ptropo, m):
-    """(plcl, plfc, pel, cape, cin, ladder steps of plfc and pel)"""
+def cape_column(p, t, h2o, ps, ptropo, m, ties=None):
+    """(plcl, plfc, pel, cape, cin).  An infinite ps is taken as NaN."""
     n = len(p)
+    if math.isinf(ps):
+        ps = NAN
     pbot = fmin(ps, p[0])
     th = h = 0.
     cnt = 0
     for k in range(n):
+        _tie(ties, "cape_pbot", p[k], pbot)
+        _tie(ties, "cape_50", p[k], pbot - 50.)
         if pbot >= p[k] >= pbot - 50.:
             th += THETA(p[k], t[k])
             h += h2o[k]
@@ -292,10 +366,12 @@ def cape_column(p, t, h2o, ps, ptropo, m):
         return plcl, plfc, pel, cape, cin
     ptop = P(20.)
     pbot = ps
-    while True:
+    for passes in range(CAP + 1):
+        if passes == CAP:
+            raise RuntimeError("the bisection of the lifted condensation level does not end")
         plcl = 0.5 * (pbot + ptop)
-        tp = th / math.pow(1000. / plcl, KAPPA)
-        rh = 100. * PW(plcl, h) / PSAT(tp)
+        tp = _div(th, _pow(_div(1000., plcl), KAPPA))
+        rh = _div(100. * PW(plcl, h), PSAT(tp))
         m.see(rh, 100.)
         if rh > 100.:
             ptop = plcl
@@ -307,15 +383,18 @@ def cape_column(p, t, h2o, ps, ptropo, m):
     dz0 = RI / MA / G0 * math.log(PFAC)
     cape = cin = 0.
     pp = ps
+    TV = TVIRT
 
     def buoyancy(tp, hp, q, dz):
         te, he = env(p, t, q, m), env(p, h2o, q, m)
         m.see(TVIRT(tp, hp), TVIRT(te, he))       # the sign of d
-        return 1e3 * G0 * (TVIRT(tp, hp) - TVIRT(te, he)) / TVIRT(te, he) * dz
-    while True:
+        return _div(1e3 * G0 * (TV(tp, hp) - TV(te, he)), TV(te, he)) * dz
+    for passes in range(CAP + 1):
+        if passes == CAP:
+            raise RuntimeError("the dry ascent does not end")
         dz = dz0 * TVIRT(tp, h)
         pp /= PFAC
-        tp = th / math.pow(1000. / pp, KAPPA)
+        tp = _div(th, _pow(_div(1000., pp), KAPPA))
         d = buoyancy(tp, h, pp, dz)
         if d < 0:
             cin += abs(d)
@@ -324,14 +403,16 @@ def cape_column(p, t, h2o, ps, ptropo, m):
             break
     d = 0.
     pp = plcl
-    tp = th / math.pow(1000. / pp, KAPPA)
+    tp = _div(th, _pow(_div(1000., pp), KAPPA))
     ptop = 0.75 * ptropo
-    while True:
+    for passes in range(CAP + 1):
+        if passes == CAP:
+            raise RuntimeError("the moist ascent does not end")
         dz = dz0 * TVIRT(tp, h)
         pp /= PFAC
         tp -= lapse_rate(tp, h) * dz
         e = PSAT(tp)
-        h = e / (pp - (1. - EPS) * e)
+        h = _div(e, pp - (1. - EPS) * e)
         d_old = d
         d = buoyancy(tp, h, pp, dz)
         if d > 0:
@@ -357,10 +438,10 @@ def _f64(met, name, three=True):
     return src[name].astype(np.float64).tolist() if name in src else None
 
 
-@functools.lru_cache(maxsize=None)
-def _columns(key):
-    """Everything but the smoothing and PBL 2 of the snapshot atmosphere(*key): {name: float32 [nx][ny]}, z raw, margins."""
-    met = atmosphere(*key)
+def columns_of(met, met_pbl_min=DEFAULTS["met_pbl_min"], met_pbl_max=DEFAULTS["met_pbl_max"],
+               met_cloud_min=DEFAULTS["met_cloud_min"], lat=None, ties=None):
+    """Everything but the smoothing and PBL 2 of a snapshot: {name: float32 [nx][ny]}, z raw, margins.  `lat`: the latitude
+    of the climatological tropopause in every column (met_utm_ref_lat on a Cartesian grid) instead of the row's."""
     clim = load_clim_tropo()
     p = met.p.tolist()
     nx, ny, n = met.nx, met.ny, met.np
@@ -371,28 +452,28 @@ def _columns(key):
     out["pbl3"] = np.empty((nx, ny), dtype=np.float32)
     out["z"] = np.empty((nx, ny, n), dtype=np.float32)
     margin = np.empty((nx, ny))
-    for ix in range(nx):
-        for iy in range(ny):
-            m = Margin()
-            t, h2o, ps = f["t"][ix][iy], f["h2o"][ix][iy], g["ps"][ix][iy]
-            out["z"][ix, iy] = geopot_column(p, t, h2o, ps, g["zs"][ix][iy])
-            out["o3c"][ix, iy] = o3c_column(p, f["o3"][ix][iy], ps)
-            out["pct"][ix, iy], out["pcb"][ix, iy], out["cl"][ix, iy] = cloud_column(
-                p, f["lwc"][ix][iy], f["rwc"][ix][iy] if f["rwc"] else zero, f["iwc"][ix][iy],
-                f["swc"][ix][iy] if f["swc"] else zero, ps, DEFAULTS["met_cloud_min"])
-            out["pbl3"][ix, iy] = pbl3_column(p, t, ps, g["ts"][ix][iy], DEFAULTS["met_pbl_min"], DEFAULTS["met_pbl_max"], m)
-            five = cape_column(p, t, h2o, ps, clim_tropo(clim, met.time, met.lat[iy]), m)
-            for name, val in zip(("plcl", "plfc", "pel", "cape", "cin"), five):
-                out[name][ix, iy] = val
-            margin[ix, iy] = m.value
+    with np.errstate(over="ignore", invalid="ignore"):
+        for ix in range(nx):
+            for iy in range(ny):
+                m = Margin()
+                t, h2o, ps = f["t"][ix][iy], f["h2o"][ix][iy], g["ps"][ix][iy]
+                out["z"][ix, iy] = geopot_column(p, t, h2o, ps, g["zs"][ix][iy], ties)
+                out["o3c"][ix, iy] = o3c_column(p, f["o3"][ix][iy], ps, ties)
+                out["pct"][ix, iy], out["pcb"][ix, iy], out["cl"][ix, iy] = cloud_column(
+                    p, f["lwc"][ix][iy], f["rwc"][ix][iy] if f["rwc"] else zero, f["iwc"][ix][iy],
+                    f["swc"][ix][iy] if f["swc"] else zero, ps, met_cloud_min, ties)
+                out["pbl3"][ix, iy] = pbl3_column(p, t, ps, g["ts"][ix][iy], met_pbl_min, met_pbl_max, m, ties)
+                five = cape_column(p, t, h2o, ps, clim_tropo(clim, met.time, met.lat[iy] if lat is None else lat), m, ties)
+                for name, val in zip(("plcl", "plfc", "pel", "cape", "cin"), five):
+                    out[name][ix, iy] = val
+                margin[ix, iy] = m.value
     return out, margin
 
 
-@functools.lru_cache(maxsize=None)
-def reference(key, met_pbl=3, sx=-1, sy=-1):
-    """({name: float32 array} of all eleven outputs, margin [nx][ny]) for the snapshot atmosphere(*key)."""
-    cols, margin = _columns(key)
-    met = atmosphere(*key)
+def reference_of(met, met_pbl=3, sx=-1, sy=-1, met_pbl_min=DEFAULTS["met_pbl_min"], met_pbl_max=DEFAULTS["met_pbl_max"],
+                 met_cloud_min=DEFAULTS["met_cloud_min"], lat=None, ties=None, cols=None):
+    """({name: float32 array} of all eleven outputs, margin [nx][ny]) of a snapshot; `cols`: columns_of, if at hand."""
+    cols, margin = cols or columns_of(met, met_pbl_min, met_pbl_max, met_cloud_min, lat, ties)
     out = {k: v for k, v in cols.items() if k not in ("pbl3", "z")}
     out["z"] = smooth(cols["z"], met.lon, sx, sy)
     if met_pbl == 3:
@@ -404,14 +485,29 @@ def reference(key, met_pbl=3, sx=-1, sy=-1):
     g = {k: _f64(met, k, False) for k in ("ps", "ts", "zs", "us", "vs")}
     z = out["z"].astype(np.float64).tolist()
     out["pbl"] = np.empty((met.nx, met.ny), dtype=np.float32)
-    for ix in range(met.nx):
-        for iy in range(met.ny):
-            m = Margin()
-            out["pbl"][ix, iy] = pbl2_column(p, f["t"][ix][iy], f["h2o"][ix][iy], f["u"][ix][iy], f["v"][ix][iy], z[ix][iy],
-                                             g["ps"][ix][iy], g["ts"][ix][iy], g["zs"][ix][iy], g["us"][ix][iy], g["vs"][ix][iy],
-                                             DEFAULTS["met_pbl_min"], DEFAULTS["met_pbl_max"], m)
-            margin[ix, iy] = min(margin[ix, iy], m.value)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for ix in range(met.nx):
+            for iy in range(met.ny):
+                m = Margin()
+                out["pbl"][ix, iy] = pbl2_column(p, f["t"][ix][iy], f["h2o"][ix][iy], f["u"][ix][iy], f["v"][ix][iy], z[ix][iy],
+                                                 g["ps"][ix][iy], g["ts"][ix][iy], g["zs"][ix][iy], g["us"][ix][iy],
+                                                 g["vs"][ix][iy], met_pbl_min, met_pbl_max, m)
+                margin[ix, iy] = min(margin[ix, iy], m.value)
     return out, margin
+
+
+@functools.lru_cache(maxsize=None)
+def _columns(key, met_pbl_min=DEFAULTS["met_pbl_min"], met_pbl_max=DEFAULTS["met_pbl_max"],
+             met_cloud_min=DEFAULTS["met_cloud_min"], lat=None):
+    return columns_of(atmosphere(*key), met_pbl_min, met_pbl_max, met_cloud_min, lat)
+
+
+@functools.lru_cache(maxsize=None)
+def reference(key, met_pbl=3, sx=-1, sy=-1, met_pbl_min=DEFAULTS["met_pbl_min"], met_pbl_max=DEFAULTS["met_pbl_max"],
+              met_cloud_min=DEFAULTS["met_cloud_min"], lat=None):
+    """reference_of for the snapshot atmosphere(*key); the columns are computed once per set of options."""
+    return reference_of(atmosphere(*key), met_pbl, sx, sy, met_pbl_min, met_pbl_max, met_cloud_min, lat,
+                        cols=_columns(key, met_pbl_min, met_pbl_max, met_cloud_min, lat))
 
 
 # ---- the input --------------------------------------------------------------------------------------------------------------

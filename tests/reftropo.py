@@ -104,8 +104,9 @@ def spline_coeffs(zc, y):
     return c
 
 
-def spline(zc, y, x2, method=1):
-    """The profile y on the ascending axis zc at the ascending points x2 (the definition's spline(y)[i])."""
+def spline(zc, y, x2, method=1, ties=None):
+    """The profile y on the ascending axis zc at the ascending points x2 (the definition's spline(y)[i]).  `ties` (a
+    refmetprep.Ties) counts the points that took the value of an end node: "spline_low", "spline_high"."""
     n = len(zc)
     c = spline_coeffs(zc, y) if method == 1 else None
     out = []
@@ -113,9 +114,13 @@ def spline(zc, y, x2, method=1):
     for x in x2:
         if x <= zc[0]:
             out.append(y[0])
+            if ties is not None:
+                ties.count["spline_low"] += 1
             continue
         if x >= zc[n - 1]:
             out.append(y[n - 1])
+            if ties is not None:
+                ties.count["spline_high"] += 1
             continue
         while k < n - 2 and zc[k + 1] <= x:      # (k only grows: x2 ascends)
             k += 1
@@ -161,21 +166,28 @@ def _inside(iz):
     return P2[iz] if iz is not None and 0 < iz < TOP else NAN
 
 
-def tropo_pt(mode, method, zc, p, t, pv, m, pv_thr=3.5, theta_thr=380., pclim=NAN):
+def tropo_pt(mode, method, zc, p, t, pv, m, pv_thr=3.5, theta_thr=380., pclim=NAN, ties=None):
     """pt of one column (t, pv: lists of doubles)."""
     if mode == 1:
         return pclim
     if mode == 2:
-        t2 = spline(zc, t, Z2[:TOP + 1], method)
+        t2 = spline(zc, t, Z2[:TOP + 1], method, ties)
         if any(x != x for x in t2):
             return NAN
         iz = t2.index(min(t2))
+
+        def end(i):          # the value is an end node's, copied: an input, the same number in any arithmetic
+            return Z2[i] <= zc[0] or Z2[i] >= zc[-1]
         for i, x in enumerate(t2):
             if i != iz:
+                if end(i) and end(iz) and x == t2[iz]:
+                    if ties is not None:
+                        ties.count["coldpoint_end"] += 1
+                    continue
                 m.see(x, t2[iz])
         return _inside(iz)
     if mode in (3, 4):
-        t2 = spline(zc, t, Z2, method)
+        t2 = spline(zc, t, Z2, method, ties)
         if any(x != x for x in t2):
             return NAN
         iz = _first(0, lambda i: _B(t2, i, m))
@@ -185,8 +197,8 @@ def tropo_pt(mode, method, zc, p, t, pv, m, pv_thr=3.5, theta_thr=380., pclim=NA
                 iz = _first(iz, lambda i: _B(t2, i, m))
         return _inside(iz)
     if mode == 5:
-        pv2 = spline(zc, pv, Z2[:TOP + 1], method)
-        th2 = spline(zc, [THETA(p[k], t[k]) for k in range(len(p))], Z2[:TOP + 1], method)
+        pv2 = spline(zc, pv, Z2[:TOP + 1], method, ties)
+        th2 = spline(zc, [THETA(p[k], t[k]) for k in range(len(p))], Z2[:TOP + 1], method, ties)
         if any(x != x for x in pv2 + th2):
             return NAN
 
@@ -257,26 +269,22 @@ def pv_reference(key, second=False):
     return pv, S
 
 
-@functools.lru_cache(maxsize=None)
-def tropo_reference(key, mode, method=1, second=False, pv_thr=3.5, theta_thr=380.):
-    """({pt, tt, zt, h2ot: float32 [nx][ny]}, margin [nx][ny]) with z = z_field and pv = pv_reference (both as floats)."""
-    if mode in (2, 3, 4) and len(key) > 4 and key[4]:
-        # nothing these modes read depends on the latitudes: the columns of the ascending snapshot
-        return tropo_reference(key[:4] + (False,) + key[5:], mode, method, second, pv_thr, theta_thr)
-    met = snapshot(key, second)
+def tropo_of(met, z, pv, mode, method=1, pv_thr=3.5, theta_thr=380., lat=None, ties=None):
+    """({pt, tt, zt, h2ot: float32 [nx][ny]}, margin [nx][ny]) of a snapshot with the float fields z and (met_tropo 5) pv.
+    `lat`: the latitude of the climatological tropopause (met_utm_ref_lat on a Cartesian grid) instead of the row's."""
     p = met.p.tolist()
     zc = [Z(x) for x in p]
     t, h2o = R._f64(met, "t"), R._f64(met, "h2o")
-    z = z_field(key, second).astype(np.float64).tolist()
-    pv = pv_reference(key, second)[0].astype(np.float64).tolist() if mode == 5 else None
+    z = np.asarray(z, dtype=np.float64).tolist()
+    pv = np.asarray(pv, dtype=np.float64).tolist() if mode == 5 else None
     clim = R.load_clim_tropo() if mode == 1 else None
     out = {k: np.empty((met.nx, met.ny), dtype=np.float32) for k in TROPO_OUTPUTS}
     margin = np.empty((met.nx, met.ny))
     for ix in range(met.nx):
         for iy in range(met.ny):
             m = Margin()
-            pclim = clim_tropo(clim, met.time, met.lat[iy]) if mode == 1 else NAN
-            pt = tropo_pt(mode, method, zc, p, t[ix][iy], pv[ix][iy] if pv else None, m, pv_thr, theta_thr, pclim)
+            pclim = clim_tropo(clim, met.time, met.lat[iy] if lat is None else lat) if mode == 1 else NAN
+            pt = tropo_pt(mode, method, zc, p, t[ix][iy], pv[ix][iy] if pv else None, m, pv_thr, theta_thr, pclim, ties)
             if pt == pt:
                 vals = (pt, env(p, t[ix][iy], pt, m), env(p, z[ix][iy], pt, m), env(p, h2o[ix][iy], pt, m))
             else:
@@ -285,3 +293,13 @@ def tropo_reference(key, mode, method=1, second=False, pv_thr=3.5, theta_thr=380
                 out[name][ix, iy] = val
             margin[ix, iy] = m.value
     return out, margin
+
+
+@functools.lru_cache(maxsize=None)
+def tropo_reference(key, mode, method=1, second=False, pv_thr=3.5, theta_thr=380.):
+    """tropo_of with z = z_field and pv = pv_reference (both as floats)."""
+    if mode in (2, 3, 4) and len(key) > 4 and key[4]:
+        # nothing these modes read depends on the latitudes: the columns of the ascending snapshot
+        return tropo_reference(key[:4] + (False,) + key[5:], mode, method, second, pv_thr, theta_thr)
+    return tropo_of(snapshot(key, second), z_field(key, second), pv_reference(key, second)[0] if mode == 5 else None, mode,
+                    method, pv_thr, theta_thr)
