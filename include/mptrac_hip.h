@@ -668,6 +668,17 @@ int mphip_comm_query(mphip_ctx *ctx, int *nranks, int *rank);
 int mphip_set_option(mphip_ctx *ctx, const char *name, double value);
 int mphip_synchronize(mphip_ctx *ctx);
 
+/* The bounds of the four early exits as the next launch would use them, from the two uploaded snapshots and the control
+ * parameters: bounds[0] ps_skip (module_dry_depo returns for p < ps_skip - DRY_DEPO_DP), [1] pct_skip (module_wet_depo
+ * for p <= pct_skip), [2] turb_skip (module_diff_turb: no boundary layer for 1.01 p < turb_skip), [3] conv_skip
+ * (module_convection for p < conv_skip); each only for a particle time between the snapshots.  -inf: that exit is never
+ * taken -- a field value that is not finite, no control parameters yet, or a grid on which the reference's horizontal
+ * weights can leave [0, 1]: a longitude / latitude grid whose longitude axis spans less than 360 degrees or starts
+ * outside [-360, 0] (intpol_check_lon_lat shifts a longitude by one period and never clamps it, so beyond such an axis
+ * the interpolation extrapolates below every node value).  A longitude axis that passes for periodic (|span - 360| <
+ * 0.01) and still spans less than 360 loses the exits too; mphip_update_met says so once on stderr. */
+int mphip_get_shortcuts(mphip_ctx *ctx, double bounds[4]);
+
 /* Timing of the fused step kernel with HIP events on the context's stream:
  * between begin and end every launch is bracketed; end returns the launch
  * count and the summed device time. */

@@ -192,6 +192,7 @@ struct mphip_ctx {
   bool emit_keys = true;              // option "emit_keys": the launch that moves the particles writes the keys of the sort ahead
   unsigned char *d_depo_busy = nullptr;   // EmitKeys::depo_busy (np bytes) ...
   long long depo_busy_cap = 0;
+  bool told_shortcuts_off = false;    // mphip_update_met's note about a nearly periodic longitude axis was printed
   bool depo_busy_valid = false;       // ... written by the last launch and not yet used by the deposition launch of its step
   bool sort_repair = true;            // option "sort_repair"
   bool ahead_priority = false;        // option "ahead_priority": the stream of the sort ahead at the highest priority (C5: no difference, profiles/r05_variants.txt item 3)
@@ -371,6 +372,13 @@ DevAtm dev_atm(const mphip_ctx *c) {
   return a;
 }
 
+// Can the reference's horizontal weights leave [0, 1] on this grid?  Not on a Cartesian grid (both coordinates are
+// clamped), and not on a longitude axis that spans the circle and starts in [-360, 0]: one shift by 360 degrees
+// (intpol_check_lon_lat) then always lands inside.  A span below 360 by any amount leaves a gap.
+static bool weights_stay_inside(int coord_type, double first, double last) {
+  return coord_type != 0 || (last - first >= 360.0 && first <= 0.0 && first >= -360.0);
+}
+
 DevMet dev_met(const mphip_ctx *c) {
   DevMet M;
   M.wind = c->pk.wind;
@@ -459,6 +467,14 @@ DevMet dev_met(const mphip_ctx *c) {
         M.conv_skip = lo - 1e-6 * std::fabs(lo) - 1e-6;
     }
   }
+  // All four bounds rest on "an interpolated value is not below the smallest node value", which needs horizontal
+  // weights inside [0, 1].  The latitude is always clamped and so is the longitude of a Cartesian grid, but
+  // intpol_check_lon_lat only shifts a longitude by 360 degrees: on an axis that does not span the circle (a regional
+  // grid, or a first longitude above 0 or below -360) the shifted value can lie outside the axis, locate_reg clamps
+  // the index, and the interpolation continues the end cell's slope -- below every node value.  A particle that left
+  // such a domain within the step still has its dt.  No shortcut there (tests/depo_cases.py: extrap-regional-*).
+  if (!weights_stay_inside(c->coord_type, c->h_lon[0], c->h_lon[c->nx - 1]))
+    M.ps_skip = M.pct_skip = M.turb_skip = M.conv_skip = -HUGE_VAL;
   M.meso_dt = std::fabs(c->ctl.dt_mod);
   M.meso_r = 1 - 2 * M.meso_dt / c->ctl.dt_met;
   M.meso_r2 = std::sqrt(1 - M.meso_r * M.meso_r);
@@ -3239,6 +3255,14 @@ int mphip_update_met(mphip_ctx *ctx, int slot, const mphip_met_t *met) {
     ctx->h_p = S.p;
     if (upload_axes(ctx))
       return 1;
+    // an axis that passes for periodic and still leaves a gap: the early exits are off (dev_met), which costs time only
+    const double first = ctx->h_lon[0], last = ctx->h_lon[ctx->nx - 1];
+    if (!ctx->told_shortcuts_off && std::fabs(last - first - 360.0) < 0.01
+        && !weights_stay_inside(ctx->coord_type, first, last)) {
+      ctx->told_shortcuts_off = true;
+      fprintf(stderr, "mptrac_hip: longitude axis %.17g ... %.17g does not span 360 degrees from a start in [-360, 0]: "
+              "the early exits of deposition, convection and turbulent diffusion are off (mphip_get_shortcuts)\n", first, last);
+    }
   }
   if (upload_fields(ctx, S, met, new_grid, ctx->stream))
     return 1;
@@ -5096,6 +5120,19 @@ int mphip_set_option(mphip_ctx *ctx, const char *name, double value) {
     return 0;
   }
   return fail(ctx, std::string("unknown option ") + name);
+}
+
+int mphip_get_shortcuts(mphip_ctx *ctx, double bounds[4]) {
+  if (!ctx || !bounds)
+    return fail(ctx, "null argument");
+  if (!ctx->slot[0].valid || !ctx->slot[1].valid)
+    return fail(ctx, "mphip_get_shortcuts: needs both meteo snapshots");
+  const DevMet M = dev_met(ctx);
+  bounds[0] = M.ps_skip;
+  bounds[1] = M.pct_skip;
+  bounds[2] = M.turb_skip;
+  bounds[3] = M.conv_skip;
+  return 0;
 }
 
 int mphip_synchronize(mphip_ctx *ctx) {

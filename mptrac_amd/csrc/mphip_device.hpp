@@ -480,6 +480,16 @@ __device__ __forceinline__ double zfromp(double p) {   // mptrac.h:2243
   return kH0 * libm_log(kP0 / p);
 }
 
+// Z(pa) - Z(pb), both products rounded before the difference.  Contracted into a fused multiply-add the difference of
+// two EQUAL heights is the rounding residue of one product, of either sign, where the reference has exactly 0: the depth
+// of the cloud for pct == pcb and of the surface layer for DRY_DEPO_DP 0, which the deposition modules divide by -- a
+// rate of +inf and a factor exp(-inf) = 0 there, a finite rate or a factor of +inf here (tests/depo_cases.py).
+__device__ __forceinline__ double zdiff(double pa, double pb) {
+#pragma clang fp contract(off)
+  const double za = kH0 * libm_log(kP0 / pa), zb = kH0 * libm_log(kP0 / pb);
+  return za - zb;
+}
+
 __device__ __forceinline__ double lin(double x0, double y0, double x1, double y1, double x) {   // mptrac.h:1351
   return y0 + fdiv(y1 - y0, x1 - x0) * (x - x0);
 }

@@ -320,7 +320,7 @@ __device__ __forceinline__ void wet_depo(const mphip_ctl_t &ctl, const DevMet &M
         const double K_2 = kSO2K2Ref * libm_exp(kSO2K2Temp * (1. / t - 1. / kTRef));
         h *= (1. + K_1 / H_ion + K_1 * K_2 / (H_ion * H_ion));
       }
-      const double dz = 1e3 * (zfromp(pct) - zfromp(pcb));
+      const double dz = 1e3 * zdiff(pct, pcb);
       lambda = h * kRI * t * Is / 3.6e6 / dz * eta;
     }
   } else {
@@ -329,7 +329,7 @@ __device__ __forceinline__ void wet_depo(const mphip_ctl_t &ctl, const DevMet &M
       lambda = ctl.wet_depo_bc_a * libm_pow(Is, ctl.wet_depo_bc_b) * eta;
     else if (ctl.wet_depo_bc_h[0] > 0) {
       const double h = ctl.wet_depo_bc_h[0] * libm_exp(ctl.wet_depo_bc_h[1] * (1. / t - 1. / kTRef));
-      const double dz = 1e3 * (zfromp(pct) - zfromp(pcb));
+      const double dz = 1e3 * zdiff(pct, pcb);
       lambda = h * kRI * t * Is / 3.6e6 / dz * eta;
     }
   }
@@ -349,7 +349,7 @@ __device__ __forceinline__ void dry_depo(const mphip_ctl_t &ctl, const DevMet &M
   const double ps = sfa_time_2d(c2, s, time_weight(M, P.time), 0);
   if (P.p < ps - ctl.dry_depo_dp)
     return;
-  const double dz = 1000. * (zfromp(ps - ctl.dry_depo_dp) - zfromp(ps));
+  const double dz = 1000. * zdiff(ps - ctl.dry_depo_dp, ps);
   double v_dep;
   if (ctl.qnt_rp > 0 && ctl.qnt_rhop > 0) {   // "> 0" as the reference, mptrac.c:4769
     const double t = temperature_at(M, A, P.time, P.p, P.lon, P.lat);
@@ -398,7 +398,7 @@ __device__ __forceinline__ void depo_pair_factor(const mphip_ctl_t &ctl, const D
     const double ps = pair_time_2d_fast(c1, s, wt, 0);
     dry_go = !(P.p < ps - ctl.dry_depo_dp);
     if (dry_go)
-      dz_dry = 1000. * (zfromp(ps - ctl.dry_depo_dp) - zfromp(ps));
+      dz_dry = 1000. * zdiff(ps - ctl.dry_depo_dp, ps);
   }
   if (!(wet_go | dry_go))
     return;
@@ -436,7 +436,7 @@ __device__ __forceinline__ void depo_pair_factor(const mphip_ctl_t &ctl, const D
           const double K_2 = kSO2K2Ref * libm_exp(kSO2K2Temp * (1. / t - 1. / kTRef));
           h *= (1. + K_1 / H_ion + K_1 * K_2 / (H_ion * H_ion));
         }
-        const double dz = 1e3 * (zfromp(pct) - zfromp(pcb));
+        const double dz = 1e3 * zdiff(pct, pcb);
         lambda = h * kRI * t * Is / 3.6e6 / dz * eta;
       }
     } else {
@@ -445,7 +445,7 @@ __device__ __forceinline__ void depo_pair_factor(const mphip_ctl_t &ctl, const D
         lambda = ctl.wet_depo_bc_a * libm_pow(Is, ctl.wet_depo_bc_b) * eta;
       else if (ctl.wet_depo_bc_h[0] > 0) {
         const double h = ctl.wet_depo_bc_h[0] * libm_exp(ctl.wet_depo_bc_h[1] * (1. / t - 1. / kTRef));
-        const double dz = 1e3 * (zfromp(pct) - zfromp(pcb));
+        const double dz = 1e3 * zdiff(pct, pcb);
         lambda = h * kRI * t * Is / 3.6e6 / dz * eta;
       }
     }

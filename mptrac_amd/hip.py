@@ -150,6 +150,7 @@ def load(build=True):
     if hasattr(L, "mphip_set_radio_depo"):      # (absent from libraries built before module_radio_depo: A/B runs through MPHIP_LIB)
         L.mphip_set_radio_depo.argtypes = [C.c_void_p, C.c_int, C.POINTER(MphipBox)]
         L.mphip_get_radio_depo.argtypes = [C.c_void_p, _dp, _dp, _dp]
+        L.mphip_get_shortcuts.argtypes = [C.c_void_p, _dp]
     L.mphip_set_allreduce.argtypes = [C.c_void_p, ALLREDUCE_FN, C.c_void_p]
     L.mphip_comm_unique_id.argtypes = [C.c_void_p]
     L.mphip_comm_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -609,6 +610,12 @@ class Simulation:
         t_inv = C.c_double(0.0)
         self._chk(self.L.mphip_get_radio_depo(self.h, C.byref(t_inv), _ptr(wet, _dp), _ptr(dry, _dp)))
         return t_inv.value, wet, dry
+
+    def shortcuts(self):
+        """{"ps", "pct", "turb", "conv"}: the bounds of the four early exits (mphip_get_shortcuts); -inf = never taken"""
+        b = (C.c_double * 4)()
+        self._chk(self.L.mphip_get_shortcuts(self.h, b))
+        return dict(zip(("ps", "pct", "turb", "conv"), (float(v) for v in b)))
 
     def synchronize(self):
         self._chk(self.L.mphip_synchronize(self.h))

@@ -188,11 +188,17 @@ class Weights:
     """ci / cw of INTPOL_INIT: what an interpolation call with init = 1 leaves behind"""
 
     def __init__(self, met, p, lon, lat, three_d=True):
-        # intpol_check_lon_lat, mptrac.c:2755-2778 (latitude / longitude grids only here)
-        lon2 = FMOD(lon, 360.0)
-        lon2 = np.where(lon2 < met.lon[0], lon2 + 360.0, np.where(lon2 > met.lon[-1], lon2 - 360.0, lon2))
         lo, hi = (met.lat[0], met.lat[-1]) if met.lat[0] < met.lat[-1] else (met.lat[-1], met.lat[0])
         lat2 = np.minimum(np.maximum(lat, lo), hi)
+        if met.coord_type == 0:
+            # intpol_check_lon_lat, mptrac.c:2755-2778: the longitude is shifted by one period, never clamped -- on an
+            # axis that does not span 360 degrees it can stay outside, and the weight wx then leaves [0, 1]
+            lon2 = FMOD(lon, 360.0)
+            lon2 = np.where(lon2 < met.lon[0], lon2 + 360.0, np.where(lon2 > met.lon[-1], lon2 - 360.0, lon2))
+        else:
+            # intpol_check_cartesian, mptrac.c:2782-2803: both coordinates clamped to the axes
+            xlo, xhi = (met.lon[0], met.lon[-1]) if met.lon[0] < met.lon[-1] else (met.lon[-1], met.lon[0])
+            lon2 = np.minimum(np.maximum(lon, xlo), xhi)
         self.ix = locate_reg(met.lon, lon2)
         self.iy = locate_irr(met.lat, lat2)
         self.wx = (met.lon[self.ix + 1] - lon2) / (met.lon[self.ix + 1] - met.lon[self.ix])
@@ -627,11 +633,18 @@ class Ref:
                 if c.conv_cin > 0:
                     deep &= np.isfinite(cin) & (cin >= c.conv_cin)
                 ptop = np.where(deep, np.minimum(ptop, pel), ptop)
-        act = (ptop != pbot) & (p >= ptop)
+        with np.errstate(invalid="ignore"):
+            act = (ptop != pbot) & (p >= ptop)
+        self.diag = dict(ps=ps, ptop=ptop, act=act, w=w2)
+        if c.conv_mix_pbl:
+            self.diag["pbl"] = pbl
+        if c.conv_cape >= 0:
+            self.diag.update(cape=cape, cin=cin, pel=pel, deep=deep)
         tbot = self.time_3d("t", time, pbot, lon, lat)
         ttop = self.time_3d("t", time, ptop, lon, lat)
-        rhobot, rhotop = pbot / tbot, ptop / ttop
-        rho = rhobot + (rhotop - rhobot) * rs
+        with np.errstate(all="ignore"):
+            rhobot, rhotop = pbot / tbot, ptop / ttop
+            rho = rhobot + (rhotop - rhobot) * rs
         with np.errstate(all="ignore"):
             mixed = LIN(rhobot, pbot, rhotop, ptop, rho)
         return np.where(act, mixed, p)
@@ -731,21 +744,27 @@ class Ref:
                 lam_bc = h * RI * t * Is / 3.6e6 / dzc * eta_bc
             lam = np.where(inside, lam_ic, lam_bc)
             aux = np.exp(-dt * lam)
+        self.diag = dict(pct=pct, pcb=pcb, cl=cl, Is=Is, inside=inside, t=t, lwc=lwc, rwc=rwc, iwc=iwc, swc=swc, dzc=dzc,
+                         act=act, lam=lam, w=w2)
         return act, aux, lam
 
     # -- module_dry_depo (mptrac.c:4738-4797): returns (acts, aux, rate) ---------------------------------------------
     def dry_depo(self, time, lon, lat, p, dt, rp=None, rhop=None):
         c = self.c
-        ps = self.time_2d("ps", time, lon, lat)
-        act = ~(p < ps - c.dry_depo_dp)
-        dz = 1000.0 * (Z(ps - c.dry_depo_dp) - Z(ps))
-        if c.qnt_rp > 0 and c.qnt_rhop > 0:                 # "> 0" as the reference writes it
-            t = self.time_3d("t", time, p, lon, lat)
-            v_dep = self.sedi(p, t, rp, rhop)
-        else:
-            v_dep = np.full_like(p, c.dry_depo_vdep)
-        aux = np.exp(-dt * v_dep / dz)
-        return act, aux, v_dep / dz
+        w2 = Weights(self.m0, None, lon, lat, three_d=False)
+        ps = self.time_2d("ps", time, lon, lat, w2)
+        with np.errstate(all="ignore"):
+            act = ~(p < ps - c.dry_depo_dp)
+            dz = 1000.0 * (Z(ps - c.dry_depo_dp) - Z(ps))
+            if c.qnt_rp > 0 and c.qnt_rhop > 0:                 # "> 0" as the reference writes it
+                t = self.time_3d("t", time, p, lon, lat)
+                v_dep = self.sedi(p, t, rp, rhop)
+            else:
+                v_dep = np.full_like(p, c.dry_depo_vdep)
+            aux = np.exp(-dt * v_dep / dz)
+            rate = v_dep / dz
+        self.diag = dict(ps=ps, dz=dz, act=act, w=w2)
+        return act, aux, rate
 
     def apply_loss(self, q, act, aux, rate, which):
         """the bookkeeping both deposition modules share (mptrac.c:6276-6287, 4784-4794); q: dict name -> array"""
