@@ -400,7 +400,7 @@ int mphip_discard_prefetch(mphip_ctx *ctx);
  * clamp is the last).  A NaN in t[k] makes z NaN on the levels from k away from the surface (on all levels if the surface's
  * LIN reads it); an infinite h2o makes z NaN on every level; a NaN zs makes z NaN on every level; a NaN ts makes PBL 3's pbl
  * pmin (it is not finite) and keeps PBL 2's criterion false, which is pmin as well.
- *   Out of scope: MET_PBL 1, detrending, down-sampling, model-to-pressure-level regridding. */
+ *   Out of scope: MET_PBL 1, detrending.  (Down-sampling and model-to-pressure-level regridding: mphip_regrid_met.) */
 enum { MPHIP_PREP_GEOPOT = 1, MPHIP_PREP_O3C = 2, MPHIP_PREP_PBL = 4, MPHIP_PREP_CLOUD = 8, MPHIP_PREP_CAPE = 16,
        MPHIP_PREP_PV = 32, MPHIP_PREP_TROPO = 64 };
 typedef struct {
@@ -420,6 +420,66 @@ typedef struct {
 } mphip_met_out_t;   /* same strides as `in` */
 int mphip_derive_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const mphip_prep_t *opt,
                      const mphip_met_out_t *out);
+
+/* The two grid-changing steps of the reference's meteo preprocessing, from one snapshot "as stored": model levels to
+ * pressure levels (MPHIP_REGRID_ML2PL, the reference's read_met_ml2pl) and smoothing with down-sampling
+ * (MPHIP_REGRID_SAMPLE, read_met_sample).  `in` is a host view as for mphip_derive_met; the shape changes, so `out` names
+ * its own strides (as mphip_met_t does: sy >= np2, sx a multiple of sy and >= ny2 sy, sx2 >= ny2) and the output axes.
+ * mphip_regrid_shape gives the output extents without a context, so that a caller can allocate; it returns non-zero
+ * where mphip_regrid_met would refuse the grid or the options.  The call keeps the contract of mphip_derive_met: the same
+ * stream and lock (calls are serialised with mphip_derive_met), scratch of its own that is kept between calls and freed by
+ * mphip_destroy, no meteo slot, no prefetch state and no particle touched, callable from a file-reader thread, and a
+ * refused call writes nothing.  Every input is uploaded before any output is written, so `out` may alias `in` (the host
+ * layer regrids its met_t in place).  Fields that are NULL in `in` or NULL in `out` are skipped, axes that are NULL in `out`
+ * likewise.  With both bits ML2PL runs first and SAMPLE works on its result on the device.  The model-level slots
+ * (MPHIP_PL, UL, VL, WL, ZETAL, ZETA_DOTL) are never written.
+ *
+ *   DEFINITIONS.  This project's own statement, as for mphip_derive_met (the reference's source was not available),
+ * restated independently in tests/refregrid.py.  Arithmetic in double from the float inputs unless "float" is written,
+ * products and quotients from left to right, each output value rounded to float once; LIN as above.
+ *   ML2PL.  Input: n = in->npl model levels, in->np == in->npl; in->f3[MPHIP_PL] the pressure [hPa] with the strides sx_ml,
+ * sy_ml; the fields are the non-NULL slots MPHIP_T, U, V, W, H2O, O3, LWC, RWC, IWC, SWC, CC with the strides sx, sy and n
+ * levels; in->p is not read.  Per column, pl[0 ... n-1], and per target level j, q = met_p[j]:  clamp -- if pl[0] > pl[1]:
+ * { if (q > pl[0]) q = pl[0]; else if (q < pl[n-1]) q = pl[n-1]; } else { if (q < pl[0]) q = pl[0]; else if (q > pl[n-1]) q =
+ * pl[n-1]; } --; k = locate_irr(pl, n, q): ilo = 0, ihi = n-1, i = (ihi+ilo)>>1; if (pl[i] < pl[i+1]) while (ihi > ilo+1) { i
+ * = (ihi+ilo)>>1; if (pl[i] > q) ihi = i; else ilo = i; } else while (ihi > ilo+1) { i = (ihi+ilo)>>1; if (pl[i] <= q) ihi =
+ * i; else ilo = i; }; k = ilo (on a strictly descending column the largest k <= n-2 with pl[k] > q, else 0); out[j] =
+ * LIN(pl[k], f[k], pl[k+1], f[k+1], q).  Nothing is refused for its values: equal neighbouring pressures, NaN and
+ * non-monotone columns give what IEEE arithmetic and the bisection as written give.  The 2-D fields, lon and lat pass
+ * through; out->p = met_p; np2 = met_np.
+ *   Refused: npl < 2 or np != npl; a missing MPHIP_PL; met_np < 2; a met_p that is not finite, positive and strictly
+ * descending; a level count whose staged columns do not fit 64 KB of LDS (8 met_np + 4 (npl | 1) bytes for one column).
+ *   SAMPLE.  Input: a pressure-level snapshot (nx, ny, np, axes lon, lat, p) or the result of ML2PL.  nx2 = (nx + met_dx -
+ * 1) / met_dx, ny2 and np2 likewise; output index i is input index i met_dx; lon, lat and p are sampled the same way.
+ * With sx, sy, sp = met_sx, met_sy, met_sp: for every kept point (ix, iy, ip) of every non-NULL 3-D pressure-level field
+ * (the eleven above, MPHIP_Z and MPHIP_PV): if sx = sy = sp = 1 the value is copied.  Otherwise float sums a = 0, ws = 0;
+ * for ix2 = ix-sx+1 ... ix+sx-1 (outer loop; ix3 = ix2 wrapped once by +-nx, on regional grids too), iy2 = max(iy-sy+1,0)
+ * ... min(iy+sy-1,ny-1) (middle loop), ip2 = max(ip-sp+1,0) ... min(ip+sp-1,np-1) (inner loop): float w = (1 -
+ * |ix-ix2|/sx) (1 - |iy-iy2|/sy) (1 - |ip-ip2|/sp), each factor formed in float (a float quotient, a float difference) and
+ * multiplied from left to right; a += w f[ix3][iy2][ip2] (the product rounded before the sum, never contracted); ws += w.
+ * The value is a / ws in float.  Every value enters: a NaN spreads (unlike the geopotential's smoothing).  Every non-NULL
+ * 2-D field gets the same with the two horizontal factors only (copied if sx = sy = 1).  Only the kept points are
+ * computed.  With all six options 1 the output is the input, bit for bit.
+ *   Refused: an option < 1; met_sx - 1 > nx; nx2 < 2, ny2 < 2 or np2 < 2; a tile with halo beyond 64 KB of LDS -- hx hy hk
+ * floats with hx = 7 min(met_dx, 2 sx - 1) + 2 sx - 1, hy = 7 min(met_dy, 2 sy - 1) + 2 sy - 1, hk = 15 min(met_dp, 2 sp -
+ * 1) + 2 sp - 1.
+ *   Both: refused as either; nx < 2, ny < 2, strides that do not hold the extents, a missing axis (lon, lat; p for SAMPLE
+ * alone), `what` other than an OR of the two bits. */
+enum { MPHIP_REGRID_ML2PL = 1, MPHIP_REGRID_SAMPLE = 2 };
+typedef struct {
+  int met_np; const double *met_p;      /* ML2PL: target pressure levels [hPa] */
+  int met_dx, met_dy, met_dp;           /* SAMPLE: keep every dx-th longitude, dy-th latitude, dp-th level */
+  int met_sx, met_sy, met_sp;           /* SAMPLE: smoothing half-widths (1 = none) */
+} mphip_regrid_t;
+typedef struct {                        /* the caller's arrays and their strides: the shape changes */
+  long long sx, sy, sx2;
+  double *lon, *lat, *p;                /* the output axes (nx2, ny2, np2 values) */
+  float *f3[MPHIP_N3D]; float *f2[MPHIP_N2D];
+} mphip_regrid_out_t;
+size_t mphip_sizeof_regrid(void);       /* sizeof(mphip_regrid_t), for mirrors of the structure in other languages */
+int mphip_regrid_shape(const mphip_met_t *in, unsigned what, const mphip_regrid_t *opt, int *nx2, int *ny2, int *np2);
+int mphip_regrid_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const mphip_regrid_t *opt,
+                     const mphip_regrid_out_t *out);
 
 /* mptrac_update_device(..., atm), mptrac.c:8050-8055.  This process owns the
  * particles [ip0, ip0 + np) of a simulation with np_total particles; random

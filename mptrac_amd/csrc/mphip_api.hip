@@ -17,6 +17,7 @@
 
 #include "mphip_kernels.hpp"
 #include "mphip_metprep.hpp"
+#include "mphip_regrid.hpp"
 
 using namespace mphip;
 
@@ -283,6 +284,15 @@ struct mphip_ctx {
   float *prep_pv = nullptr;           // potential vorticity (MPHIP_PREP_PV; what MPHIP_PREP_TROPO with met_tropo 5 reads)
   double *prep_axes = nullptr;        // p[np] | lat[ny] | lon[nx] | the tropopause's tables (PrepTropo::tab)
   int prep_profile_phase = 0;         // option "derive_profile_phase": what mphip_profile_begin / _end time of a call
+  // mphip_regrid_met (prep_stream, prep_lock): the uploaded fields, ML2PL's result and SAMPLE's result; each array grows
+  // to the largest size asked for and is kept
+  struct RegridBuf {
+    float *p = nullptr;
+    size_t n = 0;
+  };
+  RegridBuf rg_in3[MPHIP_N3D], rg_mid3[MPHIP_N3D], rg_out3[MPHIP_N3D], rg_in2[MPHIP_N2D], rg_out2[MPHIP_N2D];
+  double *rg_p = nullptr;             // met_p on the device
+  size_t rg_p_n = 0;
 
   // profiling of the fused step kernel
   bool prof = false;
@@ -2796,6 +2806,151 @@ int prep_tropo_columns(int np, int mode, size_t *lds, int *nprof, int *fine) {
   return 0;
 }
 
+// ---- mphip_regrid_met: scratch, copies and the checks it shares with mphip_regrid_shape ------------------------------
+void regrid_release(mphip_ctx *ctx) {
+  for (auto *set : { ctx->rg_in3, ctx->rg_mid3, ctx->rg_out3 })
+    for (int f = 0; f < MPHIP_N3D; f++) {
+      dev_free(set[f].p);
+      set[f] = mphip_ctx::RegridBuf();
+    }
+  for (auto *set : { ctx->rg_in2, ctx->rg_out2 })
+    for (int f = 0; f < MPHIP_N2D; f++) {
+      dev_free(set[f].p);
+      set[f] = mphip_ctx::RegridBuf();
+    }
+  dev_free(ctx->rg_p);
+  ctx->rg_p = nullptr;
+  ctx->rg_p_n = 0;
+}
+
+int regrid_reserve(mphip_ctx *ctx, mphip_ctx::RegridBuf &b, size_t n) {
+  if (b.n >= n)
+    return 0;
+  b.n = 0;
+  if (dev_alloc(ctx, &b.p, n))
+    return 1;
+  b.n = n;
+  return 0;
+}
+
+// a level field of nx x ny x np values between a host array of strides sx, sy and a compact device array
+int regrid_copy3(mphip_ctx *ctx, float *dev, const float *host, int nx, int ny, int np, long long sx, long long sy,
+                 bool to_device, hipStream_t stream) {
+  mphip_met_t m;
+  memset(&m, 0, sizeof(m));
+  m.nx = nx;
+  m.ny = ny;
+  m.np = np;
+  m.sx = sx;
+  m.sy = sy;
+  return prep_copy3(ctx, dev, host, &m, to_device, stream);
+}
+
+int regrid_copy2(mphip_ctx *ctx, float *dev, const float *host, int nx, int ny, long long sx2, bool to_device,
+                 hipStream_t stream) {
+  mphip_met_t m;
+  memset(&m, 0, sizeof(m));
+  m.nx = nx;
+  m.ny = ny;
+  m.sx2 = sx2;
+  return prep_copy2(ctx, dev, host, &m, to_device, stream);
+}
+
+bool regrid_strides_ok(int ny, int np, long long sx, long long sy) {
+  return sy >= np && sx >= sy * ny && sx % sy == 0;
+}
+
+// the fields ML2PL regrids; SAMPLE takes these and z, pv
+const int kRegridMl[kRgFields] = { MPHIP_T, MPHIP_U, MPHIP_V, MPHIP_W, MPHIP_H2O, MPHIP_O3, MPHIP_LWC, MPHIP_RWC,
+                                   MPHIP_IWC, MPHIP_SWC, MPHIP_CC };
+const int kRegridPl[kRgFields + 2] = { MPHIP_T, MPHIP_U, MPHIP_V, MPHIP_W, MPHIP_H2O, MPHIP_O3, MPHIP_LWC, MPHIP_RWC,
+                                       MPHIP_IWC, MPHIP_SWC, MPHIP_CC, MPHIP_Z, MPHIP_PV };
+
+struct RegridPlan {
+  int nx, ny, np0;         // input extents (np0: levels of the uploaded level fields)
+  int np1;                 // levels SAMPLE reads: met_np behind ML2PL, else np0
+  int nx2, ny2, np2;       // output extents
+  int ml_cpb;              // ML2PL: columns per workgroup
+  size_t ml_lds;
+  RegridSample S3, S2;     // SAMPLE: the level fields and the surface fields
+  size_t lds3, lds2;
+};
+
+// everything that can be refused for the grid and the options (not for missing arrays); NULL = accepted
+const char *regrid_plan(const mphip_met_t *in, unsigned what, const mphip_regrid_t *opt, RegridPlan *P) {
+  const bool ml = what & MPHIP_REGRID_ML2PL, sample = what & MPHIP_REGRID_SAMPLE;
+  if (!what || (what & ~(unsigned) (MPHIP_REGRID_ML2PL | MPHIP_REGRID_SAMPLE)))
+    return "`what` must be an OR of MPHIP_REGRID_* bits";
+  if (in->nx < 2 || in->ny < 2)
+    return "meteo grid dimensions out of range";
+  memset(P, 0, sizeof(*P));
+  P->nx = in->nx;
+  P->ny = in->ny;
+  P->np0 = P->np1 = in->np;
+  if (ml) {
+    if (in->npl < 2 || in->np != in->npl)
+      return "MPHIP_REGRID_ML2PL needs two model levels or more and np == npl";
+    if (opt->met_np < 2 || !opt->met_p)
+      return "MPHIP_REGRID_ML2PL needs two target levels or more (met_np < 2)";
+    for (int j = 0; j < opt->met_np; j++)
+      if (!(opt->met_p[j] > 0 && opt->met_p[j] < INFINITY) || (j > 0 && !(opt->met_p[j] < opt->met_p[j - 1])))
+        return "MPHIP_REGRID_ML2PL: met_p must be finite, positive and strictly descending";
+    const int pitch = in->npl | 1;
+    for (int cpb = kPrepLanes; cpb >= 1 && !P->ml_cpb; cpb >>= 1) {
+      P->ml_lds = (size_t) opt->met_np * sizeof(double) + (size_t) cpb * pitch * sizeof(float);
+      if (P->ml_lds <= 64 * 1024)
+        P->ml_cpb = cpb;
+    }
+    if (!P->ml_cpb)
+      return "MPHIP_REGRID_ML2PL: too many levels for one column in 64 KB of LDS";
+    P->np1 = opt->met_np;
+  } else if (in->np < 2)
+    return "needs two pressure levels or more (np < 2)";
+  if ((long long) in->nx * in->ny >= (1LL << 24) || (long long) in->nx * in->ny * std::max(P->np0, P->np1) >= (1LL << 31))
+    return "meteo grid too large for the device index arithmetic";
+  P->nx2 = in->nx;
+  P->ny2 = in->ny;
+  P->np2 = P->np1;
+  if (sample) {
+    const int d[3] = { opt->met_dx, opt->met_dy, opt->met_dp }, s[3] = { opt->met_sx, opt->met_sy, opt->met_sp };
+    for (int a = 0; a < 3; a++)
+      if (d[a] < 1 || s[a] < 1)
+        return "MPHIP_REGRID_SAMPLE: every stride and half-width must be 1 or more";
+    if (s[0] - 1 > in->nx)
+      return "MPHIP_REGRID_SAMPLE: smoothing half-width too large (met_sx - 1 <= nx)";
+    // (the extents in 64 bits, and a half-width beyond 2^20 refused at once: no overflow for absurd options)
+    const int n1[3] = { in->nx, in->ny, P->np1 }, tile[3] = { kRgTX, kRgTY, kRgKC };
+    long long e[3], h[3];
+    int n2[3];
+    for (int a = 0; a < 3; a++) {
+      n2[a] = (int) (((long long) n1[a] + d[a] - 1) / d[a]);
+      if (s[a] > (1 << 20))
+        return "MPHIP_REGRID_SAMPLE: smoothing tile with halo beyond 64 KB of LDS";
+      e[a] = std::min<long long>(d[a], 2LL * s[a] - 1);
+      h[a] = (tile[a] - 1) * e[a] + 2LL * s[a] - 1;
+    }
+    if (n2[0] < 2 || n2[1] < 2 || n2[2] < 2)
+      return "MPHIP_REGRID_SAMPLE: the sampled grid needs two points or more per axis";
+    if (h[0] * h[1] > 16 * 1024 || h[0] * h[1] * h[2] > 16 * 1024)
+      return "MPHIP_REGRID_SAMPLE: smoothing tile with halo beyond 64 KB of LDS";
+    P->nx2 = n2[0];
+    P->ny2 = n2[1];
+    P->np2 = n2[2];
+    RegridSample &S = P->S3;
+    S.nx = n1[0], S.ny = n1[1], S.np = n1[2];
+    S.nx2 = n2[0], S.ny2 = n2[1], S.np2 = n2[2];
+    S.dx = d[0], S.dy = d[1], S.dp = d[2];
+    S.sx = s[0], S.sy = s[1], S.sp = s[2];
+    S.ex = (int) e[0], S.ey = (int) e[1], S.ep = (int) e[2];
+    S.hx = (int) h[0], S.hy = (int) h[1], S.hk = (int) h[2];
+    P->lds3 = (size_t) (h[0] * h[1] * h[2]) * sizeof(float);
+    P->S2 = S;
+    P->S2.np = P->S2.np2 = P->S2.dp = P->S2.sp = P->S2.ep = P->S2.hk = 1;
+    P->lds2 = (size_t) (h[0] * h[1]) * sizeof(float);
+  }
+  return nullptr;
+}
+
 }   // namespace
 
 // ---------------------------------------------------------------------------
@@ -2874,6 +3029,7 @@ void mphip_destroy(mphip_ctx *ctx) {
       dev_free(p);
   }
   prep_release(ctx);
+  regrid_release(ctx);
   if (ctx->prep_stream)
     (void) hipStreamDestroy(ctx->prep_stream);
   dev_free(ctx->d_clim);
@@ -3768,6 +3924,188 @@ int mphip_derive_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const
   if (mark_end())
     return 1;
   HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+
+size_t mphip_sizeof_regrid(void) {
+  return sizeof(mphip_regrid_t);
+}
+
+int mphip_regrid_shape(const mphip_met_t *in, unsigned what, const mphip_regrid_t *opt, int *nx2, int *ny2, int *np2) {
+  if (!in || !opt)
+    return 1;
+  RegridPlan P;
+  if (regrid_plan(in, what, opt, &P))
+    return 1;
+  if (nx2)
+    *nx2 = P.nx2;
+  if (ny2)
+    *ny2 = P.ny2;
+  if (np2)
+    *np2 = P.np2;
+  return 0;
+}
+
+int mphip_regrid_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const mphip_regrid_t *opt,
+                     const mphip_regrid_out_t *out) {
+  if (!ctx || !in || !opt || !out)
+    return fail(ctx, "mphip_regrid_met: null argument");
+  RegridPlan P;
+  if (const char *why = regrid_plan(in, what, opt, &P))
+    return fail(ctx, std::string("mphip_regrid_met: ") + why);
+  const bool ml = what & MPHIP_REGRID_ML2PL, sample = what & MPHIP_REGRID_SAMPLE;
+  if (!in->lon || !in->lat || (!ml && !in->p))
+    return fail(ctx, "mphip_regrid_met: the input axes are missing");
+  if (ml && !in->f3[MPHIP_PL])
+    return fail(ctx, "mphip_regrid_met: MPHIP_REGRID_ML2PL needs the field pl");
+  if (!regrid_strides_ok(P.ny, P.np0, in->sx, in->sy) || in->sx2 < P.ny
+      || (ml && !regrid_strides_ok(P.ny, P.np0, in->sx_ml, in->sy_ml)))
+    return fail(ctx, "mphip_regrid_met: unsupported meteo strides");
+  if (!regrid_strides_ok(P.ny2, P.np2, out->sx, out->sy) || out->sx2 < P.ny2)
+    return fail(ctx, "mphip_regrid_met: the output strides do not hold the output grid");
+  // the fields of this call: present on both sides
+  int f3[kRgFields + 2], n3 = 0, f2[MPHIP_N2D], n2 = 0;
+  for (int i = 0; i < (ml ? kRgFields : kRgFields + 2); i++) {
+    const int f = ml ? kRegridMl[i] : kRegridPl[i];
+    if (in->f3[f] && out->f3[f])
+      f3[n3++] = f;
+  }
+  for (int f = 0; f < MPHIP_N2D; f++)
+    if (in->f2[f] && out->f2[f])
+      f2[n2++] = f;
+
+  std::lock_guard<std::mutex> guard(ctx->prep_lock);
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!ctx->prep_stream)
+    HIPCHK(hipStreamCreateWithFlags(&ctx->prep_stream, hipStreamNonBlocking));
+  hipStream_t st = ctx->prep_stream;
+  const size_t ncol = (size_t) P.nx * P.ny, ncol2 = (size_t) P.nx2 * P.ny2;
+  const size_t ncell0 = ncol * P.np0, ncell1 = ncol * P.np1, ncell2 = ncol2 * P.np2;
+  // the axes of the output are taken before anything is written (`out` may alias `in`)
+  std::vector<double> lon2(P.nx2), lat2(P.ny2), p2(P.np2);
+  const int ddx = sample ? opt->met_dx : 1, ddy = sample ? opt->met_dy : 1, ddp = sample ? opt->met_dp : 1;
+  for (int i = 0; i < P.nx2; i++)
+    lon2[i] = in->lon[(size_t) i * ddx];
+  for (int i = 0; i < P.ny2; i++)
+    lat2[i] = in->lat[(size_t) i * ddy];
+  for (int i = 0; i < P.np2; i++)
+    p2[i] = (ml ? opt->met_p : in->p)[(size_t) i * ddp];
+
+  // uploads
+  hipEvent_t ev_stop = nullptr;
+  auto mark_begin = [&](int phase) {
+    ev_stop = nullptr;
+    if (!ctx->prof || ctx->prep_profile_phase != phase)
+      return 0;
+    while (ctx->ev_used + 2 > ctx->ev.size()) {
+      hipEvent_t e;
+      HIPCHK(hipEventCreate(&e));
+      ctx->ev.push_back(e);
+    }
+    HIPCHK(hipEventRecord(ctx->ev[ctx->ev_used++], st));
+    ev_stop = ctx->ev[ctx->ev_used++];
+    return 0;
+  };
+  auto mark_end = [&]() {
+    if (ev_stop)
+      HIPCHK(hipEventRecord(ev_stop, st));
+    return 0;
+  };
+  if (mark_begin(1))
+    return 1;
+  if (ml) {
+    if (ctx->rg_p_n < (size_t) opt->met_np) {
+      ctx->rg_p_n = 0;
+      if (dev_alloc(ctx, &ctx->rg_p, (size_t) opt->met_np))
+        return 1;
+      ctx->rg_p_n = (size_t) opt->met_np;
+    }
+    HIPCHK(hipMemcpyAsync(ctx->rg_p, opt->met_p, (size_t) opt->met_np * sizeof(double), hipMemcpyHostToDevice, st));
+    if (regrid_reserve(ctx, ctx->rg_in3[MPHIP_PL], ncell0)
+        || regrid_copy3(ctx, ctx->rg_in3[MPHIP_PL].p, in->f3[MPHIP_PL], P.nx, P.ny, P.np0, in->sx_ml, in->sy_ml, true, st))
+      return 1;
+  }
+  for (int i = 0; i < n3; i++) {
+    const int f = f3[i];
+    if (regrid_reserve(ctx, ctx->rg_in3[f], ncell0)
+        || regrid_copy3(ctx, ctx->rg_in3[f].p, in->f3[f], P.nx, P.ny, P.np0, in->sx, in->sy, true, st))
+      return 1;
+    if (ml && regrid_reserve(ctx, ctx->rg_mid3[f], ncell1))
+      return 1;
+    if (sample && regrid_reserve(ctx, ctx->rg_out3[f], ncell2))
+      return 1;
+  }
+  for (int i = 0; i < n2; i++) {
+    const int f = f2[i];
+    if (regrid_reserve(ctx, ctx->rg_in2[f], ncol) || regrid_copy2(ctx, ctx->rg_in2[f].p, in->f2[f], P.nx, P.ny, in->sx2, true, st))
+      return 1;
+    if (sample && regrid_reserve(ctx, ctx->rg_out2[f], ncol2))
+      return 1;
+  }
+  if (mark_end())
+    return 1;
+  // (pageable memory: the copies above have read the caller's arrays when they return; the synchronisation makes that
+  // hold for pinned arrays too, before the first download below overwrites an aliased input)
+  HIPCHK(hipStreamSynchronize(st));
+
+  if (ml && n3 > 0) {
+    RegridFields F;
+    F.n = n3;
+    for (int i = 0; i < n3; i++) {
+      F.in[i] = ctx->rg_in3[f3[i]].p;
+      F.out[i] = ctx->rg_mid3[f3[i]].p;
+    }
+    if (mark_begin(0))
+      return 1;
+    hipLaunchKernelGGL(regrid_ml2pl_kernel, dim3((unsigned) ((ncol + P.ml_cpb - 1) / P.ml_cpb)), dim3(kRgThreads), P.ml_lds, st,
+                       (int) ncol, P.np0, opt->met_np, P.ml_cpb, P.np0 | 1, ctx->rg_p, ctx->rg_in3[MPHIP_PL].p, F);
+    HIPCHK(hipGetLastError());
+    if (mark_end())
+      return 1;
+  }
+  if (sample) {
+    const dim3 tiles3((P.nx2 + kRgTX - 1) / kRgTX, (P.ny2 + kRgTY - 1) / kRgTY, (P.np2 + kRgKC - 1) / kRgKC);
+    const dim3 tiles2(tiles3.x, tiles3.y, 1);
+    for (int i = 0; i < n3; i++) {
+      if (mark_begin(0))
+        return 1;
+      hipLaunchKernelGGL(regrid_sample_kernel<kRgKC>, tiles3, dim3(kRgThreads), P.lds3, st, P.S3,
+                         ml ? ctx->rg_mid3[f3[i]].p : ctx->rg_in3[f3[i]].p, ctx->rg_out3[f3[i]].p);
+      HIPCHK(hipGetLastError());
+      if (mark_end())
+        return 1;
+    }
+    for (int i = 0; i < n2; i++) {
+      if (mark_begin(0))
+        return 1;
+      hipLaunchKernelGGL(regrid_sample_kernel<1>, tiles2, dim3(kRgTX * kRgTY), P.lds2, st, P.S2, ctx->rg_in2[f2[i]].p,
+                         ctx->rg_out2[f2[i]].p);
+      HIPCHK(hipGetLastError());
+      if (mark_end())
+        return 1;
+    }
+  }
+  if (mark_begin(2))
+    return 1;
+  for (int i = 0; i < n3; i++) {
+    const float *res = sample ? ctx->rg_out3[f3[i]].p : ctx->rg_mid3[f3[i]].p;
+    if (regrid_copy3(ctx, const_cast<float *>(res), out->f3[f3[i]], P.nx2, P.ny2, P.np2, out->sx, out->sy, false, st))
+      return 1;
+  }
+  for (int i = 0; i < n2; i++) {
+    const float *res = sample ? ctx->rg_out2[f2[i]].p : ctx->rg_in2[f2[i]].p;
+    if (regrid_copy2(ctx, const_cast<float *>(res), out->f2[f2[i]], P.nx2, P.ny2, out->sx2, false, st))
+      return 1;
+  }
+  if (mark_end())
+    return 1;
+  HIPCHK(hipStreamSynchronize(st));
+  if (out->lon)
+    memcpy(out->lon, lon2.data(), lon2.size() * sizeof(double));
+  if (out->lat)
+    memcpy(out->lat, lat2.data(), lat2.size() * sizeof(double));
+  if (out->p)
+    memcpy(out->p, p2.data(), p2.size() * sizeof(double));
   return 0;
 }
 

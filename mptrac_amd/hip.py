@@ -58,6 +58,38 @@ PREP = {"geopot": 1, "o3c": 2, "pbl": 4, "cloud": 8, "cape": 16, "pv": 32, "trop
 PREP_OUTPUTS = {"geopot": ("z",), "o3c": ("o3c",), "pbl": ("pbl",), "cloud": ("pct", "pcb", "cl"),
                 "cape": ("plcl", "plfc", "pel", "cape", "cin"), "pv": ("pv",), "tropo": ("pt", "tt", "zt", "h2ot")}
 
+
+class MphipRegrid(C.Structure):
+    """mphip_regrid_t: the options of mphip_regrid_met."""
+    _fields_ = [("met_np", C.c_int), ("met_p", _dp), ("met_dx", C.c_int), ("met_dy", C.c_int), ("met_dp", C.c_int),
+                ("met_sx", C.c_int), ("met_sy", C.c_int), ("met_sp", C.c_int)]
+
+
+class MphipRegridOut(C.Structure):
+    """mphip_regrid_out_t: the output arrays of mphip_regrid_met, their strides and the output axes."""
+    _fields_ = [("sx", C.c_longlong), ("sy", C.c_longlong), ("sx2", C.c_longlong), ("lon", _dp), ("lat", _dp), ("p", _dp),
+                ("f3", _fp * len(FIELDS_3D)), ("f2", _fp * len(FIELDS_2D))]
+
+
+REGRID = {"ml2pl": 1, "sample": 2}
+REGRID_ML = ("t", "u", "v", "w", "h2o", "o3", "lwc", "rwc", "iwc", "swc", "cc")      # what ML2PL regrids
+REGRID_PL = REGRID_ML + ("z", "pv")                                                  # what SAMPLE takes
+
+
+class Snapshot:
+    """What Simulation.regrid_met returns: the axes (float64) and the float32 fields of the new shape, named as in
+    synth.Met (`strides` = (sx, sy, sx2) in floats where the arrays are views into larger ones)."""
+
+    def __init__(self, time, coord_type, lon, lat, p, f3, f2, strides=None):
+        self.time, self.coord_type = float(time), int(coord_type)
+        self.lon, self.lat, self.p = lon, lat, p
+        self.nx, self.ny, self.np = len(lon), len(lat), len(p)
+        self.npl = self.np
+        self.f3, self.f2 = f3, f2
+        if strides is not None:
+            self.strides = strides
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_void_p)
 
 _lib = None
@@ -122,6 +154,13 @@ def load(build=True):
     L.mphip_discard_prefetch.argtypes = [C.c_void_p]
     if hasattr(L, "mphip_derive_met"):      # (absent from libraries built before the meteo preprocessing: A/B runs through MPHIP_LIB)
         L.mphip_derive_met.argtypes = [C.c_void_p, C.POINTER(MphipMet), C.c_uint, C.POINTER(MphipPrep), C.POINTER(MphipMetOut)]
+    if hasattr(L, "mphip_regrid_met"):      # (absent from libraries built before the regridding: A/B runs through MPHIP_LIB)
+        L.mphip_regrid_met.argtypes = [C.c_void_p, C.POINTER(MphipMet), C.c_uint, C.POINTER(MphipRegrid), C.POINTER(MphipRegridOut)]
+        L.mphip_regrid_shape.argtypes = [C.POINTER(MphipMet), C.c_uint, C.POINTER(MphipRegrid), C.POINTER(C.c_int),
+                                         C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.mphip_sizeof_regrid.restype = C.c_size_t
+        if L.mphip_sizeof_regrid() != C.sizeof(MphipRegrid):
+            raise MphipError("mphip_regrid_t layout mismatch between header and Python mirror")
     if hasattr(L, "mphip_sizeof_prep"):     # (absent from libraries built before pv and the tropopause: they read the old members)
         L.mphip_sizeof_prep.restype = C.c_size_t
         if L.mphip_sizeof_prep() != C.sizeof(MphipPrep):
@@ -310,7 +349,7 @@ class Simulation:
         # (`strides` = (sx, sy, sx2) in floats: a view into arrays of the reference's fixed extents; derive_met)
         m.sx, m.sy, m.sx2 = getattr(met, "strides", None) or (met.ny * met.np, met.np, met.ny)
         m.npl = met.npl if any(k in met.f3 for k in FIELDS_ML) else 0
-        m.sx_ml, m.sy_ml = met.ny * met.npl, met.npl
+        m.sx_ml, m.sy_ml = getattr(met, "strides_ml", None) or (met.ny * met.npl, met.npl)
         for i, k in enumerate(FIELDS_3D):
             m.f3[i] = _ptr(met.f3[k], _fp) if k in met.f3 else None
         for i, k in enumerate(FIELDS_2D):
@@ -363,6 +402,63 @@ class Simulation:
                     mo.f2[FIELDS_2D.index(f)] = _ptr(a, _fp)
         self._chk(self.L.mphip_derive_met(self.h, C.byref(m), bits, C.byref(o), C.byref(mo)))
         return res
+
+    def regrid_met(self, met, what, out=None, out_strides=None, **opts):
+        """Model levels to pressure levels and / or smoothing with down-sampling (mphip_regrid_met).  `met`: a snapshot
+        with the conventions of derive_met; for ml2pl its level fields have npl levels, f3["pl"] is the pressure (a view
+        names its strides as `strides_ml` = (sx_ml, sy_ml)) and `p` is not read.  `what`: names among ml2pl, sample (or
+        the OR of their MPHIP_REGRID_* bits).  Options: met_p (the target levels of ml2pl), met_dx, met_dy, met_dp, met_sx,
+        met_sy, met_sp (1).  `out`: {name: float32 array of the new shape to write into, or None to leave a field out}
+        -- views into larger arrays name their strides in floats as `out_strides` = (sx, sy, sx2), which then hold for
+        every output array (tests; in-place use); by default new compact arrays.  Returns a Snapshot of the new shape."""
+        if isinstance(what, str):
+            what = (what,)
+        bits = what if isinstance(what, int) else sum(REGRID[w] for w in set(what))
+        met_p = np.ascontiguousarray(opts.pop("met_p", ()), dtype=np.float64)
+        o = MphipRegrid(len(met_p), _ptr(met_p, _dp) if len(met_p) else None,
+                        *(int(opts.pop(k, 1)) for k in ("met_dx", "met_dy", "met_dp", "met_sx", "met_sy", "met_sp")))
+        if opts:
+            raise TypeError(f"unknown options {sorted(opts)}")
+        m = self._met_struct(met)
+        if bits & REGRID["ml2pl"]:
+            m.npl = met.npl         # (also without pl: that refusal is the library's)
+        mo = MphipRegridOut()
+        n = [C.c_int(0) for _ in range(3)]
+        if self.L.mphip_regrid_shape(C.byref(m), bits, C.byref(o), *(C.byref(k) for k in n)):
+            mo.sx, mo.sy, mo.sx2 = out_strides or (0, 0, 0)
+            for f, a in (out or {}).items():        # (the caller's arrays all the same: a refused call writes nothing)
+                if a is not None and f in FIELDS_3D:
+                    mo.f3[FIELDS_3D.index(f)] = _ptr(a, _fp)
+                elif a is not None:
+                    mo.f2[FIELDS_2D.index(f)] = _ptr(a, _fp)
+            self._chk(self.L.mphip_regrid_met(self.h, C.byref(m), bits, C.byref(o), C.byref(mo)))     # (refused: its message)
+            raise MphipError("mphip_regrid_shape refused what mphip_regrid_met accepts")
+        nx2, ny2, np2 = (k.value for k in n)
+        mo.sx, mo.sy, mo.sx2 = out_strides or (ny2 * np2, np2, ny2)
+        lon, lat, p = (np.empty(k, dtype=np.float64) for k in (nx2, ny2, np2))
+        mo.lon, mo.lat, mo.p = _ptr(lon, _dp), _ptr(lat, _dp), _ptr(p, _dp)
+        out = dict(out or {})
+        f3, f2 = {}, {}
+        for f in (REGRID_ML if bits & REGRID["ml2pl"] else REGRID_PL):
+            if f in out or f in met.f3:
+                a = out[f] if f in out else np.empty((nx2, ny2, np2), dtype=np.float32)
+                if a is None:
+                    continue
+                assert a.dtype == np.float32 and a.shape == (nx2, ny2, np2) and a.strides == (4 * mo.sx, 4 * mo.sy, 4), f
+                mo.f3[FIELDS_3D.index(f)] = _ptr(a, _fp)
+                if f in met.f3:
+                    f3[f] = a
+        for f in FIELDS_2D:
+            if f in out or f in met.f2:
+                a = out[f] if f in out else np.empty((nx2, ny2), dtype=np.float32)
+                if a is None:
+                    continue
+                assert a.dtype == np.float32 and a.shape == (nx2, ny2) and a.strides == (4 * mo.sx2, 4), f
+                mo.f2[FIELDS_2D.index(f)] = _ptr(a, _fp)
+                if f in met.f2:
+                    f2[f] = a
+        self._chk(self.L.mphip_regrid_met(self.h, C.byref(m), bits, C.byref(o), C.byref(mo)))
+        return Snapshot(met.time, met.coord_type, lon, lat, p, f3, f2, out_strides)
 
     def set_met(self, slot, met):
         m = self._met_struct(met)

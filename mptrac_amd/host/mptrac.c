@@ -430,16 +430,50 @@ void mptrac_read_ctl(const char *filename, int argc, char *argv[], ctl_t *ctl) {
     ? scan_ctl(filename, argc, argv, "MET_UTM_REF_LON", -1, "", NULL) : 0;
   REQUIRE(ctl->direction == -1 || ctl->direction == 1, "Set DIRECTION to -1 or 1!");
   if (ctl->met_type == 0) {
-    /* netCDF input is taken as stored: no down-sampling, smoothing, detrending, re-gridding (mptrac.c:7770-7830) */
+    /* netCDF input is taken as stored: no detrending, no hybrid-coefficient levels (mptrac.c:7770-7830) ... */
     static const struct {
       const char *key, *def;
-    } untouched[] = { { "MET_DX", "1" }, { "MET_DY", "1" }, { "MET_DP", "1" }, { "MET_SX", "1" }, { "MET_SY", "1" },
-      { "MET_SP", "1" }, { "MET_DETREND", "-999" }, { "MET_NP", "0" }, { "MET_VERT_COORD", "0" }, { "MET_CLAMS", "0" },
-      { "MET_CONVENTION", "0" }, { "MET_RELHUM", "0" }, { NULL, NULL } };
+    } untouched[] = { { "MET_DETREND", "-999" }, { "MET_CLAMS", "0" }, { "MET_CONVENTION", "0" }, { "MET_RELHUM", "0" },
+      { NULL, NULL } };
     for (int k = 0; untouched[k].key; k++)
       if (scan_ctl(filename, argc, argv, untouched[k].key, -1, untouched[k].def, NULL) != atof(untouched[k].def))
         ERRMSG("%s: the meteo preprocessing of the reference is not part of this build (netCDF input is used as stored)!",
                untouched[k].key);
+    /* ... but for down-sampling with smoothing and model-level input, which the device does (mphip_regrid_met) when
+     * HIP_MET_PREP is 1 or 2 */
+    static const char *const regrid[] = { "MET_DX", "MET_DY", "MET_DP", "MET_SX", "MET_SY", "MET_SP", NULL };
+    int *const regrid_to[] = { &ctl->met_dx, &ctl->met_dy, &ctl->met_dp, &ctl->met_sx, &ctl->met_sy, &ctl->met_sp };
+    for (int k = 0; regrid[k]; k++) {
+      const double v = scan_ctl(filename, argc, argv, regrid[k], -1, "1", NULL);
+      if (v != 1 && ctl->hip_met_prep < 1)
+        ERRMSG("%s: the meteo preprocessing of the reference is not part of this build (netCDF input is used as stored; "
+               "HIP_MET_PREP 1 samples it on the device)!", regrid[k]);
+      REQUIRE(v >= 1 && v == (int) v, "%s must be a whole number, 1 or more!", regrid[k]);
+      *regrid_to[k] = (int) v;
+    }
+    const double vert = scan_ctl(filename, argc, argv, "MET_VERT_COORD", -1, "0", NULL);
+    const double levels = scan_ctl(filename, argc, argv, "MET_NP", -1, "0", NULL);
+    if ((vert != 0 || levels != 0) && ctl->hip_met_prep < 1)
+      ERRMSG("%s: the meteo preprocessing of the reference is not part of this build (netCDF input is used as stored; "
+             "HIP_MET_PREP 1 interpolates model-level files to pressure levels on the device)!",
+             vert != 0 ? "MET_VERT_COORD" : "MET_NP");
+    if (vert != 0 && vert != 1)
+      ERRMSG("MET_VERT_COORD: the meteo preprocessing of the reference is not part of this build (hybrid-coefficient "
+             "levels are not read; MET_VERT_COORD 1 reads a 3-D pressure variable)!");
+    ctl->met_vert_coord = (int) vert;
+    ctl->met_np = (int) levels;
+    REQUIRE(ctl->met_np == levels && (ctl->met_np == 0 || ctl->met_vert_coord == 1), "MET_NP needs MET_VERT_COORD 1!");
+    if (ctl->met_vert_coord == 1) {
+      REQUIRE(ctl->met_np >= 2 && ctl->met_np <= EP, "MET_VERT_COORD 1 needs 2 <= MET_NP <= %d!", EP);
+      for (int k = 0; k < ctl->met_np; k++) {
+        ctl->met_p[k] = scan_ctl(filename, argc, argv, "MET_P", k, "", NULL);
+        REQUIRE(isfinite(ctl->met_p[k]) && ctl->met_p[k] > 0 && (k == 0 || ctl->met_p[k] < ctl->met_p[k - 1]),
+                "MET_P must be positive and strictly descending!");
+      }
+    }
+  } else {
+    ctl->met_dx = ctl->met_dy = ctl->met_dp = ctl->met_sx = ctl->met_sy = ctl->met_sp = 1;
+    ctl->met_vert_coord = ctl->met_np = 0;
   }
 
   /* modules (mptrac.c:7196-7263) */
@@ -581,8 +615,14 @@ void mptrac_read_ctl(const char *filename, int argc, char *argv[], ctl_t *ctl) {
   REQUIRE(ctl->advect_vert_coord != 3 || ctl->qnt_eta >= 0, "Please add eta to your quantities for etadot calculations!");
   /* MET_TYPE 1 files carry pressure-level fields only (mptrac.c:8887-9043); the model-level options of
    * the back end are reached through the C ABI (mphip_update_met with pl, ul, vl, wl, zetal, zeta_dotl) */
-  if (ctl->advect_vert_coord == 2)
+  /* ... and with netCDF files on model levels (MET_TYPE 0, MET_VERT_COORD 1) the reader keeps u, v, w and the pressure
+   * on the file's levels beside the pressure-level fields */
+  if (ctl->advect_vert_coord == 2 && !(ctl->met_type == 0 && ctl->met_vert_coord == 1))
     ERRMSG("Using ADVECT_VERT_COORD = 2 requires meteo data on model levels!");            /* mptrac.c:7002 */
+  if (ctl->advect_vert_coord == 2
+      && (ctl->met_dx != 1 || ctl->met_dy != 1 || ctl->met_dp != 1 || ctl->met_sx != 1 || ctl->met_sy != 1 || ctl->met_sp != 1))
+    ERRMSG("ADVECT_VERT_COORD = 2 with MET_DX / MET_DY / MET_DP / MET_SX / MET_SY / MET_SP other than 1: the model-level "
+           "fields are not sampled!");
   if (ctl->advect_vert_coord == 1)
     ERRMSG("Please use meteo files in netcdf format for diabatic calculations.");           /* mptrac.c:7031 */
   if (ctl->advect_vert_coord == 3)
@@ -1703,6 +1743,11 @@ static void met_periodic(met_t *met) {
     memcpy(f2[f][last], f2[f][0], sizeof(f2[f][0]));
   for (size_t f = 0; f < sizeof(f3) / sizeof(f3[0]); f++)
     memcpy(f3[f][last], f3[f][0], sizeof(f3[f][0]));
+  if (met->npl > 0) {
+    float (*ml[])[EY][EP] = { met->pl, met->ul, met->vl, met->wl };
+    for (size_t f = 0; f < sizeof(ml) / sizeof(ml[0]); f++)
+      memcpy(ml[f][last], ml[f][0], sizeof(ml[f][0]));
+  }
 }
 
 /* What the file gave, for met_derive */
@@ -1711,6 +1756,7 @@ typedef struct {
 } nc_have_t;
 
 static unsigned met_derive(const ctl_t *ctl, const clim_t *clim, met_t *met, const nc_have_t *have);
+static void met_regrid(const ctl_t *ctl, met_t *met, unsigned what);
 
 static int read_met_nc(const char *filename, const ctl_t *ctl, const clim_t *clim, met_t *met) {
   char err[256];
@@ -1756,21 +1802,27 @@ static int read_met_nc(const char *filename, const ctl_t *ctl, const clim_t *cli
   if (np < 2 || np > EP)
     ERRMSG("Number of levels out of range!");
   met->np = (int) np;
-  const int vl = ncc_find_var(nc, levname);
-  if (vl < 0 || !ncc_read_double(nc, vl, 0, 0, np, met->p))
+  met->npl = 0;
+  const int model_levels = ctl->met_vert_coord == 1;   /* the axis `u` names is a model-level index: no pressures to read */
+  const int vl = model_levels ? -1 : ncc_find_var(nc, levname);
+  if (!model_levels && (vl < 0 || !ncc_read_double(nc, vl, 0, 0, np, met->p)))
     ERRMSG("Cannot read the pressure levels!");
   /* (the level axis is the one `u` names: a reader that had to guess axis names by their length must not have
    * guessed a horizontal one, and what was read must look like pressures) */
   if (strcmp(levname, xname) == 0 || strcmp(levname, yname) == 0)
     ERRMSG("Cannot determine vertical dimension!");
-  for (int k = 0; k < met->np; k++) {
+  for (int k = 0; k < met->np && !model_levels; k++) {
     met->p[k] /= 100.0;   /* Pa -> hPa */
     REQUIRE(isfinite(met->p[k]) && met->p[k] > 0 && met->p[k] < 2000, "The levels of '%s' are not pressures!", levname);
   }
   const double dx = fabs(met->lon[1] - met->lon[0]);
   for (int i = 2; i < met->nx; i++)
     REQUIRE(fabs(fabs(met->lon[i] - met->lon[i - 1]) - dx) <= 0.001, "No regular grid spacing in longitudes!");
-  LOG(2, "Grid: %d x %d x %d, %g ... %g hPa", met->nx, met->ny, met->np, met->p[0], met->p[met->np - 1]);
+  if (model_levels) {
+    LOG(2, "Grid: %d x %d x %d model levels", met->nx, met->ny, met->np);
+  } else {
+    LOG(2, "Grid: %d x %d x %d, %g ... %g hPa", met->nx, met->ny, met->np, met->p[0], met->p[met->np - 1]);
+  }
 
   /* surface fields */
   if (NC_2D(ps, 1.0f, "lnsp", "LNSP")) {   /* logarithm of the surface pressure in Pa */
@@ -1811,7 +1863,23 @@ static int read_met_nc(const char *filename, const ctl_t *ctl, const clim_t *cli
   have.swc = NC_3D(swc, 1.0f, "cswc", "CSWC");
   have.pbl = have_pbl;
   (void) NC_3D(cc, 1.0f, "cc", "CC");
+  if (model_levels)
+    REQUIRE(NC_3D(pl, 0.01f, "pl", "PL", "pressure", "PRESSURE", "press", "PRESS"),   /* Pa -> hPa */
+            "MET_VERT_COORD 1: cannot read the 3-D pressure (pl, pressure or press)!");
   ncc_close(nc);
+  if (model_levels) {
+    /* the winds stay on the file's levels for ADVECT_VERT_COORD 2; everything else goes to the levels MET_P on the
+     * device, and from here on this is an ordinary pressure-level snapshot */
+    if (ctl->advect_vert_coord == 2) {
+      memcpy(met->ul, met->u, sizeof(met->u));
+      memcpy(met->vl, met->v, sizeof(met->v));
+      memcpy(met->wl, met->w, sizeof(met->w));
+    }
+    met->npl = met->np;
+    met_regrid(ctl, met, MPHIP_REGRID_ML2PL);
+    if (ctl->advect_vert_coord != 2)
+      met->npl = 0;
+  }
   for (int k = 1; k < met->np; k++)
     REQUIRE(met->p[k - 1] >= met->p[k], "Pressure levels must be descending!");
 
@@ -1833,6 +1901,9 @@ static int read_met_nc(const char *filename, const ctl_t *ctl, const clim_t *cli
     met_polar_winds(met);
     met_periodic(met);
   }
+  /* down-sampling with smoothing (read_met_sample): the derived fields below are those of the sampled grid */
+  if (ctl->met_dx != 1 || ctl->met_dy != 1 || ctl->met_dp != 1 || ctl->met_sx != 1 || ctl->met_sy != 1 || ctl->met_sp != 1)
+    met_regrid(ctl, met, MPHIP_REGRID_SAMPLE);
 
   /* Fields the reference derives in its preprocessing: with HIP_MET_PREP 1 the device derives what the file's fields
    * allow (met_derive); a configuration that needs a field that was not derived is refused.  The boundary-layer
@@ -2006,6 +2077,7 @@ static void describe_met(met_t *met, mphip_met_t *out) {
     m.f3[MPHIP_VL] = &met->vl[0][0][0];
     m.f3[MPHIP_ZETAL] = &met->zetal[0][0][0];
     m.f3[MPHIP_ZETA_DOTL] = &met->zeta_dotl[0][0][0];
+    m.f3[MPHIP_WL] = &met->wl[0][0][0];
   }
   m.f3[MPHIP_U] = &met->u[0][0][0];
   m.f3[MPHIP_V] = &met->v[0][0][0];
@@ -2140,6 +2212,73 @@ static unsigned met_derive(const ctl_t *ctl, const clim_t *clim, met_t *met, con
       what & MPHIP_PREP_CLOUD ? " cloud layer" : "", what & MPHIP_PREP_CAPE ? " CAPE" : "",
       what & MPHIP_PREP_PV ? " potential vorticity" : "", what & MPHIP_PREP_TROPO ? " tropopause" : "");
   return what;
+}
+
+/* HIP_MET_PREP 1 or 2: the snapshot the netCDF reader has filled, regridded in place on the device (mphip_regrid_met,
+ * which uploads every input before it writes an output): MPHIP_REGRID_ML2PL takes the level fields from the file's model
+ * levels (their pressure in met->pl) to the pressure levels MET_P, MPHIP_REGRID_SAMPLE smooths and down-samples every
+ * pressure-level and surface field.  The kept model-level fields (pl, ul, vl, wl) are not touched.  Like met_derive it
+ * may run on the read-ahead thread; the context exists by then (the first files of a run are read on the main thread). */
+static void met_regrid(const ctl_t *ctl, met_t *met, unsigned what) {
+  REQUIRE(ctl->hip_met_prep >= 1 && ctl->hip_met_prep <= 2, "HIP_MET_PREP must be 0, 1 or 2 (got %d)!", ctl->hip_met_prep);
+  need_ctx(ctl);
+  mphip_met_t in;
+  describe_met(met, &in);
+  in.f3[MPHIP_O3] = &met->o3[0][0][0];
+  in.f3[MPHIP_CC] = &met->cc[0][0][0];
+  in.f3[MPHIP_Z] = in.f3[MPHIP_PV] = NULL;       /* derived after this, on the new grid */
+  if (what & MPHIP_REGRID_ML2PL) {
+    in.npl = met->np;
+    in.f3[MPHIP_PL] = &met->pl[0][0][0];
+  }
+  /* the surface fields the reader fills (the derived ones follow on the new grid) */
+  memset(in.f2, 0, sizeof(in.f2));
+  if (what & MPHIP_REGRID_SAMPLE) {
+    in.f2[MPHIP_PS] = &met->ps[0][0];
+    in.f2[MPHIP_ZS] = &met->zs[0][0];
+    in.f2[MPHIP_TS] = &met->ts[0][0];
+    in.f2[MPHIP_US] = &met->us[0][0];
+    in.f2[MPHIP_VS] = &met->vs[0][0];
+    in.f2[MPHIP_ESS] = &met->ess[0][0];
+    in.f2[MPHIP_NSS] = &met->nss[0][0];
+    in.f2[MPHIP_SHF] = &met->shf[0][0];
+    in.f2[MPHIP_LSM] = &met->lsm[0][0];
+    in.f2[MPHIP_SST] = &met->sst[0][0];
+    in.f2[MPHIP_PBL] = &met->pbl[0][0];
+    in.f2[MPHIP_CAPE] = &met->cape[0][0];
+    in.f2[MPHIP_CIN] = &met->cin[0][0];
+  }
+  const mphip_regrid_t opt = { ctl->met_np, ctl->met_p, ctl->met_dx, ctl->met_dy, ctl->met_dp, ctl->met_sx, ctl->met_sy,
+    ctl->met_sp };
+  mphip_regrid_out_t out;
+  memset(&out, 0, sizeof(out));
+  out.sx = in.sx;
+  out.sy = in.sy;
+  out.sx2 = in.sx2;
+  out.lon = met->lon;
+  out.lat = met->lat;
+  out.p = met->p;
+  for (int f = 0; f < MPHIP_N3D; f++)
+    if (f != MPHIP_PL && f != MPHIP_UL && f != MPHIP_VL && f != MPHIP_WL && f != MPHIP_ZETAL && f != MPHIP_ZETA_DOTL)
+      out.f3[f] = (float *) in.f3[f];
+  for (int f = 0; f < MPHIP_N2D; f++)
+    out.f2[f] = (float *) in.f2[f];
+  int nx2 = 0, ny2 = 0, np2 = 0;
+  /* (not through HIP(): that macro first submits the main thread's queued time steps; the extents before the call,
+   * which overwrites the axes in place -- a grid mphip_regrid_shape refuses is refused by the call with a message) */
+  (void) mphip_regrid_shape(&in, what, &opt, &nx2, &ny2, &np2);
+  if (mphip_regrid_met(g_ctx, &in, what, &opt, &out) != 0)
+    ERRMSG("HIP back end: %s", mphip_last_error(g_ctx));
+  met->nx = nx2;
+  met->ny = ny2;
+  met->np = np2;
+  if (what & MPHIP_REGRID_ML2PL) {
+    LOG(2, "Interpolated on the device: %d model levels to %d pressure levels, %g ... %g hPa", in.npl, np2, met->p[0],
+        met->p[np2 - 1]);
+  }
+  if (what & MPHIP_REGRID_SAMPLE) {
+    LOG(2, "Sampled on the device: %d x %d x %d", nx2, ny2, np2);
+  }
 }
 
 /* Read-ahead of the next meteo file (HIP_MET_PREFETCH 1, forward runs): while the time steps of the current

@@ -148,6 +148,13 @@ typedef struct {
   /* ... and of HIP_MET_PREP 2: the tropopause definition (1 climatology, 2 cold point, 3 WMO, 4 second WMO, 5 dynamical) */
   int met_tropo, met_tropo_spline;
   double met_tropo_pv, met_tropo_theta;
+  /* ... and of the regridding of netCDF input on the device (mphip_regrid_met; HIP_MET_PREP >= 1): down-sampling strides
+   * and smoothing half-widths (MET_DX ... MET_SP, 1 = none), and model-level input (MET_VERT_COORD 1: the level axis of
+   * the file is a model-level index and its 3-D pressure variable gives the pressure; the fields are interpolated to
+   * the MET_NP pressure levels MET_P[k]) */
+  int met_dx, met_dy, met_dp, met_sx, met_sy, met_sp;
+  int met_vert_coord, met_np;
+  double met_p[EP];
   double t_start, t_stop, dt_mod, dt_met, met_utm_ref_lat, met_utm_ref_lon, met_dt_out;
   /* zonal-mean climatologies module_meteo samples (mptrac.c:7461-7470) and the diurnal scaling of OH (mptrac.c:7394) */
   char clim_hno3_filename[LEN], clim_oh_filename[LEN], clim_h2o2_filename[LEN], clim_ho2_filename[LEN],
@@ -311,6 +318,8 @@ typedef struct {
   float lwc[EX][EY][EP], rwc[EX][EY][EP], iwc[EX][EY][EP], swc[EX][EY][EP];
   /* model levels (mptrac.h:3997-4012); not part of the MET_TYPE 1 file format, filled by the caller */
   float pl[EX][EY][EP], ul[EX][EY][EP], vl[EX][EY][EP], zetal[EX][EY][EP], zeta_dotl[EX][EY][EP];
+  float wl[EX][EY][EP];   /* vertical velocity on model levels (ADVECT_VERT_COORD 2); with pl, ul, vl filled by the netCDF
+                             reader from model-level files (MET_VERT_COORD 1) */
 } met_t;
 
 /* not used on the hot path; kept so that the reference's signatures hold */
