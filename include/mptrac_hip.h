@@ -763,6 +763,11 @@ int mphip_test_libm(mphip_ctx *ctx, int op, const double *x, const double *y, lo
  * interpolation, the random-number triple, ...; list in mphip_kernels.hpp:piece_kernel) `reps` times per
  * resident particle; tools/piece_cost.py reads the instruction counters of these launches. */
 int mphip_test_piece(mphip_ctx *ctx, int piece, int reps, double *checksum);
+/* The table of module_diff_meso's wind deviations of the current meteo pair -- {sd_u, sd_v, sd_w} per raw grid cell,
+ * what the lean kernels read instead of summing the cell's 16 wind values per particle and step (mptrac.c:4287-4318) --
+ * in plain order: out[((ix (ny - 1) + iy) (np - 1) + ip) 3 + k], cells = (nx - 1) (ny - 1) (np - 1).  Builds the table
+ * if the current packed grids have none. */
+int mphip_test_meso_table(mphip_ctx *ctx, float *out, size_t cells);
 #ifdef __cplusplus
 }
 #endif

@@ -111,10 +111,15 @@ struct mphip_ctx {
     f32x4 *cp2 = nullptr;                                     // {cape,pel} pair records (module_convection)
     int *ml_mono = nullptr;                                   // cleared by the pack kernel if a height column is not monotonic
     bool ml_monotonic = false;
+    // module_diff_meso's wind deviations per raw cell (DevMet::meso), a function of `wind` alone: valid for exactly the
+    // records it was built from (pack_launch, which writes `wind`, voids or rebuilds it; ensure_meso_table builds it for a
+    // set packed while the module was off).  Allocated only in a context whose control parameters switch the module on.
+    float *meso = nullptr;
+    bool meso_valid = false;
     void release() {
       for (void *q : { (void *) wind, (void *) temp, (void *) h2o, (void *) mlw, (void *) zl2, (void *) pl2, (void *) mx,
                        (void *) mx2, (void *) cloud, (void *) sfa, (void *) sfb, (void *) sfc, (void *) sfd, (void *) cp2,
-                       (void *) ml_mono })
+                       (void *) ml_mono, (void *) meso })
         if (q)
           (void) hipFree(q);
       *this = PackedGrids();
@@ -405,6 +410,8 @@ DevMet dev_met(const mphip_ctx *c) {
   M.mlw = c->pk.mlw;
   M.zl2 = c->pk.zl2;
   M.pl2 = c->pk.pl2;
+  M.meso = c->pk.meso_valid ? c->pk.meso : nullptr;
+  M.meso_nty = (c->ny + 2) / 4;   // (ny - 1 cells in bricks of four, rounded up)
   M.ml_monotonic = c->pk.ml_monotonic ? 1 : 0;
   for (int t = 0; t < 2; t++) {
     M.zl[t] = c->slot[t ^ c->flip].f3[MPHIP_ZETAL];
@@ -575,7 +582,22 @@ int upload_axes(mphip_ctx *ctx) {
 // called from the stepping thread only)
 struct PackPlan {
   bool cloud = false, ml = false, pbl = false, mx = false, mx2 = false, ml_heights = false, coord2 = false;
+  bool meso = false;   // build the table of module_diff_meso's wind deviations behind the wind records
 };
+
+// The table of module_diff_meso's wind deviations (DevMet::meso): three floats per cell, in bricks of 4 x 4 columns
+static size_t meso_table_floats(const mphip_ctx *ctx) {
+  return (size_t) ((ctx->nx + 2) / 4) * (size_t) ((ctx->ny + 2) / 4) * (size_t) (ctx->npl - 1) * 16 * 3;
+}
+static bool lean32_ok(const mphip_ctx *ctx);
+// ... is built with the packed set where the control parameters switch the module on and the lean instantiations
+// with 32-bit offsets, its readers, can run on the grid
+static bool meso_table_wanted(const mphip_ctx *ctx) {
+  // (the condition of the time step's module set, plan_step; a caller that runs the module on its own with
+  // `diffusion` off gets the table in front of its first launch)
+  return MPHIP_MESO_TABLE && ctx->have_ctl && ctx->ctl.diffusion && (ctx->ctl.turb_mesox > 0 || ctx->ctl.turb_mesoz > 0)
+    && lean32_ok(ctx);
+}
 
 PackPlan pack_plan(const mphip_ctx *ctx, const MetSlot &s0, const MetSlot &s1) {
   PackPlan P;
@@ -595,6 +617,7 @@ PackPlan pack_plan(const mphip_ctx *ctx, const MetSlot &s0, const MetSlot &s1) {
   P.coord2 = ctx->have_ctl && ctx->ctl.advect_vert_coord == 2;
   P.ml_heights = P.ml && s0.has3[MPHIP_PL] && s1.has3[MPHIP_PL]
     && (P.coord2 || (s0.has3[MPHIP_ZETAL] && s1.has3[MPHIP_ZETAL]));
+  P.meso = meso_table_wanted(ctx);
   return P;
 }
 
@@ -608,6 +631,8 @@ int pack_alloc(mphip_ctx *ctx, mphip_ctx::PackedGrids &K, const PackPlan &P) {
     return 1;
   if (!K.wind && (dev_alloc(ctx, &K.wind, 6 * ncell) || dev_alloc(ctx, &K.temp, 2 * ncell)))
     return 1;
+  if (P.meso && !K.meso && dev_alloc(ctx, &K.meso, meso_table_floats(ctx)))
+    return 1;
   if (!K.cp2 && dev_alloc(ctx, &K.cp2, ncol))
     return 1;
   if (!K.sfa && (dev_alloc(ctx, &K.sfa, ncol) || dev_alloc(ctx, &K.sfb, 2 * ncol) || dev_alloc(ctx, &K.sfc, 2 * ncol)))
@@ -620,6 +645,23 @@ int pack_alloc(mphip_ctx *ctx, mphip_ctx::PackedGrids &K, const PackPlan &P) {
     return 1;
   if (P.pbl && !K.sfd && (dev_alloc(ctx, &K.sfd, 2 * ncol) || dev_alloc(ctx, &K.h2o, 2 * ncell)))
     return 1;
+  return 0;
+}
+
+// the table of set K from its wind records, on `stream` (K.meso allocated; no hipMalloc, no use of ctx->err)
+int meso_table_launch(const mphip_ctx *ctx, mphip_ctx::PackedGrids &K, hipStream_t stream) {
+  MesoTableArgs a;
+  a.wind = K.wind;
+  a.meso = K.meso;
+  a.nx = ctx->nx;
+  a.ny = ctx->ny;
+  a.np = ctx->npl;
+  a.ntx = (ctx->nx + 2) / 4;
+  a.nty = (ctx->ny + 2) / 4;
+  hipLaunchKernelGGL(meso_table_kernel, dim3(grid_for((long long) (meso_table_floats(ctx) / 3))), dim3(256), 0, stream, a);
+  if (hipGetLastError() != hipSuccess)
+    return 1;
+  K.meso_valid = true;
   return 0;
 }
 
@@ -662,8 +704,11 @@ int pack_launch(mphip_ctx *ctx, mphip_ctx::PackedGrids &K, const PackPlan &P, co
   a.ncell = ncell;
   a.ncol = ncol;
   a.ncell_ml = (size_t) ctx->nx * ctx->ny * ctx->nml;
+  K.meso_valid = false;   // (the wind records are about to change)
   hipLaunchKernelGGL(pack_kernel, dim3(grid_for((long long) ncell)), dim3(256), 0, stream, a);
   if (hipGetLastError() != hipSuccess)
+    return 1;
+  if (P.meso && K.meso && meso_table_launch(ctx, K, stream))
     return 1;
   K.ml_monotonic = false;
   if (P.ml_heights) {   // (model levels only) the fast kernel relies on monotonic height columns
@@ -839,7 +884,9 @@ static bool lean_grid(const mphip_ctx *ctx) {
     && cols * guard_levels(ctx) < (1ull << 32);
 }
 static bool fits32(const mphip_ctx *ctx) {
-  return (unsigned long long) ctx->nx * ctx->ny * guard_levels(ctx) * 24ull < (1ull << 32);
+  // (the table of module_diff_meso's deviations rounds its bricks up: on a thin grid it can be the largest array)
+  return (unsigned long long) ctx->nx * ctx->ny * guard_levels(ctx) * 24ull < (1ull << 32)
+    && (!MPHIP_MESO_TABLE || (unsigned long long) meso_table_floats(ctx) * 4ull < (1ull << 32));
 }
 static bool lean32_ok(const mphip_ctx *ctx) { return lean_grid(ctx) && fits32(ctx) && !ctx->big_grid; }
 static bool lean64_ok(const mphip_ctx *ctx) { return lean_grid(ctx) && (!fits32(ctx) || ctx->big_grid); }
@@ -957,6 +1004,26 @@ unsigned step_kernel_mask(const mphip_ctx *ctx, unsigned mask, int nsteps) {
   return ml || (mask & kRareModules) || fg ? kMaskGeneric : kMaskGenericPL;
 }
 
+// Does instantiation `sel`, launched with module set `mask`, read the table of module_diff_meso's wind deviations?  The
+// lean instantiations with 32-bit offsets do (diff_meso_fast); the gated ones switch the module by the run-time mask.
+static bool reads_meso_table(unsigned sel, unsigned mask) {
+  return MPHIP_MESO_TABLE && sel != kNoStepKernel && sel < kMaskGenericMLMulti && (sel & MPHIP_MOD_DIFF_MESO)
+    && !(sel & kBigGrid) && (mask & MPHIP_MOD_DIFF_MESO);
+}
+
+// the table of the current packed set, for a launch that reads it: built with the set (pack_launch) where the module
+// was on then; otherwise here, in front of the first such launch (the one place that may have to allocate it)
+int ensure_meso_table(mphip_ctx *ctx) {
+  mphip_ctx::PackedGrids &K = ctx->pk;
+  if (K.meso_valid)
+    return 0;
+  if (!K.meso && dev_alloc(ctx, &K.meso, meso_table_floats(ctx)))
+    return 1;
+  if (meso_table_launch(ctx, K, ctx->stream))
+    return fail(ctx, "building the table of the mesoscale wind deviations failed");
+  return 0;
+}
+
 // nsteps > 1: that many consecutive time steps in one launch, time and counters advancing by t_stride and ctr_stride
 // (kMultiStep instantiations: step_kernel_mask says whether one exists for the module set)
 int launch_step(mphip_ctx *ctx, unsigned mask, double t, const RngCtr &rng = {}, int nsteps = 1, double t_stride = 0,
@@ -1019,6 +1086,11 @@ int launch_step(mphip_ctx *ctx, unsigned mask, double t, const RngCtr &rng = {},
     HIPCHK(hipEventRecord(e0, ctx->stream));
   }
   unsigned sel = step_kernel_mask(ctx, mask, nsteps);
+  if (reads_meso_table(sel, mask)) {
+    if (ensure_meso_table(ctx))
+      return 1;
+    S.met.meso = ctx->pk.meso;
+  }
   // module_wet_depo / module_dry_depo alone (the launch behind module_mixing): the kernel that packs the few
   // particles with anything to do into full waves
   constexpr unsigned kDepo = MPHIP_MOD_WET_DEPO | MPHIP_MOD_DRY_DEPO;
@@ -5576,6 +5648,13 @@ int mphip_test_piece(mphip_ctx *ctx, int piece, int reps, double *checksum) {
   S.ctr_meso = 5000;
   S.ctr_conv = 9000;
   S.ctr_pbl = 0;
+  if (MPHIP_MESO_TABLE && piece == 22) {   // (diff_meso_fast reads the table)
+    if (!lean32_ok(ctx))
+      return fail(ctx, "mphip_test_piece: piece 22 needs a grid the lean kernels with 32-bit offsets run on");
+    if (ensure_meso_table(ctx))
+      return 1;
+    S.met.meso = ctx->pk.meso;
+  }
   double *d = nullptr;
   HIPCHK(hipMalloc((void **) &d, (size_t) ctx->np * sizeof(double)));
   const size_t lds = axes_lds_bytes(ctx) + sizeof(DevClim) + (size_t) kLibmLogExpDoubles * sizeof(double);
@@ -5608,6 +5687,33 @@ int mphip_test_piece(mphip_ctx *ctx, int piece, int reps, double *checksum) {
     *checksum = sum;
   }
   HIPCHK(hipFree(d));
+  return 0;
+}
+
+int mphip_test_meso_table(mphip_ctx *ctx, float *out, size_t cells) {
+  if (!ctx || !out)
+    return fail(ctx, "bad argument");
+  HIPCHK(hipSetDevice(ctx->device));
+  if (ensure_packed(ctx))
+    return 1;
+  const size_t nx = (size_t) ctx->nx - 1, ny = (size_t) ctx->ny - 1, np = (size_t) ctx->npl - 1;
+  if (cells != nx * ny * np)
+    return fail(ctx, "mphip_test_meso_table: `cells` must be (nx - 1) (ny - 1) (np - 1)");
+  if (!MPHIP_MESO_TABLE || !lean32_ok(ctx))
+    return fail(ctx, "mphip_test_meso_table: no table in this build or on this grid");
+  if (ensure_meso_table(ctx))
+    return 1;
+  std::vector<float> h(meso_table_floats(ctx));
+  HIPCHK(hipMemcpyAsync(h.data(), ctx->pk.meso, h.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const size_t nty = (size_t) (ctx->ny + 2) / 4;
+  for (size_t ix = 0; ix < nx; ix++)
+    for (size_t iy = 0; iy < ny; iy++)
+      for (size_t ip = 0; ip < np; ip++) {
+        const size_t o = ((((ix >> 2) * nty + (iy >> 2)) * np + ip) << 4) + ((ix & 3) << 2) + (iy & 3);
+        for (int k = 0; k < 3; k++)
+          out[3 * ((ix * ny + iy) * np + ip) + k] = h[3 * o + k];
+      }
   return 0;
 }
 

@@ -176,6 +176,10 @@ struct DevMet {
   // module_diff_meso: r = 1 - 2 |dt| / DT_MET and sqrt(1 - r^2) for |dt| = meso_dt = |DT_MOD| (every particle of a
   // step but the last, shortened one), from the host -- IEEE division and square root as the reference's
   double meso_dt, meso_r, meso_r2;
+  // ... and its wind deviations {sd_u, sd_v, sd_w} per raw cell, built from the wind records when they are packed
+  // (meso_table_kernel; layout: meso_off32); NULL where no lean instantiation with the module is about to run
+  const float *meso;
+  int meso_nty;                  // bricks of four rows along iy, rounded up
 };
 
 struct DevAtm {
@@ -3308,20 +3312,13 @@ __device__ __forceinline__ void diff_turb_fast(const mphip_ctl_t &ctl, const Dev
   }
 }
 
-// module_diff_meso (mptrac.c:4280-4338) on the {u0,v0,u1,v1,w0,w1} records
-template <bool STREAM = false, bool BIG = false>
-__device__ __forceinline__ void diff_meso_fast(const mphip_ctl_t &ctl, const DevMet &M, const Axes &A, Particle &P,
-                                               float &up, float &vp, float &wp, uint64_t ctr, uint64_t g,
-                                               const double *pre, WindCache &wc, const double *ltab) {
+// The wind deviations of module_diff_meso (mptrac.c:4287-4318) over the 16 values of a raw cell -- 2 x 2 x 2 corners x
+// 2 snapshots -- on the {u0,v0,u1,v1,w0,w1} records: the one place that evaluates them (the table kernel and the
+// instantiations that sum per particle call it: the same bits by construction).  corner(i, j, r0, r1, r2) delivers the
+// twelve floats of column (ix + i, iy + j), levels ip and ip + 1.
+template <class Corner>
+__device__ __forceinline__ void meso_cell_sd(Corner corner, float sd[3]) {
 #pragma clang fp contract(off)
-  Stencil s;
-  raw_cell_fast(M, A, P.lon, P.lat, P.p, s);
-  if (!STREAM) {
-    load_wind_cached32<BIG>(M, s, wc);
-    wind_cache_wait(wc);
-  }
-  const WindCorners &c = wc.c;
-
   // single-precision sums in the reference's order -- i (lon), j (lat), k (level), met0 before met1 --,
   // u and v side by side in one packed accumulator
   f32x2 mean_uv = { 0.f, 0.f }, sig_uv = { 0.f, 0.f };
@@ -3331,6 +3328,71 @@ __device__ __forceinline__ void diff_meso_fast(const mphip_ctl_t &ctl, const Dev
 #pragma unroll
     for (int j = 0; j < 2; j++) {
       f32x4u r0, r1, r2;
+      corner(i, j, r0, r1, r2);
+      // level ip: uv0 = r0[0,1], uv1 = r0[2,3], w0 w1 = r1[0,1]; level ip + 1: uv0 = r1[2,3], uv1 = r2[0,1], w0 w1 = r2[2,3]
+      const f32x2 uv[2][2] = { { __builtin_shufflevector(r0, r0, 0, 1), __builtin_shufflevector(r0, r0, 2, 3) },
+                               { __builtin_shufflevector(r1, r1, 2, 3), __builtin_shufflevector(r2, r2, 0, 1) } };
+      const float ww[2][2] = { { r1[0], r1[1] }, { r2[2], r2[3] } };
+#pragma unroll
+      for (int k = 0; k < 2; k++)
+#pragma unroll
+        for (int t = 0; t < 2; t++) {
+          mean_uv = mean_uv + uv[k][t];
+          sig_uv = sig_uv + uv[k][t] * uv[k][t];
+          mean_w = mean_w + ww[k][t];
+          sig_w = sig_w + ww[k][t] * ww[k][t];
+        }
+    }
+  const float mean[3] = { mean_uv[0], mean_uv[1], mean_w }, sig[3] = { sig_uv[0], sig_uv[1], sig_w };
+#pragma unroll
+  for (int q = 0; q < 3; q++) {
+    const float m16 = mean[q] / 16.f;
+    const float var = sig[q] / 16.f - m16 * m16;
+    sd[q] = (var > 0 ? sqrtf(var) : 0.f);
+  }
+}
+
+// 1: the lean instantiations with 32-bit offsets read the deviations of a particle's raw cell from the table the pack
+// step builds (DevMet::meso) instead of summing the cell's 16 values in every step; 0: they sum (the A/B build)
+#ifndef MPHIP_MESO_TABLE
+#define MPHIP_MESO_TABLE 1
+#endif
+
+// The table is stored in bricks of 4 x 4 columns that follow the locality order of the particles (sort_key_kernel: 4 x 4
+// horizontal tile, level, column within the tile): [ix >> 2][iy >> 2][ip][ix & 3][iy & 3], 12 bytes each, so that the
+// gather of a wave -- a few consecutive levels of one tile -- touches a few lines.  Brick counts are rounded up; a cell
+// is ix <= nx - 2, iy <= ny - 2, ip <= np - 2 (raw_cell_fast's range).  32-bit byte offset (lean32_ok checks the size).
+struct MesoSd {
+  float u, v, w;
+};
+__device__ __forceinline__ unsigned meso_off32(const DevMet &M, const Stencil &s) {
+  const unsigned brick = __umul24(__umul24((unsigned) s.ix >> 2, (unsigned) M.meso_nty) + ((unsigned) s.iy >> 2),
+                                  (unsigned) (M.np - 1)) + (unsigned) s.ip;
+  return 12u * (16u * brick + (((unsigned) s.ix & 3u) << 2) + ((unsigned) s.iy & 3u));
+}
+
+// module_diff_meso (mptrac.c:4280-4338) on the {u0,v0,u1,v1,w0,w1} records
+template <bool STREAM = false, bool BIG = false>
+__device__ __forceinline__ void diff_meso_fast(const mphip_ctl_t &ctl, const DevMet &M, const Axes &A, Particle &P,
+                                               float &up, float &vp, float &wp, uint64_t ctr, uint64_t g,
+                                               const double *pre, WindCache &wc, const double *ltab) {
+#pragma clang fp contract(off)
+  Stencil s;
+  raw_cell_fast(M, A, P.lon, P.lat, P.p, s);
+  float sd[3];
+  if constexpr (MPHIP_MESO_TABLE && !BIG) {
+    // one gather, issued here and first needed behind the normals below
+    const MesoSd t = load_at<MesoSd>(M.meso, meso_off32(M, s));
+    sd[0] = t.u;
+    sd[1] = t.v;
+    sd[2] = t.w;
+  } else {
+    if (!STREAM) {
+      load_wind_cached32<BIG>(M, s, wc);
+      wind_cache_wait(wc);
+    }
+    const WindCorners &c = wc.c;
+    meso_cell_sd([&](int i, int j, f32x4u &r0, f32x4u &r1, f32x4u &r2) {
       if (STREAM) {   // (no corner cache in this instantiation: a corner is summed as it arrives)
         if constexpr (BIG) {
           const uint64_t off = (uint64_t) 24 * cell32(M, s, i, j);
@@ -3348,27 +3410,7 @@ __device__ __forceinline__ void diff_meso_fast(const mphip_ctl_t &ctl, const Dev
         r1 = c.r[i][j][1];
         r2 = c.r[i][j][2];
       }
-      // level ip: uv0 = r0[0,1], uv1 = r0[2,3], w0 w1 = r1[0,1]; level ip + 1: uv0 = r1[2,3], uv1 = r2[0,1], w0 w1 = r2[2,3]
-      const f32x2 uv[2][2] = { { __builtin_shufflevector(r0, r0, 0, 1), __builtin_shufflevector(r0, r0, 2, 3) },
-                               { __builtin_shufflevector(r1, r1, 2, 3), __builtin_shufflevector(r2, r2, 0, 1) } };
-      const float ww[2][2] = { { r1[0], r1[1] }, { r2[2], r2[3] } };
-#pragma unroll
-      for (int k = 0; k < 2; k++)
-#pragma unroll
-        for (int t = 0; t < 2; t++) {
-          mean_uv = mean_uv + uv[k][t];
-          sig_uv = sig_uv + uv[k][t] * uv[k][t];
-          mean_w = mean_w + ww[k][t];
-          sig_w = sig_w + ww[k][t] * ww[k][t];
-        }
-    }
-  const float mean[3] = { mean_uv[0], mean_uv[1], mean_w }, sig[3] = { sig_uv[0], sig_uv[1], sig_w };
-  float sd[3];
-#pragma unroll
-  for (int q = 0; q < 3; q++) {
-    const float m16 = mean[q] / 16.f;
-    const float var = sig[q] / 16.f - m16 * m16;
-    sd[q] = (var > 0 ? sqrtf(var) : 0.f);
+    }, sd);
   }
 
   double r, r2;

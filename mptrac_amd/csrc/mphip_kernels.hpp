@@ -1504,6 +1504,40 @@ __global__ void pack_kernel(PackArgs a) {
   }
 }
 
+// The table of module_diff_meso's wind deviations (DevMet::meso, layout: meso_off32) from packed wind records: one
+// thread per stored element, in storage order -- a wave is the 16 columns of a brick at four consecutive levels.  A
+// cell reads nodes ix .. ix + 1 <= nx - 1, iy .. iy + 1 <= ny - 1, ip .. ip + 1 <= np - 1; the elements of a brick
+// beyond the last cell of an axis hold 0 and are never read.
+struct MesoTableArgs {
+  const float *wind;
+  float *meso;
+  int nx, ny, np;
+  int ntx, nty;   // bricks along ix and iy
+};
+
+__global__ __launch_bounds__(256) void meso_table_kernel(MesoTableArgs a) {
+  const size_t nlev = (size_t) (a.np - 1);
+  const size_t total = (size_t) a.ntx * (size_t) a.nty * nlev * 16;
+  const size_t stride = (size_t) gridDim.x * blockDim.x;
+  for (size_t o = blockIdx.x * (size_t) blockDim.x + threadIdx.x; o < total; o += stride) {
+    const size_t brick = o >> 4, col = brick / nlev;
+    const int ip = (int) (brick - col * nlev);
+    const int ix = 4 * (int) (col / (size_t) a.nty) + (int) ((o >> 2) & 3);
+    const int iy = 4 * (int) (col % (size_t) a.nty) + (int) (o & 3);
+    float sd[3] = { 0.f, 0.f, 0.f };
+    if (ix <= a.nx - 2 && iy <= a.ny - 2)
+      meso_cell_sd([&](int i, int j, f32x4u &r0, f32x4u &r1, f32x4u &r2) {
+        const f32x4u *q = (const f32x4u *) (a.wind + 6 * (((size_t) (ix + i) * a.ny + (size_t) (iy + j)) * a.np + (size_t) ip));
+        r0 = q[0];
+        r1 = q[1];
+        r2 = q[2];
+      }, sd);
+    a.meso[3 * o] = sd[0];
+    a.meso[3 * o + 1] = sd[1];
+    a.meso[3 * o + 2] = sd[2];
+  }
+}
+
 // ---------------------------------------------------------------------------
 // module_sort: key, radix sort, gather (mptrac.c:5887-5995)
 // ---------------------------------------------------------------------------

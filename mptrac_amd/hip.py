@@ -204,6 +204,8 @@ def load(build=True):
     L.mphip_test_piece.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
     if hasattr(L, "mphip_test_libm"):      # (absent from libraries built before round 6: A/B runs through MPHIP_LIB)
         L.mphip_test_libm.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_longlong, _dp]
+    if hasattr(L, "mphip_test_meso_table"):      # (absent from libraries built before round 8)
+        L.mphip_test_meso_table.argtypes = [C.c_void_p, _fp, C.c_size_t]
     if L.mphip_sizeof_ctl() != C.sizeof(MphipCtl):
         raise MphipError("mphip_ctl_t layout mismatch between header and Python mirror")
     if L.mphip_sizeof_met() != C.sizeof(MphipMet):
@@ -778,6 +780,14 @@ class Simulation:
         chk = C.c_double(0.0)
         self._chk(self.L.mphip_test_piece(self.h, int(piece), int(reps), C.byref(chk)))
         return chk.value
+
+    def test_meso_table(self, shape):
+        """module_diff_meso's wind deviations per raw cell of the current meteo pair, [nx - 1][ny - 1][np - 1][3], as the
+        lean kernels read them (shape: the grid's (nx, ny, np))."""
+        nx, ny, npl = shape
+        out = np.empty((nx - 1, ny - 1, npl - 1, 3), dtype=np.float32)
+        self._chk(self.L.mphip_test_meso_table(self.h, _ptr(out, _fp), out.size // 3))
+        return out
 
     def test_rng(self, ctr, n, method):
         out = np.empty(n)
