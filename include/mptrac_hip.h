@@ -400,7 +400,8 @@ int mphip_discard_prefetch(mphip_ctx *ctx);
  * clamp is the last).  A NaN in t[k] makes z NaN on the levels from k away from the surface (on all levels if the surface's
  * LIN reads it); an infinite h2o makes z NaN on every level; a NaN zs makes z NaN on every level; a NaN ts makes PBL 3's pbl
  * pmin (it is not finite) and keeps PBL 2's criterion false, which is pmin as well.
- *   Out of scope: MET_PBL 1, detrending.  (Down-sampling and model-to-pressure-level regridding: mphip_regrid_met.) */
+ *   Out of scope: MET_PBL 1.  (Down-sampling and model-to-pressure-level regridding: mphip_regrid_met; detrending:
+ * mphip_detrend_met.) */
 enum { MPHIP_PREP_GEOPOT = 1, MPHIP_PREP_O3C = 2, MPHIP_PREP_PBL = 4, MPHIP_PREP_CLOUD = 8, MPHIP_PREP_CAPE = 16,
        MPHIP_PREP_PV = 32, MPHIP_PREP_TROPO = 64 };
 typedef struct {
@@ -480,6 +481,48 @@ size_t mphip_sizeof_regrid(void);       /* sizeof(mphip_regrid_t), for mirrors o
 int mphip_regrid_shape(const mphip_met_t *in, unsigned what, const mphip_regrid_t *opt, int *nx2, int *ny2, int *np2);
 int mphip_regrid_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const mphip_regrid_t *opt,
                      const mphip_regrid_out_t *out);
+
+/* Detrending (the reference's read_met_detrend): a Gaussian-weighted horizontal mean, the background, is subtracted from
+ * t, u, v and w of a pressure-level snapshot on a longitude / latitude grid.  The call keeps the contract of
+ * mphip_derive_met / mphip_regrid_met: the same stream and lock, scratch of its own that is kept between calls and freed
+ * by mphip_destroy, no meteo slot, no prefetch state and no particle touched, callable from a file-reader thread while
+ * another thread steps; a refused call writes nothing and its message starts with "mphip_detrend_met: ".  Every input
+ * is uploaded and the weights are built before any output is copied back, so `out` may alias `in`.  The shape does not
+ * change: `out` names the strides of its arrays (sy >= np, sx a multiple of sy and >= ny sy), only out->f3[MPHIP_T],
+ * [MPHIP_U], [MPHIP_V] and [MPHIP_W] are written, a field that is NULL in `in` or in `out` is skipped, and the axes and
+ * every other slot of `out` are ignored.
+ *
+ *   DEFINITION.  This project's own statement, as for mphip_derive_met (the reference's source was not available),
+ * restated independently in tests/refdetrend.py.  RE, RAD and M_PI as above; cos, sin and exp are the C library's;
+ * products, quotients and sums from left to right as written.  DX2DEG(dx,lat) = (lat < -89.999 || lat > 89.999) ? 0 : dx
+ * 180. / (M_PI RE cos(RAD(lat))).  DY2DEG(dy) = dy 180. / (M_PI RE).  geo2cart(z,lon,lat) = ((RE+z) cos(RAD(lat))
+ * cos(RAD(lon)), (RE+z) cos(RAD(lat)) sin(RAD(lon)), (RE+z) sin(RAD(lat))).  DIST2(a,b) = (a0-b0)(a0-b0) + (a1-b1)(a1-b1)
+ * + (a2-b2)(a2-b2).
+ *   In double: sigma = met_detrend / 2.355; tssq = 2. sigma sigma; dlon = |lon[1]-lon[0]|, dlat = |lat[1]-lat[0]|; sy =
+ * (int) (3. DY2DEG(sigma) / dlat) limited to [1, ny/2]; per row iy: sx(iy) = (int) (3. DX2DEG(sigma, lat[iy]) / dlon)
+ * limited to [1, nx/2] (integer halves; a quotient that is not below the upper limit gives the upper limit, so nothing
+ * depends on converting a value beyond the int range).  Next to the poles DX2DEG is 0 and sx = 1.
+ *   Weights: w(iy, iy2, d) = (float) exp(-D2 / tssq) with D2 = DIST2(geo2cart(0, 0, lat[iy]), geo2cart(0, d dlon,
+ * lat[iy2])) and d = |ix - ix2|: the weight depends on the row pair and the longitude offset only.  The reference
+ * evaluates geo2cart at the actual longitudes lon[ix], lon[ix2]; on a regular axis the two agree in exact arithmetic (the
+ * distance of two points depends on their longitude difference only), not always in the last bit.  This form was chosen
+ * because it makes the weights one table per call -- sum over iy of (rows in range) (sx(iy) + 1) floats, built on the
+ * host with the C library as the tropopause's tables are, so both libraries and the restatement use the same bits --,
+ * leaves no exp inside the stencil, and makes the weight uniform across a wave (one row per workgroup: a scalar
+ * operand).
+ *   Accumulation, for every point (ix, iy, ip) of every present field f: float b = 0, ws = 0; for ix2 = ix-sx ... ix+sx
+ * (outer loop; ix3 = ix2 wrapped once by +-nx, on regional grids too and with a periodic extra column present), iy2 =
+ * max(iy-sy,0) ... min(iy+sy,ny-1) (inner loop): ws += w; b += w f[ix3][iy2][ip] (the product rounded to float before
+ * the sum, never contracted).  out = f[ix][iy][ip] - b / ws, float throughout.  Every value enters: a NaN or an infinity
+ * spreads as IEEE arithmetic gives it.  Both libraries return these bits (the division is IEEE in both).
+ *   Refused: a NULL argument or axis (lon, lat, p); nx < 2, ny < 2, np < 2; nx ny >= 2^24 or nx ny np >= 2^31; strides
+ * that do not hold the extents; coord_type != 0; a met_detrend that is not finite or <= 0; dlon or dlat zero or not
+ * finite; none of the four fields present on both sides.  Nothing is refused for a large half-width. */
+typedef struct {
+  double met_detrend;                   /* full width at half maximum of the background's Gaussian [km] */
+} mphip_detrend_t;
+size_t mphip_sizeof_detrend(void);      /* sizeof(mphip_detrend_t), for mirrors of the structure in other languages */
+int mphip_detrend_met(mphip_ctx *ctx, const mphip_met_t *in, const mphip_detrend_t *opt, const mphip_regrid_out_t *out);
 
 /* mptrac_update_device(..., atm), mptrac.c:8050-8055.  This process owns the
  * particles [ip0, ip0 + np) of a simulation with np_total particles; random
@@ -722,9 +765,10 @@ int mphip_comm_query(mphip_ctx *ctx, int *nranks, int *rank);
  *     permutation
  *   "big_grid" (default 0): tests -- take the instantiations with 64-bit byte offsets into the packed meteo records (what a
  *     grid with more than 4 GB of wind records -- 178e6 cells -- takes by itself) on a grid that fits 32 bits too: same bits.
- *   "derive_profile_phase" (default 0; 1, 2): measurement -- what mphip_profile_begin / _end time of a mphip_derive_met
+ *   "derive_profile_phase" (default 0; 1, 2, 3): measurement -- what mphip_profile_begin / _end time of a mphip_derive_met
  *     call: every kernel (0), the uploads (1) or the downloads (2), as event pairs on the call's own stream (a caller that
- *     profiles does not step from another thread meanwhile). */
+ *     profiles does not step from another thread meanwhile); 3: the host's build of the weight table in
+ *     mphip_detrend_met (the stream is idle meanwhile, so the pair of events brackets the host's time). */
 int mphip_set_option(mphip_ctx *ctx, const char *name, double value);
 int mphip_synchronize(mphip_ctx *ctx);
 

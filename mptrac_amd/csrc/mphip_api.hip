@@ -18,6 +18,7 @@
 #include "mphip_kernels.hpp"
 #include "mphip_metprep.hpp"
 #include "mphip_regrid.hpp"
+#include "mphip_detrend.hpp"
 
 using namespace mphip;
 
@@ -298,6 +299,11 @@ struct mphip_ctx {
   RegridBuf rg_in3[MPHIP_N3D], rg_mid3[MPHIP_N3D], rg_out3[MPHIP_N3D], rg_in2[MPHIP_N2D], rg_out2[MPHIP_N2D];
   double *rg_p = nullptr;             // met_p on the device
   size_t rg_p_n = 0;
+  // mphip_detrend_met (prep_stream, prep_lock): the uploaded fields, the results, the weight table and its row records;
+  // each array grows to the largest size asked for and is kept
+  RegridBuf dt_in[kDtFields], dt_out[kDtFields], dt_w;
+  DetrendRow *dt_rows = nullptr;
+  size_t dt_rows_n = 0;
 
   // profiling of the fused step kernel
   bool prof = false;
@@ -3023,6 +3029,149 @@ const char *regrid_plan(const mphip_met_t *in, unsigned what, const mphip_regrid
   return nullptr;
 }
 
+// ---- mphip_detrend_met: scratch, the checks and the weight table -----------------------------------------------------
+void detrend_release(mphip_ctx *ctx) {
+  for (auto *b : { &ctx->dt_w, &ctx->dt_in[0], &ctx->dt_in[1], &ctx->dt_in[2], &ctx->dt_in[3], &ctx->dt_out[0],
+                   &ctx->dt_out[1], &ctx->dt_out[2], &ctx->dt_out[3] }) {
+    dev_free(b->p);
+    *b = mphip_ctx::RegridBuf();
+  }
+  dev_free(ctx->dt_rows);
+  ctx->dt_rows = nullptr;
+  ctx->dt_rows_n = 0;
+}
+
+const int kDetrendFields[kDtFields] = { MPHIP_T, MPHIP_U, MPHIP_V, MPHIP_W };
+
+struct DetrendPlan {
+  int nx, ny, np, sy, nchunk;
+  double tssq, dlon;
+  std::vector<DetrendRow> rows;      // (ws is filled by detrend_weights)
+  size_t nw;                         // floats of the table
+  double taps_mean;                  // window sizes over the rows
+  long long taps_max;
+};
+
+// everything that can be refused for the grid and the option (the axes are there); NULL = accepted
+const char *detrend_plan(const mphip_met_t *in, const mphip_detrend_t *opt, DetrendPlan *P) {
+#pragma clang fp contract(off)
+  if (in->nx < 2 || in->ny < 2)
+    return "meteo grid dimensions out of range";
+  if (in->np < 2)
+    return "needs two pressure levels or more (np < 2)";
+  if ((long long) in->nx * in->ny >= (1LL << 24) || (long long) in->nx * in->ny * in->np >= (1LL << 31))
+    return "meteo grid too large for the device index arithmetic";
+  if (in->coord_type != 0)
+    return "needs a longitude / latitude grid (coord_type != 0)";
+  if (!(opt->met_detrend > 0 && opt->met_detrend < INFINITY))
+    return "met_detrend must be finite and positive";
+  const double dlon = fabs(in->lon[1] - in->lon[0]), dlat = fabs(in->lat[1] - in->lat[0]);
+  if (!(dlon > 0 && dlon < INFINITY) || !(dlat > 0 && dlat < INFINITY))
+    return "the grid spacing (dlon, dlat) must be finite and not zero";
+  const int nx = in->nx, ny = in->ny;
+  P->nx = nx;
+  P->ny = ny;
+  P->np = in->np;
+  P->dlon = dlon;
+  const double sigma = opt->met_detrend / 2.355;
+  P->tssq = 2. * sigma * sigma;
+  // (the limits are applied before the conversion to int: a quotient beyond the int range is the upper limit)
+  auto half_width = [](double v, int hi) {
+    const int s = !(v < hi) ? hi : (int) v;
+    return s < 1 ? 1 : s;
+  };
+  const double dy_deg = sigma * 180. / (M_PI * 6367.421);                                      // DY2DEG(sigma)
+  P->sy = half_width(3. * dy_deg / dlat, ny / 2);
+  const long long ngroup = (nx + kDtTX - 1) / kDtTX;
+  P->nchunk = (int) ((ngroup * in->np + kDtThreads - 1) / kDtThreads);
+  if ((long long) P->nchunk * ny >= (1LL << 31))
+    return "meteo grid too large for the device index arithmetic";
+  P->rows.resize((size_t) ny);
+  size_t nw = 0;
+  double taps = 0;
+  P->taps_max = 0;
+  for (int iy = 0; iy < ny; iy++) {
+    const double lat = in->lat[iy];
+    const double dx_deg = (lat < -89.999 || lat > 89.999) ? 0. : sigma * 180. / (M_PI * 6367.421 * cos(lat * (M_PI / 180.0)));
+    DetrendRow &R = P->rows[(size_t) iy];
+    R.sx = half_width(3. * dx_deg / dlon, nx / 2);
+    R.ylo = std::max(iy - P->sy, 0);
+    R.nr = std::min(iy + P->sy, ny - 1) - R.ylo + 1;
+    R.off = (long long) nw;
+    R.ws = 0.f;
+    nw += (size_t) R.nr * (size_t) (R.sx + 1);
+    const long long t = (long long) R.nr * (2LL * R.sx + 1);
+    taps += (double) t;
+    P->taps_max = std::max(P->taps_max, t);
+  }
+  P->nw = nw + kDtTX;      // (padding: the kernel loads kDtTX entries at a time and ignores those beyond a row)
+  P->taps_mean = taps / ny;
+  return nullptr;
+}
+
+// the weights of the rows [iy0, iy1) and their sums: double arithmetic with the host's C library, each weight rounded to
+// float once; ws by serial float additions in the order of the stencil's loops (ix2 ascending, iy2 ascending inside)
+void detrend_weights(const DetrendPlan &P, const double *cphi, const double *sphi, const double *clam, const double *slam,
+                     int iy0, int iy1, DetrendRow *rows, float *w) {
+#pragma clang fp contract(off)
+  const double re = 6367.421 + 0.0;
+  for (int iy = iy0; iy < iy1; iy++) {
+    DetrendRow &R = rows[iy];
+    float *wr = w + R.off;
+    const double x0[3] = { re * cphi[iy] * clam[0], re * cphi[iy] * slam[0], re * sphi[iy] };
+    for (int r = 0; r < R.nr; r++) {
+      const int iy2 = R.ylo + r;
+      for (int d = 0; d <= R.sx; d++) {
+        const double x1[3] = { re * cphi[iy2] * clam[d], re * cphi[iy2] * slam[d], re * sphi[iy2] };
+        const double d2 = (x0[0] - x1[0]) * (x0[0] - x1[0]) + (x0[1] - x1[1]) * (x0[1] - x1[1])
+          + (x0[2] - x1[2]) * (x0[2] - x1[2]);
+        wr[(size_t) r * (R.sx + 1) + d] = (float) exp(-d2 / P.tssq);
+      }
+    }
+    float ws = 0.f;
+    for (int e = -R.sx; e <= R.sx; e++)
+      for (int r = 0; r < R.nr; r++)
+        ws = ws + wr[(size_t) r * (R.sx + 1) + (e < 0 ? -e : e)];
+    R.ws = ws;
+  }
+}
+
+void detrend_table(const mphip_met_t *in, DetrendPlan &P, std::vector<float> &w) {
+#pragma clang fp contract(off)
+  const int ny = P.ny, nd = P.nx / 2 + 1;
+  std::vector<double> cphi((size_t) ny), sphi((size_t) ny), clam((size_t) nd), slam((size_t) nd);
+  for (int iy = 0; iy < ny; iy++) {
+    const double phi = in->lat[iy] * (M_PI / 180.0);
+    cphi[(size_t) iy] = cos(phi);
+    sphi[(size_t) iy] = sin(phi);
+  }
+  for (int d = 0; d < nd; d++) {
+    const double lam = ((double) d * P.dlon) * (M_PI / 180.0);
+    clam[(size_t) d] = cos(lam);
+    slam[(size_t) d] = sin(lam);
+  }
+  w.resize(P.nw);
+  // the rows are independent: a large table is built by a few threads, each on rows of about equal table share
+  const int nthreads = P.nw < (1u << 20) ? 1 : 8;
+  std::vector<std::thread> pool;
+  int iy0 = 0;
+  for (int t = 0; t < nthreads; t++) {
+    int iy1 = iy0;
+    const size_t upto = P.nw / nthreads * (size_t) (t + 1);
+    while (iy1 < ny && (t == nthreads - 1 || (size_t) P.rows[(size_t) iy1].off < upto))
+      iy1++;
+    if (t == nthreads - 1)
+      detrend_weights(P, cphi.data(), sphi.data(), clam.data(), slam.data(), iy0, iy1, P.rows.data(), w.data());
+    else if (iy1 > iy0)
+      pool.emplace_back([&, iy0, iy1] {
+        detrend_weights(P, cphi.data(), sphi.data(), clam.data(), slam.data(), iy0, iy1, P.rows.data(), w.data());
+      });
+    iy0 = iy1;
+  }
+  for (auto &th : pool)
+    th.join();
+}
+
 }   // namespace
 
 // ---------------------------------------------------------------------------
@@ -3102,6 +3251,7 @@ void mphip_destroy(mphip_ctx *ctx) {
   }
   prep_release(ctx);
   regrid_release(ctx);
+  detrend_release(ctx);
   if (ctx->prep_stream)
     (void) hipStreamDestroy(ctx->prep_stream);
   dev_free(ctx->d_clim);
@@ -4178,6 +4328,108 @@ int mphip_regrid_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const
     memcpy(out->lat, lat2.data(), lat2.size() * sizeof(double));
   if (out->p)
     memcpy(out->p, p2.data(), p2.size() * sizeof(double));
+  return 0;
+}
+
+size_t mphip_sizeof_detrend(void) {
+  return sizeof(mphip_detrend_t);
+}
+
+int mphip_detrend_met(mphip_ctx *ctx, const mphip_met_t *in, const mphip_detrend_t *opt, const mphip_regrid_out_t *out) {
+  if (!ctx || !in || !opt || !out)
+    return fail(ctx, "mphip_detrend_met: null argument");
+  if (!in->lon || !in->lat || !in->p)
+    return fail(ctx, "mphip_detrend_met: the input axes are missing");
+  DetrendPlan P;
+  if (const char *why = detrend_plan(in, opt, &P))
+    return fail(ctx, std::string("mphip_detrend_met: ") + why);
+  if (!regrid_strides_ok(P.ny, P.np, in->sx, in->sy))
+    return fail(ctx, "mphip_detrend_met: unsupported meteo strides");
+  if (!regrid_strides_ok(P.ny, P.np, out->sx, out->sy))
+    return fail(ctx, "mphip_detrend_met: the output strides do not hold the grid");
+  int fld[kDtFields], nf = 0;
+  for (int i = 0; i < kDtFields; i++)
+    if (in->f3[kDetrendFields[i]] && out->f3[kDetrendFields[i]])
+      fld[nf++] = kDetrendFields[i];
+  if (!nf)
+    return fail(ctx, "mphip_detrend_met: none of the fields t, u, v, w is present in both `in` and `out`");
+
+  std::lock_guard<std::mutex> guard(ctx->prep_lock);
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!ctx->prep_stream)
+    HIPCHK(hipStreamCreateWithFlags(&ctx->prep_stream, hipStreamNonBlocking));
+  hipStream_t st = ctx->prep_stream;
+  hipEvent_t ev_stop = nullptr;
+  auto mark_begin = [&](int phase) {
+    ev_stop = nullptr;
+    if (!ctx->prof || ctx->prep_profile_phase != phase)
+      return 0;
+    while (ctx->ev_used + 2 > ctx->ev.size()) {
+      hipEvent_t e;
+      HIPCHK(hipEventCreate(&e));
+      ctx->ev.push_back(e);
+    }
+    HIPCHK(hipEventRecord(ctx->ev[ctx->ev_used++], st));
+    ev_stop = ctx->ev[ctx->ev_used++];
+    return 0;
+  };
+  auto mark_end = [&]() {
+    if (ev_stop)
+      HIPCHK(hipEventRecord(ev_stop, st));
+    return 0;
+  };
+  // the weight table (host; the stream is idle meanwhile, so the two events around it give the host's time)
+  if (mark_begin(3))
+    return 1;
+  std::vector<float> w;
+  detrend_table(in, P, w);
+  if (mark_end())
+    return 1;
+  // uploads
+  if (mark_begin(1))
+    return 1;
+  const size_t ncell = (size_t) P.nx * P.ny * P.np;
+  if (regrid_reserve(ctx, ctx->dt_w, P.nw))
+    return 1;
+  if (ctx->dt_rows_n < (size_t) P.ny) {
+    ctx->dt_rows_n = 0;
+    if (dev_alloc(ctx, &ctx->dt_rows, (size_t) P.ny))
+      return 1;
+    ctx->dt_rows_n = (size_t) P.ny;
+  }
+  HIPCHK(hipMemcpyAsync(ctx->dt_w.p, w.data(), P.nw * sizeof(float), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(ctx->dt_rows, P.rows.data(), (size_t) P.ny * sizeof(DetrendRow), hipMemcpyHostToDevice, st));
+  DetrendFields F;
+  memset(&F, 0, sizeof(F));
+  F.n = nf;
+  for (int i = 0; i < nf; i++) {
+    if (regrid_reserve(ctx, ctx->dt_in[i], ncell) || regrid_reserve(ctx, ctx->dt_out[i], ncell)
+        || regrid_copy3(ctx, ctx->dt_in[i].p, in->f3[fld[i]], P.nx, P.ny, P.np, in->sx, in->sy, true, st))
+      return 1;
+    F.in[i] = ctx->dt_in[i].p;
+    F.out[i] = ctx->dt_out[i].p;
+  }
+  if (mark_end())
+    return 1;
+  // (the table and the row records are this call's own vectors, and an aliased input must have been read before the
+  // first download overwrites it: the uploads are complete here)
+  HIPCHK(hipStreamSynchronize(st));
+
+  if (mark_begin(0))
+    return 1;
+  hipLaunchKernelGGL(detrend_kernel, dim3((unsigned) ((long long) P.nchunk * P.ny), (unsigned) nf), dim3(kDtThreads), 0, st,
+                     P.nx, P.ny, P.np, ctx->dt_rows, ctx->dt_w.p, F);
+  HIPCHK(hipGetLastError());
+  if (mark_end())
+    return 1;
+  if (mark_begin(2))
+    return 1;
+  for (int i = 0; i < nf; i++)
+    if (regrid_copy3(ctx, ctx->dt_out[i].p, out->f3[fld[i]], P.nx, P.ny, P.np, out->sx, out->sy, false, st))
+      return 1;
+  if (mark_end())
+    return 1;
+  HIPCHK(hipStreamSynchronize(st));
   return 0;
 }
 
@@ -5440,8 +5692,9 @@ int mphip_set_option(mphip_ctx *ctx, const char *name, double value) {
     return 0;
   }
   if (strcmp(name, "derive_profile_phase") == 0) {
-    if (value != 0 && value != 1 && value != 2)
-      return fail(ctx, "derive_profile_phase must be 0 (kernels), 1 (uploads) or 2 (downloads)");
+    if (value != 0 && value != 1 && value != 2 && value != 3)
+      return fail(ctx, "derive_profile_phase must be 0 (kernels), 1 (uploads), 2 (downloads) or 3 (the weight table of "
+                       "mphip_detrend_met)");
     ctx->prep_profile_phase = (int) value;
     return 0;
   }

@@ -76,6 +76,14 @@ REGRID_ML = ("t", "u", "v", "w", "h2o", "o3", "lwc", "rwc", "iwc", "swc", "cc") 
 REGRID_PL = REGRID_ML + ("z", "pv")                                                  # what SAMPLE takes
 
 
+class MphipDetrend(C.Structure):
+    """mphip_detrend_t: the option of mphip_detrend_met."""
+    _fields_ = [("met_detrend", C.c_double)]
+
+
+DETREND_FIELDS = ("t", "u", "v", "w")
+
+
 class Snapshot:
     """What Simulation.regrid_met returns: the axes (float64) and the float32 fields of the new shape, named as in
     synth.Met (`strides` = (sx, sy, sx2) in floats where the arrays are views into larger ones)."""
@@ -161,6 +169,11 @@ def load(build=True):
         L.mphip_sizeof_regrid.restype = C.c_size_t
         if L.mphip_sizeof_regrid() != C.sizeof(MphipRegrid):
             raise MphipError("mphip_regrid_t layout mismatch between header and Python mirror")
+    if hasattr(L, "mphip_detrend_met"):     # (absent from libraries built before the detrending: A/B runs through MPHIP_LIB)
+        L.mphip_detrend_met.argtypes = [C.c_void_p, C.POINTER(MphipMet), C.POINTER(MphipDetrend), C.POINTER(MphipRegridOut)]
+        L.mphip_sizeof_detrend.restype = C.c_size_t
+        if L.mphip_sizeof_detrend() != C.sizeof(MphipDetrend):
+            raise MphipError("mphip_detrend_t layout mismatch between header and Python mirror")
     if hasattr(L, "mphip_sizeof_prep"):     # (absent from libraries built before pv and the tropopause: they read the old members)
         L.mphip_sizeof_prep.restype = C.c_size_t
         if L.mphip_sizeof_prep() != C.sizeof(MphipPrep):
@@ -461,6 +474,39 @@ class Simulation:
                     f2[f] = a
         self._chk(self.L.mphip_regrid_met(self.h, C.byref(m), bits, C.byref(o), C.byref(mo)))
         return Snapshot(met.time, met.coord_type, lon, lat, p, f3, f2, out_strides)
+
+    def detrend_met(self, met, met_detrend, fields=None, out=None, out_strides=None):
+        """Detrending (mphip_detrend_met): the Gaussian-weighted horizontal mean of full width at half maximum
+        `met_detrend` [km] is subtracted from t, u, v and w.  `met`: a pressure-level snapshot with the conventions of
+        derive_met.  `fields`: the names to detrend (default: those of t, u, v, w the snapshot has).  `out`: {name:
+        float32 array of the snapshot's shape to write into} -- an input array itself for in-place use; views into
+        larger arrays name their strides in floats as `out_strides` = (sx, sy), which then hold for every output array
+        (tests); by default new compact arrays.  Returns {name: array} of the detrended fields."""
+        m = self._met_struct(met)
+        o = MphipDetrend(float(met_detrend))
+        mo = MphipRegridOut()
+        mo.sx, mo.sy = out_strides or (met.ny * met.np, met.np)
+        mo.sx2 = met.ny
+        names = DETREND_FIELDS if fields is None else tuple(fields)
+        if any(f not in FIELDS_3D for f in names):
+            raise TypeError(f"unknown fields {sorted(set(names) - set(FIELDS_3D))}")
+        res = {}
+        for f in names:
+            if out is not None and f in out:
+                a = out[f]
+            elif f in met.f3:
+                a = np.empty((met.nx, met.ny, met.np), dtype=np.float32)
+            else:
+                continue
+            assert a.dtype == np.float32 and a.shape == (met.nx, met.ny, met.np) and a.strides == (4 * mo.sx, 4 * mo.sy, 4), f
+            mo.f3[FIELDS_3D.index(f)] = _ptr(a, _fp)
+            if f in met.f3 and f in DETREND_FIELDS:
+                res[f] = a
+        for i, k in enumerate(FIELDS_3D):       # (a field that was not asked for is not passed: NULL on the input side too)
+            if k in DETREND_FIELDS and k not in names:
+                m.f3[i] = None
+        self._chk(self.L.mphip_detrend_met(self.h, C.byref(m), C.byref(o), C.byref(mo)))
+        return res
 
     def set_met(self, slot, met):
         m = self._met_struct(met)

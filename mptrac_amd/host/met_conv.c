@@ -5,7 +5,9 @@
  * by default and no device is involved; with HIP_MET_PREP 1 the device derives the geopotential heights, the ozone
  * column, the boundary-layer pressure, the cloud layer and CAPE / CIN with their levels from the file's fields
  * (mphip_derive_met), and the output carries them: every plane of a MET_TYPE 1 file, the surface variables of a netCDF
- * file.  With HIP_MET_PREP 2 also potential vorticity and the tropopause of MET_TROPO (pt, tt, zt, h2ot).
+ * file.  With HIP_MET_PREP 2 also potential vorticity and the tropopause of MET_TROPO (pt, tt, zt, h2ot), and with
+ * MET_DETREND > 0 the planes t, u, v, w of either output format are the detrended ones (mphip_detrend_met, applied last:
+ * the derived fields are those of the full fields).
  *
  *   met_conv <ctl> <met_in> <met_in_type> <met_out> <met_out_type> [KEY VALUE ...]
  */

@@ -430,15 +430,21 @@ void mptrac_read_ctl(const char *filename, int argc, char *argv[], ctl_t *ctl) {
     ? scan_ctl(filename, argc, argv, "MET_UTM_REF_LON", -1, "", NULL) : 0;
   REQUIRE(ctl->direction == -1 || ctl->direction == 1, "Set DIRECTION to -1 or 1!");
   if (ctl->met_type == 0) {
-    /* netCDF input is taken as stored: no detrending, no hybrid-coefficient levels (mptrac.c:7770-7830) ... */
+    /* netCDF input is taken as stored: no hybrid-coefficient levels (mptrac.c:7770-7830) ... */
     static const struct {
       const char *key, *def;
-    } untouched[] = { { "MET_DETREND", "-999" }, { "MET_CLAMS", "0" }, { "MET_CONVENTION", "0" }, { "MET_RELHUM", "0" },
-      { NULL, NULL } };
+    } untouched[] = { { "MET_CLAMS", "0" }, { "MET_CONVENTION", "0" }, { "MET_RELHUM", "0" }, { NULL, NULL } };
     for (int k = 0; untouched[k].key; k++)
       if (scan_ctl(filename, argc, argv, untouched[k].key, -1, untouched[k].def, NULL) != atof(untouched[k].def))
         ERRMSG("%s: the meteo preprocessing of the reference is not part of this build (netCDF input is used as stored)!",
                untouched[k].key);
+    /* ... but for detrending, which the device does (mphip_detrend_met) when HIP_MET_PREP is 2: MET_DETREND is the
+     * full width at half maximum of the background's Gaussian in km, any value <= 0 (the default -999) means off */
+    ctl->met_detrend = scan_ctl(filename, argc, argv, "MET_DETREND", -1, "-999", NULL);
+    REQUIRE(isfinite(ctl->met_detrend), "MET_DETREND must be a finite number (<= 0: no detrending)!");
+    if (ctl->met_detrend > 0 && ctl->hip_met_prep != 2)
+      ERRMSG("MET_DETREND: the meteo preprocessing of the reference is not part of this build (netCDF input is used as "
+             "stored; HIP_MET_PREP 2 detrends it on the device)!");
     /* ... but for down-sampling with smoothing and model-level input, which the device does (mphip_regrid_met) when
      * HIP_MET_PREP is 1 or 2 */
     static const char *const regrid[] = { "MET_DX", "MET_DY", "MET_DP", "MET_SX", "MET_SY", "MET_SP", NULL };
@@ -474,6 +480,7 @@ void mptrac_read_ctl(const char *filename, int argc, char *argv[], ctl_t *ctl) {
   } else {
     ctl->met_dx = ctl->met_dy = ctl->met_dp = ctl->met_sx = ctl->met_sy = ctl->met_sp = 1;
     ctl->met_vert_coord = ctl->met_np = 0;
+    ctl->met_detrend = -999;
   }
 
   /* modules (mptrac.c:7196-7263) */
@@ -623,6 +630,8 @@ void mptrac_read_ctl(const char *filename, int argc, char *argv[], ctl_t *ctl) {
       && (ctl->met_dx != 1 || ctl->met_dy != 1 || ctl->met_dp != 1 || ctl->met_sx != 1 || ctl->met_sy != 1 || ctl->met_sp != 1))
     ERRMSG("ADVECT_VERT_COORD = 2 with MET_DX / MET_DY / MET_DP / MET_SX / MET_SY / MET_SP other than 1: the model-level "
            "fields are not sampled!");
+  if (ctl->advect_vert_coord == 2 && ctl->met_detrend > 0)
+    ERRMSG("ADVECT_VERT_COORD = 2 with MET_DETREND > 0: the model-level winds are not detrended!");
   if (ctl->advect_vert_coord == 1)
     ERRMSG("Please use meteo files in netcdf format for diabatic calculations.");           /* mptrac.c:7031 */
   if (ctl->advect_vert_coord == 3)
@@ -1757,6 +1766,7 @@ typedef struct {
 
 static unsigned met_derive(const ctl_t *ctl, const clim_t *clim, met_t *met, const nc_have_t *have);
 static void met_regrid(const ctl_t *ctl, met_t *met, unsigned what);
+static void met_detrend(const ctl_t *ctl, met_t *met);
 
 static int read_met_nc(const char *filename, const ctl_t *ctl, const clim_t *clim, met_t *met) {
   char err[256];
@@ -1945,6 +1955,10 @@ static int read_met_nc(const char *filename, const ctl_t *ctl, const clim_t *cli
                ctl->qnt_name[iq], derived[k].bit & (MPHIP_PREP_PV | MPHIP_PREP_TROPO) ?
                " without HIP_MET_PREP 2 and the fields it is derived from" :
                " without HIP_MET_PREP 1 and the fields it is derived from");
+  /* detrending comes last (this project's choice of order): z, pv, the tropopause, the cloud layer and CAPE above are
+   * those of the full fields; t, u, v, w on the pressure levels become perturbations, ul, vl, wl, pl are not touched */
+  if (ctl->met_detrend > 0)
+    met_detrend(ctl, met);
   return 1;
 }
 
@@ -2279,6 +2293,31 @@ static void met_regrid(const ctl_t *ctl, met_t *met, unsigned what) {
   if (what & MPHIP_REGRID_SAMPLE) {
     LOG(2, "Sampled on the device: %d x %d x %d", nx2, ny2, np2);
   }
+}
+
+/* HIP_MET_PREP 2 with MET_DETREND > 0: t, u, v and w of the snapshot the netCDF reader has filled, detrended in place on
+ * the device (mphip_detrend_met, which uploads every input before it writes an output).  Like met_derive it may run on
+ * the read-ahead thread; the context exists by then. */
+static void met_detrend(const ctl_t *ctl, met_t *met) {
+  REQUIRE(ctl->hip_met_prep == 2, "MET_DETREND needs HIP_MET_PREP 2 (got %d)!", ctl->hip_met_prep);
+  need_ctx(ctl);
+  mphip_met_t in;
+  describe_met(met, &in);
+  in.npl = 0;
+  mphip_regrid_out_t out;
+  memset(&out, 0, sizeof(out));
+  out.sx = in.sx;
+  out.sy = in.sy;
+  out.sx2 = in.sx2;
+  out.f3[MPHIP_T] = &met->t[0][0][0];
+  out.f3[MPHIP_U] = &met->u[0][0][0];
+  out.f3[MPHIP_V] = &met->v[0][0][0];
+  out.f3[MPHIP_W] = &met->w[0][0][0];
+  const mphip_detrend_t opt = { ctl->met_detrend };
+  /* (not through HIP(): that macro first submits the main thread's queued time steps) */
+  if (mphip_detrend_met(g_ctx, &in, &opt, &out) != 0)
+    ERRMSG("HIP back end: %s", mphip_last_error(g_ctx));
+  LOG(2, "Detrended on the device: t, u, v, w minus a background of %g km", ctl->met_detrend);
 }
 
 /* Read-ahead of the next meteo file (HIP_MET_PREFETCH 1, forward runs): while the time steps of the current

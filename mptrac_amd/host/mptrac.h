@@ -155,6 +155,9 @@ typedef struct {
   int met_dx, met_dy, met_dp, met_sx, met_sy, met_sp;
   int met_vert_coord, met_np;
   double met_p[EP];
+  /* ... and of the detrending of netCDF input on the device (mphip_detrend_met; HIP_MET_PREP 2): MET_DETREND, the full
+   * width at half maximum [km] of the Gaussian-weighted background that is subtracted from t, u, v, w; <= 0: off */
+  double met_detrend;
   double t_start, t_stop, dt_mod, dt_met, met_utm_ref_lat, met_utm_ref_lon, met_dt_out;
   /* zonal-mean climatologies module_meteo samples (mptrac.c:7461-7470) and the diurnal scaling of OH (mptrac.c:7394) */
   char clim_hno3_filename[LEN], clim_oh_filename[LEN], clim_h2o2_filename[LEN], clim_ho2_filename[LEN],
