@@ -726,6 +726,11 @@ int mphip_comm_query(mphip_ctx *ctx, int *nranks, int *rank);
  *   module set, no module_isosurf) has no gather pass of its own: the launch reads the particles through the sort's
  *   permutation and takes the due step with the others; 0 = the re-sort gathers in its own pass and its step is a
  *   launch of its own, as in mphip_run_timestep.  Not observable;
+ *   "turb_strat" (default 1): module_diff_turb in the lean kernels with 32-bit offsets: a wavefront whose particles all
+ *   lie above the boundary layer and above 0.866877899 x the smallest tropopause pressure the climatology can give at
+ *   any time and any latitude in [-90, 90] (1 % margin; with TURB_DX_STRAT 0, finite parameters >= 0, MET_COORD_TYPE
+ *   0) takes the stratosphere's TURB_DZ_STRAT directly, without the tropopause look-up, the weights and the first pair
+ *   of normals; 0 = every wavefront evaluates them.  Not observable;
  *   "pin_host_atm" (default 0): page-lock the caller's particle arrays handed to
  *   mphip_update_atm / mphip_get_atm with one registration spanning them (for
  *   a persistent atm_t whose arrays lie in one allocation);

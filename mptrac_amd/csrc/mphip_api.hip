@@ -64,6 +64,7 @@ struct mphip_ctx {
   mphip_ctl_t ctl;
   bool have_ctl = false;
   DevClim *d_clim = nullptr;
+  DevClim h_clim = {};               // host copy of *d_clim (DevMet::strat_skip)
   bool have_clim = false;
   double *d_zm[MPHIP_NZM] = {};      // zonal-mean climatologies: [time | p | lat | vmr] each
   DevZm zm[MPHIP_NZM] = {};
@@ -181,6 +182,7 @@ struct mphip_ctx {
   size_t prec_cap = 0;
   int multi_step = 64;                // mphip_run_timesteps: most time steps per launch (0 = always one by one)
   bool fold_resort = true;            // ... and a launch that follows the locality re-sort does its gather (0: a pass of its own)
+  bool turb_strat = true;             // module_diff_turb's short path above every tropopause (DevMet::strat_skip; 0: never taken)
   bool force_generic = false;
   bool compact_depo = true;           // deposition-only launches through depo_kernel (0: the fused kernel's tail)
   int sort_bits = 0;                  // digit width of the radix sort (0 = fewest passes; 8, 9, 10: tuning / tests)
@@ -400,6 +402,39 @@ static bool weights_stay_inside(int coord_type, double first, double last) {
   return coord_type != 0 || (last - first >= 360.0 && first <= 0.0 && first >= -360.0);
 }
 
+// The smallest tropopause pressure clim_tropo_at can return at a latitude in [-90, 90] and a second of the year in
+// [0, 365.25 d].  Inside a latitude interval the value lies between the interval's nodes; in time it is A + s (B - A),
+// linear in s, with s in [0, 1] inside the month axis and beyond that before the first and behind the last node (the
+// first and the last interval are continued to the ends of the year).  So the minimum is at a latitude node and at an
+// end of s of some month interval.  +inf (no bound) for a table the argument does not cover.
+static double clim_tropo_min(const DevClim &h) {
+  const double year = 365.25 * 86400.;
+  if (h.ntime < 2 || h.nlat < 2 || !(h.lat[0] <= -90.0 && h.lat[h.nlat - 1] >= 90.0))
+    return HUGE_VAL;
+  for (int i = 0; i + 1 < h.ntime; i++)
+    if (!(h.time[i] < h.time[i + 1]))
+      return HUGE_VAL;
+  for (int j = 0; j + 1 < h.nlat; j++)
+    if (!(h.lat[j] < h.lat[j + 1]))
+      return HUGE_VAL;
+  double lo = HUGE_VAL;
+  for (int i = 0; i + 1 < h.ntime; i++) {
+    const double w = h.time[i + 1] - h.time[i];
+    const double s0 = i == 0 ? std::min(0.0, (0.0 - h.time[0]) / w) : 0.0;
+    const double s1 = i + 2 == h.ntime ? std::max(1.0, (year - h.time[i]) / w) : 1.0;
+    for (int j = 0; j < h.nlat; j++) {
+      const double a = h.tropo[i][j], b = h.tropo[i + 1][j];
+      for (double s : { s0, s1 }) {
+        const double v = a + s * (b - a);
+        if (!(v == v))
+          return HUGE_VAL;
+        lo = std::min(lo, v);
+      }
+    }
+  }
+  return lo;
+}
+
 DevMet dev_met(const mphip_ctx *c) {
   DevMet M;
   M.wind = c->pk.wind;
@@ -498,6 +533,25 @@ DevMet dev_met(const mphip_ctx *c) {
   // such a domain within the step still has its dt.  No shortcut there (tests/depo_cases.py: extrap-regional-*).
   if (!weights_stay_inside(c->coord_type, c->h_lon[0], c->h_lon[c->nx - 1]))
     M.ps_skip = M.pct_skip = M.turb_skip = M.conv_skip = -HUGE_VAL;
+  // module_diff_turb's short path (diff_turb_fast): below this pressure, at a latitude in [-90, 90], a particle is
+  // above 0.866877899 x every tropopause pressure of the climatology -- tropo_weight_pt's upper edge.  It needs what
+  // the boundary-layer bound needs, parameters with which "weight 1 of the stratosphere" means its parameters exactly
+  // (finite, not negative; a finite transition factor of pbl_weight), no horizontal diffusion there (the path takes no
+  // horizontal step), the tropopause looked up at the particle's latitude, and an axis top (where the probes of the Kz
+  // gradient are clamped to) inside both regimes.
+  M.strat_skip = -HUGE_VAL;
+  if (c->turb_strat && c->have_ctl && c->have_clim && M.turb_skip > -HUGE_VAL && c->ctl.met_coord_type == 0) {
+    const mphip_ctl_t &k = c->ctl;
+    bool ok = std::isfinite(k.turb_pbl_trans);
+    for (double v : { k.turb_dx_pbl, k.turb_dx_trop, k.turb_dx_strat, k.turb_dz_pbl, k.turb_dz_trop, k.turb_dz_strat })
+      ok = ok && std::isfinite(v) && v >= 0;
+    ok = ok && k.turb_dx_strat == 0;
+    const double b = 0.866877899 * clim_tropo_min(c->h_clim);
+    const double bound = b - 1e-6 * std::fabs(b) - 1e-6;
+    const double ptop = c->h_p[c->npl - 1] * 1.01;
+    if (ok && std::isfinite(bound) && ptop < bound && ptop < M.turb_skip)
+      M.strat_skip = bound;
+  }
   M.meso_dt = std::fabs(c->ctl.dt_mod);
   M.meso_r = 1 - 2 * M.meso_dt / c->ctl.dt_met;
   M.meso_r2 = std::sqrt(1 - M.meso_r * M.meso_r);
@@ -3431,6 +3485,7 @@ int mphip_update_clim(mphip_ctx *ctx, int ntime, int nlat, const double *tropo_t
     HIPCHK(hipMalloc((void **) &ctx->d_clim, sizeof(DevClim)));
   HIPCHK(hipMemcpyAsync(ctx->d_clim, &h, sizeof(DevClim), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
+  ctx->h_clim = h;
   ctx->have_clim = true;
   return 0;
 }
@@ -5677,6 +5732,10 @@ int mphip_set_option(mphip_ctx *ctx, const char *name, double value) {
   }
   if (strcmp(name, "fold_resort") == 0) {   // 0: the locality re-sort always gathers in a pass of its own
     ctx->fold_resort = value != 0;
+    return 0;
+  }
+  if (strcmp(name, "turb_strat") == 0) {   // 0: module_diff_turb never takes its short path above the tropopause
+    ctx->turb_strat = value != 0;
     return 0;
   }
   if (strcmp(name, "fuse_sort_quantities") == 0) {   // 0: module_sort moves the quantity arrays in a pass of its own

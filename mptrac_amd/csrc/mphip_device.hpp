@@ -173,6 +173,10 @@ struct DevMet {
   // its transition zone wherever it is (weight 0) and more than its +-10 m probes below the surface;
   // module_convection: one with p < conv_skip lies above every top the convective column can have (-inf = unknown)
   double turb_skip, conv_skip;
+  // module_diff_turb: a particle with 1.01 p < strat_skip and a latitude in [-90, 90] lies above 0.866877899 x the
+  // climatological tropopause pressure of every latitude and time, probes and the axis top included: tropopause
+  // weight 0, stratosphere weight 1 (-inf = unknown, switched off, or parameters it does not hold for)
+  double strat_skip;
   // module_diff_meso: r = 1 - 2 |dt| / DT_MET and sqrt(1 - r^2) for |dt| = meso_dt = |DT_MOD| (every particle of a
   // step but the last, shortened one), from the host -- IEEE division and square root as the reference's
   double meso_dt, meso_r, meso_r2;
@@ -288,6 +292,17 @@ __device__ __forceinline__ double div_const(double x, double y, double inv_y) {
 }
 
 // ---- arithmetic conventions ------------------------------------------------
+
+// x * y + c where two products meet in one sum and the bits depend on which of them the default build fuses (the
+// compiler's choice moves with the code around it): that build fuses this one; the reference-rounding build is
+// compiled without contraction and rounds both
+__device__ __forceinline__ double mul_add(double x, double y, double c) {
+#if MPHIP_EXACT_DIV
+  return x * y + c;
+#else
+  return __builtin_fma(x, y, c);
+#endif
+}
 
 // Division, square root and log of the default build (MPHIP_EXACT_DIV = 0).  On gfx950 an IEEE fp64
 // division costs ~68 cycles per wave, the library sqrt ~104 and the library log ~420
@@ -1646,6 +1661,16 @@ __device__ __forceinline__ void libm_log_unit_pair(const double *__restrict__ lt
   }
 }
 
+// the same for one uniform: libm_log_unit_pair's pieces in its order, so the same bits as either of its results
+__device__ __forceinline__ double libm_log_unit(const double *__restrict__ lt, double xa) {
+  const double ua = xa * 0x1p-64;     // exact
+  const uint64_t ia = mphip_libm_bits(ua);
+  double la = mphip_libm_log_away(lt, ia);
+  if (mphip_libm_log_is_near_one(ia) | (xa == 0.0))
+    la = ua == 1.0 ? 0.0 : (ua == 0.0 ? -__builtin_inf() : mphip_libm_log_near_one(ua));
+  return la;
+}
+
 // Element i of the array module_rng(..., method = 1) would have produced for
 // base counter c0 (mptrac.c:5821-5826): Box-Muller over the flat pairs
 // (2j, 2j+1) of the uniform stream.
@@ -1710,7 +1735,10 @@ __device__ __forceinline__ double normal_third(const double *__restrict__ ltab, 
   const uint64_t i0 = 3 * g;
   const uint64_t y = (c0 + (i0 & ~1ull)) * kSquaresKey;
   double eb, ob;
-  normal_pair_from(ltab, y + 2 * kSquaresKey, eb, ob);
+  // (normal_two_pairs_from's second pair, with its logarithm: the lean one of the uniforms, not the library's full entry)
+  double lb = libm_log_unit(ltab, u64_to_double(squares_from(y + 2 * kSquaresKey)));
+  asm volatile("" : "+v"(lb));
+  box_muller(lb, squares_from(y + 3 * kSquaresKey), eb, ob);
   return (i0 & 1) ? ob : eb;
 }
 
@@ -3214,101 +3242,133 @@ __device__ __forceinline__ void advect_rk4_fast(const DevMet &M, const Axes &A, 
   advect_fast<4>(M, A, P, hook, wc);
 }
 
+// The end of module_diff_turb's vertical step (mptrac.c:4712-4731): the trial pressure reflected at the surface and at
+// the axis top.  `far`: ps is the bound DevMet::turb_skip, not the surface pressure; a trial pressure that reaches it is
+// reflected again with the surface pressure interpolated at (lon0, lat0), where the particle stood before the module.
+__device__ __forceinline__ void turb_reflect(const DevMet &M, const Axes &A, Particle &P, double ptrial0, double ps,
+                                             double ptop, bool far, double lon0, double lat0, double wt) {
+  double ptrial = ptrial0;
+  bool at_surface = false;
+  for (int iter = 0; iter < 10; iter++) {
+    if (ptrial > ps) {
+      at_surface = true;
+      ptrial = ps * ps / ptrial;
+    } else if (ptrial < ptop)
+      ptrial = ptop * ptop / ptrial;
+    else
+      break;
+  }
+  if (far & (at_surface | !(ptrial <= ps))) {   // (rare: a displacement of kilometres) -- now the surface pressure is needed
+    Stencil s = stencil_zero();
+    horiz_fast(M, A, lon0, lat0, s);
+    SurfA c;
+    load_pair_2d32(M.sfa, M, s, c);
+    ps = pair_time_2d_fast(c, s, wt, 0);
+    ptrial = ptrial0;
+    for (int iter = 0; iter < 10; iter++) {
+      if (ptrial > ps)
+        ptrial = ps * ps / ptrial;
+      else if (ptrial < ptop)
+        ptrial = ptop * ptop / ptrial;
+      else
+        break;
+    }
+  }
+  P.p = dmax(ptop, dmin(ps, ptrial));
+}
+
 // module_diff_turb (mptrac.c:4603-4733).  The surface pressure and the boundary-layer top only matter near the
 // ground: for a particle whose pressure (with a 1 % margin for the +-10 m probes of the Kz gradient) is below
 // DevMet::turb_skip the boundary-layer weight is 0 wherever it is, and the surface can only come into play if the
 // vertical displacement reaches it.  Such a particle runs with ps = pbl = the bound -- every expression below then
 // evaluates exactly as with the interpolated values -- and gathers nothing; if its trial pressure does reach the
 // bound, the reflection is redone with the interpolated surface pressure.
+//
+// The short path: a wave whose lanes ALL lie above the boundary layer and, by DevMet::strat_skip, above the tropopause
+// layer of every latitude in [-90, 90] and every time.  Boundary-layer and tropopause weight are then exactly 0 and the
+// stratosphere's exactly 1 -- at the particle, at both probes of the Kz gradient and at the axis top the probes are
+// clamped to --, so Kz is the stratosphere's parameter (0 a + 0 b + 1 K = K for finite parameters >= 0), Kz_up = Kz_dn,
+// the gradient is +0, and Kx = turb_dx_strat = 0 (the bound is off otherwise): no horizontal step, so only rs[3 g + 2] is
+// drawn.  None of it depends on the particle; the tropopause look-up with its time part, the weights, the blends and
+// the first Box-Muller pair are left out, and the vertical step is the one below on the same operands: the same bits.
+// A lane outside [-90, 90] (behind an advection step across a pole) sees the climatology continue its end cell's
+// slope, which no bound covers; it fails the test, as a NaN does, and its wave takes the general body.
+// STRAT false: without the short path (the instantiations with 64-bit offsets, which have no register to spare for it).
+template <bool STRAT = true>
 __device__ __forceinline__ void diff_turb_fast(const mphip_ctl_t &ctl, const DevMet &M, const Axes &A, const DevClim &C,
                                                Particle &P, uint64_t ctr, uint64_t g, const double *pre,
                                                const double *ltab) {
   const double wt = time_weight(M, P.time);
   const bool far = (P.p * 1.01 < M.turb_skip) & (wt >= 0.0) & (wt <= 1.0);
-  double pbl = M.turb_skip, ps = M.turb_skip;
+  double ps = M.turb_skip;
   const double lon0 = P.lon, lat0 = P.lat;
-  if (!far) {
-    Stencil s = stencil_zero();
-    horiz_fast(M, A, P.lon, P.lat, s);
-    SurfA c;
-    load_pair_2d32(M.sfa, M, s, c);
-    pbl = pair_time_2d_fast(c, s, wt, 1);
-    if (ctl.turb_pbl_scheme > 0 && P.p >= pbl)
-      return;
-    ps = pair_time_2d_fast(c, s, wt, 0);
-  }
   const double ptop = A.p[M.np - 1];
-
-  const TropoTime tt = tropo_time(C, P.time);
-  const double wpbl = pbl_weight(ctl, P.p, pbl, ps);
-  double pt = tropo_pressure_at(ctl, C, tt, P.lat);
-  const double wtrop = tropo_weight_pt(pt, P.p) * (1.0 - wpbl);
-  const double wstrat = 1.0 - wpbl - wtrop;
-  const double Kx = wpbl * ctl.turb_dx_pbl + wtrop * ctl.turb_dx_trop + wstrat * ctl.turb_dx_strat;
-  const double Kz = wpbl * ctl.turb_dz_pbl + wtrop * ctl.turb_dz_trop + wstrat * ctl.turb_dz_strat;
-  const double dt_abs = fabs(P.dt);
-
-  // Without horizontal diffusion (Kx = 0: the stratosphere of the default parameters) only rs[3 g + 2] is used --
-  // one Box-Muller pair instead of two -- and the latitude keeps the tropopause pressure found above
-  double rs0 = 0, rs1 = 0, rs2;
-  if (pre) {
-    rs0 = pre[0];
-    rs1 = pre[1];
-    rs2 = pre[2];
-  } else if (Kx > 0 || !MPHIP_TURB_SHORTCUT)
-    normal_triple(ltab, ctr, g, rs0, rs1, rs2);
-  else
-    rs2 = normal_third(ltab, ctr, g);
-
-  if (Kx > 0) {
-    const double sigma_h = fsqrt(2.0 * Kx * dt_abs);
-    const DegPerMetre dm = deg_per_metre(P.lat);
-    P.lon += dx2deg_k(dm, rs0 * sigma_h);
-    P.lat += dy2deg_k(rs1 * sigma_h);
-    pt = tropo_pressure_at(ctl, C, tt, P.lat);   // (mptrac.c:4669: at the displaced latitude)
-  }
-  if (Kz > 0) {
-    const double sigma_z = fsqrt(2.0 * Kz * dt_abs) * 1e-3;
-    const double p_save = P.p;
-    const double eps_km = 0.01;
-    const double p_up = p_save + dz2dp(eps_km, p_save);
-    const double p_dn = p_save + dz2dp(-eps_km, p_save);
-    const double Kz_up = kz_blend(ctl, pt, vmax(ptop, vmin(ps, p_up)), pbl, ps);
-    const double Kz_dn = kz_blend(ctl, pt, vmax(ptop, vmin(ps, p_dn)), pbl, ps);
-    const double dKz_dz = div_const(Kz_up - Kz_dn, 2.0 * eps_km * 1e3, 1.0 / (2.0 * eps_km * 1e3));
-    const double dlnrho_dz = -1.0 / (1e3 * kH0);
-    const double w_drift = dKz_dz + Kz * dlnrho_dz;
-    const double dz_drift = w_drift * dt_abs * 1e-3;
-    const double dz_tot = rs2 * sigma_z + dz_drift;
-    const double ptrial0 = p_save + dz2dp(dz_tot, p_save);
-    double ptrial = ptrial0;
-    bool at_surface = false;
-    for (int iter = 0; iter < 10; iter++) {
-      if (ptrial > ps) {
-        at_surface = true;
-        ptrial = ps * ps / ptrial;
-      } else if (ptrial < ptop)
-        ptrial = ptop * ptop / ptrial;
-      else
-        break;
-    }
-    if (far & (at_surface | !(ptrial <= ps))) {   // (rare: a displacement of kilometres) -- now the surface pressure is needed
+  const double eps_km = 0.01;
+  const double dlnrho_dz = -1.0 / (1e3 * kH0);
+  double Kz, rs2, w_drift = 0.0;
+  if (STRAT && __all(far & (P.p * 1.01 < M.strat_skip) & (fabs(P.lat) <= 90.0))) {   // (one scalar branch)
+    Kz = ctl.turb_dz_strat;
+    w_drift = Kz * dlnrho_dz;   // (the general body's value for a gradient of +0)
+    rs2 = pre ? pre[2] : normal_third(ltab, ctr, g);
+  } else {
+    double pbl = M.turb_skip;
+    if (!far) {
       Stencil s = stencil_zero();
-      horiz_fast(M, A, lon0, lat0, s);
+      horiz_fast(M, A, P.lon, P.lat, s);
       SurfA c;
       load_pair_2d32(M.sfa, M, s, c);
+      pbl = pair_time_2d_fast(c, s, wt, 1);
+      if (ctl.turb_pbl_scheme > 0 && P.p >= pbl)
+        return;
       ps = pair_time_2d_fast(c, s, wt, 0);
-      ptrial = ptrial0;
-      for (int iter = 0; iter < 10; iter++) {
-        if (ptrial > ps)
-          ptrial = ps * ps / ptrial;
-        else if (ptrial < ptop)
-          ptrial = ptop * ptop / ptrial;
-        else
-          break;
-      }
     }
-    P.p = dmax(ptop, dmin(ps, ptrial));
+
+    const TropoTime tt = tropo_time(C, P.time);
+    const double wpbl = pbl_weight(ctl, P.p, pbl, ps);
+    double pt = tropo_pressure_at(ctl, C, tt, P.lat);
+    const double wtrop = tropo_weight_pt(pt, P.p) * (1.0 - wpbl);
+    const double wstrat = 1.0 - wpbl - wtrop;
+    const double Kx = wpbl * ctl.turb_dx_pbl + wtrop * ctl.turb_dx_trop + wstrat * ctl.turb_dx_strat;
+    Kz = wpbl * ctl.turb_dz_pbl + wtrop * ctl.turb_dz_trop + wstrat * ctl.turb_dz_strat;
+
+    // Without horizontal diffusion (Kx = 0: the stratosphere of the default parameters) only rs[3 g + 2] is used --
+    // one Box-Muller pair instead of two -- and the latitude keeps the tropopause pressure found above
+    double rs0 = 0, rs1 = 0;
+    if (pre) {
+      rs0 = pre[0];
+      rs1 = pre[1];
+      rs2 = pre[2];
+    } else if (Kx > 0 || !MPHIP_TURB_SHORTCUT)
+      normal_triple(ltab, ctr, g, rs0, rs1, rs2);
+    else
+      rs2 = normal_third(ltab, ctr, g);
+
+    if (Kx > 0) {
+      const double sigma_h = fsqrt(2.0 * Kx * fabs(P.dt));
+      const DegPerMetre dm = deg_per_metre(P.lat);
+      P.lon += dx2deg_k(dm, rs0 * sigma_h);
+      P.lat += dy2deg_k(rs1 * sigma_h);
+      pt = tropo_pressure_at(ctl, C, tt, P.lat);   // (mptrac.c:4669: at the displaced latitude)
+    }
+    if (Kz > 0) {
+      const double p_up = P.p + dz2dp(eps_km, P.p);
+      const double p_dn = P.p + dz2dp(-eps_km, P.p);
+      const double Kz_up = kz_blend(ctl, pt, vmax(ptop, vmin(ps, p_up)), pbl, ps);
+      const double Kz_dn = kz_blend(ctl, pt, vmax(ptop, vmin(ps, p_dn)), pbl, ps);
+#if MPHIP_EXACT_DIV
+      w_drift = (Kz_up - Kz_dn) / (2.0 * eps_km * 1e3) + Kz * dlnrho_dz;
+#else
+      w_drift = __builtin_fma(Kz_up - Kz_dn, 1.0 / (2.0 * eps_km * 1e3), Kz * dlnrho_dz);   // dKz_dz + Kz dlnrho_dz
+#endif
+    }
+  }
+  if (Kz > 0) {
+    const double dt_abs = fabs(P.dt);
+    const double sigma_z = fsqrt(2.0 * Kz * dt_abs) * 1e-3;
+    const double p_save = P.p;
+    const double dz_drift = w_drift * dt_abs * 1e-3;
+    const double dz_tot = mul_add(rs2, sigma_z, dz_drift);
+    turb_reflect(M, A, P, p_save + dz2dp(dz_tot, p_save), ps, ptop, far, lon0, lat0, wt);
   }
 }
 

@@ -918,7 +918,7 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
     const unsigned opt = (lean && (CT & kGated)) ? (mask & S.mask & kOptionalModules) : (mask & kOptionalModules);
     if (opt & MPHIP_MOD_DIFF_TURB) {
       if (lean)
-        diff_turb_fast(ctl, M, A, *clim, P, c_turb, g_now(), early ? pre.turb : nullptr, ltab);
+        diff_turb_fast<!kBig<CT>>(ctl, M, A, *clim, P, c_turb, g_now(), early ? pre.turb : nullptr, ltab);
       else
         diff_turb(ctl, M, A, *clim, P, c_turb, g_now(), early ? pre.turb : nullptr, ltab);
     }
