@@ -288,8 +288,9 @@ int mphip_discard_prefetch(mphip_ctx *ctx);
  * pcb / cl, plcl / plfc / pel / cape / cin, potential vorticity pv and the tropopause pt / tt / zt / h2ot.  `in` is a host
  * view exactly as for mphip_update_met (compact or [EX][EY][EP]-strided); `what` an OR of MPHIP_PREP_* bits; the arrays
  * of `out` have the strides of `in`.  The call uploads
- * the inputs it needs into scratch of its own (kept for the grid size of the last call, freed by mphip_destroy), runs its
- * kernels on a stream of its own, copies the results into the caller's arrays and returns when they are there.  It touches
+ * the inputs it needs into device scratch -- one pool that it shares with mphip_regrid_met and mphip_detrend_met under their
+ * common lock; the pool grows to what the largest call needs, is kept between calls and freed by mphip_destroy --, runs its
+ * kernels on the stream of these three calls, copies the results into the caller's arrays and returns when they are there.  It touches
  * no meteo slot, no prefetch state and no particle state and may be called from a file-reader thread while another thread
  * steps (the contract of mphip_prefetch_met); calls from several threads are serialised.  Only the outputs of the
  * requested bits are written; a refused call writes nothing.
@@ -428,8 +429,8 @@ int mphip_derive_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const
  * its own strides (as mphip_met_t does: sy >= np2, sx a multiple of sy and >= ny2 sy, sx2 >= ny2) and the output axes.
  * mphip_regrid_shape gives the output extents without a context, so that a caller can allocate; it returns non-zero
  * where mphip_regrid_met would refuse the grid or the options.  The call keeps the contract of mphip_derive_met: the same
- * stream and lock (calls are serialised with mphip_derive_met), scratch of its own that is kept between calls and freed by
- * mphip_destroy, no meteo slot, no prefetch state and no particle touched, callable from a file-reader thread, and a
+ * stream and lock (calls are serialised with mphip_derive_met), the same scratch pool (grow-only, freed by
+ * mphip_destroy), no meteo slot, no prefetch state and no particle touched, callable from a file-reader thread, and a
  * refused call writes nothing.  Every input is uploaded before any output is written, so `out` may alias `in` (the host
  * layer regrids its met_t in place).  Fields that are NULL in `in` or NULL in `out` are skipped, axes that are NULL in `out`
  * likewise.  With both bits ML2PL runs first and SAMPLE works on its result on the device.  The model-level slots
@@ -484,8 +485,8 @@ int mphip_regrid_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const
 
 /* Detrending (the reference's read_met_detrend): a Gaussian-weighted horizontal mean, the background, is subtracted from
  * t, u, v and w of a pressure-level snapshot on a longitude / latitude grid.  The call keeps the contract of
- * mphip_derive_met / mphip_regrid_met: the same stream and lock, scratch of its own that is kept between calls and freed
- * by mphip_destroy, no meteo slot, no prefetch state and no particle touched, callable from a file-reader thread while
+ * mphip_derive_met / mphip_regrid_met: the same stream and lock, the same scratch pool (grow-only, freed by
+ * mphip_destroy), no meteo slot, no prefetch state and no particle touched, callable from a file-reader thread while
  * another thread steps; a refused call writes nothing and its message starts with "mphip_detrend_met: ".  Every input
  * is uploaded and the weights are built before any output is copied back, so `out` may alias `in`.  The shape does not
  * change: `out` names the strides of its arrays (sy >= np, sx a multiple of sy and >= ny sy), only out->f3[MPHIP_T],

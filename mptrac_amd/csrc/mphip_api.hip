@@ -53,6 +53,32 @@ struct MetSlot {
   double ps_max = HUGE_VAL, pbl_min = -HUGE_VAL, pbl_max = HUGE_VAL, pel_min = -HUGE_VAL;
 };
 
+// What mphip_derive_met, mphip_regrid_met and mphip_detrend_met share (PrepCall below is one call's view of it): a stream
+// of their own, so that a file-reader thread may call them while another thread steps; the lock that serialises their
+// callers; and the scratch of the call in progress.  No buffer carries a value from one call to the next, so the pool
+// hands its buffers out from the first again at every call (PrepCall::take); a buffer grows when a call needs more than
+// it holds and is kept otherwise, so a repeating sequence of calls allocates nothing after its first round.
+struct PrepState {
+  std::mutex lock;
+  hipStream_t stream = nullptr;
+  int profile_phase = 0;              // option "derive_profile_phase": what mphip_profile_begin / _end time of a call
+  struct Buf {
+    char *p = nullptr;
+    size_t bytes = 0;
+  };
+  std::vector<Buf> pool;
+  size_t taken = 0;                   // buffers of the pool the call in progress has taken
+  void release() {
+    for (Buf &b : pool)
+      if (b.p)
+        (void) hipFree(b.p);
+    pool.clear();
+    if (stream)
+      (void) hipStreamDestroy(stream);
+    stream = nullptr;
+  }
+};
+
 }   // namespace
 
 struct mphip_ctx {
@@ -281,31 +307,8 @@ struct mphip_ctx {
   void *comm = nullptr;               // RCCL communicator (ncclComm_t) of mphip_comm_init, NULL = single rank / hook
   int comm_ranks = 1, comm_rank = 0;
 
-  // mphip_derive_met: a stream and scratch of its own (inputs, outputs and axes of one snapshot, kept for the grid size
-  // of the last call), so that a file-reader thread may call it while another thread steps; prep_lock serialises callers
-  std::mutex prep_lock;
-  hipStream_t prep_stream = nullptr;
-  int prep_nx = 0, prep_ny = 0, prep_np = 0;
-  float *prep_in3[MPHIP_N3D] = {}, *prep_in2[MPHIP_N2D] = {};
-  float *prep_out2[MPHIP_N2D] = {};
-  float *prep_z[2] = {};              // geopotential height before and after the smoothing
-  float *prep_pv = nullptr;           // potential vorticity (MPHIP_PREP_PV; what MPHIP_PREP_TROPO with met_tropo 5 reads)
-  double *prep_axes = nullptr;        // p[np] | lat[ny] | lon[nx] | the tropopause's tables (PrepTropo::tab)
-  int prep_profile_phase = 0;         // option "derive_profile_phase": what mphip_profile_begin / _end time of a call
-  // mphip_regrid_met (prep_stream, prep_lock): the uploaded fields, ML2PL's result and SAMPLE's result; each array grows
-  // to the largest size asked for and is kept
-  struct RegridBuf {
-    float *p = nullptr;
-    size_t n = 0;
-  };
-  RegridBuf rg_in3[MPHIP_N3D], rg_mid3[MPHIP_N3D], rg_out3[MPHIP_N3D], rg_in2[MPHIP_N2D], rg_out2[MPHIP_N2D];
-  double *rg_p = nullptr;             // met_p on the device
-  size_t rg_p_n = 0;
-  // mphip_detrend_met (prep_stream, prep_lock): the uploaded fields, the results, the weight table and its row records;
-  // each array grows to the largest size asked for and is kept
-  RegridBuf dt_in[kDtFields], dt_out[kDtFields], dt_w;
-  DetrendRow *dt_rows = nullptr;
-  size_t dt_rows_n = 0;
+  // mphip_derive_met, mphip_regrid_met, mphip_detrend_met: their stream, lock and scratch (released by mphip_destroy)
+  PrepState prep;
 
   // profiling of the fused step kernel
   bool prof = false;
@@ -2765,6 +2768,44 @@ void unpin_all(mphip_ctx *ctx, std::vector<std::pair<uintptr_t, uintptr_t>> &lis
   list.clear();
 }
 
+// a host array of strides sx, sy holds a level field of ny x np values per column, a whole number of rows apart
+bool regrid_strides_ok(int ny, int np, long long sx, long long sy) {
+  return sy >= np && sx >= sy * ny && sx % sy == 0;
+}
+
+// a level field of nx x ny x np values between such a host array and a compact device array (asynchronous on `stream`)
+int copy3(mphip_ctx *ctx, hipStream_t stream, float *dev, const float *host, int nx, int ny, int np, long long sx, long long sy,
+          bool to_device) {
+  if (sy == np && sx == (long long) ny * np) {
+    const size_t bytes = (size_t) nx * ny * np * sizeof(float);
+    if (to_device)
+      HIPCHK(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, stream));
+    else
+      HIPCHK(hipMemcpyAsync((void *) host, dev, bytes, hipMemcpyDeviceToHost, stream));
+    return 0;
+  }
+  hipMemcpy3DParms p;
+  memset(&p, 0, sizeof(p));
+  const hipPitchedPtr h = make_hipPitchedPtr((void *) host, (size_t) sy * sizeof(float), (size_t) np, (size_t) (sx / sy));
+  const hipPitchedPtr d = make_hipPitchedPtr(dev, (size_t) np * sizeof(float), (size_t) np, (size_t) ny);
+  p.srcPtr = to_device ? h : d;
+  p.dstPtr = to_device ? d : h;
+  p.extent = make_hipExtent((size_t) np * sizeof(float), (size_t) ny, (size_t) nx);
+  p.kind = to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+  HIPCHK(hipMemcpy3DAsync(&p, stream));
+  return 0;
+}
+
+// a surface field of nx x ny values between a host array of row stride sx2 and a compact device array
+int copy2(mphip_ctx *ctx, hipStream_t stream, float *dev, const float *host, int nx, int ny, long long sx2, bool to_device) {
+  const size_t row = (size_t) ny * sizeof(float), hrow = (size_t) sx2 * sizeof(float);
+  if (to_device)
+    HIPCHK(hipMemcpy2DAsync(dev, row, host, hrow, row, (size_t) nx, hipMemcpyHostToDevice, stream));
+  else
+    HIPCHK(hipMemcpy2DAsync((void *) host, hrow, dev, row, row, (size_t) nx, hipMemcpyDeviceToHost, stream));
+  return 0;
+}
+
 // host -> device copies of one snapshot's fields into the staging arrays of slot S (asynchronous on `stream`)
 int upload_fields(mphip_ctx *ctx, MetSlot &S, const mphip_met_t *met, bool new_grid, hipStream_t stream) {
   const int nml = met->npl > 0 ? met->npl : 0;
@@ -2780,20 +2821,10 @@ int upload_fields(mphip_ctx *ctx, MetSlot &S, const mphip_met_t *met, bool new_g
     if (new_grid || !S.f3[f])
       if (dev_alloc(ctx, &S.f3[f], n3))
         return 1;
-    if (sy == nlev && sx == (long long) met->ny * nlev) {
-      HIPCHK(hipMemcpyAsync(S.f3[f], met->f3[f], n3 * sizeof(float), hipMemcpyHostToDevice, stream));
-    } else {
-      if (sy < nlev || sx < sy * met->ny || sx % sy != 0)
-        return fail(ctx, "unsupported 3-D meteo strides");
-      hipMemcpy3DParms p;
-      memset(&p, 0, sizeof(p));
-      p.srcPtr = make_hipPitchedPtr((void *) met->f3[f], (size_t) sy * sizeof(float), (size_t) nlev,
-                                    (size_t) (sx / sy));
-      p.dstPtr = make_hipPitchedPtr(S.f3[f], (size_t) nlev * sizeof(float), (size_t) nlev, (size_t) met->ny);
-      p.extent = make_hipExtent((size_t) nlev * sizeof(float), (size_t) met->ny, (size_t) met->nx);
-      p.kind = hipMemcpyHostToDevice;
-      HIPCHK(hipMemcpy3DAsync(&p, stream));
-    }
+    if (!regrid_strides_ok(met->ny, (int) nlev, sx, sy))
+      return fail(ctx, "unsupported 3-D meteo strides");
+    if (copy3(ctx, stream, S.f3[f], met->f3[f], met->nx, met->ny, (int) nlev, sx, sy, true))
+      return 1;
   }
   S.ps11 = met->f2[MPHIP_PS] ? met->f2[MPHIP_PS][(size_t) met->sx2 + 1] : 0.f;
   S.ps_min = S.pct_min = S.pbl_min = S.pel_min = -HUGE_VAL;
@@ -2856,141 +2887,118 @@ int upload_fields(mphip_ctx *ctx, MetSlot &S, const mphip_met_t *met, bool new_g
   return 0;
 }
 
-// ---- mphip_derive_met: scratch and copies --------------------------------------------------------------------------
-void prep_release(mphip_ctx *ctx) {
-  for (auto &q : ctx->prep_in3) {
-    dev_free(q);
-    q = nullptr;
-  }
-  for (auto &q : ctx->prep_in2) {
-    dev_free(q);
-    q = nullptr;
-  }
-  for (auto &q : ctx->prep_out2) {
-    dev_free(q);
-    q = nullptr;
-  }
-  for (auto &q : ctx->prep_z) {
-    dev_free(q);
-    q = nullptr;
-  }
-  dev_free(ctx->prep_pv);
-  ctx->prep_pv = nullptr;
-  dev_free(ctx->prep_axes);
-  ctx->prep_axes = nullptr;
-  ctx->prep_nx = ctx->prep_ny = ctx->prep_np = 0;
-}
+// ---- mphip_derive_met, mphip_regrid_met, mphip_detrend_met: what a call of the three shares ------------------------
+// One call, from open() to the end of its scope: it holds the lock, hands out the scratch (PrepState), brackets what
+// mphip_profile_begin / _end time with event pairs (tools/gpu_*_cost.py; a caller that profiles does not step from another
+// thread) and, however the call ends, leaves nothing queued on the stream.  A copy may read the call's own vectors: those
+// are declared before the PrepCall, so that they are destroyed after it.
+struct PrepCall {
+  mphip_ctx *ctx;
+  PrepState &S;
+  std::lock_guard<std::mutex> guard;
+  hipStream_t st = nullptr;
+  hipEvent_t ev_stop = nullptr;
 
-// a level field between the caller's (possibly strided) array and a compact device array
-int prep_copy3(mphip_ctx *ctx, float *dev, const float *host, const mphip_met_t *m, bool to_device, hipStream_t stream) {
-  const size_t n3 = (size_t) m->nx * m->ny * m->np;
-  if (m->sy == m->np && m->sx == (long long) m->ny * m->np) {
-    if (to_device)
-      HIPCHK(hipMemcpyAsync(dev, host, n3 * sizeof(float), hipMemcpyHostToDevice, stream));
-    else
-      HIPCHK(hipMemcpyAsync((void *) host, dev, n3 * sizeof(float), hipMemcpyDeviceToHost, stream));
+  explicit PrepCall(mphip_ctx *c) : ctx(c), S(c->prep), guard(c->prep.lock) {}
+  ~PrepCall() {
+    if (st)
+      (void) hipStreamSynchronize(st);
+  }
+  int open() {
+    HIPCHK(hipSetDevice(ctx->device));
+    if (!S.stream)
+      HIPCHK(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
+    st = S.stream;
+    S.taken = 0;
     return 0;
   }
-  hipMemcpy3DParms p;
-  memset(&p, 0, sizeof(p));
-  const hipPitchedPtr h = make_hipPitchedPtr((void *) host, (size_t) m->sy * sizeof(float), (size_t) m->np, (size_t) (m->sx / m->sy));
-  const hipPitchedPtr d = make_hipPitchedPtr(dev, (size_t) m->np * sizeof(float), (size_t) m->np, (size_t) m->ny);
-  p.srcPtr = to_device ? h : d;
-  p.dstPtr = to_device ? d : h;
-  p.extent = make_hipExtent((size_t) m->np * sizeof(float), (size_t) m->ny, (size_t) m->nx);
-  p.kind = to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
-  HIPCHK(hipMemcpy3DAsync(&p, stream));
-  return 0;
-}
+  // the end of an accepted call: its results are in the caller's arrays
+  int close() {
+    const hipStream_t s = st;
+    st = nullptr;
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+  }
+  // the next buffer of the pool, for n > 0 values of T; NULL: the allocation failed (the buffer is empty then)
+  template <typename T>
+  T *take(size_t n) {
+    if (S.taken == S.pool.size())
+      S.pool.emplace_back();
+    PrepState::Buf &b = S.pool[S.taken++];
+    if (b.bytes < n * sizeof(T)) {
+      b.bytes = 0;
+      if (dev_alloc(ctx, &b.p, n * sizeof(T)))
+        return nullptr;
+      b.bytes = n * sizeof(T);
+    }
+    return (T *) b.p;
+  }
+  // event pairs around every kernel (phase 0), around the uploads (1), around the downloads (2) or around the weight table
+  // of mphip_detrend_met (3)
+  int mark_begin(int phase) {
+    ev_stop = nullptr;
+    if (!ctx->prof || S.profile_phase != phase)
+      return 0;
+    while (ctx->ev_used + 2 > ctx->ev.size()) {
+      hipEvent_t e;
+      HIPCHK(hipEventCreate(&e));
+      ctx->ev.push_back(e);
+    }
+    HIPCHK(hipEventRecord(ctx->ev[ctx->ev_used++], st));
+    ev_stop = ctx->ev[ctx->ev_used++];
+    return 0;
+  }
+  int mark_end() {
+    if (ev_stop)
+      HIPCHK(hipEventRecord(ev_stop, st));
+    return 0;
+  }
+  template <typename K, typename... Args>
+  int enqueue(K kernel, dim3 grid, dim3 block, size_t lds, Args... args) {
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+  // a kernel as one profiled event pair
+  template <typename K, typename... Args>
+  int launch(K kernel, dim3 grid, dim3 block, size_t lds, Args... args) {
+    return mark_begin(0) || enqueue(kernel, grid, block, lds, args...) || mark_end();
+  }
+};
 
-int prep_copy2(mphip_ctx *ctx, float *dev, const float *host, const mphip_met_t *m, bool to_device, hipStream_t stream) {
-  const size_t row = (size_t) m->ny * sizeof(float), hrow = (size_t) m->sx2 * sizeof(float);
-  if (to_device)
-    HIPCHK(hipMemcpy2DAsync(dev, row, host, hrow, row, (size_t) m->nx, hipMemcpyHostToDevice, stream));
-  else
-    HIPCHK(hipMemcpy2DAsync((void *) host, hrow, dev, row, row, (size_t) m->nx, hipMemcpyDeviceToHost, stream));
-  return 0;
-}
-
-// columns per workgroup of a column kernel that stages nf fields: the largest power of two up to 64 within 64 KB of LDS
-int prep_columns(int np, int nf, size_t *lds) {
-  const int pitch = np | 1;
+// columns per workgroup of a kernel that stages whole columns in lds_of(columns) bytes of LDS: the largest power of two up
+// to kPrepLanes within 64 KB (0: not even one column fits)
+template <typename F>
+int columns_per_workgroup(F lds_of, size_t *lds) {
   for (int cpb = kPrepLanes; cpb >= 1; cpb >>= 1) {
-    *lds = 2 * (size_t) np * sizeof(double) + (size_t) nf * cpb * pitch * sizeof(float);
+    *lds = lds_of(cpb);
     if (*lds <= 64 * 1024)
       return cpb;
   }
   return 0;
 }
 
-// the same for the tropopause kernel: the axis tables, per column c[np] and (met_tropo 3, 4) the fine profile in double, and
-// the staged profiles (t; t and pv with met_tropo 5)
-int prep_tropo_columns(int np, int mode, size_t *lds, int *nprof, int *fine) {
-  const int pitch = np | 1;
-  *nprof = mode == 1 ? 0 : (mode == 5 ? 2 : 1);
-  *fine = mode == 3 || mode == 4 ? kTropoFine : 0;
-  for (int cpb = kPrepLanes; cpb >= 1; cpb >>= 1) {
-    *lds = ((size_t) 6 * np + 2 * kTropoFine + (size_t) cpb * (np + *fine)) * sizeof(double)
-      + (size_t) *nprof * cpb * pitch * sizeof(float);
-    if (*lds <= 64 * 1024)
-      return cpb;
-  }
-  return 0;
+// the refusals every call of the three makes of a grid; NULL = accepted
+const char *grid_dims_refusal(int nx, int ny, bool axes_given = true) {
+  return nx < 2 || ny < 2 || !axes_given ? "meteo grid dimensions out of range" : nullptr;
 }
 
-// ---- mphip_regrid_met: scratch, copies and the checks it shares with mphip_regrid_shape ------------------------------
-void regrid_release(mphip_ctx *ctx) {
-  for (auto *set : { ctx->rg_in3, ctx->rg_mid3, ctx->rg_out3 })
-    for (int f = 0; f < MPHIP_N3D; f++) {
-      dev_free(set[f].p);
-      set[f] = mphip_ctx::RegridBuf();
-    }
-  for (auto *set : { ctx->rg_in2, ctx->rg_out2 })
-    for (int f = 0; f < MPHIP_N2D; f++) {
-      dev_free(set[f].p);
-      set[f] = mphip_ctx::RegridBuf();
-    }
-  dev_free(ctx->rg_p);
-  ctx->rg_p = nullptr;
-  ctx->rg_p_n = 0;
+// nlev: the most levels a field of the call has
+const char *grid_size_refusal(int nx, int ny, long long nlev) {
+  return (long long) nx * ny >= (1LL << 24) || (long long) nx * ny * nlev >= (1LL << 31)
+    ? "meteo grid too large for the device index arithmetic" : nullptr;
 }
 
-int regrid_reserve(mphip_ctx *ctx, mphip_ctx::RegridBuf &b, size_t n) {
-  if (b.n >= n)
-    return 0;
-  b.n = 0;
-  if (dev_alloc(ctx, &b.p, n))
-    return 1;
-  b.n = n;
-  return 0;
+// ... of a pressure-level grid, in the order the calls report them
+const char *grid_refusal(int nx, int ny, int np, bool axes_given = true) {
+  if (const char *why = grid_dims_refusal(nx, ny, axes_given))
+    return why;
+  if (np < 2)
+    return "needs two pressure levels or more (np < 2)";
+  return grid_size_refusal(nx, ny, np);
 }
 
-// a level field of nx x ny x np values between a host array of strides sx, sy and a compact device array
-int regrid_copy3(mphip_ctx *ctx, float *dev, const float *host, int nx, int ny, int np, long long sx, long long sy,
-                 bool to_device, hipStream_t stream) {
-  mphip_met_t m;
-  memset(&m, 0, sizeof(m));
-  m.nx = nx;
-  m.ny = ny;
-  m.np = np;
-  m.sx = sx;
-  m.sy = sy;
-  return prep_copy3(ctx, dev, host, &m, to_device, stream);
-}
-
-int regrid_copy2(mphip_ctx *ctx, float *dev, const float *host, int nx, int ny, long long sx2, bool to_device,
-                 hipStream_t stream) {
-  mphip_met_t m;
-  memset(&m, 0, sizeof(m));
-  m.nx = nx;
-  m.ny = ny;
-  m.sx2 = sx2;
-  return prep_copy2(ctx, dev, host, &m, to_device, stream);
-}
-
-bool regrid_strides_ok(int ny, int np, long long sx, long long sy) {
-  return sy >= np && sx >= sy * ny && sx % sy == 0;
-}
+// ---- mphip_regrid_met: the checks it shares with mphip_regrid_shape --------------------------------------------------
 
 // the fields ML2PL regrids; SAMPLE takes these and z, pv
 const int kRegridMl[kRgFields] = { MPHIP_T, MPHIP_U, MPHIP_V, MPHIP_W, MPHIP_H2O, MPHIP_O3, MPHIP_LWC, MPHIP_RWC,
@@ -3013,8 +3021,9 @@ const char *regrid_plan(const mphip_met_t *in, unsigned what, const mphip_regrid
   const bool ml = what & MPHIP_REGRID_ML2PL, sample = what & MPHIP_REGRID_SAMPLE;
   if (!what || (what & ~(unsigned) (MPHIP_REGRID_ML2PL | MPHIP_REGRID_SAMPLE)))
     return "`what` must be an OR of MPHIP_REGRID_* bits";
-  if (in->nx < 2 || in->ny < 2)
-    return "meteo grid dimensions out of range";
+  // (ML2PL has refusals of its own for the levels, between those of the dimensions and of the size)
+  if (const char *why = ml ? grid_dims_refusal(in->nx, in->ny) : grid_refusal(in->nx, in->ny, in->np))
+    return why;
   memset(P, 0, sizeof(*P));
   P->nx = in->nx;
   P->ny = in->ny;
@@ -3027,19 +3036,15 @@ const char *regrid_plan(const mphip_met_t *in, unsigned what, const mphip_regrid
     for (int j = 0; j < opt->met_np; j++)
       if (!(opt->met_p[j] > 0 && opt->met_p[j] < INFINITY) || (j > 0 && !(opt->met_p[j] < opt->met_p[j - 1])))
         return "MPHIP_REGRID_ML2PL: met_p must be finite, positive and strictly descending";
-    const int pitch = in->npl | 1;
-    for (int cpb = kPrepLanes; cpb >= 1 && !P->ml_cpb; cpb >>= 1) {
-      P->ml_lds = (size_t) opt->met_np * sizeof(double) + (size_t) cpb * pitch * sizeof(float);
-      if (P->ml_lds <= 64 * 1024)
-        P->ml_cpb = cpb;
-    }
+    const size_t pitch = in->npl | 1;
+    P->ml_cpb = columns_per_workgroup(
+      [&](int cpb) { return (size_t) opt->met_np * sizeof(double) + cpb * pitch * sizeof(float); }, &P->ml_lds);
     if (!P->ml_cpb)
       return "MPHIP_REGRID_ML2PL: too many levels for one column in 64 KB of LDS";
     P->np1 = opt->met_np;
-  } else if (in->np < 2)
-    return "needs two pressure levels or more (np < 2)";
-  if ((long long) in->nx * in->ny >= (1LL << 24) || (long long) in->nx * in->ny * std::max(P->np0, P->np1) >= (1LL << 31))
-    return "meteo grid too large for the device index arithmetic";
+    if (const char *why = grid_size_refusal(in->nx, in->ny, std::max(P->np0, P->np1)))
+      return why;
+  }
   P->nx2 = in->nx;
   P->ny2 = in->ny;
   P->np2 = P->np1;
@@ -3083,18 +3088,7 @@ const char *regrid_plan(const mphip_met_t *in, unsigned what, const mphip_regrid
   return nullptr;
 }
 
-// ---- mphip_detrend_met: scratch, the checks and the weight table -----------------------------------------------------
-void detrend_release(mphip_ctx *ctx) {
-  for (auto *b : { &ctx->dt_w, &ctx->dt_in[0], &ctx->dt_in[1], &ctx->dt_in[2], &ctx->dt_in[3], &ctx->dt_out[0],
-                   &ctx->dt_out[1], &ctx->dt_out[2], &ctx->dt_out[3] }) {
-    dev_free(b->p);
-    *b = mphip_ctx::RegridBuf();
-  }
-  dev_free(ctx->dt_rows);
-  ctx->dt_rows = nullptr;
-  ctx->dt_rows_n = 0;
-}
-
+// ---- mphip_detrend_met: the checks and the weight table -------------------------------------------------------------
 const int kDetrendFields[kDtFields] = { MPHIP_T, MPHIP_U, MPHIP_V, MPHIP_W };
 
 struct DetrendPlan {
@@ -3109,12 +3103,8 @@ struct DetrendPlan {
 // everything that can be refused for the grid and the option (the axes are there); NULL = accepted
 const char *detrend_plan(const mphip_met_t *in, const mphip_detrend_t *opt, DetrendPlan *P) {
 #pragma clang fp contract(off)
-  if (in->nx < 2 || in->ny < 2)
-    return "meteo grid dimensions out of range";
-  if (in->np < 2)
-    return "needs two pressure levels or more (np < 2)";
-  if ((long long) in->nx * in->ny >= (1LL << 24) || (long long) in->nx * in->ny * in->np >= (1LL << 31))
-    return "meteo grid too large for the device index arithmetic";
+  if (const char *why = grid_refusal(in->nx, in->ny, in->np))
+    return why;
   if (in->coord_type != 0)
     return "needs a longitude / latitude grid (coord_type != 0)";
   if (!(opt->met_detrend > 0 && opt->met_detrend < INFINITY))
@@ -3303,11 +3293,7 @@ void mphip_destroy(mphip_ctx *ctx) {
     for (auto p : s->f2)
       dev_free(p);
   }
-  prep_release(ctx);
-  regrid_release(ctx);
-  detrend_release(ctx);
-  if (ctx->prep_stream)
-    (void) hipStreamDestroy(ctx->prep_stream);
+  ctx->prep.release();
   dev_free(ctx->d_clim);
   for (auto p : ctx->d_zm)
     dev_free(p);
@@ -3821,14 +3807,9 @@ int mphip_derive_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const
     | MPHIP_PREP_PV | MPHIP_PREP_TROPO;
   if (!what || (what & ~kAll))
     return fail(ctx, "mphip_derive_met: `what` must be an OR of MPHIP_PREP_* bits");
-  if (in->nx < 2 || in->ny < 2 || !in->lon || !in->lat || !in->p)
-    return fail(ctx, "mphip_derive_met: meteo grid dimensions out of range");
-  if (in->np < 2)
-    return fail(ctx, "mphip_derive_met: needs two pressure levels or more (np < 2)");
-  if ((long long) in->nx * in->ny >= (1LL << 24) || (long long) in->nx * in->ny * in->np >= (1LL << 31))
-    return fail(ctx, "mphip_derive_met: meteo grid too large for the device index arithmetic");
-  const bool compact = in->sy == in->np && in->sx == (long long) in->ny * in->np;
-  if ((!compact && (in->sy < in->np || in->sx < in->sy * in->ny || in->sx % in->sy != 0)) || in->sx2 < in->ny)
+  if (const char *why = grid_refusal(in->nx, in->ny, in->np, in->lon && in->lat && in->p))
+    return fail(ctx, std::string("mphip_derive_met: ") + why);
+  if (!regrid_strides_ok(in->ny, in->np, in->sx, in->sy) || in->sx2 < in->ny)
     return fail(ctx, "mphip_derive_met: unsupported meteo strides");
   for (int k = 1; k < in->np; k++)
     if (!(in->p[k] < in->p[k - 1]))
@@ -3961,57 +3942,46 @@ int mphip_derive_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const
                   "(mphip_update_ctl first)");
     if (!outputs({ MPHIP_PT, MPHIP_TT, MPHIP_ZT, MPHIP_H2OT }))
       return fail(ctx, "mphip_derive_met: MPHIP_PREP_TROPO needs the output arrays pt, tt, zt, h2ot");
-    c_tropo = prep_tropo_columns(in->np, mode, &lds_tropo, &tropo_nprof, &tropo_fine);
+    // the axis tables, per column c[np] and (met_tropo 3, 4) the fine profile in double, and the staged profiles (t; t and
+    // pv with met_tropo 5)
+    tropo_nprof = mode == 1 ? 0 : (mode == 5 ? 2 : 1);
+    tropo_fine = mode == 3 || mode == 4 ? kTropoFine : 0;
+    c_tropo = columns_per_workgroup(
+      [&](int cpb) {
+        return ((size_t) 6 * in->np + 2 * kTropoFine + (size_t) cpb * (in->np + tropo_fine)) * sizeof(double)
+          + (size_t) tropo_nprof * cpb * (in->np | 1) * sizeof(float);
+      },
+      &lds_tropo);
   }
   const int np = in->np;
+  // a column kernel that stages nf fields
+  auto columns = [np](int nf, size_t *lds) {
+    return columns_per_workgroup(
+      [=](int cpb) { return 2 * (size_t) np * sizeof(double) + (size_t) nf * cpb * (np | 1) * sizeof(float); }, lds);
+  };
   size_t lds_geo = 0, lds_o3 = 0, lds_cloud = 0, lds_pbl = 0, lds_cape = 0;
-  const int c_geo = prep_columns(np, 3, &lds_geo), c_o3 = prep_columns(np, 1, &lds_o3), c_cloud = prep_columns(np, 4, &lds_cloud);
-  const int c_pbl = prep_columns(np, opt->met_pbl == 2 ? 5 : 1, &lds_pbl), c_cape = prep_columns(np, 2, &lds_cape);
+  const int c_geo = columns(3, &lds_geo), c_o3 = columns(1, &lds_o3), c_cloud = columns(4, &lds_cloud);
+  const int c_pbl = columns(opt->met_pbl == 2 ? 5 : 1, &lds_pbl), c_cape = columns(2, &lds_cape);
   if ((geopot && !c_geo) || ((what & MPHIP_PREP_O3C) && !c_o3) || ((what & MPHIP_PREP_CLOUD) && !c_cloud)
       || ((what & MPHIP_PREP_PBL) && !c_pbl) || ((what & MPHIP_PREP_CAPE) && !c_cape) || (tropo && !c_tropo))
     return fail(ctx, "mphip_derive_met: too many pressure levels for one column in 64 KB of LDS");
 
-  std::lock_guard<std::mutex> guard(ctx->prep_lock);
-  HIPCHK(hipSetDevice(ctx->device));
-  if (!ctx->prep_stream)
-    HIPCHK(hipStreamCreateWithFlags(&ctx->prep_stream, hipStreamNonBlocking));
-  hipStream_t st = ctx->prep_stream;
-  if (in->nx != ctx->prep_nx || in->ny != ctx->prep_ny || np != ctx->prep_np) {
-    prep_release(ctx);
-    ctx->prep_nx = in->nx;
-    ctx->prep_ny = in->ny;
-    ctx->prep_np = np;
-    if (dev_alloc(ctx, &ctx->prep_axes, (size_t) np + in->ny + in->nx + 5 * (size_t) np + 2 * kTropoFine))
-      return 1;
-  }
-  const size_t ncol = (size_t) in->nx * in->ny, ncell = ncol * np;
-  // mphip_profile_begin / _end (tools/gpu_met_prep_cost.py; a caller that profiles does not step from another thread):
-  // event pairs around every kernel (phase 0), around the uploads (1) or around the downloads (2)
-  hipEvent_t ev_stop = nullptr;
-  auto mark_begin = [&](int phase) {
-    ev_stop = nullptr;
-    if (!ctx->prof || ctx->prep_profile_phase != phase)
-      return 0;
-    while (ctx->ev_used + 2 > ctx->ev.size()) {
-      hipEvent_t e;
-      HIPCHK(hipEventCreate(&e));
-      ctx->ev.push_back(e);
-    }
-    HIPCHK(hipEventRecord(ctx->ev[ctx->ev_used++], st));
-    ev_stop = ctx->ev[ctx->ev_used++];
-    return 0;
-  };
-  auto mark_end = [&]() {
-    if (ev_stop)
-      HIPCHK(hipEventRecord(ev_stop, st));
-    return 0;
-  };
-  if (mark_begin(1))
+  std::vector<double> tab;      // (declared before the call scope: it outlives the scope's last synchronisation)
+  PrepCall call(ctx);
+  if (call.open())
     return 1;
-  HIPCHK(hipMemcpyAsync(ctx->prep_axes, in->p, (size_t) np * sizeof(double), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(ctx->prep_axes + np, in->lat, (size_t) in->ny * sizeof(double), hipMemcpyHostToDevice, st));
-  double *const d_lon = ctx->prep_axes + np + in->ny, *const d_tab = d_lon + in->nx;
-  std::vector<double> tab;      // (alive until the stream is synchronised below)
+  hipStream_t st = call.st;
+  const int nx = in->nx, ny = in->ny;
+  const size_t ncol = (size_t) nx * ny, ncell = ncol * np;
+  if (call.mark_begin(1))
+    return 1;
+  // p[np] | lat[ny] | lon[nx] | the tropopause's tables (PrepTropo::tab)
+  double *const d_p = call.take<double>((size_t) np + ny + nx + 5 * (size_t) np + 2 * kTropoFine);
+  if (!d_p)
+    return 1;
+  double *const d_lat = d_p + np, *const d_lon = d_lat + ny, *const d_tab = d_lon + nx;
+  HIPCHK(hipMemcpyAsync(d_p, in->p, (size_t) np * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_lat, in->lat, (size_t) ny * sizeof(double), hipMemcpyHostToDevice, st));
   if (do_pv || tropo) {
     // what depends on the pressure axis alone, with the host's C library -- the one mphip_libm.h restates, so these are
     // the values the device functions would give --: pows = pow(1000 / p, 0.286) and, for met_tropo 2 ... 5 only, zc =
@@ -4040,43 +4010,38 @@ int mphip_derive_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const
         p2[i] = 1013.25 * exp(-z2[i] / 7.);
       }
     }
-    HIPCHK(hipMemcpyAsync(d_lon, in->lon, (size_t) in->nx * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_lon, in->lon, (size_t) nx * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, st));
   }
+  float *i3[MPHIP_N3D] = {}, *i2[MPHIP_N2D] = {}, *o2[MPHIP_N2D] = {};
   for (int f = 0; f < MPHIP_N3D; f++)
-    if (need3[f]) {
-      if (!ctx->prep_in3[f] && dev_alloc(ctx, &ctx->prep_in3[f], ncell))
+    if (need3[f])
+      if (!(i3[f] = call.take<float>(ncell)) || copy3(ctx, st, i3[f], in->f3[f], nx, ny, np, in->sx, in->sy, true))
         return 1;
-      if (prep_copy3(ctx, ctx->prep_in3[f], in->f3[f], in, true, st))
-        return 1;
-    }
   for (int f = 0; f < MPHIP_N2D; f++) {
-    if (need2[f]) {
-      if (!ctx->prep_in2[f] && dev_alloc(ctx, &ctx->prep_in2[f], ncol))
+    if (need2[f])
+      if (!(i2[f] = call.take<float>(ncol)) || copy2(ctx, st, i2[f], in->f2[f], nx, ny, in->sx2, true))
         return 1;
-      if (prep_copy2(ctx, ctx->prep_in2[f], in->f2[f], in, true, st))
-        return 1;
-    }
-    if (give2[f] && !ctx->prep_out2[f] && dev_alloc(ctx, &ctx->prep_out2[f], ncol))
+    if (give2[f] && !(o2[f] = call.take<float>(ncol)))
       return 1;
   }
-  if (geopot)
-    for (auto &q : ctx->prep_z)
-      if (!q && dev_alloc(ctx, &q, ncell))
-        return 1;
-  if (do_pv && !ctx->prep_pv && dev_alloc(ctx, &ctx->prep_pv, ncell))
+  // geopotential height before and after the smoothing; potential vorticity
+  float *z_raw = nullptr, *z_smooth = nullptr, *pv = nullptr;
+  if (geopot && (!(z_raw = call.take<float>(ncell)) || (sx > 0 && !(z_smooth = call.take<float>(ncell)))))
     return 1;
-  if (mark_end())
+  if (do_pv && !(pv = call.take<float>(ncell)))
+    return 1;
+  if (call.mark_end())
     return 1;
 
   PrepGrid G;
-  G.nx = in->nx;
-  G.ny = in->ny;
+  G.nx = nx;
+  G.ny = ny;
   G.np = np;
   G.pitch = np | 1;
   G.ncol = (int) ncol;
-  G.p = ctx->prep_axes;
-  G.lat = ctx->prep_axes + np;
+  G.p = d_p;
+  G.lat = d_lat;
   PrepOpt O;
   O.met_pbl = opt->met_pbl;
   O.pbl_min = opt->met_pbl_min;
@@ -4085,90 +4050,61 @@ int mphip_derive_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const
   O.time = in->time;
   O.coord_type = in->coord_type;
   O.ref_lat = ctx->have_ctl ? ctx->ctl.met_utm_ref_lat : 0.0;
+  const dim3 lanes(kPrepLanes);
   auto blocks = [&](int cpb) {
     G.cpb = cpb;
     return dim3((unsigned) ((ncol + cpb - 1) / cpb));
   };
-  float *const *i3 = ctx->prep_in3, *const *i2 = ctx->prep_in2, *const *o2 = ctx->prep_out2;
-  const float *z_final = i3[MPHIP_Z];
+  float *z_final = i3[MPHIP_Z];
   if (geopot) {
     const dim3 nb = blocks(c_geo);
-    if (mark_begin(0))
+    if (call.launch(prep_geopot_kernel, nb, lanes, lds_geo, G, i3[MPHIP_T], i3[MPHIP_H2O], i2[MPHIP_PS], i2[MPHIP_ZS], z_raw))
       return 1;
-    hipLaunchKernelGGL(prep_geopot_kernel, nb, dim3(kPrepLanes), lds_geo, st, G, i3[MPHIP_T], i3[MPHIP_H2O], i2[MPHIP_PS],
-                       i2[MPHIP_ZS], ctx->prep_z[0]);
-    HIPCHK(hipGetLastError());
-    if (mark_end())
-      return 1;
-    z_final = ctx->prep_z[0];
+    z_final = z_raw;
     if (sx > 0) {
       const size_t lds = (size_t) (kSmTX + 2 * (sx - 1)) * (kSmTY + 2 * (sy - 1)) * kSmKC * sizeof(float);
-      const dim3 tiles((in->nx + kSmTX - 1) / kSmTX, (in->ny + kSmTY - 1) / kSmTY, (np + kSmKC - 1) / kSmKC);
-      if (mark_begin(0))
+      const dim3 tiles((nx + kSmTX - 1) / kSmTX, (ny + kSmTY - 1) / kSmTY, (np + kSmKC - 1) / kSmKC);
+      if (call.launch(prep_smooth_kernel, tiles, dim3(256), lds, G, sx, sy, z_raw, z_smooth))
         return 1;
-      hipLaunchKernelGGL(prep_smooth_kernel, tiles, dim3(256), lds, st, G, sx, sy, ctx->prep_z[0], ctx->prep_z[1]);
-      HIPCHK(hipGetLastError());
-      if (mark_end())
-        return 1;
-      z_final = ctx->prep_z[1];
+      z_final = z_smooth;
     }
   }
   if (what & MPHIP_PREP_O3C) {
     const dim3 nb = blocks(c_o3);
-    if (mark_begin(0))
-      return 1;
-    hipLaunchKernelGGL(prep_o3c_kernel, nb, dim3(kPrepLanes), lds_o3, st, G, i3[MPHIP_O3], i2[MPHIP_PS], o2[MPHIP_O3C]);
-    HIPCHK(hipGetLastError());
-    if (mark_end())
+    if (call.launch(prep_o3c_kernel, nb, lanes, lds_o3, G, i3[MPHIP_O3], i2[MPHIP_PS], o2[MPHIP_O3C]))
       return 1;
   }
   if (what & MPHIP_PREP_CLOUD) {
     const dim3 nb = blocks(c_cloud);
-    if (mark_begin(0))
-      return 1;
-    hipLaunchKernelGGL(prep_cloud_kernel, nb, dim3(kPrepLanes), lds_cloud, st, G, O, i3[MPHIP_LWC],
-                       need3[MPHIP_RWC] ? i3[MPHIP_RWC] : nullptr, i3[MPHIP_IWC], need3[MPHIP_SWC] ? i3[MPHIP_SWC] : nullptr,
-                       i2[MPHIP_PS], o2[MPHIP_PCT], o2[MPHIP_PCB], o2[MPHIP_CL]);
-    HIPCHK(hipGetLastError());
-    if (mark_end())
+    if (call.launch(prep_cloud_kernel, nb, lanes, lds_cloud, G, O, i3[MPHIP_LWC], i3[MPHIP_RWC], i3[MPHIP_IWC], i3[MPHIP_SWC],
+                    i2[MPHIP_PS], o2[MPHIP_PCT], o2[MPHIP_PCB], o2[MPHIP_CL]))
       return 1;
   }
   if (what & MPHIP_PREP_PBL) {
     const dim3 nb = blocks(c_pbl);
     const bool ri = opt->met_pbl == 2;
-    if (mark_begin(0))
-      return 1;
-    hipLaunchKernelGGL(prep_pbl_kernel, nb, dim3(kPrepLanes), lds_pbl, st, G, O, i3[MPHIP_T], ri ? i3[MPHIP_H2O] : nullptr,
-                       ri ? i3[MPHIP_U] : nullptr, ri ? i3[MPHIP_V] : nullptr, ri ? z_final : nullptr, i2[MPHIP_PS], i2[MPHIP_TS],
-                       ri ? i2[MPHIP_ZS] : nullptr, ri ? i2[MPHIP_US] : nullptr, ri ? i2[MPHIP_VS] : nullptr, o2[MPHIP_PBL]);
-    HIPCHK(hipGetLastError());
-    if (mark_end())
+    if (call.launch(prep_pbl_kernel, nb, lanes, lds_pbl, G, O, i3[MPHIP_T], ri ? i3[MPHIP_H2O] : nullptr,
+                    ri ? i3[MPHIP_U] : nullptr, ri ? i3[MPHIP_V] : nullptr, ri ? z_final : nullptr, i2[MPHIP_PS], i2[MPHIP_TS],
+                    ri ? i2[MPHIP_ZS] : nullptr, ri ? i2[MPHIP_US] : nullptr, ri ? i2[MPHIP_VS] : nullptr, o2[MPHIP_PBL]))
       return 1;
   }
   if (what & MPHIP_PREP_CAPE) {
     const dim3 nb = blocks(c_cape);
-    if (mark_begin(0))
-      return 1;
-    hipLaunchKernelGGL(prep_cape_kernel, nb, dim3(kPrepLanes), lds_cape, st, G, O, ctx->d_clim, i3[MPHIP_T], i3[MPHIP_H2O],
-                       i2[MPHIP_PS], o2[MPHIP_PLCL], o2[MPHIP_PLFC], o2[MPHIP_PEL], o2[MPHIP_CAPE], o2[MPHIP_CIN]);
-    HIPCHK(hipGetLastError());
-    if (mark_end())
+    if (call.launch(prep_cape_kernel, nb, lanes, lds_cape, G, O, ctx->d_clim, i3[MPHIP_T], i3[MPHIP_H2O], i2[MPHIP_PS],
+                    o2[MPHIP_PLCL], o2[MPHIP_PLFC], o2[MPHIP_PEL], o2[MPHIP_CAPE], o2[MPHIP_CIN]))
       return 1;
   }
-  const float *pv_final = i3[MPHIP_PV];
+  float *pv_final = i3[MPHIP_PV];
   if (do_pv) {
-    const dim3 tiles((in->nx + kPvTX - 1) / kPvTX, (in->ny + kPvTY - 1) / kPvTY, (np + kPvKC - 1) / kPvKC);
-    if (mark_begin(0))
+    // (the field and its polar rows: one event pair)
+    const dim3 tiles((nx + kPvTX - 1) / kPvTX, (ny + kPvTY - 1) / kPvTY, (np + kPvKC - 1) / kPvKC);
+    if (call.mark_begin(0)
+        || call.enqueue(prep_pv_kernel, tiles, dim3(256), kPvLds, G, d_lon, d_tab + 4 * (size_t) np, i3[MPHIP_T], i3[MPHIP_U],
+                        i3[MPHIP_V], pv)
+        || call.enqueue(prep_pv_polar_kernel, dim3((unsigned) (((size_t) nx * np + 255) / 256)), dim3(256), 0, G, pv)
+        || call.mark_end())
       return 1;
-    hipLaunchKernelGGL(prep_pv_kernel, tiles, dim3(256), kPvLds, st, G, d_lon, d_tab + 4 * (size_t) np, i3[MPHIP_T],
-                       i3[MPHIP_U], i3[MPHIP_V], ctx->prep_pv);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(prep_pv_polar_kernel, dim3((unsigned) (((size_t) in->nx * np + 255) / 256)), dim3(256), 0, st, G,
-                       ctx->prep_pv);
-    HIPCHK(hipGetLastError());
-    if (mark_end())
-      return 1;
-    pv_final = ctx->prep_pv;
+    pv_final = pv;
   }
   if (tropo) {
     const dim3 nb = blocks(c_tropo);
@@ -4180,28 +4116,22 @@ int mphip_derive_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const
     T.nprof = tropo_nprof;
     T.fine = tropo_fine;
     T.tab = d_tab;
-    if (mark_begin(0))
-      return 1;
-    hipLaunchKernelGGL(prep_tropo_kernel, nb, dim3(kPrepLanes), lds_tropo, st, G, O, T, ctx->d_clim, i3[MPHIP_T],
-                       i3[MPHIP_H2O], z_final, T.mode == 5 ? pv_final : nullptr, o2[MPHIP_PT], o2[MPHIP_TT], o2[MPHIP_ZT],
-                       o2[MPHIP_H2OT]);
-    HIPCHK(hipGetLastError());
-    if (mark_end())
+    if (call.launch(prep_tropo_kernel, nb, lanes, lds_tropo, G, O, T, ctx->d_clim, i3[MPHIP_T], i3[MPHIP_H2O], z_final,
+                    T.mode == 5 ? pv_final : nullptr, o2[MPHIP_PT], o2[MPHIP_TT], o2[MPHIP_ZT], o2[MPHIP_H2OT]))
       return 1;
   }
-  if (mark_begin(2))
+  if (call.mark_begin(2))
     return 1;
-  if (do_pv && prep_copy3(ctx, ctx->prep_pv, out->f3[MPHIP_PV], in, false, st))
+  if (do_pv && copy3(ctx, st, pv, out->f3[MPHIP_PV], nx, ny, np, in->sx, in->sy, false))
     return 1;
-  if (geopot && prep_copy3(ctx, const_cast<float *>(z_final), out->f3[MPHIP_Z], in, false, st))
+  if (geopot && copy3(ctx, st, z_final, out->f3[MPHIP_Z], nx, ny, np, in->sx, in->sy, false))
     return 1;
   for (int f = 0; f < MPHIP_N2D; f++)
-    if (give2[f] && prep_copy2(ctx, ctx->prep_out2[f], out->f2[f], in, false, st))
+    if (give2[f] && copy2(ctx, st, o2[f], out->f2[f], nx, ny, in->sx2, false))
       return 1;
-  if (mark_end())
+  if (call.mark_end())
     return 1;
-  HIPCHK(hipStreamSynchronize(st));
-  return 0;
+  return call.close();
 }
 
 size_t mphip_sizeof_regrid(void) {
@@ -4251,11 +4181,10 @@ int mphip_regrid_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const
     if (in->f2[f] && out->f2[f])
       f2[n2++] = f;
 
-  std::lock_guard<std::mutex> guard(ctx->prep_lock);
-  HIPCHK(hipSetDevice(ctx->device));
-  if (!ctx->prep_stream)
-    HIPCHK(hipStreamCreateWithFlags(&ctx->prep_stream, hipStreamNonBlocking));
-  hipStream_t st = ctx->prep_stream;
+  PrepCall call(ctx);
+  if (call.open())
+    return 1;
+  hipStream_t st = call.st;
   const size_t ncol = (size_t) P.nx * P.ny, ncol2 = (size_t) P.nx2 * P.ny2;
   const size_t ncell0 = ncol * P.np0, ncell1 = ncol * P.np1, ncell2 = ncol2 * P.np2;
   // the axes of the output are taken before anything is written (`out` may alias `in`)
@@ -4268,58 +4197,34 @@ int mphip_regrid_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const
   for (int i = 0; i < P.np2; i++)
     p2[i] = (ml ? opt->met_p : in->p)[(size_t) i * ddp];
 
-  // uploads
-  hipEvent_t ev_stop = nullptr;
-  auto mark_begin = [&](int phase) {
-    ev_stop = nullptr;
-    if (!ctx->prof || ctx->prep_profile_phase != phase)
-      return 0;
-    while (ctx->ev_used + 2 > ctx->ev.size()) {
-      hipEvent_t e;
-      HIPCHK(hipEventCreate(&e));
-      ctx->ev.push_back(e);
-    }
-    HIPCHK(hipEventRecord(ctx->ev[ctx->ev_used++], st));
-    ev_stop = ctx->ev[ctx->ev_used++];
-    return 0;
-  };
-  auto mark_end = [&]() {
-    if (ev_stop)
-      HIPCHK(hipEventRecord(ev_stop, st));
-    return 0;
-  };
-  if (mark_begin(1))
+  // uploads; per field of the call the uploaded array, ML2PL's result and SAMPLE's result
+  float *in3[kRgFields + 2] = {}, *mid3[kRgFields + 2] = {}, *out3[kRgFields + 2] = {}, *in2[MPHIP_N2D] = {}, *out2[MPHIP_N2D] = {};
+  double *d_metp = nullptr;
+  float *d_pl = nullptr;
+  if (call.mark_begin(1))
     return 1;
   if (ml) {
-    if (ctx->rg_p_n < (size_t) opt->met_np) {
-      ctx->rg_p_n = 0;
-      if (dev_alloc(ctx, &ctx->rg_p, (size_t) opt->met_np))
-        return 1;
-      ctx->rg_p_n = (size_t) opt->met_np;
-    }
-    HIPCHK(hipMemcpyAsync(ctx->rg_p, opt->met_p, (size_t) opt->met_np * sizeof(double), hipMemcpyHostToDevice, st));
-    if (regrid_reserve(ctx, ctx->rg_in3[MPHIP_PL], ncell0)
-        || regrid_copy3(ctx, ctx->rg_in3[MPHIP_PL].p, in->f3[MPHIP_PL], P.nx, P.ny, P.np0, in->sx_ml, in->sy_ml, true, st))
+    if (!(d_metp = call.take<double>((size_t) opt->met_np)))
+      return 1;
+    HIPCHK(hipMemcpyAsync(d_metp, opt->met_p, (size_t) opt->met_np * sizeof(double), hipMemcpyHostToDevice, st));
+    if (!(d_pl = call.take<float>(ncell0)) || copy3(ctx, st, d_pl, in->f3[MPHIP_PL], P.nx, P.ny, P.np0, in->sx_ml, in->sy_ml, true))
       return 1;
   }
   for (int i = 0; i < n3; i++) {
-    const int f = f3[i];
-    if (regrid_reserve(ctx, ctx->rg_in3[f], ncell0)
-        || regrid_copy3(ctx, ctx->rg_in3[f].p, in->f3[f], P.nx, P.ny, P.np0, in->sx, in->sy, true, st))
+    if (!(in3[i] = call.take<float>(ncell0)) || copy3(ctx, st, in3[i], in->f3[f3[i]], P.nx, P.ny, P.np0, in->sx, in->sy, true))
       return 1;
-    if (ml && regrid_reserve(ctx, ctx->rg_mid3[f], ncell1))
+    if (ml && !(mid3[i] = call.take<float>(ncell1)))
       return 1;
-    if (sample && regrid_reserve(ctx, ctx->rg_out3[f], ncell2))
+    if (sample && !(out3[i] = call.take<float>(ncell2)))
       return 1;
   }
   for (int i = 0; i < n2; i++) {
-    const int f = f2[i];
-    if (regrid_reserve(ctx, ctx->rg_in2[f], ncol) || regrid_copy2(ctx, ctx->rg_in2[f].p, in->f2[f], P.nx, P.ny, in->sx2, true, st))
+    if (!(in2[i] = call.take<float>(ncol)) || copy2(ctx, st, in2[i], in->f2[f2[i]], P.nx, P.ny, in->sx2, true))
       return 1;
-    if (sample && regrid_reserve(ctx, ctx->rg_out2[f], ncol2))
+    if (sample && !(out2[i] = call.take<float>(ncol2)))
       return 1;
   }
-  if (mark_end())
+  if (call.mark_end())
     return 1;
   // (pageable memory: the copies above have read the caller's arrays when they return; the synchronisation makes that
   // hold for pinned arrays too, before the first download below overwrites an aliased input)
@@ -4329,54 +4234,33 @@ int mphip_regrid_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const
     RegridFields F;
     F.n = n3;
     for (int i = 0; i < n3; i++) {
-      F.in[i] = ctx->rg_in3[f3[i]].p;
-      F.out[i] = ctx->rg_mid3[f3[i]].p;
+      F.in[i] = in3[i];
+      F.out[i] = mid3[i];
     }
-    if (mark_begin(0))
-      return 1;
-    hipLaunchKernelGGL(regrid_ml2pl_kernel, dim3((unsigned) ((ncol + P.ml_cpb - 1) / P.ml_cpb)), dim3(kRgThreads), P.ml_lds, st,
-                       (int) ncol, P.np0, opt->met_np, P.ml_cpb, P.np0 | 1, ctx->rg_p, ctx->rg_in3[MPHIP_PL].p, F);
-    HIPCHK(hipGetLastError());
-    if (mark_end())
+    if (call.launch(regrid_ml2pl_kernel, dim3((unsigned) ((ncol + P.ml_cpb - 1) / P.ml_cpb)), dim3(kRgThreads), P.ml_lds,
+                    (int) ncol, P.np0, opt->met_np, P.ml_cpb, P.np0 | 1, d_metp, d_pl, F))
       return 1;
   }
   if (sample) {
     const dim3 tiles3((P.nx2 + kRgTX - 1) / kRgTX, (P.ny2 + kRgTY - 1) / kRgTY, (P.np2 + kRgKC - 1) / kRgKC);
     const dim3 tiles2(tiles3.x, tiles3.y, 1);
-    for (int i = 0; i < n3; i++) {
-      if (mark_begin(0))
+    for (int i = 0; i < n3; i++)
+      if (call.launch(regrid_sample_kernel<kRgKC>, tiles3, dim3(kRgThreads), P.lds3, P.S3, ml ? mid3[i] : in3[i], out3[i]))
         return 1;
-      hipLaunchKernelGGL(regrid_sample_kernel<kRgKC>, tiles3, dim3(kRgThreads), P.lds3, st, P.S3,
-                         ml ? ctx->rg_mid3[f3[i]].p : ctx->rg_in3[f3[i]].p, ctx->rg_out3[f3[i]].p);
-      HIPCHK(hipGetLastError());
-      if (mark_end())
+    for (int i = 0; i < n2; i++)
+      if (call.launch(regrid_sample_kernel<1>, tiles2, dim3(kRgTX * kRgTY), P.lds2, P.S2, in2[i], out2[i]))
         return 1;
-    }
-    for (int i = 0; i < n2; i++) {
-      if (mark_begin(0))
-        return 1;
-      hipLaunchKernelGGL(regrid_sample_kernel<1>, tiles2, dim3(kRgTX * kRgTY), P.lds2, st, P.S2, ctx->rg_in2[f2[i]].p,
-                         ctx->rg_out2[f2[i]].p);
-      HIPCHK(hipGetLastError());
-      if (mark_end())
-        return 1;
-    }
   }
-  if (mark_begin(2))
+  if (call.mark_begin(2))
     return 1;
-  for (int i = 0; i < n3; i++) {
-    const float *res = sample ? ctx->rg_out3[f3[i]].p : ctx->rg_mid3[f3[i]].p;
-    if (regrid_copy3(ctx, const_cast<float *>(res), out->f3[f3[i]], P.nx2, P.ny2, P.np2, out->sx, out->sy, false, st))
+  for (int i = 0; i < n3; i++)
+    if (copy3(ctx, st, sample ? out3[i] : mid3[i], out->f3[f3[i]], P.nx2, P.ny2, P.np2, out->sx, out->sy, false))
       return 1;
-  }
-  for (int i = 0; i < n2; i++) {
-    const float *res = sample ? ctx->rg_out2[f2[i]].p : ctx->rg_in2[f2[i]].p;
-    if (regrid_copy2(ctx, const_cast<float *>(res), out->f2[f2[i]], P.nx2, P.ny2, out->sx2, false, st))
+  for (int i = 0; i < n2; i++)
+    if (copy2(ctx, st, sample ? out2[i] : in2[i], out->f2[f2[i]], P.nx2, P.ny2, out->sx2, false))
       return 1;
-  }
-  if (mark_end())
+  if (call.mark_end() || call.close())
     return 1;
-  HIPCHK(hipStreamSynchronize(st));
   if (out->lon)
     memcpy(out->lon, lon2.data(), lon2.size() * sizeof(double));
   if (out->lat)
@@ -4409,83 +4293,56 @@ int mphip_detrend_met(mphip_ctx *ctx, const mphip_met_t *in, const mphip_detrend
   if (!nf)
     return fail(ctx, "mphip_detrend_met: none of the fields t, u, v, w is present in both `in` and `out`");
 
-  std::lock_guard<std::mutex> guard(ctx->prep_lock);
-  HIPCHK(hipSetDevice(ctx->device));
-  if (!ctx->prep_stream)
-    HIPCHK(hipStreamCreateWithFlags(&ctx->prep_stream, hipStreamNonBlocking));
-  hipStream_t st = ctx->prep_stream;
-  hipEvent_t ev_stop = nullptr;
-  auto mark_begin = [&](int phase) {
-    ev_stop = nullptr;
-    if (!ctx->prof || ctx->prep_profile_phase != phase)
-      return 0;
-    while (ctx->ev_used + 2 > ctx->ev.size()) {
-      hipEvent_t e;
-      HIPCHK(hipEventCreate(&e));
-      ctx->ev.push_back(e);
-    }
-    HIPCHK(hipEventRecord(ctx->ev[ctx->ev_used++], st));
-    ev_stop = ctx->ev[ctx->ev_used++];
-    return 0;
-  };
-  auto mark_end = [&]() {
-    if (ev_stop)
-      HIPCHK(hipEventRecord(ev_stop, st));
-    return 0;
-  };
-  // the weight table (host; the stream is idle meanwhile, so the two events around it give the host's time)
-  if (mark_begin(3))
+  std::vector<float> w;         // (as P.rows, declared before the call scope: it outlives the scope's last synchronisation)
+  PrepCall call(ctx);
+  if (call.open())
     return 1;
-  std::vector<float> w;
+  hipStream_t st = call.st;
+  // the weight table (host; the stream is idle meanwhile, so the two events around it give the host's time)
+  if (call.mark_begin(3))
+    return 1;
   detrend_table(in, P, w);
-  if (mark_end())
+  if (call.mark_end())
     return 1;
   // uploads
-  if (mark_begin(1))
+  if (call.mark_begin(1))
     return 1;
   const size_t ncell = (size_t) P.nx * P.ny * P.np;
-  if (regrid_reserve(ctx, ctx->dt_w, P.nw))
+  float *const d_w = call.take<float>(P.nw);
+  DetrendRow *const d_rows = d_w ? call.take<DetrendRow>((size_t) P.ny) : nullptr;
+  if (!d_rows)
     return 1;
-  if (ctx->dt_rows_n < (size_t) P.ny) {
-    ctx->dt_rows_n = 0;
-    if (dev_alloc(ctx, &ctx->dt_rows, (size_t) P.ny))
-      return 1;
-    ctx->dt_rows_n = (size_t) P.ny;
-  }
-  HIPCHK(hipMemcpyAsync(ctx->dt_w.p, w.data(), P.nw * sizeof(float), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(ctx->dt_rows, P.rows.data(), (size_t) P.ny * sizeof(DetrendRow), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_w, w.data(), P.nw * sizeof(float), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_rows, P.rows.data(), (size_t) P.ny * sizeof(DetrendRow), hipMemcpyHostToDevice, st));
   DetrendFields F;
   memset(&F, 0, sizeof(F));
   F.n = nf;
+  float *res[kDtFields] = {};
   for (int i = 0; i < nf; i++) {
-    if (regrid_reserve(ctx, ctx->dt_in[i], ncell) || regrid_reserve(ctx, ctx->dt_out[i], ncell)
-        || regrid_copy3(ctx, ctx->dt_in[i].p, in->f3[fld[i]], P.nx, P.ny, P.np, in->sx, in->sy, true, st))
+    float *const d_in = call.take<float>(ncell);
+    if (!d_in || !(res[i] = call.take<float>(ncell))
+        || copy3(ctx, st, d_in, in->f3[fld[i]], P.nx, P.ny, P.np, in->sx, in->sy, true))
       return 1;
-    F.in[i] = ctx->dt_in[i].p;
-    F.out[i] = ctx->dt_out[i].p;
+    F.in[i] = d_in;
+    F.out[i] = res[i];
   }
-  if (mark_end())
+  if (call.mark_end())
     return 1;
   // (the table and the row records are this call's own vectors, and an aliased input must have been read before the
   // first download overwrites it: the uploads are complete here)
   HIPCHK(hipStreamSynchronize(st));
 
-  if (mark_begin(0))
+  if (call.launch(detrend_kernel, dim3((unsigned) ((long long) P.nchunk * P.ny), (unsigned) nf), dim3(kDtThreads), 0, P.nx, P.ny,
+                  P.np, d_rows, d_w, F))
     return 1;
-  hipLaunchKernelGGL(detrend_kernel, dim3((unsigned) ((long long) P.nchunk * P.ny), (unsigned) nf), dim3(kDtThreads), 0, st,
-                     P.nx, P.ny, P.np, ctx->dt_rows, ctx->dt_w.p, F);
-  HIPCHK(hipGetLastError());
-  if (mark_end())
-    return 1;
-  if (mark_begin(2))
+  if (call.mark_begin(2))
     return 1;
   for (int i = 0; i < nf; i++)
-    if (regrid_copy3(ctx, ctx->dt_out[i].p, out->f3[fld[i]], P.nx, P.ny, P.np, out->sx, out->sy, false, st))
+    if (copy3(ctx, st, res[i], out->f3[fld[i]], P.nx, P.ny, P.np, out->sx, out->sy, false))
       return 1;
-  if (mark_end())
+  if (call.mark_end())
     return 1;
-  HIPCHK(hipStreamSynchronize(st));
-  return 0;
+  return call.close();
 }
 
 // waits for the uploader thread; 0 = the snapshot is on its way (next_ready recorded)
@@ -5754,7 +5611,7 @@ int mphip_set_option(mphip_ctx *ctx, const char *name, double value) {
     if (value != 0 && value != 1 && value != 2 && value != 3)
       return fail(ctx, "derive_profile_phase must be 0 (kernels), 1 (uploads), 2 (downloads) or 3 (the weight table of "
                        "mphip_detrend_met)");
-    ctx->prep_profile_phase = (int) value;
+    ctx->prep.profile_phase = (int) value;
     return 0;
   }
   if (strcmp(name, "xcd_map") == 0) {

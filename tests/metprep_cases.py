@@ -218,7 +218,8 @@ def short_axis(name, seed=7):
 
 def level_limit(nf=5):
     """The largest np with 16 np + 4 nf (np | 1) <= 65536: two doubles per level and nf float planes of one column at a
-    pitch of np | 1 within 64 KB (prep_columns; nf = 5: met_pbl 2, the most any of the five older kernels stages)."""
+    pitch of np | 1 within 64 KB (columns_per_workgroup as mphip_derive_met calls it; nf = 5: met_pbl 2, the most any of
+    the five older kernels stages)."""
     n = 2
     while 16 * (n + 1) + 4 * nf * ((n + 1) | 1) <= 65536:
         n += 1
