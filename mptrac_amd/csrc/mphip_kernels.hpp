@@ -18,10 +18,13 @@ namespace mphip {
 
 // ---------------------------------------------------------------------------
 // module_mixing (mptrac.c:5169-5347) per particle: the box a particle is in, and the relaxation towards the
-// box mean (kernels box_index_kernel and mix_relax_kernel below).  Both were also tried as parts of the
-// time-step launches around module_mixing: the box index at the end of the launch that moves the particles cost
-// that launch 40 - 70 us (a logarithm and three true divisions per particle) against 67 us for the kernel of its
-// own, the relaxation at the start of the launch of the deposition modules 150 us against 127 us -- no gain.
+// box mean (kernels box_index_kernel and mix_relax_kernel below).  box_cell has three callers that give the same
+// cell (tests/test_gpu_box_edges.py): box_index_kernel; sort_key_kernel with BoxArgs, beside the keys of a
+// module_sort that runs ahead; and the launch that moves the particles itself, through EmitKeys, where such a sort
+// is due in the next step -- alone at the end of that launch the box index cost it 40 - 70 us (a logarithm and
+// three true divisions per particle) against 67 us for the kernel of its own, no gain; with the sort keys it
+// replaces a pass over the particles.  The relaxation was tried at the start of the launch of the deposition
+// modules: 150 us against 127 us, dropped.
 // ---------------------------------------------------------------------------
 
 struct BoxGrid {

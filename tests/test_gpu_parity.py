@@ -758,9 +758,10 @@ def test_gridded_sums_from_value_records_equal_the_sums_from_the_arrays(path):
 @pytest.mark.parametrize("mode", ["groups", "chains", "atomics"])
 def test_gridded_sums_with_a_vertical_weighting_function(mode):
     """GRID_KERNEL: every summand of the gridded output is kernel(z) * q (and its square), the kernel linear
-    between its nodes and constant beyond them (kernel_weight, mptrac.c:3298-3320, 13866).  The weight goes through
-    the device's logarithm (Z(p)), so the sums agree with the serial code to rounding, not to the bit; without
-    nodes the weight is exactly one again."""
+    between its nodes and constant beyond them (kernel_weight, mptrac.c:3298-3320, 13866).  In the default build the
+    weight's interpolation and its product with q are compiled with contraction allowed, so the sums agree to rounding
+    (measured: 2e-16 of the largest), not to the bit; the reference-rounding build returns the serial code's bits
+    (tests/test_gpu_box_edges_exact.py asserts it).  Without nodes the weight is exactly one again."""
     ctl, clim, m0, m1, atm = cases.make_case("conv_sedi", n=30011)
     ctl = dict(ctl, grid_nx=36, grid_ny=18, grid_nz=4, grid_z0=0.0, grid_z1=32.0)
     kz = np.array([2.0, 5.0, 9.0, 14.0, 20.0])
