@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """No instruction may touch the destination of a load that has not been waited for.
 
-The wind / model-level corner caches issue their gathers as inline assembly and wait for them in a second
+The wind-corner caches issue their gathers as inline assembly and wait for them in a second
 asm statement, so that the work between the two overlaps the gather (mphip_device.hpp: load_wind_cached,
-wind_cache_wait, load_ml_cached).  The compiler does not know about those loads: if the register allocator
+load_wind_cached32, wind_cache_wait).  The compiler does not know about those loads: if the register allocator
 moved, copied or spilled one of the destination registers between the load and the wait, the kernel would
 read stale data -- silently, and only in the build where it happens.  This check reads the machine code of the
 built library and fails when that happened:

@@ -658,7 +658,7 @@ static bool lean32_ok(const mphip_ctx *ctx);
 static bool meso_table_wanted(const mphip_ctx *ctx) {
   // (the condition of the time step's module set, plan_step; a caller that runs the module on its own with
   // `diffusion` off gets the table in front of its first launch)
-  return MPHIP_MESO_TABLE && ctx->have_ctl && ctx->ctl.diffusion && (ctx->ctl.turb_mesox > 0 || ctx->ctl.turb_mesoz > 0)
+  return ctx->have_ctl && ctx->ctl.diffusion && (ctx->ctl.turb_mesox > 0 || ctx->ctl.turb_mesoz > 0)
     && lean32_ok(ctx);
 }
 
@@ -949,7 +949,7 @@ static bool lean_grid(const mphip_ctx *ctx) {
 static bool fits32(const mphip_ctx *ctx) {
   // (the table of module_diff_meso's deviations rounds its bricks up: on a thin grid it can be the largest array)
   return (unsigned long long) ctx->nx * ctx->ny * guard_levels(ctx) * 24ull < (1ull << 32)
-    && (!MPHIP_MESO_TABLE || (unsigned long long) meso_table_floats(ctx) * 4ull < (1ull << 32));
+    && (unsigned long long) meso_table_floats(ctx) * 4ull < (1ull << 32);
 }
 static bool lean32_ok(const mphip_ctx *ctx) { return lean_grid(ctx) && fits32(ctx) && !ctx->big_grid; }
 static bool lean64_ok(const mphip_ctx *ctx) { return lean_grid(ctx) && (!fits32(ctx) || ctx->big_grid); }
@@ -1070,7 +1070,7 @@ unsigned step_kernel_mask(const mphip_ctx *ctx, unsigned mask, int nsteps) {
 // Does instantiation `sel`, launched with module set `mask`, read the table of module_diff_meso's wind deviations?  The
 // lean instantiations with 32-bit offsets do (diff_meso_fast); the gated ones switch the module by the run-time mask.
 static bool reads_meso_table(unsigned sel, unsigned mask) {
-  return MPHIP_MESO_TABLE && sel != kNoStepKernel && sel < kMaskGenericMLMulti && (sel & MPHIP_MOD_DIFF_MESO)
+  return sel != kNoStepKernel && sel < kMaskGenericMLMulti && (sel & MPHIP_MOD_DIFF_MESO)
     && !(sel & kBigGrid) && (mask & MPHIP_MOD_DIFF_MESO);
 }
 
@@ -4732,10 +4732,8 @@ int mphip_run_timestep(mphip_ctx *ctx, double t) {
       ek.t_stop = c.t_stop;
       ek.t_next = t_next;
       constexpr unsigned kDepo = MPHIP_MOD_WET_DEPO | MPHIP_MOD_DRY_DEPO;
-#ifndef MPHIP_DEPO_FLAGS
-#define MPHIP_DEPO_FLAGS 1      // 0: experiment -- the deposition launch decides from dt, time, p itself (profiles/r06_ab_depo_flags.txt)
-#endif
-      if (MPHIP_DEPO_FLAGS && (tail & kDepo) && !(tail & ~kDepo) && ctx->compact_depo) {   // the deposition launch behind module_mixing will be depo_kernel
+      // (the flags measured against a deposition launch that decides from dt, time, p itself: profiles/r06_ab_depo_flags.txt)
+      if ((tail & kDepo) && !(tail & ~kDepo) && ctx->compact_depo) {   // the deposition launch behind module_mixing will be depo_kernel
         if (ctx->np > ctx->depo_busy_cap) {
           if (dev_alloc(ctx, &ctx->d_depo_busy, (size_t) ctx->np))
             return 1;
@@ -5817,7 +5815,7 @@ int mphip_test_piece(mphip_ctx *ctx, int piece, int reps, double *checksum) {
   S.ctr_meso = 5000;
   S.ctr_conv = 9000;
   S.ctr_pbl = 0;
-  if (MPHIP_MESO_TABLE && piece == 22) {   // (diff_meso_fast reads the table)
+  if (piece == 22) {   // (diff_meso_fast reads the table)
     if (!lean32_ok(ctx))
       return fail(ctx, "mphip_test_piece: piece 22 needs a grid the lean kernels with 32-bit offsets run on");
     if (ensure_meso_table(ctx))
@@ -5868,8 +5866,8 @@ int mphip_test_meso_table(mphip_ctx *ctx, float *out, size_t cells) {
   const size_t nx = (size_t) ctx->nx - 1, ny = (size_t) ctx->ny - 1, np = (size_t) ctx->npl - 1;
   if (cells != nx * ny * np)
     return fail(ctx, "mphip_test_meso_table: `cells` must be (nx - 1) (ny - 1) (np - 1)");
-  if (!MPHIP_MESO_TABLE || !lean32_ok(ctx))
-    return fail(ctx, "mphip_test_meso_table: no table in this build or on this grid");
+  if (!lean32_ok(ctx))
+    return fail(ctx, "mphip_test_meso_table: no table on this grid");
   if (ensure_meso_table(ctx))
     return 1;
   std::vector<float> h(meso_table_floats(ctx));

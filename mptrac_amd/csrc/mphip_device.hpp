@@ -270,15 +270,6 @@ __device__ __forceinline__ Axes load_axes(const DevMet &M, double *smem) {
 #ifndef MPHIP_EXACT_DIV
 #define MPHIP_EXACT_DIV 0
 #endif
-// 1: keep the last wind corners of a particle and reload only where its grid cell changed
-#ifndef MPHIP_WIND_CACHE
-#define MPHIP_WIND_CACHE 1
-#endif
-// > 0: wave priority (s_setprio) while a wave computes the addresses of a gather round of the Runge-Kutta
-// stages and issues the loads -- the sooner a round is in flight, the more of its latency other waves cover
-#ifndef MPHIP_SETPRIO
-#define MPHIP_SETPRIO 0
-#endif
 
 
 __device__ __forceinline__ double div_const(double x, double y, double inv_y) {
@@ -778,7 +769,7 @@ struct WindCache {
 };
 
 __device__ __forceinline__ void wind_cache_reset(WindCache &w, bool enabled) {
-  w.enabled = enabled && MPHIP_WIND_CACHE;
+  w.enabled = enabled;
   w.ix = w.iy = w.ip = -1;
   // the corners have no value yet (every lane loads them at the first stencil: no cell is -1); an empty
   // asm gives the registers a definition without the 48 moves a zero fill costs per particle
@@ -1724,12 +1715,6 @@ __device__ __forceinline__ void normal_triple(const double *__restrict__ ltab, u
   r2 = odd ? ob : eb;
 }
 
-// 1: module_diff_turb evaluates only the Box-Muller pair of rs[3g + 2] where there is no horizontal diffusion
-// (Kx = 0: 57 % of the C3 particles, 46 % of the waves entirely).  Measured on C3: 0.766-0.771 ms per step against
-// 0.758-0.762 without, and no fewer instructions issued (profiles/r04_variants.txt) -- off
-#ifndef MPHIP_TURB_SHORTCUT
-#define MPHIP_TURB_SHORTCUT 0
-#endif
 // rs[3g + 2] alone: the second Box-Muller pair of the triple
 __device__ __forceinline__ double normal_third(const double *__restrict__ ltab, uint64_t c0, uint64_t g) {
   const uint64_t i0 = 3 * g;
@@ -1803,14 +1788,8 @@ __device__ __forceinline__ void position(const DevMet &M, const Axes &A, Particl
 }
 
 // module_advect, pressure-level branch, mptrac.c:3612-3677
-// `hook(i)` runs right after the gathers of stage i were issued: work that does
-// not depend on them (the random numbers of the later modules) fills the wait.
-struct NoHook {
-  __device__ __forceinline__ void operator()(int) const {}
-};
-
-template <int ADVECT, class Hook>
-__device__ __forceinline__ void advect_n(const DevMet &M, const Axes &A, Particle &P, Hook &hook, WindCache &wc) {
+template <int ADVECT>
+__device__ __forceinline__ void advect_n(const DevMet &M, const Axes &A, Particle &P, WindCache &wc) {
   const int ct = M.coord_type;
   const double dt = P.dt;
   double u = 0, v = 0, w = 0, um = 0, vm = 0, wm = 0;
@@ -1834,12 +1813,9 @@ __device__ __forceinline__ void advect_n(const DevMet &M, const Axes &A, Particl
     stencil_3d(M, A, x2, x0, x1, s);
     if (wc.enabled) {
       load_wind_cached(M, s, wc);
-      hook(i);
       wind_cache_wait(wc);
-    } else {
+    } else
       load_wind(M, s, wc.c);
-      hook(i);
-    }
     const WindCorners &c = wc.c;
     const double wt = time_weight(M, tm);
     u = wind_time_3d(c, s, wt, 0);
@@ -1860,21 +1836,14 @@ __device__ __forceinline__ void advect_n(const DevMet &M, const Axes &A, Particl
   P.p += dt * wm;
 }
 
-template <class Hook>
-__device__ __forceinline__ void advect(const mphip_ctl_t &ctl, const DevMet &M, const Axes &A, Particle &P,
-                                       Hook &hook, WindCache &wc) {
-  if (ctl.advect == 4)
-    advect_n<4>(M, A, P, hook, wc);
-  else if (ctl.advect == 2)
-    advect_n<2>(M, A, P, hook, wc);
-  else
-    advect_n<1>(M, A, P, hook, wc);
-}
-
 __device__ __forceinline__ void advect(const mphip_ctl_t &ctl, const DevMet &M, const Axes &A, Particle &P,
                                        WindCache &wc) {
-  NoHook none;
-  advect(ctl, M, A, P, none, wc);
+  if (ctl.advect == 4)
+    advect_n<4>(M, A, P, wc);
+  else if (ctl.advect == 2)
+    advect_n<2>(M, A, P, wc);
+  else
+    advect_n<1>(M, A, P, wc);
 }
 
 // module_advect, zeta / eta branch (mptrac.c:3681-3757); zeta is the particle's
@@ -2138,9 +2107,6 @@ __device__ __forceinline__ double level_pair_value(const Stencil4 &s, const f32x
 // which hold the pairs b, b + 1, b + 2.  If all eight searches (four columns, two snapshots) end inside it, the
 // indices, the records at the lowest index and the records the while loop steps through are all in registers.
 // A lane with a search that leaves the window takes the lockstep search and loads what it needs.
-#ifndef MPHIP_LEVEL_WINDOW
-#define MPHIP_LEVEL_WINDOW 1
-#endif
 
 // index of snapshot t among the pairs b, b + 1, b + 2 (w0: levels b, b + 1; w1: b + 2, b + 3), or -1
 __device__ __forceinline__ int window_index(const f32x4u w0, const f32x4u w1, int t, int b, int n, float xd) {
@@ -2170,9 +2136,6 @@ __device__ __forceinline__ f32x4u window_record(const float *__restrict__ h2, CO
 }
 
 // stencil_4d on a packed height field; `hint` is any earlier vertical index (e.g. of the previous stage)
-#ifndef MPHIP_ML_HORIZ_FAST
-#define MPHIP_ML_HORIZ_FAST 1
-#endif
 __device__ __forceinline__ bool lat_fast(const DevMet &M, const Axes &A, double lat2, int &iy, double &y1, double &yinv);
 template <class COL = size_t>
 __device__ __forceinline__ void stencil_4d_fast(const DevMet &M, const Axes &A, const float *__restrict__ h2, double ts,
@@ -2180,7 +2143,6 @@ __device__ __forceinline__ void stencil_4d_fast(const DevMet &M, const Axes &A, 
   double lon2, lat2;
   AxisHit hy;
   bool guessed = false;
-#if MPHIP_ML_HORIZ_FAST
   if constexpr (std::is_same<COL, uint32_t>::value) {
     // the lean instantiations (32-bit columns: a lat/lon grid with the look-up tables, launch_step): the horizontal
     // indices from verified guesses, as the pressure-level kernels take them (lon_fast / lat_fast)
@@ -2195,7 +2157,6 @@ __device__ __forceinline__ void stencil_4d_fast(const DevMet &M, const Axes &A, 
     guessed &= (fabs(lon) < 360.0) & lat_fast(M, A, lat2, hy.i, hy.x1, hy.inv);
     hy.x0 = A.lat[hy.i];
   }
-#endif
   if (!guessed) {
     check_horizontal(M, A, lon, lat, lon2, lat2);
     hy = hit_lat(M, A, lat2);
@@ -2207,7 +2168,6 @@ __device__ __forceinline__ void stencil_4d_fast(const DevMet &M, const Axes &A, 
             c01 = col_ml_as<COL>(M, s.ix, s.iy + 1), c11 = col_ml_as<COL>(M, s.ix + 1, s.iy + 1);
   const float hd = float_below(height);
   int kmin, kmax;
-#if MPHIP_LEVEL_WINDOW
   const int b = min(max(hint - 1, 0), max(n - 4, 0));
   f32x4u a0 = {}, a1 = {}, b0 = {}, b1 = {}, e0 = {}, e1 = {}, f0 = {}, f1 = {};   // windows of c00, c10, c01, c11
   bool have = false;
@@ -2229,12 +2189,6 @@ __device__ __forceinline__ void stencil_4d_fast(const DevMet &M, const Axes &A, 
   s.iz = kmin;
   f32x4u q00 = window_record(h2, c00, a0, a1, b, have, s.iz), q10 = window_record(h2, c10, b0, b1, b, have, s.iz),
          q01 = window_record(h2, c01, e0, e1, b, have, s.iz), q11 = window_record(h2, c11, f0, f1, b, have, s.iz);
-#else
-  locate_pairs4(h2, c00, c10, c01, c11, n, hd, hint, kmin, kmax);
-  s.iz = kmin;
-  f32x4u q00 = load_h4(h2, c00, s.iz), q10 = load_h4(h2, c10, s.iz), q01 = load_h4(h2, c01, s.iz),
-         q11 = load_h4(h2, c11, s.iz);
-#endif
   s.wt = div_const(ts - M.time0, M.time1 - M.time0, M.inv_dtime);
   s.wx = div_const(lon2 - A.lon[s.ix], A.lon[s.ix + 1] - A.lon[s.ix], A.inv_lon[s.ix]);
   s.wy = div_const(lat2 - hy.x0, hy.x1 - hy.x0, hy.inv);
@@ -2245,17 +2199,10 @@ __device__ __forceinline__ void stencil_4d_fast(const DevMet &M, const Axes &A, 
          || ((g0 < g1) && ((bot >= height) || (top < height)) && (bot <= height) && (s.iz < kmax))) {
     s.iz++;
     bot = top;
-#if MPHIP_LEVEL_WINDOW
     q00 = window_record(h2, c00, a0, a1, b, have, s.iz);
     q01 = window_record(h2, c01, e0, e1, b, have, s.iz);
     q10 = window_record(h2, c10, b0, b1, b, have, s.iz);
     q11 = window_record(h2, c11, f0, f1, b, have, s.iz);
-#else
-    q00 = load_h4(h2, c00, s.iz);
-    q01 = load_h4(h2, c01, s.iz);
-    q10 = load_h4(h2, c10, s.iz);
-    q11 = load_h4(h2, c11, s.iz);
-#endif
     top = level_pair_value(s, q00, q01, q10, q11, 1);
   }
   s.wz = (height - bot) / (top - bot);
@@ -2278,29 +2225,9 @@ __device__ __forceinline__ double ml_field_fast(const DevMet &M, const float *__
                     v[1][1][1]);
 }
 
-// {ul,vl,zeta_dot} corners with the cell they belong to (as WindCache)
-struct MlCache {
-  MlCorners c;
-  int ix, iy, iz;
-};
-
-__device__ __forceinline__ void ml_cache_reset(MlCache &w) {
-  w.ix = w.iy = w.iz = -1;
-#pragma unroll
-  for (int di = 0; di < 2; di++)
-#pragma unroll
-    for (int dj = 0; dj < 2; dj++)
-#pragma unroll
-      for (int k = 0; k < 3; k++)
-        w.c.r[di][dj][k] = f32x4u{ 0.f, 0.f, 0.f, 0.f };
-}
-
-#ifndef MPHIP_ML_CACHE
-#define MPHIP_ML_CACHE 0
-#endif
+// the {ul,vl,zeta_dot} corners of a stencil from the packed model-level wind records
 template <class COL = size_t>
-__device__ __forceinline__ void load_ml_cached(const DevMet &M, const Stencil4 &s, MlCache &w) {
-#if !MPHIP_ML_CACHE
+__device__ __forceinline__ void load_ml_fast(const DevMet &M, const Stencil4 &s, MlCorners &c) {
 #pragma unroll
   for (int di = 0; di < 2; di++)
 #pragma unroll
@@ -2308,33 +2235,8 @@ __device__ __forceinline__ void load_ml_cached(const DevMet &M, const Stencil4 &
       const COL off = (COL) 24 * (col_ml_as<COL>(M, s.ix + di, s.iy + dj) + (COL) s.iz);
 #pragma unroll
       for (int k = 0; k < 3; k++)
-        w.c.r[di][dj][k] = *(const f32x4u *) ((const char *) M.mlw + off + (COL) (16 * k));
+        c.r[di][dj][k] = *(const f32x4u *) ((const char *) M.mlw + off + (COL) (16 * k));
     }
-  return;
-#endif
-  if (s.ix != w.ix || s.iy != w.iy || s.iz != w.iz) {
-#pragma unroll
-    for (int di = 0; di < 2; di++)
-#pragma unroll
-      for (int dj = 0; dj < 2; dj++) {
-        const float *q = M.mlw + 6 * (col_ml(M, s.ix + di, s.iy + dj) + (size_t) s.iz);
-        asm volatile("global_load_dwordx4 %0, %3, off\n\t"
-                     "global_load_dwordx4 %1, %3, off offset:16\n\t"
-                     "global_load_dwordx4 %2, %3, off offset:32"
-                     : "+v"(w.c.r[di][dj][0]), "+v"(w.c.r[di][dj][1]), "+v"(w.c.r[di][dj][2])
-                     : "v"(q)
-                     : "memory");
-      }
-    w.ix = s.ix;
-    w.iy = s.iy;
-    w.iz = s.iz;
-  }
-  asm volatile("s_waitcnt vmcnt(0)"
-               : "+v"(w.c.r[0][0][0]), "+v"(w.c.r[0][0][1]), "+v"(w.c.r[0][0][2]), "+v"(w.c.r[0][1][0]),
-                 "+v"(w.c.r[0][1][1]), "+v"(w.c.r[0][1][2]), "+v"(w.c.r[1][0][0]), "+v"(w.c.r[1][0][1]),
-                 "+v"(w.c.r[1][0][2]), "+v"(w.c.r[1][1][0]), "+v"(w.c.r[1][1][1]), "+v"(w.c.r[1][1][2])
-               :
-               : "memory");
 }
 
 // module_advect, zeta / eta branch, on the packed height fields (same arithmetic as advect_ml_n)
@@ -2346,8 +2248,7 @@ __device__ __forceinline__ void advect_ml_fast_n(const DevMet &M, const Axes &A,
   stencil_4d_fast<COL>(M, A, M.pl2, P.time, P.p, P.lon, P.lat, kz, s);
   zeta = ml_field_fast<COL>(M, M.zl2, s);
   double u = 0, v = 0, wdot = 0, um = 0, vm = 0, wdotm = 0, x0 = 0, x1 = 0, x2 = 0;
-  MlCache mc;
-  ml_cache_reset(mc);
+  MlCorners mc;
 #pragma unroll
   for (int i = 0; i < ADVECT; i++) {
     double dts;
@@ -2363,10 +2264,10 @@ __device__ __forceinline__ void advect_ml_fast_n(const DevMet &M, const Axes &A,
       x2 = zeta + dts * wdot;
     }
     stencil_4d_fast<COL>(M, A, M.zl2, P.time + dts, x2, x0, x1, s.iz, s);
-    load_ml_cached<COL>(M, s, mc);
-    u = ml_packed(mc.c, s, 0);
-    v = ml_packed(mc.c, s, 1);
-    wdot = ml_packed(mc.c, s, 2);
+    load_ml_fast<COL>(M, s, mc);
+    u = ml_packed(mc, s, 0);
+    v = ml_packed(mc, s, 1);
+    wdot = ml_packed(mc, s, 2);
     double k = 1.0;
     if (ADVECT == 2)
       k = (i == 0 ? 0.0 : 1.0);
@@ -2404,8 +2305,7 @@ __device__ __forceinline__ void advect_mlp_fast_n(const DevMet &M, const Axes &A
   Stencil4 s;
   s.iz = kz;
   double u = 0, v = 0, w = 0, um = 0, vm = 0, wm = 0, x0 = 0, x1 = 0, x2 = 0;
-  MlCache mc;
-  ml_cache_reset(mc);
+  MlCorners mc;
 #pragma unroll
   for (int i = 0; i < ADVECT; i++) {
     double dts;
@@ -2421,10 +2321,10 @@ __device__ __forceinline__ void advect_mlp_fast_n(const DevMet &M, const Axes &A
       x2 = P.p + dts * w;
     }
     stencil_4d_fast<COL>(M, A, M.pl2, P.time + dts, x2, x0, x1, s.iz, s);
-    load_ml_cached<COL>(M, s, mc);
-    u = ml_packed(mc.c, s, 0);
-    v = ml_packed(mc.c, s, 1);
-    w = ml_packed(mc.c, s, 2);
+    load_ml_fast<COL>(M, s, mc);
+    u = ml_packed(mc, s, 0);
+    v = ml_packed(mc, s, 1);
+    w = ml_packed(mc, s, 2);
     double k = 1.0;
     if (ADVECT == 2)
       k = (i == 0 ? 0.0 : 1.0);
@@ -2469,7 +2369,7 @@ __device__ __forceinline__ double kz_blend(const mphip_ctl_t &ctl, double pt, do
 
 // module_diff_turb, mptrac.c:4603-4733
 __device__ __forceinline__ void diff_turb(const mphip_ctl_t &ctl, const DevMet &M, const Axes &A, const DevClim &C,
-                                          Particle &P, uint64_t ctr, uint64_t g, const double *pre, const double *ltab) {
+                                          Particle &P, uint64_t ctr, uint64_t g, const double *ltab) {
   const int ct = M.coord_type;
   Stencil s = stencil_zero();
   stencil_2d(M, A, P.lon, P.lat, s);
@@ -2490,12 +2390,7 @@ __device__ __forceinline__ void diff_turb(const mphip_ctl_t &ctl, const DevMet &
   const double dt_abs = fabs(P.dt);
 
   double rs0, rs1, rs2;
-  if (pre) {
-    rs0 = pre[0];
-    rs1 = pre[1];
-    rs2 = pre[2];
-  } else
-    normal_triple(ltab, ctr, g, rs0, rs1, rs2);
+  normal_triple(ltab, ctr, g, rs0, rs1, rs2);
 
   if (Kx > 0) {
     const double sigma_h = fsqrt(2.0 * Kx * dt_abs);
@@ -2543,7 +2438,7 @@ __device__ __forceinline__ void meso_coeffs(const mphip_ctl_t &ctl, const DevMet
 // module_diff_meso, mptrac.c:4280-4338
 __device__ __forceinline__ void diff_meso(const mphip_ctl_t &ctl, const DevMet &M, const Axes &A, Particle &P,
                                           float &up, float &vp, float &wp, uint64_t ctr, uint64_t g,
-                                          const double *pre, WindCache &wc, const double *ltab) {
+                                          WindCache &wc, const double *ltab) {
   // HIP's __fadd_rn / __fmul_rn are plain operators, so contraction has to be
   // switched off here for the single-precision statistics to round like the
   // reference's separate multiply and add (the variance is a small difference
@@ -2590,12 +2485,7 @@ __device__ __forceinline__ void diff_meso(const mphip_ctl_t &ctl, const DevMet &
   double r, r2;
   meso_coeffs(ctl, M, P.dt, r, r2);
   double rs0, rs1, rs2;
-  if (pre) {
-    rs0 = pre[0];
-    rs1 = pre[1];
-    rs2 = pre[2];
-  } else
-    normal_triple(ltab, ctr, g, rs0, rs1, rs2);
+  normal_triple(ltab, ctr, g, rs0, rs1, rs2);
 
   if (ctl.turb_mesox > 0) {
     up = (float) (r * up + r2 * rs0 * ctl.turb_mesox * sd[0]);
@@ -2619,7 +2509,7 @@ __device__ __forceinline__ double temperature_at(const DevMet &M, const Axes &A,
 
 // module_convection, mptrac.c:4116-4170
 __device__ __forceinline__ void convection(const mphip_ctl_t &ctl, const DevMet &M, const Axes &A, Particle &P,
-                                           uint64_t ctr, uint64_t g, const double *pre = nullptr) {
+                                           uint64_t ctr, uint64_t g) {
   Stencil s = stencil_zero();
   stencil_2d(M, A, P.lon, P.lat, s);
   SurfA c;
@@ -2654,7 +2544,7 @@ __device__ __forceinline__ void convection(const mphip_ctl_t &ctl, const DevMet 
     const double ttop = temperature_at(M, A, P.time, ptop, P.lon, P.lat);
     const double rhobot = fdiv(pbot, tbot);
     const double rhotop = fdiv(ptop, ttop);
-    const double rs = pre ? *pre : uniform01(ctr + g);
+    const double rs = uniform01(ctr + g);
     const double rho = rhobot + (rhotop - rhobot) * rs;
     P.p = lin(rhobot, pbot, rhotop, ptop, rho);
   }
@@ -3045,9 +2935,6 @@ __device__ __forceinline__ void load_pair_2d32(const f32x4 *__restrict__ g, cons
 }
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-#ifndef MPHIP_WIND_SERIAL
-#define MPHIP_WIND_SERIAL 1
-#endif
 
 // Wind records of the lean kernels: {u0,v0,u1,v1,w0,w1} per level (snapshots 0 / 1), so that a level pair
 // is twelve floats whose (u,v) pairs of one snapshot sit in an aligned register pair -- the single-
@@ -3067,7 +2954,7 @@ __device__ __forceinline__ float wind_at(const WindCorners &c, int di, int dj, i
 __device__ __forceinline__ void wind_uvw_fast(const WindCorners &c, const Stencil &s, double wt, double &u, double &v,
                                               double &w) {
   double val[6];
-  // one register pair of elements at a time (u0 v0 | u1 v1 | w0 w1): with MPHIP_WIND_SERIAL the scheduler may
+  // one register pair of elements at a time (u0 v0 | u1 v1 | w0 w1): behind the sched_barrier the scheduler may
   // not start the next pair before this one is reduced to its two values -- 16 instead of 48 live registers
 #pragma unroll
   for (int pr = 0; pr < 3; pr++) {
@@ -3092,9 +2979,7 @@ __device__ __forceinline__ void wind_uvw_fast(const WindCorners &c, const Stenci
       const double r1 = s.wy * (col[1][0][e] - col[1][1][e]) + col[1][1][e];
       val[2 * pr + e] = s.wx * (r0 - r1) + r1;
     }
-#if MPHIP_WIND_SERIAL
     __builtin_amdgcn_sched_barrier(0);
-#endif
   }
   u = wt * (val[0] - val[2]) + val[2];
   v = wt * (val[1] - val[3]) + val[3];
@@ -3183,9 +3068,9 @@ __device__ __forceinline__ void position_fast(const DevMet &M, const Axes &A, Pa
 
 // module_advect on pressure levels (mptrac.c:3612-3677), STAGES = 4: classical Runge-Kutta (ADVECT 4);
 // STAGES = 2: the midpoint scheme (ADVECT 2, the reference's default) -- and, with `euler` set (wave-uniform,
-// from the control parameters), its first stage alone (ADVECT 1).  `hook(i)` runs behind the gathers of stage i.
-template <int STAGES, bool BIG = false, class Hook>
-__device__ __forceinline__ void advect_fast(const DevMet &M, const Axes &A, Particle &P, Hook &hook, WindCache &wc,
+// from the control parameters), its first stage alone (ADVECT 1).
+template <int STAGES, bool BIG = false>
+__device__ __forceinline__ void advect_fast(const DevMet &M, const Axes &A, Particle &P, WindCache &wc,
                                             bool euler = false, const WindTile *tile = nullptr) {
   const double dt = P.dt;
   const DegPerMetre dm = deg_per_metre(P.lat);   // every stage converts at the latitude the step starts from
@@ -3204,15 +3089,8 @@ __device__ __forceinline__ void advect_fast(const DevMet &M, const Axes &A, Part
       x2 = P.p + dts * w;
     }
     Stencil s;
-#if MPHIP_SETPRIO
-    __builtin_amdgcn_s_setprio(MPHIP_SETPRIO);   // a wave on its way to a gather round goes first
-#endif
     stencil_3d_fast(M, A, x2, x0, x1, s);
     load_wind_cached32<BIG>(M, s, wc, tile);
-#if MPHIP_SETPRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
-    hook(i);
     wind_cache_wait(wc);
     wind_uvw_fast(wc.c, s, time_weight(M, P.time + dts), u, v, w);
     if (STAGES == 4) {
@@ -3235,11 +3113,6 @@ __device__ __forceinline__ void advect_fast(const DevMet &M, const Axes &A, Part
     P.lon += dx2deg_k(dm, dt * um);
   P.lat += dy2deg_k(dt * vm);
   P.p += dt * wm;
-}
-
-template <class Hook>
-__device__ __forceinline__ void advect_rk4_fast(const DevMet &M, const Axes &A, Particle &P, Hook &hook, WindCache &wc) {
-  advect_fast<4>(M, A, P, hook, wc);
 }
 
 // The end of module_diff_turb's vertical step (mptrac.c:4712-4731): the trial pressure reflected at the surface and at
@@ -3296,8 +3169,7 @@ __device__ __forceinline__ void turb_reflect(const DevMet &M, const Axes &A, Par
 // STRAT false: without the short path (the instantiations with 64-bit offsets, which have no register to spare for it).
 template <bool STRAT = true>
 __device__ __forceinline__ void diff_turb_fast(const mphip_ctl_t &ctl, const DevMet &M, const Axes &A, const DevClim &C,
-                                               Particle &P, uint64_t ctr, uint64_t g, const double *pre,
-                                               const double *ltab) {
+                                               Particle &P, uint64_t ctr, uint64_t g, const double *ltab) {
   const double wt = time_weight(M, P.time);
   const bool far = (P.p * 1.01 < M.turb_skip) & (wt >= 0.0) & (wt <= 1.0);
   double ps = M.turb_skip;
@@ -3309,7 +3181,7 @@ __device__ __forceinline__ void diff_turb_fast(const mphip_ctl_t &ctl, const Dev
   if (STRAT && __all(far & (P.p * 1.01 < M.strat_skip) & (fabs(P.lat) <= 90.0))) {   // (one scalar branch)
     Kz = ctl.turb_dz_strat;
     w_drift = Kz * dlnrho_dz;   // (the general body's value for a gradient of +0)
-    rs2 = pre ? pre[2] : normal_third(ltab, ctr, g);
+    rs2 = normal_third(ltab, ctr, g);
   } else {
     double pbl = M.turb_skip;
     if (!far) {
@@ -3331,17 +3203,11 @@ __device__ __forceinline__ void diff_turb_fast(const mphip_ctl_t &ctl, const Dev
     const double Kx = wpbl * ctl.turb_dx_pbl + wtrop * ctl.turb_dx_trop + wstrat * ctl.turb_dx_strat;
     Kz = wpbl * ctl.turb_dz_pbl + wtrop * ctl.turb_dz_trop + wstrat * ctl.turb_dz_strat;
 
-    // Without horizontal diffusion (Kx = 0: the stratosphere of the default parameters) only rs[3 g + 2] is used --
-    // one Box-Muller pair instead of two -- and the latitude keeps the tropopause pressure found above
+    // Without horizontal diffusion (Kx = 0: the stratosphere of the default parameters) only rs[3 g + 2] is used and
+    // the latitude keeps the tropopause pressure found above; the whole triple is drawn all the same (one Box-Muller
+    // pair there instead of two: 0.766-0.771 against 0.758-0.762 ms per step of C3, profiles/r04_variants.txt item 4)
     double rs0 = 0, rs1 = 0;
-    if (pre) {
-      rs0 = pre[0];
-      rs1 = pre[1];
-      rs2 = pre[2];
-    } else if (Kx > 0 || !MPHIP_TURB_SHORTCUT)
-      normal_triple(ltab, ctr, g, rs0, rs1, rs2);
-    else
-      rs2 = normal_third(ltab, ctr, g);
+    normal_triple(ltab, ctr, g, rs0, rs1, rs2);
 
     if (Kx > 0) {
       const double sigma_h = fsqrt(2.0 * Kx * fabs(P.dt));
@@ -3412,12 +3278,8 @@ __device__ __forceinline__ void meso_cell_sd(Corner corner, float sd[3]) {
   }
 }
 
-// 1: the lean instantiations with 32-bit offsets read the deviations of a particle's raw cell from the table the pack
-// step builds (DevMet::meso) instead of summing the cell's 16 values in every step; 0: they sum (the A/B build)
-#ifndef MPHIP_MESO_TABLE
-#define MPHIP_MESO_TABLE 1
-#endif
-
+// The lean instantiations with 32-bit offsets read the deviations of a particle's raw cell from the table the pack
+// step builds (DevMet::meso) instead of summing the cell's 16 values in every step; those with 64-bit offsets sum.
 // The table is stored in bricks of 4 x 4 columns that follow the locality order of the particles (sort_key_kernel: 4 x 4
 // horizontal tile, level, column within the tile): [ix >> 2][iy >> 2][ip][ix & 3][iy & 3], 12 bytes each, so that the
 // gather of a wave -- a few consecutive levels of one tile -- touches a few lines.  Brick counts are rounded up; a cell
@@ -3435,12 +3297,12 @@ __device__ __forceinline__ unsigned meso_off32(const DevMet &M, const Stencil &s
 template <bool STREAM = false, bool BIG = false>
 __device__ __forceinline__ void diff_meso_fast(const mphip_ctl_t &ctl, const DevMet &M, const Axes &A, Particle &P,
                                                float &up, float &vp, float &wp, uint64_t ctr, uint64_t g,
-                                               const double *pre, WindCache &wc, const double *ltab) {
+                                               WindCache &wc, const double *ltab) {
 #pragma clang fp contract(off)
   Stencil s;
   raw_cell_fast(M, A, P.lon, P.lat, P.p, s);
   float sd[3];
-  if constexpr (MPHIP_MESO_TABLE && !BIG) {
+  if constexpr (!BIG) {
     // one gather, issued here and first needed behind the normals below
     const MesoSd t = load_at<MesoSd>(M.meso, meso_off32(M, s));
     sd[0] = t.u;
@@ -3476,12 +3338,7 @@ __device__ __forceinline__ void diff_meso_fast(const mphip_ctl_t &ctl, const Dev
   double r, r2;
   meso_coeffs(ctl, M, P.dt, r, r2);
   double rs0, rs1, rs2;
-  if (pre) {
-    rs0 = pre[0];
-    rs1 = pre[1];
-    rs2 = pre[2];
-  } else
-    normal_triple(ltab, ctr, g, rs0, rs1, rs2);
+  normal_triple(ltab, ctr, g, rs0, rs1, rs2);
 
   if (ctl.turb_mesox > 0) {
     up = (float) (r * up + r2 * rs0 * ctl.turb_mesox * sd[0]);
@@ -3501,7 +3358,7 @@ __device__ __forceinline__ void diff_meso_fast(const mphip_ctl_t &ctl, const Dev
 // temperature columns
 template <bool BIG = false>
 __device__ __forceinline__ void conv_sedi_fast(const mphip_ctl_t &ctl, const DevMet &M, const Axes &A, Particle &P,
-                                               unsigned mask, uint64_t ctr, uint64_t g, const double *pre, double rp,
+                                               unsigned mask, uint64_t ctr, uint64_t g, double rp,
                                                double rhop, const double *ltab) {
   Stencil s = stencil_zero();
   horiz_fast(M, A, P.lon, P.lat, s);
@@ -3541,7 +3398,7 @@ __device__ __forceinline__ void conv_sedi_fast(const mphip_ctl_t &ctl, const Dev
       const double ttop = temp_fast<BIG>(M, s, wt);
       const double rhobot = fdiv(pbot, tbot);
       const double rhotop = fdiv(ptop, ttop);
-      const double rs = pre ? *pre : uniform01(ctr + g);
+      const double rs = uniform01(ctr + g);
       const double rho = rhobot + (rhotop - rhobot) * rs;
       P.p = lin(rhobot, pbot, rhotop, ptop, rho);
     }

@@ -474,8 +474,8 @@ __device__ __forceinline__ void depo_pair_fast(const mphip_ctl_t &ctl, const Dev
 // arrays: with cell-sorted particles each XCD's L2 then holds one region of
 // the meteo grid instead of all of it.
 // Waves per SIMD the register allocation aims at: 4 for the lean instantiations (128 VGPRs without scratch --
-// reached by reducing the wind interpolation one element pair at a time, MPHIP_WIND_SERIAL, and by drawing
-// the random numbers where they are used, MPHIP_RNG_EARLY 0), 3 for the general ones
+// reached by reducing the wind interpolation one element pair at a time, wind_uvw_fast, and by drawing
+// the random numbers where they are used, not early between the gathers), 3 for the general ones
 #ifndef MPHIP_STEP_WAVES_PER_SIMD
 #define MPHIP_STEP_WAVES_PER_SIMD 3
 #endif
@@ -487,50 +487,6 @@ __device__ __forceinline__ void depo_pair_fast(const mphip_ctl_t &ctl, const Dev
 #endif
 #ifndef MPHIP_LEAN_WAVES_PER_SIMD
 #define MPHIP_LEAN_WAVES_PER_SIMD 4
-#endif
-// 1: the specialised instantiations evaluate the random numbers of the
-// stochastic modules between the gathers of the Runge-Kutta stages and their
-// first use (rs[] is a pure function of counter and particle index)
-#ifndef MPHIP_PARAMS_RELOAD
-#define MPHIP_PARAMS_RELOAD 1
-#endif
-#ifndef MPHIP_RNG_EARLY
-#define MPHIP_RNG_EARLY 0
-#endif
-
-// Particle state is streamed: every array element is read once and written once per launch, while the lines of
-// the meteo records are shared by neighbouring waves.  MPHIP_STATE_NT 1 marks the state accesses of the step
-// kernel non-temporal, so that they do not push meteo lines out of the L2.
-#ifndef MPHIP_STATE_NT
-#define MPHIP_STATE_NT 0
-#endif
-template <class T>
-__device__ __forceinline__ T ld_state(const T *p) {
-#if MPHIP_STATE_NT
-  return __builtin_nontemporal_load(p);
-#else
-  return *p;
-#endif
-}
-template <class T>
-__device__ __forceinline__ void st_state(T *p, T v) {
-#if MPHIP_STATE_NT
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
-}
-
-// keeps a value where it was computed (the optimiser would sink the whole chain to its first use)
-__device__ __forceinline__ void pin(double &x) {
-  asm volatile("" : "+v"(x));
-}
-
-// 1: one Box-Muller pair behind the gathers of every Runge-Kutta stage (turb A, turb B, meso A, meso B + the
-// convection uniform) instead of a whole triple behind stages 0 and 1: every wait of the integrator has
-// independent arithmetic to cover it
-#ifndef MPHIP_RNG_BALANCED
-#define MPHIP_RNG_BALANCED 1
 #endif
 
 __device__ __forceinline__ void emit_sort_keys(const EmitKeys &E, const mphip_ctl_t &ctl, const DevMet &M, const Axes &A,
@@ -552,77 +508,11 @@ __device__ __forceinline__ void emit_sort_keys(const EmitKeys &E, const mphip_ct
   E.keys[i] = (uint32_t) ((s.ix * M.ny + s.iy) * M.np + s.ip);
 }
 
-struct RngEarly {
-  unsigned mask;
-  uint64_t ctr_turb, ctr_meso, ctr_conv, g;
-  const double *ltab;
-  double turb[3], meso[3], conv;
-  double e, o;   // first pair of the triple under construction
-  // pair `which` (0, 1) of the triple rs[3g .. 3g + 2] of a module_rng call with base counter c0; the second
-  // pair completes out[0 .. 2] (selection as normal_triple)
-  __device__ __forceinline__ void pair_of(uint64_t c0, int which, double *out) {
-    const uint64_t i0 = 3 * g;
-    const uint64_t y = (c0 + (i0 & ~1ull)) * kSquaresKey;
-    if (which == 0) {
-      normal_pair_from(ltab, y, e, o);
-      pin(e);
-      pin(o);
-    } else {
-      double eb, ob;
-      normal_pair_from(ltab, y + 2 * kSquaresKey, eb, ob);
-      const bool odd = (i0 & 1) != 0;
-      out[0] = odd ? o : e;
-      out[1] = odd ? eb : o;
-      out[2] = odd ? ob : eb;
-      pin(out[0]);
-      pin(out[1]);
-      pin(out[2]);
-    }
-  }
-  __device__ __forceinline__ void operator()(int stage) {
-#if MPHIP_RNG_BALANCED
-    if (stage < 2 && (mask & MPHIP_MOD_DIFF_TURB))
-      pair_of(ctr_turb, stage, turb);
-    if (stage >= 2 && (mask & MPHIP_MOD_DIFF_MESO))
-      pair_of(ctr_meso, stage - 2, meso);
-    if (stage == 3 && (mask & MPHIP_MOD_CONVECTION)) {
-      conv = uniform01(ctr_conv + g);
-      pin(conv);
-    }
-#else
-    if (stage == 0 && (mask & MPHIP_MOD_DIFF_TURB)) {
-      normal_triple(ltab, ctr_turb, g, turb[0], turb[1], turb[2]);
-      pin(turb[0]);
-      pin(turb[1]);
-      pin(turb[2]);
-    }
-    if (stage == 1 && (mask & MPHIP_MOD_DIFF_MESO)) {
-      normal_triple(ltab, ctr_meso, g, meso[0], meso[1], meso[2]);
-      pin(meso[0]);
-      pin(meso[1]);
-      pin(meso[2]);
-    }
-    if (stage == 2 && (mask & MPHIP_MOD_CONVECTION)) {
-      conv = uniform01(ctr_conv + g);
-      pin(conv);
-    }
-#endif
-  }
-};
-// multi-step instantiations: 1 = the wind corners stay cached from one time step to the next too.  Measured (C3,
-// 1e7 particles, 20 steps per launch): 0.94 ms per step against 0.78 without -- the 51 registers are then live
-// through every module and the kernel keeps ~200 bytes per lane in scratch; off
-#ifndef MPHIP_MULTI_KEEP_WIND
-#define MPHIP_MULTI_KEEP_WIND 0
-#endif
 #ifndef MPHIP_MULTI_WAVES_PER_SIMD
 #define MPHIP_MULTI_WAVES_PER_SIMD 4
 #endif
 #ifndef MPHIP_SPLITB_WAVES_PER_SIMD
 #define MPHIP_SPLITB_WAVES_PER_SIMD 4
-#endif
-#ifndef MPHIP_ML_OFF32
-#define MPHIP_ML_OFF32 1
 #endif
 #ifndef MPHIP_ML_WAVES_PER_SIMD
 #define MPHIP_ML_WAVES_PER_SIMD 3   // the lean model-level instantiations: 148-158 VGPRs without scratch; at four waves (128 VGPRs) they spill 35-56 dwords: C3z 1.98 -> 1.81 ms per step (profiles/r04_variants.txt item 11)
@@ -697,7 +587,7 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
   double *const s_axes = s_lds + (park ? kParkDoubles : 0);   // (the parking area in front)
   const unsigned mask = kRuntimeMask<CT> ? S.mask : (CT & ~kTemplateFlags);
   // column indices of the model-level fields: 32 bits in the lean instantiations (launch_step's size check)
-  using MLCol = std::conditional_t<kLeanML<CT> && MPHIP_ML_OFF32 && !kBig<CT>, uint32_t, size_t>;
+  using MLCol = std::conditional_t<kLeanML<CT> && !kBig<CT>, uint32_t, size_t>;
   const DevMet &M = S.met;
   const DevAtm &a = S.atm;
   const mphip_ctl_t &ctl = S.ctl;
@@ -729,7 +619,6 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
   block_range(S, a.np, first, last);
 
   for (long long i = first + threadIdx.x; i < last; i += (park ? 256 : blockDim.x)) {   // (256: the launch's block size)
-#if MPHIP_PARAMS_RELOAD
     // re-read the launch parameters from the kernarg segment in every iteration (scalar loads at
     // the point of use) instead of keeping all of them live across the loop, which spills SGPRs
     auto kp = (const __attribute__((address_space(4))) StepParams *) __builtin_amdgcn_kernarg_segment_ptr();
@@ -738,7 +627,6 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
     const DevMet &M = S.met;
     const DevAtm &a = S.atm;
     const mphip_ctl_t &ctl = S.ctl;
-#endif
     constexpr bool multi = (!kRuntimeMask<CT> && (CT & kMultiStep) != 0) || CT == kMaskGenericMLMulti;
     const int nsteps = multi ? S.nsteps : 1;
     double t_now = S.t;
@@ -789,26 +677,22 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
         }
       }
     } else {
-      P.time = ld_state(&a.time[i]);
-      P.lon = ld_state(&a.lon[i]);
-      P.lat = ld_state(&a.lat[i]);
-      P.p = ld_state(&a.p[i]);
+      P.time = a.time[i];
+      P.lon = a.lon[i];
+      P.lat = a.lat[i];
+      P.p = a.p[i];
     }
-    if (multi) {   // (before any step can leave early: dt = 0 ...)
-      if (MPHIP_MULTI_KEEP_WIND)
-        wind_cache_reset(wc, true);
-      if ((mask & MPHIP_MOD_DIFF_MESO) && !perm_all) {
-        up = ld_state(&a.up[i]);
-        vp = ld_state(&a.vp[i]);
-        wp = ld_state(&a.wp[i]);
-      }
+    if (multi && (mask & MPHIP_MOD_DIFF_MESO) && !perm_all) {   // (before any step can leave early: dt = 0 ...)
+      up = a.up[i];
+      vp = a.vp[i];
+      wp = a.wp[i];
     }
     if constexpr (park) {   // (behind the gather of module_sort, which writes a.q[k][i])
       if (a.ext && !perm_all)
-        *park_slot<int>(s_lds, kParkExt, i) = ld_state(&a.ext[i]);
+        *park_slot<int>(s_lds, kParkExt, i) = a.ext[i];
       if (((CT & kGated) ? mask & S.mask : mask) & MPHIP_MOD_SEDI) {
-        *park_slot<double>(s_lds, kParkRp, i) = ld_state(&a.q[ctl.qnt_rp][i]);
-        *park_slot<double>(s_lds, kParkRhop, i) = ld_state(&a.q[ctl.qnt_rhop][i]);
+        *park_slot<double>(s_lds, kParkRp, i) = a.q[ctl.qnt_rp][i];
+        *park_slot<double>(s_lds, kParkRhop, i) = a.q[ctl.qnt_rhop][i];
       }
     }
     }
@@ -855,7 +739,7 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
     // random numbers belong to the external slot (rs[3 * ip + k], mptrac.c:4645)
     // (parking instantiations: every module that draws reads the index from the slot -- held from here it would
     // occupy two registers through the advection)
-    const uint64_t g_held = park ? 0 : (uint64_t) (a.ip0 + (a.ext ? (long long) ld_state(&a.ext[i]) : i));
+    const uint64_t g_held = park ? 0 : (uint64_t) (a.ip0 + (a.ext ? (long long) a.ext[i] : i));
     auto g_now = [&]() -> uint64_t {
       if constexpr (park)
         return (uint64_t) (a.ip0 + (a.ext ? (long long) *park_slot<int>(s_lds, kParkExt, i) : i));
@@ -863,19 +747,9 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
         return g_held;
     };
 
-    // specialised instantiations = RK4 on pressure levels (launch_step): 4 stages, all hooks run
-    constexpr bool early = MPHIP_RNG_EARLY && !kRuntimeMask<CT> && (CT & MPHIP_MOD_ADVECT) && !(CT & kTwoStage) && !kLeanML<CT>;   // (the hooks belong to the four-stage integrator)
-    RngEarly pre;
-    pre.mask = mask;
-    pre.ctr_turb = c_turb;
-    pre.ctr_meso = c_meso;
-    pre.ctr_conv = c_conv;
-    pre.g = early ? g_now() : 0;
-    pre.ltab = ltab;
-
     // the specialised instantiations run the lean versions (lat/lon grid, pressure table: launch_step)
     constexpr bool lean = !kRuntimeMask<CT>;
-    if (!kModelLevels<CT> && !(multi && MPHIP_MULTI_KEEP_WIND))   // (model-level winds: the corners are first needed by module_diff_meso -- defined there,
+    if (!kModelLevels<CT>)   // (model-level winds: the corners are first needed by module_diff_meso -- defined there,
       wind_cache_reset(wc, CT != kMaskGeneric && (lean || !MPHIP_EXACT_DIV));   //  or 48 registers would be held through the whole advection)
     // (MPHIP_EXACT_DIV: the general kernels gather with plain loads -- with the IEEE division sequences between the
     // asynchronous gathers and their wait the register allocator reuses their registers, which the machine-code
@@ -906,37 +780,30 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
         advect_ml_fast<MLCol>(ctl, M, A, P, zeta, kz);
         a.kz[i] = kz;
         a.q[qnt][i] = zeta;
-      } else if (lean && early)
-        advect_rk4_fast(M, A, P, pre, wc);
-      else if (lean && (CT & kTwoStage)) {
-        NoHook none;
-        advect_fast<2, kBig<CT>>(M, A, P, none, wc, ctl.advect == 1);
-      } else if (lean) {
-        NoHook none;
-        advect_fast<4, kBig<CT>>(M, A, P, none, wc);
-      } else
+      } else if (lean && (CT & kTwoStage))
+        advect_fast<2, kBig<CT>>(M, A, P, wc, ctl.advect == 1);
+      else if (lean)
+        advect_fast<4, kBig<CT>>(M, A, P, wc);
+      else
         advect(ctl, M, A, P, wc);
     }
     // (S.mask is wave-uniform: scalar tests)
     const unsigned opt = (lean && (CT & kGated)) ? (mask & S.mask & kOptionalModules) : (mask & kOptionalModules);
     if (opt & MPHIP_MOD_DIFF_TURB) {
       if (lean)
-        diff_turb_fast<!kBig<CT>>(ctl, M, A, *clim, P, c_turb, g_now(), early ? pre.turb : nullptr, ltab);
+        diff_turb_fast<!kBig<CT>>(ctl, M, A, *clim, P, c_turb, g_now(), ltab);
       else
-        diff_turb(ctl, M, A, *clim, P, c_turb, g_now(), early ? pre.turb : nullptr, ltab);
+        diff_turb(ctl, M, A, *clim, P, c_turb, g_now(), ltab);
     }
-#ifndef MPHIP_PBL_EMPTY
-#define MPHIP_PBL_EMPTY 0     // 1: experiment -- the kPblClosure instantiations without the closure's code
-#endif
-    constexpr bool lean_pbl = lean && (CT & kPblClosure) != 0 && !MPHIP_PBL_EMPTY;
+    constexpr bool lean_pbl = lean && (CT & kPblClosure) != 0;
     if (((CT == kMaskGeneric && (mask & MPHIP_MOD_DIFF_PBL)) || (lean_pbl && (S.mask & MPHIP_MOD_DIFF_PBL)))
         && !above_every_boundary_layer(M, P)) {
       // (the perturbations live in the cache arrays; a multi-step launch with module_diff_meso holds them in registers)
       const bool held = multi && (mask & MPHIP_MOD_DIFF_MESO);
       if (!held) {
-        up = ld_state(&a.up[i]);
-        vp = ld_state(&a.vp[i]);
-        wp = ld_state(&a.wp[i]);
+        up = a.up[i];
+        vp = a.vp[i];
+        wp = a.wp[i];
       }
       if constexpr (lean_pbl) {   // a call: the kernel keeps the registers of the instantiation without the closure
         PblState st = { P.time, P.lon, P.lat, P.p, P.dt, up, vp, wp };
@@ -951,39 +818,39 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
       } else
         diff_pbl<false>(M, A, P, up, vp, wp, c_pbl, g_now(), ltab);
       if (!(store_once && held)) {
-        st_state(&a.up[i], up);
-        st_state(&a.vp[i], vp);
-        st_state(&a.wp[i], wp);
+        a.up[i] = up;
+        a.vp[i] = vp;
+        a.wp[i] = wp;
       }
     }
     if (opt & MPHIP_MOD_DIFF_MESO) {
       if (!multi) {
-        up = ld_state(&a.up[i]);
-        vp = ld_state(&a.vp[i]);
-        wp = ld_state(&a.wp[i]);
+        up = a.up[i];
+        vp = a.vp[i];
+        wp = a.wp[i];
       }
       if (kGenericML<CT>)
         wind_cache_reset(wc, true);
       if (lean)   // (without a pressure-level advection before it there are no cached corners: the streaming version)
-        diff_meso_fast<!(CT & MPHIP_MOD_ADVECT) || kLeanML<CT>, kBig<CT>>(ctl, M, A, P, up, vp, wp, c_meso, g_now(), early ? pre.meso : nullptr, wc, ltab);
+        diff_meso_fast<!(CT & MPHIP_MOD_ADVECT) || kLeanML<CT>, kBig<CT>>(ctl, M, A, P, up, vp, wp, c_meso, g_now(), wc, ltab);
       else
-        diff_meso(ctl, M, A, P, up, vp, wp, c_meso, g_now(), early ? pre.meso : nullptr, wc, ltab);
+        diff_meso(ctl, M, A, P, up, vp, wp, c_meso, g_now(), wc, ltab);
       if (!store_once) {
-        st_state(&a.up[i], up);
-        st_state(&a.vp[i], vp);
-        st_state(&a.wp[i], wp);
+        a.up[i] = up;
+        a.vp[i] = vp;
+        a.wp[i] = wp;
       }
     }
     if (lean) {
       if (opt & (MPHIP_MOD_CONVECTION | MPHIP_MOD_SEDI)) {
         const bool sedi_on = (opt & MPHIP_MOD_SEDI) != 0;
-        conv_sedi_fast<kBig<CT>>(ctl, M, A, P, opt, c_conv, g_now(), early ? &pre.conv : nullptr,
-                       !sedi_on ? 0.0 : park ? *park_slot<double>(s_lds, kParkRp, i) : ld_state(&a.q[ctl.qnt_rp][i]),
-                       !sedi_on ? 0.0 : park ? *park_slot<double>(s_lds, kParkRhop, i) : ld_state(&a.q[ctl.qnt_rhop][i]), ltab);
+        conv_sedi_fast<kBig<CT>>(ctl, M, A, P, opt, c_conv, g_now(),
+                       !sedi_on ? 0.0 : park ? *park_slot<double>(s_lds, kParkRp, i) : a.q[ctl.qnt_rp][i],
+                       !sedi_on ? 0.0 : park ? *park_slot<double>(s_lds, kParkRhop, i) : a.q[ctl.qnt_rhop][i], ltab);
       }
     } else {
       if (opt & MPHIP_MOD_CONVECTION)
-        convection(ctl, M, A, P, c_conv, g_now(), early ? &pre.conv : nullptr);
+        convection(ctl, M, A, P, c_conv, g_now());
       if (opt & MPHIP_MOD_SEDI)
         sedimentation(M, A, P, a.q[ctl.qnt_rp][i], a.q[ctl.qnt_rhop][i]);
     }
@@ -1001,11 +868,11 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
 
     if (!store_once) {
       if ((mask & MPHIP_MOD_ADVECT) || fused_sort)
-        st_state(&a.time[i], P.time);
+        a.time[i] = P.time;
       if ((mask & kMovers) || fused_sort) {
-        st_state(&a.lon[i], P.lon);
-        st_state(&a.lat[i], P.lat);
-        st_state(&a.p[i], P.p);
+        a.lon[i] = P.lon;
+        a.lat[i] = P.lat;
+        a.p[i] = P.p;
       }
     }
     if constexpr (lean && (CT & kEmitKeys) != 0)
@@ -1053,14 +920,14 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
     // dt = 0 in every step gets back what it was loaded with, or its fused_sort gather)
     if constexpr (store_once) {
       static_assert((CT & MPHIP_MOD_ADVECT) != 0, "a lean multi-step instantiation without the advection");
-      st_state(&a.time[i], P.time);
-      st_state(&a.lon[i], P.lon);
-      st_state(&a.lat[i], P.lat);
-      st_state(&a.p[i], P.p);
+      a.time[i] = P.time;
+      a.lon[i] = P.lon;
+      a.lat[i] = P.lat;
+      a.p[i] = P.p;
       if (mask & MPHIP_MOD_DIFF_MESO) {
-        st_state(&a.up[i], up);
-        st_state(&a.vp[i], vp);
-        st_state(&a.wp[i], wp);
+        a.up[i] = up;
+        a.vp[i] = vp;
+        a.wp[i] = wp;
       }
     }
   }
@@ -1105,10 +972,10 @@ __global__ __launch_bounds__(256, MPHIP_TILE_WAVES_PER_SIMD) void traj_tile_kern
     P.time = P.lon = P.lat = P.p = P.dt = 0;
     int lo[3] = { 1 << 30, 1 << 30, 1 << 30 }, hi[3] = { -1, -1, -1 };
     if (live) {
-      P.time = ld_state(&a.time[i]);
-      P.lon = ld_state(&a.lon[i]);
-      P.lat = ld_state(&a.lat[i]);
-      P.p = ld_state(&a.p[i]);
+      P.time = a.time[i];
+      P.lon = a.lon[i];
+      P.lat = a.lat[i];
+      P.p = a.p[i];
       Stencil s0;
       stencil_3d_fast(M, A, P.p, P.lon, P.lat, s0);   // the cell the first stage will start in
       lo[0] = hi[0] = s0.ix;
@@ -1165,13 +1032,12 @@ __global__ __launch_bounds__(256, MPHIP_TILE_WAVES_PER_SIMD) void traj_tile_kern
       WindCache wc;
       wind_cache_reset(wc, true);
       position_fast(M, A, P);
-      NoHook none;
-      advect_fast<STAGES, false>(M, A, P, none, wc, STAGES == 2 && ctl.advect == 1, &T);
+      advect_fast<STAGES, false>(M, A, P, wc, STAGES == 2 && ctl.advect == 1, &T);
       position_fast(M, A, P);
-      st_state(&a.time[i], P.time);
-      st_state(&a.lon[i], P.lon);
-      st_state(&a.lat[i], P.lat);
-      st_state(&a.p[i], P.p);
+      a.time[i] = P.time;
+      a.lon[i] = P.lon;
+      a.lat[i] = P.lat;
+      a.p[i] = P.p;
     }
   }
 }
@@ -3752,7 +3618,7 @@ __global__ __launch_bounds__(256, MPHIP_STEP_WAVES_PER_SIMD) void piece_kernel(c
         Q.lon = lon;
         Q.lat = lat;
         Q.p = p;
-        diff_turb(ctl, M, A, clim, Q, S.ctr_turb + (uint64_t) r, g, nullptr, ltab);
+        diff_turb(ctl, M, A, clim, Q, S.ctr_turb + (uint64_t) r, g, ltab);
         acc += Q.lon + Q.lat + Q.p;
       } else if (PIECE == 13) {   // module_convection + module_sedi
         Particle Q = P;
@@ -3770,7 +3636,7 @@ __global__ __launch_bounds__(256, MPHIP_STEP_WAVES_PER_SIMD) void piece_kernel(c
         float up = 0.1f * r, vp = 0.2f, wp = 1e-4f;
         WindCache wc;
         wind_cache_reset(wc, false);
-        diff_meso(ctl, M, A, Q, up, vp, wp, S.ctr_meso + (uint64_t) r, g, nullptr, wc, ltab);
+        diff_meso(ctl, M, A, Q, up, vp, wp, S.ctr_meso + (uint64_t) r, g, wc, ltab);
         acc += Q.lon + Q.lat + Q.p + (double) (up + vp + wp);
       } else if (PIECE == 15) {   // module_advect (RK4) without the wind-corner cache
         Particle Q = P;
@@ -3779,8 +3645,7 @@ __global__ __launch_bounds__(256, MPHIP_STEP_WAVES_PER_SIMD) void piece_kernel(c
         Q.p = p;
         WindCache wc;
         wind_cache_reset(wc, false);
-        NoHook none;
-        advect_n<4>(M, A, Q, none, wc);
+        advect_n<4>(M, A, Q, wc);
         acc += Q.lon + Q.lat + Q.p;
       } else if (PIECE == 16) {
         Stencil s;
@@ -3810,14 +3675,14 @@ __global__ __launch_bounds__(256, MPHIP_STEP_WAVES_PER_SIMD) void piece_kernel(c
         Q.lon = lon;
         Q.lat = lat;
         Q.p = p;
-        diff_turb_fast(ctl, M, A, clim, Q, S.ctr_turb + (uint64_t) r, g, nullptr, ltab);
+        diff_turb_fast(ctl, M, A, clim, Q, S.ctr_turb + (uint64_t) r, g, ltab);
         acc += Q.lon + Q.lat + Q.p;
       } else if (PIECE == 21) {
         Particle Q = P;
         Q.lon = lon;
         Q.lat = lat;
         Q.p = p;
-        conv_sedi_fast(ctl, M, A, Q, MPHIP_MOD_CONVECTION | MPHIP_MOD_SEDI, S.ctr_conv + (uint64_t) r, g, nullptr, 1.0, 1000.0, ltab);
+        conv_sedi_fast(ctl, M, A, Q, MPHIP_MOD_CONVECTION | MPHIP_MOD_SEDI, S.ctr_conv + (uint64_t) r, g, 1.0, 1000.0, ltab);
         acc += Q.p;
       } else if (PIECE == 22) {
         Particle Q = P;
@@ -3827,7 +3692,7 @@ __global__ __launch_bounds__(256, MPHIP_STEP_WAVES_PER_SIMD) void piece_kernel(c
         float up = 0.1f * r, vp = 0.2f, wp = 1e-4f;
         WindCache wc;
         wind_cache_reset(wc, true);
-        diff_meso_fast(ctl, M, A, Q, up, vp, wp, S.ctr_meso + (uint64_t) r, g, nullptr, wc, ltab);
+        diff_meso_fast(ctl, M, A, Q, up, vp, wp, S.ctr_meso + (uint64_t) r, g, wc, ltab);
         acc += Q.lon + Q.lat + Q.p + (double) (up + vp + wp);
       } else if (PIECE == 23) {
         Particle Q = P;
@@ -3836,8 +3701,7 @@ __global__ __launch_bounds__(256, MPHIP_STEP_WAVES_PER_SIMD) void piece_kernel(c
         Q.p = p;
         WindCache wc;
         wind_cache_reset(wc, true);
-        NoHook none;
-        advect_rk4_fast(M, A, Q, none, wc);
+        advect_fast<4>(M, A, Q, wc);
         acc += Q.lon + Q.lat + Q.p;
       } else if (PIECE == 24) {
         double rr = 0.0, ee = 0.0;
