@@ -525,6 +525,58 @@ typedef struct {
 size_t mphip_sizeof_detrend(void);      /* sizeof(mphip_detrend_t), for mirrors of the structure in other languages */
 int mphip_detrend_met(mphip_ctx *ctx, const mphip_met_t *in, const mphip_detrend_t *opt, const mphip_regrid_out_t *out);
 
+/* 16-bit packed level fields (the reference's MET_TYPE 2 files): every level field as unsigned 16-bit codes with one scale
+ * and one offset per level -- half the bytes on disk and over PCIe.  The codes travel to the device as they are and become
+ * floats there (2 bytes read and 4 written per value, once per snapshot); no arithmetic on meteo values on the host.
+ *
+ *   DEFINITION.  This project's own statement (the reference's source was not available), restated independently in
+ * tests/refpack.py.  A level field is nx ny columns of nlev values, level fastest: the compact [ix][iy][ip] order of a
+ * MET_TYPE 1 file.  Every operation below is the IEEE operation on the named type, rounded once, never fused with its
+ * neighbour; both libraries return these bits.
+ *   Decoding, code q (0 ... 65535, every one of them, also 65534 and 65535, which the encoder never writes) at level ip:
+ * v = (float) ((double) q * scl[ip] + off[ip]) -- the product rounded to double, the sum rounded to double, then one
+ * rounding to float --, then the limits of the reader, fminf(fmaxf(v, lo), hi) as the C library evaluates them: v < lo or
+ * v a NaN gives lo, v > hi gives hi, and a zero that compares equal to a limit keeps its own sign.  scl / off that are
+ * not finite are not refused: they decode to what the arithmetic gives.
+ *   Encoding, per level: min and max over all columns, compared as doubles; off = min + 0. (a minimum that is a zero of
+ * either sign is stored as +0.: the result does not depend on the order in which the values were compared); scl = (max !=
+ * min) ? (max - min) / 65533. : 1.; q = (unsigned short) (((double) x - off) / scl + .5), a true division, truncated.  The
+ * largest code written is 65533.  A level that holds a value that is not finite has no code: the call is refused.
+ *   File (MET_TYPE 2, extension pck): [2] [104] time nx ny np lon[] lat[] p[]; the 24 surface fields as raw floats as in a
+ * MET_TYPE 1 file; the 13 level fields in the same order, each scl[np] doubles, off[np] doubles, nx ny np unsigned shorts;
+ * [999].
+ *
+ * mphip_met_packed_t describes a snapshot some of whose level fields are codes: `base` carries the axes, extents,
+ * strides, the surface fields and the level fields that stay float; q3[f] the compact codes [nx][ny][nlev] of field f
+ * (nlev = np, or npl for the model-level fields), scl[f] / off[f] their nlev scales and offsets, lo[f] / hi[f] the limits
+ * applied after decoding.  A field is given in base.f3 or in q3, never both. */
+typedef struct {
+  mphip_met_t base;
+  const unsigned short *q3[MPHIP_N3D];
+  const double *scl[MPHIP_N3D], *off[MPHIP_N3D];
+  float lo[MPHIP_N3D], hi[MPHIP_N3D];
+} mphip_met_packed_t;
+size_t mphip_sizeof_met_packed(void);   /* sizeof(mphip_met_packed_t), for mirrors of the structure in other languages */
+/* mphip_update_met / mphip_prefetch_met for such a snapshot, the same in every respect (checks and messages, axes, "Meteo
+ * grid dimensions do not match!", what may be called from which thread): a packed field is uploaded as codes into a
+ * grow-only code buffer -- one per stream, sized for the largest field, reused in stream order, freed with the slot arrays
+ * on a new grid and by mphip_destroy -- and decoded behind its copy into the staging array a float upload fills; nothing
+ * behind the staging arrays differs.  Refused with a message, nothing written: a field given both ways, codes without scl
+ * or off, lo > hi (or a limit that is a NaN). */
+int mphip_update_met_packed(mphip_ctx *ctx, int slot, const mphip_met_packed_t *met);
+int mphip_prefetch_met_packed(mphip_ctx *ctx, const mphip_met_packed_t *met);
+/* Decoding and encoding between host arrays, members of the family of mphip_derive_met (the same stream, lock and scratch
+ * pool; no meteo slot, no prefetch state and no particle touched; callable from a file-reader thread while another thread
+ * steps; a refused call writes nothing; every input is uploaded before an output is copied back).  The float arrays may be
+ * strided as for mphip_detrend_met (sy >= nlev, sx a multiple of sy and >= ny sy; base.sx_ml / sy_ml for the model-level
+ * fields), the codes are compact.
+ *   mphip_unpack_met writes out->f3[f] for every field that `in` gives as codes and `out` names (base.f3 of `in` and the
+ * surface fields are ignored).  mphip_pack_met encodes in->f3[f] into the arrays out->q3[f], out->scl[f], out->off[f]
+ * point to, for every field present in both (a NULL q3[f] skips the field; out->base.f3, lo and hi are ignored); a value
+ * that is not finite refuses the call with the field's name and the level.  Messages start with the call's name. */
+int mphip_unpack_met(mphip_ctx *ctx, const mphip_met_packed_t *in, const mphip_met_t *out);
+int mphip_pack_met(mphip_ctx *ctx, const mphip_met_t *in, const mphip_met_packed_t *out);
+
 /* mptrac_update_device(..., atm), mptrac.c:8050-8055.  This process owns the
  * particles [ip0, ip0 + np) of a simulation with np_total particles; random
  * numbers are drawn for the global index so results do not depend on the
@@ -771,10 +823,12 @@ int mphip_comm_query(mphip_ctx *ctx, int *nranks, int *rank);
  *     permutation
  *   "big_grid" (default 0): tests -- take the instantiations with 64-bit byte offsets into the packed meteo records (what a
  *     grid with more than 4 GB of wind records -- 178e6 cells -- takes by itself) on a grid that fits 32 bits too: same bits.
- *   "derive_profile_phase" (default 0; 1, 2, 3): measurement -- what mphip_profile_begin / _end time of a mphip_derive_met
+ *   "derive_profile_phase" (default 0; 1 ... 6): measurement -- what mphip_profile_begin / _end time of a mphip_derive_met
  *     call: every kernel (0), the uploads (1) or the downloads (2), as event pairs on the call's own stream (a caller that
  *     profiles does not step from another thread meanwhile); 3: the host's build of the weight table in
- *     mphip_detrend_met (the stream is idle meanwhile, so the pair of events brackets the host's time). */
+ *     mphip_detrend_met (the stream is idle meanwhile, so the pair of events brackets the host's time); 4, 5, 6: of the
+ *     kernels of mphip_pack_met only the extremes, their reduction, the quantisation (mphip_unpack_met and mphip_pack_met
+ *     are calls of the same family: 0, 1 and 2 hold for them as well). */
 int mphip_set_option(mphip_ctx *ctx, const char *name, double value);
 int mphip_synchronize(mphip_ctx *ctx);
 

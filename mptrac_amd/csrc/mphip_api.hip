@@ -19,6 +19,7 @@
 #include "mphip_metprep.hpp"
 #include "mphip_regrid.hpp"
 #include "mphip_detrend.hpp"
+#include "mphip_pack.hpp"
 
 using namespace mphip;
 
@@ -35,6 +36,9 @@ constexpr unsigned kDiffConvSediOnly = MPHIP_MOD_TIMESTEPS | MPHIP_MOD_DIFF_TURB
 constexpr unsigned kTailOnly = MPHIP_MOD_TIMESTEPS;   // no mover: a launch of loss / decay / deposition modules only
 constexpr unsigned kBound = MPHIP_MOD_BOUND_COND | MPHIP_MOD_BOUND_COND2;
 constexpr unsigned kParticleBits = 0x3fffu | MPHIP_MOD_ISOSURF | kBound | MPHIP_MOD_ISOSURF_INIT;
+
+const char *const kField3Name[MPHIP_N3D] = { "u", "v", "w", "t", "lwc", "rwc", "iwc", "swc", "pl", "ul", "vl", "zetal",
+                                             "zeta_dotl", "h2o", "z", "pv", "o3", "cc", "wl" };
 
 struct MetSlot {
   bool valid = false;
@@ -106,6 +110,13 @@ struct mphip_ctx {
   hipStream_t copy_stream = nullptr;  // uploads of `next` run here, beside the kernels on `stream`
   hipEvent_t next_ready = nullptr;
   hipEvent_t main_mark = nullptr;     // copies into `next` start after the kernels queued so far (they may read its arrays)
+  // mphip_update_met_packed / mphip_prefetch_met_packed: where a field's {scl | off | codes} wait for met_unpack_kernel,
+  // one buffer per stream ([0] stream, [1] copy_stream), sized for the largest field and reused in stream order; grow-only,
+  // freed with the slot arrays on a new grid and by mphip_destroy
+  struct CodeBuf {
+    char *p = nullptr;
+    size_t bytes = 0;
+  } codes[2];
   // module_meteo only writes quantities nothing on the device reads: its launch is deferred until someone
   // can see the result (a download, gridded output, a single-module call) or its inputs change; a pending
   // launch that the next time step would overwrite unseen is dropped
@@ -1320,8 +1331,7 @@ int check_meteo(mphip_ctx *ctx) {
       return fail(ctx, "module_meteo: quantity index out of range");
   if (!both_have(ctx, 0))
     return fail(ctx, "meteo data for both met0 and met1 must be uploaded before stepping");
-  static const char *const n3[MPHIP_N3D] = { "u", "v", "w", "t", "lwc", "rwc", "iwc", "swc", "pl", "ul", "vl", "zetal",
-                                             "zeta_dotl", "h2o", "z", "pv", "o3", "cc", "wl" };
+  const char *const *const n3 = kField3Name;
   static const char *const n2[MPHIP_N2D] = { "ps", "pbl", "cape", "cin", "pel", "pct", "pcb", "cl", "ess", "nss", "shf",
                                              "ts", "zs", "us", "vs", "lsm", "sst", "pt", "tt", "zt", "h2ot", "plcl",
                                              "plfc", "o3c" };
@@ -2806,21 +2816,124 @@ int copy2(mphip_ctx *ctx, hipStream_t stream, float *dev, const float *host, int
   return 0;
 }
 
-// host -> device copies of one snapshot's fields into the staging arrays of slot S (asynchronous on `stream`)
-int upload_fields(mphip_ctx *ctx, MetSlot &S, const mphip_met_t *met, bool new_grid, hipStream_t stream) {
+// ---- 16-bit packed level fields (mphip_pack.hpp) ------------------------------------------------------------------------
+// is field f of a snapshot on model levels?
+bool field_on_model_levels(int f) {
+  return (f >= MPHIP_PL && f <= MPHIP_ZETA_DOTL) || f == MPHIP_WL;
+}
+
+// what is refused of a packed description whatever the call; NULL = accepted (`why` holds the message otherwise)
+const char *packed_refusal(const mphip_met_packed_t *pk, std::string &why) {
+  for (int f = 0; f < MPHIP_N3D; f++) {
+    if (!pk->q3[f])
+      continue;
+    if (pk->base.f3[f])
+      why = std::string("field ") + kField3Name[f] + " is given both as floats and as codes";
+    else if (!pk->scl[f] || !pk->off[f])
+      why = std::string("field ") + kField3Name[f] + " is given as codes without scl or off";
+    else if (!(pk->lo[f] <= pk->hi[f]))
+      why = std::string("field ") + kField3Name[f] + ": the limits need lo <= hi";
+    else
+      continue;
+    return why.c_str();
+  }
+  return nullptr;
+}
+
+// One field on the device on its way through a streaming kernel: {scl[nlev] | off[nlev]} doubles, then the codes, which
+// keep their host array's offset from a 16-byte boundary (`shift` codes: the copy moves aligned runs to aligned runs, and
+// the kernels' vector path starts where the codes are aligned).
+struct PackedField {
+  size_t n;                // values
+  int nlev;
+  size_t shift;            // codes in front of the first one, 0 ... 7
+  size_t bytes;            // of the whole block
+  double *scl(char *blk) const { return (double *) blk; }
+  double *off(char *blk) const { return (double *) blk + nlev; }
+  unsigned short *q(char *blk) const { return (unsigned short *) (blk + 2 * (size_t) nlev * sizeof(double)) + shift; }
+};
+
+PackedField packed_field(size_t n, int nlev, const void *host_codes) {
+  PackedField B;
+  B.n = n;
+  B.nlev = nlev;
+  B.shift = ((uintptr_t) host_codes & 15) / sizeof(unsigned short);
+  B.bytes = 2 * (size_t) nlev * sizeof(double) + (n + 2 * kPkVec) * sizeof(unsigned short);
+  return B;
+}
+
+// grid, LDS and the scalar head of met_unpack_kernel / met_pack_quantise_kernel for n values whose codes start at q
+struct PackStream {
+  unsigned n, nlev, head;
+  dim3 grid;
+  size_t lds;
+  bool table_in_lds;
+};
+
+PackStream pack_stream(const unsigned short *q, size_t n, int nlev) {
+  PackStream P;
+  P.n = (unsigned) n;
+  P.nlev = (unsigned) nlev;
+  P.head = (unsigned) std::min<size_t>(n, ((16 - ((uintptr_t) q & 15)) & 15) / sizeof(unsigned short));
+  const size_t nvec = (n - P.head) / kPkVec;
+  P.grid = dim3((unsigned) std::min<size_t>(std::max<size_t>((nvec + kPkThreads - 1) / kPkThreads, 1), kPkMaxBlocks));
+  P.table_in_lds = nlev <= kPkLdsLevels;
+  P.lds = P.table_in_lds ? 2 * (size_t) nlev * sizeof(double) : 0;
+  return P;
+}
+
+// the largest block a packed snapshot's fields need (0: no field is given as codes)
+size_t packed_block_bytes(const mphip_met_packed_t *pk) {
+  const mphip_met_t *met = &pk->base;
+  size_t need = 0;
+  for (int f = 0; f < MPHIP_N3D; f++) {
+    const int nlev = field_on_model_levels(f) ? std::max(met->npl, 0) : met->np;
+    if (pk->q3[f] && nlev > 0)
+      need = std::max(need, packed_field((size_t) met->nx * met->ny * (size_t) nlev, nlev, pk->q3[f]).bytes);
+  }
+  return need;
+}
+
+// the code buffer of a stream, grown to `need` bytes (on the calling thread: nothing is queued on the stream that reads it)
+int reserve_codes(mphip_ctx *ctx, mphip_ctx::CodeBuf &B, size_t need) {
+  if (B.bytes >= need)
+    return 0;
+  B.bytes = 0;
+  if (dev_alloc(ctx, &B.p, need))
+    return 1;
+  B.bytes = need;
+  return 0;
+}
+
+// host -> device copies of one snapshot's fields into the staging arrays of slot S (asynchronous on `stream`); a field
+// that `pk` gives as codes goes into the block `codes` (reserve_codes) and is decoded from there behind its copy
+int upload_fields(mphip_ctx *ctx, MetSlot &S, const mphip_met_t *met, bool new_grid, hipStream_t stream,
+                  const mphip_met_packed_t *pk = nullptr, char *codes = nullptr) {
   const int nml = met->npl > 0 ? met->npl : 0;
   const size_t ncell = (size_t) met->nx * met->ny * met->np, ncol = (size_t) met->nx * met->ny;
   for (int f = 0; f < MPHIP_N3D; f++) {
-    const bool is_ml = (f >= MPHIP_PL && f <= MPHIP_ZETA_DOTL) || f == MPHIP_WL;
+    const bool is_ml = field_on_model_levels(f);
     const long long nlev = is_ml ? nml : met->np;
     const long long sx = is_ml ? met->sx_ml : met->sx, sy = is_ml ? met->sy_ml : met->sy;
-    S.has3[f] = met->f3[f] != nullptr && nlev > 0;
+    const bool coded = pk && pk->q3[f];
+    S.has3[f] = (met->f3[f] != nullptr || coded) && nlev > 0;
     if (!S.has3[f])
       continue;
     const size_t n3 = (size_t) met->nx * met->ny * (size_t) nlev;
     if (new_grid || !S.f3[f])
       if (dev_alloc(ctx, &S.f3[f], n3))
         return 1;
+    if (coded) {
+      const PackedField B = packed_field(n3, (int) nlev, pk->q3[f]);
+      HIPCHK(hipMemcpyAsync(B.scl(codes), pk->scl[f], (size_t) nlev * sizeof(double), hipMemcpyHostToDevice, stream));
+      HIPCHK(hipMemcpyAsync(B.off(codes), pk->off[f], (size_t) nlev * sizeof(double), hipMemcpyHostToDevice, stream));
+      HIPCHK(hipMemcpyAsync(B.q(codes), pk->q3[f], n3 * sizeof(unsigned short), hipMemcpyHostToDevice, stream));
+      const PackStream P = pack_stream(B.q(codes), n3, (int) nlev);
+      hipLaunchKernelGGL(P.table_in_lds ? met_unpack_kernel<true> : met_unpack_kernel<false>, P.grid, dim3(kPkThreads), P.lds,
+                         stream, B.q(codes), B.scl(codes), B.off(codes), S.f3[f], P.n, P.nlev, P.head, pk->lo[f], pk->hi[f]);
+      HIPCHK(hipGetLastError());
+      continue;
+    }
     if (!regrid_strides_ok(met->ny, (int) nlev, sx, sy))
       return fail(ctx, "unsupported 3-D meteo strides");
     if (copy3(ctx, stream, S.f3[f], met->f3[f], met->nx, met->ny, (int) nlev, sx, sy, true))
@@ -2963,6 +3076,12 @@ struct PrepCall {
   template <typename K, typename... Args>
   int launch(K kernel, dim3 grid, dim3 block, size_t lds, Args... args) {
     return mark_begin(0) || enqueue(kernel, grid, block, lds, args...) || mark_end();
+  }
+  // ... which a phase of its own singles out as well (4, 5, 6: the extremes, their reduction and the quantisation of
+  // mphip_pack_met)
+  template <typename K, typename... Args>
+  int launch_as(int phase, K kernel, dim3 grid, dim3 block, size_t lds, Args... args) {
+    return mark_begin(S.profile_phase == phase ? phase : 0) || enqueue(kernel, grid, block, lds, args...) || mark_end();
   }
 };
 
@@ -3293,6 +3412,8 @@ void mphip_destroy(mphip_ctx *ctx) {
     for (auto p : s->f2)
       dev_free(p);
   }
+  for (auto &b : ctx->codes)
+    dev_free(b.p);
   ctx->prep.release();
   dev_free(ctx->d_clim);
   for (auto p : ctx->d_zm)
@@ -3612,11 +3733,15 @@ int mphip_update_clim_ts(mphip_ctx *ctx, int which, int ntime, const double *tim
   return 0;
 }
 
-int mphip_update_met(mphip_ctx *ctx, int slot, const mphip_met_t *met) {
+// mphip_update_met, and mphip_update_met_packed (pk: the description `met` is the base of)
+static int update_met_any(mphip_ctx *ctx, int slot, const mphip_met_t *met, const mphip_met_packed_t *pk) {
   if (ctx && ahead_drop(ctx))
     return 1;
   if (!ctx || !met || slot < 0 || slot > 1)
     return fail(ctx, "bad argument");
+  std::string why;
+  if (pk && packed_refusal(pk, why))
+    return fail(ctx, "mphip_update_met_packed: " + why);
   if (met->nx < 2 || met->ny < 2 || met->np < 2 || !met->lon || !met->lat || !met->p)
     return fail(ctx, "meteo grid dimensions out of range");
   // index arithmetic of the kernels (cell_of / col_of): 24-bit factors, 31-bit cell index
@@ -3649,6 +3774,10 @@ int mphip_update_met(mphip_ctx *ctx, int slot, const mphip_met_t *met) {
     for (auto &q : ctx->next.f2) {
       dev_free(q);
       q = nullptr;
+    }
+    for (auto &b : ctx->codes) {   // (idle: every upload into a slot ends with its stream synchronised, the uploader was joined)
+      dev_free(b.p);
+      b = mphip_ctx::CodeBuf();
     }
     ctx->next.valid = false;
     ctx->next_pending = false;
@@ -3683,13 +3812,23 @@ int mphip_update_met(mphip_ctx *ctx, int slot, const mphip_met_t *met) {
               "the early exits of deposition, convection and turbulent diffusion are off (mphip_get_shortcuts)\n", first, last);
     }
   }
-  if (upload_fields(ctx, S, met, new_grid, ctx->stream))
+  if (pk && reserve_codes(ctx, ctx->codes[0], packed_block_bytes(pk)))
+    return 1;
+  if (upload_fields(ctx, S, met, new_grid, ctx->stream, pk, ctx->codes[0].p))
     return 1;
   HIPCHK(hipStreamSynchronize(ctx->stream));   // the host arrays may be reused by the caller
   S.time = met->time;
   S.valid = true;
   ctx->packed_dirty = true;
   return 0;
+}
+
+int mphip_update_met(mphip_ctx *ctx, int slot, const mphip_met_t *met) {
+  return update_met_any(ctx, slot, met, nullptr);
+}
+
+int mphip_update_met_packed(mphip_ctx *ctx, int slot, const mphip_met_packed_t *met) {
+  return update_met_any(ctx, slot, met ? &met->base : nullptr, met);
 }
 
 int mphip_swap_met(mphip_ctx *ctx) {
@@ -3733,9 +3872,13 @@ static void pin_host_span(mphip_ctx *ctx, const void *const *ptrs, int n, size_t
     (void) hipGetLastError();
 }
 
-int mphip_prefetch_met(mphip_ctx *ctx, const mphip_met_t *met) {
+// mphip_prefetch_met, and mphip_prefetch_met_packed (pk: the description `met` is the base of)
+static int prefetch_met_any(mphip_ctx *ctx, const mphip_met_t *met, const mphip_met_packed_t *pk) {
   if (!ctx || !met)
     return fail(ctx, "bad argument");
+  std::string why;
+  if (pk && packed_refusal(pk, why))
+    return fail(ctx, "mphip_prefetch_met_packed: " + why);
   HIPCHK(hipSetDevice(ctx->device));
   const int nml = met->npl > 0 ? met->npl : 0;
   if (!ctx->slot[0].valid || !ctx->slot[1].valid)
@@ -3756,7 +3899,16 @@ int mphip_prefetch_met(mphip_ctx *ctx, const mphip_met_t *met) {
   // page-locking arrays the caller owns is fragile (a copy has to lie inside one registration, arrays of
   // one allocation share pages, the caller may free them): an uploader thread of the library issues them
   // instead.  mphip_commit_met / mphip_discard_prefetch join it.
-  const mphip_met_t desc = *met;
+  if (pk && reserve_codes(ctx, ctx->codes[1], packed_block_bytes(pk)))
+    return 1;
+  // (the uploader thread reads its own copy of the description: its base, and the packed one when there is one)
+  mphip_met_packed_t desc_pk;
+  memset(&desc_pk, 0, sizeof(desc_pk));
+  if (pk)
+    desc_pk = *pk;
+  else
+    desc_pk.base = *met;
+  const bool coded = pk != nullptr;
   ctx->uploader_rc = 0;
   ctx->uploader_done = false;
   ctx->uploader_err.clear();
@@ -3776,17 +3928,17 @@ int mphip_prefetch_met(mphip_ctx *ctx, const mphip_met_t *met) {
   if (pack_ahead) {
     MetSlot probe = ctx->next;   // (presence flags only)
     for (int f = 0; f < MPHIP_N3D; f++)
-      probe.has3[f] = met->f3[f] != nullptr;
+      probe.has3[f] = met->f3[f] != nullptr || (pk && pk->q3[f]);
     for (int f = 0; f < MPHIP_N2D; f++)
       probe.has2[f] = met->f2[f] != nullptr;
     plan = pack_plan(ctx, ctx->slot[1 ^ ctx->flip], probe);
     if (pack_alloc(ctx, ctx->pk_next, plan))
       return 1;
   }
-  ctx->uploader = std::thread([ctx, desc, pack_ahead, plan]() {
+  ctx->uploader = std::thread([ctx, desc_pk, coded, pack_ahead, plan]() {
     int rc = hipSetDevice(ctx->device) == hipSuccess ? 0 : 1;
-    if (!rc)
-      rc = upload_fields(ctx, ctx->next, &desc, false, ctx->copy_stream);
+    if (!rc)   // (a packed field: its copy, then its decode, on the copy stream)
+      rc = upload_fields(ctx, ctx->next, &desc_pk.base, false, ctx->copy_stream, coded ? &desc_pk : nullptr, ctx->codes[1].p);
     if (!rc && pack_ahead) {
       // met1 of today is met0 after the commit; its staging arrays are not written while it is a current slot
       rc = pack_launch(ctx, ctx->pk_next, plan, ctx->slot[1 ^ ctx->flip], ctx->next, ctx->copy_stream);
@@ -3798,6 +3950,14 @@ int mphip_prefetch_met(mphip_ctx *ctx, const mphip_met_t *met) {
     ctx->uploader_done = true;
   });
   return 0;
+}
+
+int mphip_prefetch_met(mphip_ctx *ctx, const mphip_met_t *met) {
+  return prefetch_met_any(ctx, met, nullptr);
+}
+
+int mphip_prefetch_met_packed(mphip_ctx *ctx, const mphip_met_packed_t *met) {
+  return prefetch_met_any(ctx, met ? &met->base : nullptr, met);
 }
 
 int mphip_derive_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const mphip_prep_t *opt, const mphip_met_out_t *out) {
@@ -4340,6 +4500,185 @@ int mphip_detrend_met(mphip_ctx *ctx, const mphip_met_t *in, const mphip_detrend
   for (int i = 0; i < nf; i++)
     if (copy3(ctx, st, res[i], out->f3[fld[i]], P.nx, P.ny, P.np, out->sx, out->sy, false))
       return 1;
+  if (call.mark_end())
+    return 1;
+  return call.close();
+}
+
+size_t mphip_sizeof_met_packed(void) {
+  return sizeof(mphip_met_packed_t);
+}
+
+// what mphip_unpack_met and mphip_pack_met refuse of the grid of their base description; NULL = accepted
+static const char *pack_grid_refusal(const mphip_met_t *m) {
+  if (const char *why = grid_dims_refusal(m->nx, m->ny))
+    return why;
+  if (m->np < 1)
+    return "needs one pressure level or more (np < 1)";
+  return grid_size_refusal(m->nx, m->ny, std::max(m->np, m->npl));
+}
+
+int mphip_unpack_met(mphip_ctx *ctx, const mphip_met_packed_t *in, const mphip_met_t *out) {
+  if (!ctx || !in || !out)
+    return fail(ctx, "mphip_unpack_met: null argument");
+  const mphip_met_t *m = &in->base;
+  if (const char *why = pack_grid_refusal(m))
+    return fail(ctx, std::string("mphip_unpack_met: ") + why);
+  std::string msg;
+  if (packed_refusal(in, msg))
+    return fail(ctx, "mphip_unpack_met: " + msg);
+  int fld[MPHIP_N3D], nlev[MPHIP_N3D], nf = 0;
+  for (int f = 0; f < MPHIP_N3D; f++) {
+    const bool is_ml = field_on_model_levels(f);
+    const int nl = is_ml ? std::max(m->npl, 0) : m->np;
+    if (!in->q3[f] || !out->f3[f] || nl < 1)
+      continue;
+    if (!regrid_strides_ok(m->ny, nl, is_ml ? out->sx_ml : out->sx, is_ml ? out->sy_ml : out->sy))
+      return fail(ctx, "mphip_unpack_met: the output strides do not hold the grid");
+    fld[nf] = f;
+    nlev[nf++] = nl;
+  }
+  if (!nf)
+    return fail(ctx, "mphip_unpack_met: no field is given as codes in `in` and named in `out`");
+
+  PrepCall call(ctx);
+  if (call.open())
+    return 1;
+  hipStream_t st = call.st;
+  const size_t ncol = (size_t) m->nx * m->ny;
+  char *blk[MPHIP_N3D];
+  float *res[MPHIP_N3D];
+  if (call.mark_begin(1))
+    return 1;
+  for (int i = 0; i < nf; i++) {
+    const int f = fld[i];
+    const PackedField B = packed_field(ncol * nlev[i], nlev[i], in->q3[f]);
+    if (!(blk[i] = call.take<char>(B.bytes)) || !(res[i] = call.take<float>(B.n)))
+      return 1;
+    HIPCHK(hipMemcpyAsync(B.scl(blk[i]), in->scl[f], (size_t) nlev[i] * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(B.off(blk[i]), in->off[f], (size_t) nlev[i] * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(B.q(blk[i]), in->q3[f], B.n * sizeof(unsigned short), hipMemcpyHostToDevice, st));
+  }
+  if (call.mark_end())
+    return 1;
+  HIPCHK(hipStreamSynchronize(st));     // (an output may lie where an input does: the uploads are complete here)
+  for (int i = 0; i < nf; i++) {
+    const int f = fld[i];
+    const PackedField B = packed_field(ncol * nlev[i], nlev[i], in->q3[f]);
+    const PackStream P = pack_stream(B.q(blk[i]), B.n, nlev[i]);
+    if (call.launch(P.table_in_lds ? met_unpack_kernel<true> : met_unpack_kernel<false>, P.grid, dim3(kPkThreads), P.lds,
+                    (const unsigned short *) B.q(blk[i]), (const double *) B.scl(blk[i]), (const double *) B.off(blk[i]), res[i],
+                    P.n, P.nlev, P.head, in->lo[f], in->hi[f]))
+      return 1;
+  }
+  if (call.mark_begin(2))
+    return 1;
+  for (int i = 0; i < nf; i++) {
+    const bool is_ml = field_on_model_levels(fld[i]);
+    if (copy3(ctx, st, res[i], out->f3[fld[i]], m->nx, m->ny, nlev[i], is_ml ? out->sx_ml : out->sx,
+              is_ml ? out->sy_ml : out->sy, false))
+      return 1;
+  }
+  if (call.mark_end())
+    return 1;
+  return call.close();
+}
+
+int mphip_pack_met(mphip_ctx *ctx, const mphip_met_t *in, const mphip_met_packed_t *out) {
+  if (!ctx || !in || !out)
+    return fail(ctx, "mphip_pack_met: null argument");
+  if (const char *why = pack_grid_refusal(in))
+    return fail(ctx, std::string("mphip_pack_met: ") + why);
+  int fld[MPHIP_N3D], nlev[MPHIP_N3D], nf = 0, nlev_max = 0, nlev_sum = 0;
+  for (int f = 0; f < MPHIP_N3D; f++) {
+    const bool is_ml = field_on_model_levels(f);
+    const int nl = is_ml ? std::max(in->npl, 0) : in->np;
+    if (!in->f3[f] || !out->q3[f] || nl < 1)
+      continue;
+    if (!out->scl[f] || !out->off[f])
+      return fail(ctx, std::string("mphip_pack_met: field ") + kField3Name[f] + " is given as codes without scl or off");
+    if (!regrid_strides_ok(in->ny, nl, is_ml ? in->sx_ml : in->sx, is_ml ? in->sy_ml : in->sy))
+      return fail(ctx, "mphip_pack_met: unsupported meteo strides");
+    fld[nf] = f;
+    nlev[nf++] = nl;
+    nlev_max = std::max(nlev_max, nl);
+    nlev_sum += nl;
+  }
+  if (!nf)
+    return fail(ctx, "mphip_pack_met: no field is present in `in` and named as codes in `out`");
+  // the extremes: the columns a workgroup stages within 64 KB of LDS at the pitch nlev | 1, up to 64 of them
+  const int ncol = in->nx * in->ny;
+  int cpb[MPHIP_N3D], nblk[MPHIP_N3D];
+  size_t npart = 0;
+  for (int i = 0; i < nf; i++) {
+    const size_t col_bytes = (size_t) (nlev[i] | 1) * sizeof(float);
+    cpb[i] = (int) std::min<size_t>(64, (64 * 1024) / col_bytes);
+    if (cpb[i] < 1)
+      return fail(ctx, "mphip_pack_met: too many levels for one column in 64 KB of LDS");
+    nblk[i] = (ncol + cpb[i] - 1) / cpb[i];
+    npart = std::max(npart, (size_t) nblk[i] * (size_t) nlev[i]);
+  }
+
+  std::vector<int> bad((size_t) nlev_sum);      // (declared before the call scope: a copy writes it)
+  PrepCall call(ctx);
+  if (call.open())
+    return 1;
+  hipStream_t st = call.st;
+  float *x[MPHIP_N3D];
+  char *blk[MPHIP_N3D];
+  if (call.mark_begin(1))
+    return 1;
+  for (int i = 0; i < nf; i++) {
+    const bool is_ml = field_on_model_levels(fld[i]);
+    const PackedField B = packed_field((size_t) ncol * nlev[i], nlev[i], out->q3[fld[i]]);
+    if (!(x[i] = call.take<float>(B.n)) || !(blk[i] = call.take<char>(B.bytes))
+        || copy3(ctx, st, x[i], in->f3[fld[i]], in->nx, in->ny, nlev[i], is_ml ? in->sx_ml : in->sx, is_ml ? in->sy_ml : in->sy,
+                 true))
+      return 1;
+  }
+  if (call.mark_end())
+    return 1;
+  // the partials of one field at a time (the stream's order), and the flags of every level of every field
+  float *const pmin = call.take<float>(npart), *const pmax = pmin ? call.take<float>(npart) : nullptr;
+  int *const pbad = pmax ? call.take<int>(npart) : nullptr, *const d_bad = pbad ? call.take<int>((size_t) nlev_sum) : nullptr;
+  if (!d_bad)
+    return 1;
+  HIPCHK(hipStreamSynchronize(st));     // (an output may lie where an input does: the uploads are complete here)
+  for (int i = 0, at = 0; i < nf; at += nlev[i], i++) {
+    const PackedField B = packed_field((size_t) ncol * nlev[i], nlev[i], out->q3[fld[i]]);
+    const int pitch = nlev[i] | 1;
+    if (call.launch_as(4, met_pack_extremes_kernel, dim3((unsigned) nblk[i]), dim3(kPkThreads),
+                       (size_t) cpb[i] * pitch * sizeof(float), (const float *) x[i], ncol, nlev[i], cpb[i], pitch, pmin, pmax, pbad)
+        || call.launch_as(5, met_pack_reduce_kernel, dim3((unsigned) ((nlev[i] + kPkRedLevels - 1) / kPkRedLevels)),
+                          dim3(kPkRedThreads), 0, (const float *) pmin, (const float *) pmax, (const int *) pbad, nblk[i], nlev[i],
+                          B.scl(blk[i]), B.off(blk[i]), d_bad + at))
+      return 1;
+  }
+  // a level with a value that is not finite has no code: refused before anything is written
+  HIPCHK(hipMemcpyAsync(bad.data(), d_bad, bad.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (int i = 0, at = 0; i < nf; at += nlev[i], i++)
+    for (int k = 0; k < nlev[i]; k++)
+      if (bad[(size_t) at + k])
+        return fail(ctx, std::string("mphip_pack_met: field ") + kField3Name[fld[i]] + " holds a value that is not finite at level "
+                           + std::to_string(k));
+  for (int i = 0; i < nf; i++) {
+    const PackedField B = packed_field((size_t) ncol * nlev[i], nlev[i], out->q3[fld[i]]);
+    const PackStream P = pack_stream(B.q(blk[i]), B.n, nlev[i]);
+    if (call.launch_as(6, P.table_in_lds ? met_pack_quantise_kernel<true> : met_pack_quantise_kernel<false>, P.grid,
+                       dim3(kPkThreads), P.lds, (const float *) x[i], (const double *) B.scl(blk[i]),
+                       (const double *) B.off(blk[i]), B.q(blk[i]), P.n, P.nlev, P.head))
+      return 1;
+  }
+  if (call.mark_begin(2))
+    return 1;
+  for (int i = 0; i < nf; i++) {
+    const int f = fld[i];
+    const PackedField B = packed_field((size_t) ncol * nlev[i], nlev[i], out->q3[fld[i]]);
+    HIPCHK(hipMemcpyAsync((void *) out->scl[f], B.scl(blk[i]), (size_t) nlev[i] * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync((void *) out->off[f], B.off(blk[i]), (size_t) nlev[i] * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync((void *) out->q3[f], B.q(blk[i]), B.n * sizeof(unsigned short), hipMemcpyDeviceToHost, st));
+  }
   if (call.mark_end())
     return 1;
   return call.close();
@@ -5606,9 +5945,9 @@ int mphip_set_option(mphip_ctx *ctx, const char *name, double value) {
     return 0;
   }
   if (strcmp(name, "derive_profile_phase") == 0) {
-    if (value != 0 && value != 1 && value != 2 && value != 3)
-      return fail(ctx, "derive_profile_phase must be 0 (kernels), 1 (uploads), 2 (downloads) or 3 (the weight table of "
-                       "mphip_detrend_met)");
+    if (value != 0 && value != 1 && value != 2 && value != 3 && value != 4 && value != 5 && value != 6)
+      return fail(ctx, "derive_profile_phase must be 0 (kernels), 1 (uploads), 2 (downloads), 3 (the weight table of "
+                       "mphip_detrend_met) or 4, 5, 6 (the extremes, their reduction, the quantisation of mphip_pack_met)");
     ctx->prep.profile_phase = (int) value;
     return 0;
   }

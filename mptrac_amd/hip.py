@@ -83,6 +83,20 @@ class MphipDetrend(C.Structure):
 
 DETREND_FIELDS = ("t", "u", "v", "w")
 
+_up = C.POINTER(C.c_ushort)
+
+
+class MphipMetPacked(C.Structure):
+    """mphip_met_packed_t: a snapshot some of whose level fields are 16-bit codes (MET_TYPE 2)."""
+    _fields_ = [("base", MphipMet), ("q3", _up * len(FIELDS_3D)), ("scl", _dp * len(FIELDS_3D)), ("off", _dp * len(FIELDS_3D)),
+                ("lo", C.c_float * len(FIELDS_3D)), ("hi", C.c_float * len(FIELDS_3D))]
+
+
+# the limits the reader of the binary files applies to a level field (every other field: PACK_LIMITS_OPEN)
+PACK_LIMITS_OPEN = (-1e34, 1e34)
+PACK_LIMITS = {"t": (0., 1e34), "h2o": (0., 1e34), "o3": (0., 1e34), "lwc": (0., 1e34), "rwc": (0., 1e34), "iwc": (0., 1e34),
+               "swc": (0., 1e34), "cc": (0., 1.)}
+
 
 class Snapshot:
     """What Simulation.regrid_met returns: the axes (float64) and the float32 fields of the new shape, named as in
@@ -174,6 +188,14 @@ def load(build=True):
         L.mphip_sizeof_detrend.restype = C.c_size_t
         if L.mphip_sizeof_detrend() != C.sizeof(MphipDetrend):
             raise MphipError("mphip_detrend_t layout mismatch between header and Python mirror")
+    if hasattr(L, "mphip_update_met_packed"):      # (absent from libraries built before the packed files: A/B runs through MPHIP_LIB)
+        L.mphip_update_met_packed.argtypes = [C.c_void_p, C.c_int, C.POINTER(MphipMetPacked)]
+        L.mphip_prefetch_met_packed.argtypes = [C.c_void_p, C.POINTER(MphipMetPacked)]
+        L.mphip_unpack_met.argtypes = [C.c_void_p, C.POINTER(MphipMetPacked), C.POINTER(MphipMet)]
+        L.mphip_pack_met.argtypes = [C.c_void_p, C.POINTER(MphipMet), C.POINTER(MphipMetPacked)]
+        L.mphip_sizeof_met_packed.restype = C.c_size_t
+        if L.mphip_sizeof_met_packed() != C.sizeof(MphipMetPacked):
+            raise MphipError("mphip_met_packed_t layout mismatch between header and Python mirror")
     if hasattr(L, "mphip_sizeof_prep"):     # (absent from libraries built before pv and the tropopause: they read the old members)
         L.mphip_sizeof_prep.restype = C.c_size_t
         if L.mphip_sizeof_prep() != C.sizeof(MphipPrep):
@@ -507,6 +529,91 @@ class Simulation:
                 m.f3[i] = None
         self._chk(self.L.mphip_detrend_met(self.h, C.byref(m), C.byref(o), C.byref(mo)))
         return res
+
+    # -- 16-bit packed level fields (MET_TYPE 2) ------------------------------
+    def _met_packed_struct(self, met, packed):
+        """mphip_met_packed_t of a snapshot `met` (axes, surface fields, the level fields that stay float) and `packed`:
+        {name: (codes, scl, off[, lo, hi])} -- codes uint16 [nx][ny][nlev], C-contiguous (a view that starts anywhere in a
+        larger array will do), scl / off float64 [nlev] (None: not given, which the library refuses); the limits default
+        to PACK_LIMITS, those of the reader of the binary files."""
+        m = MphipMetPacked()
+        m.base = self._met_struct(met)
+        if any(k in FIELDS_ML for k in packed):
+            m.base.npl = met.npl
+        for name, rec in packed.items():
+            i = FIELDS_3D.index(name)
+            q, scl, off = rec[:3]
+            nlev = met.npl if name in FIELDS_ML else met.np
+            assert q.dtype == np.uint16 and q.shape == (met.nx, met.ny, nlev) and q.flags["C_CONTIGUOUS"], name
+            m.q3[i] = _ptr(q, _up)
+            for slot, a in ((m.scl, scl), (m.off, off)):
+                if a is not None:
+                    assert a.dtype == np.float64 and a.shape == (nlev,) and a.flags["C_CONTIGUOUS"], name
+                    slot[i] = _ptr(a, _dp)
+            m.lo[i], m.hi[i] = rec[3:5] if len(rec) > 3 else PACK_LIMITS.get(name, PACK_LIMITS_OPEN)
+        return m
+
+    def update_met_packed(self, slot, met, packed):
+        """set_met for a snapshot whose fields `packed` go to the device as codes and are decoded there
+        (mphip_update_met_packed; the conventions of _met_packed_struct)."""
+        m = self._met_packed_struct(met, packed)
+        self._chk(self.L.mphip_update_met_packed(self.h, slot, C.byref(m)))
+        self._mets[slot] = met
+
+    def prefetch_met_packed(self, next_met, packed):
+        """prefetch_met for such a snapshot (mphip_prefetch_met_packed); its arrays, the codes, scales and offsets
+        included, must stay untouched until commit_met()."""
+        m = self._met_packed_struct(next_met, packed)
+        self._chk(self.L.mphip_prefetch_met_packed(self.h, C.byref(m)))
+        self._next_met = next_met
+        self._next_packed = packed
+
+    def unpack_met(self, met, packed, out=None, out_strides=None):
+        """Decode the fields `packed` on the device into float arrays (mphip_unpack_met).  `met`: the snapshot the codes
+        belong to (its extents; its own fields are not read).  `out`: {name: float32 array [nx][ny][nlev] to write into}
+        -- views into larger arrays name their strides in floats as `out_strides` = (sx, sy), which then hold for every
+        output array; by default new compact arrays for every packed field.  Returns {name: array}."""
+        m = self._met_packed_struct(met, packed)
+        mo = MphipMet()
+        mo.nx, mo.ny, mo.np, mo.npl = met.nx, met.ny, met.np, m.base.npl
+        res = {}
+        for name in (packed if out is None else out):
+            nlev = met.npl if name in FIELDS_ML else met.np
+            a = np.empty((met.nx, met.ny, nlev), dtype=np.float32) if out is None else out[name]
+            sx, sy = out_strides or (met.ny * nlev, nlev)
+            assert a.dtype == np.float32 and a.shape == (met.nx, met.ny, nlev) and a.strides == (4 * sx, 4 * sy, 4), name
+            if name in FIELDS_ML:
+                mo.sx_ml, mo.sy_ml = sx, sy
+            else:
+                mo.sx, mo.sy = sx, sy
+            mo.f3[FIELDS_3D.index(name)] = _ptr(a, _fp)
+            res[name] = a
+        mo.sx2 = met.ny
+        self._chk(self.L.mphip_unpack_met(self.h, C.byref(m), C.byref(mo)))
+        return res
+
+    def pack_met(self, met, fields=None, out=None):
+        """Encode level fields of `met` (a snapshot with the conventions of derive_met) on the device
+        (mphip_pack_met).  `fields`: the names to encode (default: every level field the snapshot has).  `out`: {name:
+        (codes, scl, off)} arrays to write into (codes uint16 [nx][ny][nlev] C-contiguous, scl / off float64 [nlev] or
+        None); by default new arrays.  Returns {name: (codes, scl, off)}."""
+        m = self._met_struct(met)
+        names = tuple(met.f3) if fields is None else tuple(fields)
+        if any(k in FIELDS_ML for k in names):
+            m.npl = met.npl
+        for i, k in enumerate(FIELDS_3D):       # (a field that was not asked for is not passed)
+            if k not in names:
+                m.f3[i] = None
+        out = dict(out or {})
+        packed = {}
+        for name in set(names) | set(out):
+            nlev = met.npl if name in FIELDS_ML else met.np
+            packed[name] = out.get(name) or (np.empty((met.nx, met.ny, nlev), dtype=np.uint16), np.empty(nlev), np.empty(nlev))
+        empty = Snapshot(met.time, met.coord_type, met.lon, met.lat, met.p, {}, {})
+        empty.npl = met.npl
+        mo = self._met_packed_struct(empty, packed)
+        self._chk(self.L.mphip_pack_met(self.h, C.byref(m), C.byref(mo)))
+        return {k: packed[k] for k in names if k in met.f3}
 
     def set_met(self, slot, met):
         m = self._met_struct(met)

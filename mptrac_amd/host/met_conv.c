@@ -1,7 +1,8 @@
 /*
  * met_conv.c -- conversion between the meteo file formats, MI355X build: the reference's met_conv tool
  * (src/met_conv.c) on the host layer's readers and writers -- MET_TYPE 0 (netCDF: classic or netCDF-4 in, classic
- * out) and 1 (the reference's binary format).  As in mptrac_read_met of this build, netCDF input is taken as stored
+ * out), 1 (the reference's binary format) and 2 (the same with every level field as 16-bit codes, encoded and decoded on
+ * the device: mphip_pack_met, mphip_unpack_met), in every direction.  As in mptrac_read_met of this build, netCDF input is taken as stored
  * by default and no device is involved; with HIP_MET_PREP 1 the device derives the geopotential heights, the ozone
  * column, the boundary-layer pressure, the cloud layer and CAPE / CIN with their levels from the file's fields
  * (mphip_derive_met), and the output carries them: every plane of a MET_TYPE 1 file, the surface variables of a netCDF
@@ -25,7 +26,7 @@ int main(int argc, char *argv[]) {
     if (!strcmp(argv[i], "-h") || !strcmp(argv[i], "--help")) {
       printf("\nMPTRAC met_conv tool (MI355X build).\n\nConverts meteo files between the formats of MET_TYPE.\n\n"
              "Usage:\n  met_conv <ctl> <met_in> <met_in_type> <met_out> <met_out_type> [KEY VALUE ...]\n\n"
-             "Types: 0 netCDF, 1 binary.\n\n");
+             "Types: 0 netCDF, 1 binary, 2 binary with 16-bit packed level fields.\n\n");
       return EXIT_SUCCESS;
     }
   if (argc < 6)

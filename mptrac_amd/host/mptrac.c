@@ -79,6 +79,25 @@ static void flush_steps(void) {
 /* a condition the input has to meet, else the run stops with the message */
 #define REQUIRE(ok, ...) { if (!(ok)) ERRMSG(__VA_ARGS__); }
 
+/* The level fields of a MET_TYPE 2 file as they were read (met_t::packed): 13 fields in file order, each `n` = nx ny np
+ * compact codes [ix][iy][ip] with one scale and one offset per level.  `floats`: the float level members of the met_t
+ * hold the decoded fields (met_need_floats has run for this content); `valid`: the met_t was last filled from such a file. */
+#define MET_NLEVEL 13
+typedef struct {
+  int valid, floats;
+  size_t n, cap;           /* codes per field; codes per field the allocation holds */
+  unsigned short *q;       /* field k: q + k * cap */
+  double scl[MET_NLEVEL][EP], off[MET_NLEVEL][EP];
+} met_packed_t;
+
+static void met_packed_free(met_t *met) {
+  if (!met || !met->packed)
+    return;
+  free(((met_packed_t *) met->packed)->q);
+  free(met->packed);
+  met->packed = NULL;
+}
+
 /* -------------------------------------------------------------------------- */
 /* alloc / free                                                               */
 /* -------------------------------------------------------------------------- */
@@ -107,6 +126,9 @@ void mptrac_free(ctl_t *ctl, cache_t *cache, clim_t *clim, met_t *met0, met_t *m
     g_ctx = NULL;
   }
   g_prep_ready = 0;
+  met_packed_free(g_ahead.met);
+  met_packed_free(met0);
+  met_packed_free(met1);
   free(g_ahead.met);
   g_ahead.met = NULL;
   g_met_host[0] = g_met_host[1] = NULL;
@@ -429,6 +451,12 @@ void mptrac_read_ctl(const char *filename, int argc, char *argv[], ctl_t *ctl) {
   ctl->met_utm_ref_lon = (ctl->met_coord_type != 0)
     ? scan_ctl(filename, argc, argv, "MET_UTM_REF_LON", -1, "", NULL) : 0;
   REQUIRE(ctl->direction == -1 || ctl->direction == 1, "Set DIRECTION to -1 or 1!");
+  REQUIRE(ctl->met_type >= 0 && ctl->met_type <= 2,
+          "MET_TYPE %d: this build reads MET_TYPE 0 (netCDF), 1 (raw binary) and 2 (16-bit packed binary) meteo files!",
+          ctl->met_type);
+  /* 16-bit packed files: the codes go to the device as they are (1, the default) or are decoded when the file is read */
+  ctl->hip_met_packed = ctl->met_type == 2 ? (int) scan_ctl(filename, argc, argv, "HIP_MET_PACKED", -1, "1", NULL) : 0;
+  REQUIRE(ctl->hip_met_packed == 0 || ctl->hip_met_packed == 1, "Set HIP_MET_PACKED to 0 or 1!");
   if (ctl->met_type == 0) {
     /* netCDF input is taken as stored: no hybrid-coefficient levels (mptrac.c:7770-7830) ... */
     static const struct {
@@ -1328,8 +1356,9 @@ typedef struct {
   int fd;
   off_t off;             /* file offset of the block */
   const met_t *met;
-  float *field, *buf;
-  size_t lev, stride;
+  float *field;
+  char *buf;             /* the whole block: values of `elem` bytes (floats, or the codes of a MET_TYPE 2 file) */
+  size_t elem, lev, stride;
   float lo, hi;
   int ix0, ix1, ok;
 } met_slab_t;
@@ -1337,9 +1366,9 @@ typedef struct {
 static void *met_slab_main(void *arg) {
   met_slab_t *s = (met_slab_t *) arg;
   const size_t per_ix = (size_t) s->met->ny * s->lev;
-  char *dst = (char *) (s->buf + (size_t) s->ix0 * per_ix);
-  size_t left = (size_t) (s->ix1 - s->ix0) * per_ix * sizeof(float);
-  off_t at = s->off + (off_t) ((size_t) s->ix0 * per_ix * sizeof(float));
+  char *dst = s->buf + (size_t) s->ix0 * per_ix * s->elem;
+  size_t left = (size_t) (s->ix1 - s->ix0) * per_ix * s->elem;
+  off_t at = s->off + (off_t) ((size_t) s->ix0 * per_ix * s->elem);
   s->ok = 1;
   while (left > 0) {
     const ssize_t got = pread(s->fd, dst, left, at);
@@ -1351,13 +1380,14 @@ static void *met_slab_main(void *arg) {
     at += got;
     left -= (size_t) got;
   }
-  if (s->field) {
+  if (s->field) {       /* (floats only) */
+    const float *vals = (const float *) s->buf;
     size_t k = (size_t) s->ix0 * per_ix;
     for (int ix = s->ix0; ix < s->ix1; ix++)
       for (int iy = 0; iy < s->met->ny; iy++) {
         float *cell = s->field + ((size_t) ix * EY + (size_t) iy) * s->stride;
         for (size_t ip = 0; ip < s->lev; ip++, k++)
-          cell[ip] = fminf(fmaxf(s->buf[k], s->lo), s->hi);
+          cell[ip] = fminf(fmaxf(vals[k], s->lo), s->hi);
       }
   }
   return NULL;
@@ -1377,6 +1407,39 @@ static int met_io_threads(void) {
   return n;
 }
 
+/* A block of nx ny lev values of `elem` bytes at the file's position, read into buf by a few threads side by side (a
+ * float block is limited and scattered into `field` as well, unless that is NULL).  0: not done this way -- one thread
+ * asked for or too few longitudes --, the file's position is unchanged. */
+static int met_block_slabs(FILE *f, const met_t *met, float *field, void *buf, const size_t elem, const size_t lev,
+                           const size_t stride, const float lo, const float hi) {
+  const size_t n = (size_t) met->nx * (size_t) met->ny * lev;
+  const int nthreads = met_io_threads();
+  if (nthreads <= 1 || met->nx < 2 * nthreads)
+    return 0;
+  met_slab_t slab[64];
+  pthread_t th[64];
+  const off_t off = ftello(f);
+  int started = 0;
+  for (int t = 0; t < nthreads; t++) {
+    slab[t] = (met_slab_t) { fileno(f), off, met, field, (char *) buf, elem, lev, stride, lo, hi,
+                             (int) ((long) met->nx * t / nthreads), (int) ((long) met->nx * (t + 1) / nthreads), 0 };
+    if (pthread_create(&th[t], NULL, met_slab_main, &slab[t]) != 0)
+      break;
+    started++;
+  }
+  for (int t = started; t < nthreads; t++)     /* (threads that could not be started: their slabs here) */
+    met_slab_main(&slab[t]);
+  int ok = 1;
+  for (int t = 0; t < nthreads; t++) {
+    if (t < started)
+      pthread_join(th[t], NULL);
+    ok &= slab[t].ok;
+  }
+  if (!ok || fseeko(f, off + (off_t) (n * elem), SEEK_SET) != 0)
+    ERRMSG("Error while reading!");
+  return 1;
+}
+
 /* One field of a MET_TYPE 1 file: compact [nx][ny] or [nx][ny][np] floats <-> the fixed-extent member of met_t
  * (nlev = 0: surface field).  On reading, level fields are limited to [lo, hi] as the reference does
  * (read_met_bin_3d); dst == NULL skips the block, src == NULL writes zeros. */
@@ -1384,31 +1447,8 @@ static void met_block(FILE *f, const int write, const met_t *met, float *field, 
                       const float hi, float *buf) {
   const size_t lev = nlev > 0 ? (size_t) nlev : 1, stride = nlev > 0 ? EP : 1;
   const size_t n = (size_t) met->nx * (size_t) met->ny * lev;
-  const int nthreads = met_io_threads();
-  if (!write && nlev > 0 && nthreads > 1 && met->nx >= 2 * nthreads) {
-    met_slab_t slab[64];
-    pthread_t th[64];
-    const off_t off = ftello(f);
-    int started = 0;
-    for (int t = 0; t < nthreads; t++) {
-      slab[t] = (met_slab_t) { fileno(f), off, met, field, buf, lev, stride, lo, hi,
-                               (int) ((long) met->nx * t / nthreads), (int) ((long) met->nx * (t + 1) / nthreads), 0 };
-      if (pthread_create(&th[t], NULL, met_slab_main, &slab[t]) != 0)
-        break;
-      started++;
-    }
-    for (int t = started; t < nthreads; t++)     /* (threads that could not be started: their slabs here) */
-      met_slab_main(&slab[t]);
-    int ok = 1;
-    for (int t = 0; t < nthreads; t++) {
-      if (t < started)
-        pthread_join(th[t], NULL);
-      ok &= slab[t].ok;
-    }
-    if (!ok || fseeko(f, off + (off_t) (n * sizeof(float)), SEEK_SET) != 0)
-      ERRMSG("Error while reading!");
+  if (!write && nlev > 0 && met_block_slabs(f, met, field, buf, sizeof(float), lev, stride, lo, hi))
     return;
-  }
   if (!write)
     get_items(f, buf, sizeof(float), n);
   size_t k = 0;
@@ -1426,27 +1466,159 @@ static void met_block(FILE *f, const int write, const met_t *met, float *field, 
     put_items(f, buf, sizeof(float), n);
 }
 
-/* the 24 surface and 13 level fields in file order (version 104 of the format) */
-static void met_bin_body(FILE *f, int write, met_t *met) {
-  float *buf;
-  if ((buf = malloc((size_t) met->nx * (size_t) met->ny * (size_t) met->np * sizeof(float))) == NULL)     /* (not zeroed: every block is read or written in full) */
-    ERRMSG("Out of memory!");
+/* the 13 level fields in file order (version 104 of the format): the member of met_t, the limits the reader applies,
+ * and the field's slot in the back end's descriptions */
+typedef struct {
+  float *field, lo, hi;
+  int id;
+} met_level_t;
+
+static void met_levels(met_t *met, met_level_t level[MET_NLEVEL]) {
+  const met_level_t table[MET_NLEVEL] = { { &met->z[0][0][0], -1e34f, 1e34f, MPHIP_Z }, { &met->t[0][0][0], 0, 1e34f, MPHIP_T },
+    { &met->u[0][0][0], -1e34f, 1e34f, MPHIP_U }, { &met->v[0][0][0], -1e34f, 1e34f, MPHIP_V },
+    { &met->w[0][0][0], -1e34f, 1e34f, MPHIP_W }, { &met->pv[0][0][0], -1e34f, 1e34f, MPHIP_PV },
+    { &met->h2o[0][0][0], 0, 1e34f, MPHIP_H2O }, { &met->o3[0][0][0], 0, 1e34f, MPHIP_O3 },
+    { &met->lwc[0][0][0], 0, 1e34f, MPHIP_LWC }, { &met->rwc[0][0][0], 0, 1e34f, MPHIP_RWC },
+    { &met->iwc[0][0][0], 0, 1e34f, MPHIP_IWC }, { &met->swc[0][0][0], 0, 1e34f, MPHIP_SWC },
+    { &met->cc[0][0][0], 0, 1, MPHIP_CC } };
+  memcpy(level, table, sizeof(table));
+}
+
+/* the 24 surface fields in file order, raw floats in MET_TYPE 1 and 2 alike */
+static void met_bin_surface(FILE *f, int write, met_t *met, float *buf) {
   float *surface[24] = { &met->ps[0][0], &met->ts[0][0], &met->zs[0][0], &met->us[0][0], &met->vs[0][0], &met->ess[0][0],
     &met->nss[0][0], &met->shf[0][0], &met->lsm[0][0], &met->sst[0][0], &met->pbl[0][0], &met->pt[0][0], &met->tt[0][0],
     &met->zt[0][0], &met->h2ot[0][0], &met->pct[0][0], &met->pcb[0][0], &met->cl[0][0], &met->plcl[0][0],
     &met->plfc[0][0], &met->pel[0][0], &met->cape[0][0], &met->cin[0][0], &met->o3c[0][0] };
   for (int k = 0; k < 24; k++)
     met_block(f, write, met, surface[k], 0, 0.f, 0.f, buf);
-  const struct {
-    float *field, lo, hi;
-  } level[13] = { { &met->z[0][0][0], -1e34f, 1e34f }, { &met->t[0][0][0], 0, 1e34f }, { &met->u[0][0][0], -1e34f, 1e34f },
-    { &met->v[0][0][0], -1e34f, 1e34f }, { &met->w[0][0][0], -1e34f, 1e34f }, { &met->pv[0][0][0], -1e34f, 1e34f },
-    { &met->h2o[0][0][0], 0, 1e34f }, { &met->o3[0][0][0], 0, 1e34f }, { &met->lwc[0][0][0], 0, 1e34f },
-    { &met->rwc[0][0][0], 0, 1e34f }, { &met->iwc[0][0][0], 0, 1e34f }, { &met->swc[0][0][0], 0, 1e34f },
-    { &met->cc[0][0][0], 0, 1 } };
-  for (int k = 0; k < 13; k++)
+}
+
+/* the 24 surface and 13 level fields of a MET_TYPE 1 file */
+static void met_bin_body(FILE *f, int write, met_t *met) {
+  float *buf;
+  if ((buf = malloc((size_t) met->nx * (size_t) met->ny * (size_t) met->np * sizeof(float))) == NULL)     /* (not zeroed: every block is read or written in full) */
+    ERRMSG("Out of memory!");
+  met_bin_surface(f, write, met, buf);
+  met_level_t level[MET_NLEVEL];
+  met_levels(met, level);
+  for (int k = 0; k < MET_NLEVEL; k++)
     met_block(f, write, met, level[k].field, met->np, level[k].lo, level[k].hi, buf);
   free(buf);
+}
+
+static void need_ctx(const ctl_t *ctl);
+
+/* the description of a snapshot's extents and strides for mphip_pack_met / mphip_unpack_met (no field, no axis) */
+static void met_pack_base(const met_t *met, mphip_met_t *m) {
+  memset(m, 0, sizeof(*m));
+  m->time = met->time;
+  m->coord_type = met->coord_type;
+  m->nx = met->nx;
+  m->ny = met->ny;
+  m->np = met->np;
+  m->sx = m->sx_ml = (long long) EY * EP;
+  m->sy = m->sy_ml = EP;
+  m->sx2 = EY;
+}
+
+/* field k of the block as the back end's packed description names it */
+static void met_packed_field(met_t *met, int k, mphip_met_packed_t *pk) {
+  met_packed_t *P = (met_packed_t *) met->packed;
+  met_level_t level[MET_NLEVEL];
+  met_levels(met, level);
+  const int id = level[k].id;
+  pk->base.f3[id] = NULL;
+  pk->q3[id] = P->q + (size_t) k * P->cap;
+  pk->scl[id] = P->scl[k];
+  pk->off[id] = P->off[k];
+  pk->lo[id] = level[k].lo;
+  pk->hi[id] = level[k].hi;
+}
+
+/* is the snapshot's current content the codes of a MET_TYPE 2 file? */
+static int met_is_packed(const met_t *met) {
+  return met->packed && ((const met_packed_t *) met->packed)->valid;
+}
+
+void met_need_floats(met_t *met) {
+  if (!met || !met_is_packed(met) || ((met_packed_t *) met->packed)->floats)
+    return;
+  need_ctx(NULL);
+  mphip_met_packed_t in;
+  memset(&in, 0, sizeof(in));
+  met_pack_base(met, &in.base);
+  mphip_met_t out = in.base;
+  met_level_t level[MET_NLEVEL];
+  met_levels(met, level);
+  for (int k = 0; k < MET_NLEVEL; k++) {
+    met_packed_field(met, k, &in);
+    out.f3[level[k].id] = level[k].field;
+  }
+  /* (not through HIP(): the read-ahead thread comes here with HIP_MET_PACKED 0, and that macro first submits the main
+   * thread's queued time steps; the call touches no meteo slot and no particle) */
+  if (mphip_unpack_met(g_ctx, &in, &out) != 0)
+    ERRMSG("HIP back end: %s", mphip_last_error(g_ctx));
+  ((met_packed_t *) met->packed)->floats = 1;
+  LOG(2, "Decoded on the device: %d level fields of %d x %d x %d", MET_NLEVEL, met->nx, met->ny, met->np);
+}
+
+/* the level fields of a MET_TYPE 2 file into the block of the met_t: scl[np], off[np], nx ny np codes each -- read as they
+ * are, by the threads of met_block; nothing is scattered and no value is touched */
+static void met_pck_read_levels(FILE *in, met_t *met) {
+  met_packed_t *P = (met_packed_t *) met->packed;
+  const size_t n = (size_t) met->nx * (size_t) met->ny * (size_t) met->np;
+  if (!P) {
+    ALLOC(P, met_packed_t, 1);
+    met->packed = P;
+  }
+  if (P->cap < n) {
+    free(P->q);
+    if ((P->q = malloc(MET_NLEVEL * n * sizeof(unsigned short))) == NULL)
+      ERRMSG("Out of memory!");
+    P->cap = n;
+  }
+  P->n = n;
+  P->valid = P->floats = 0;
+  for (int k = 0; k < MET_NLEVEL; k++) {
+    get_items(in, P->scl[k], sizeof(double), (size_t) met->np);
+    get_items(in, P->off[k], sizeof(double), (size_t) met->np);
+    unsigned short *q = P->q + (size_t) k * P->cap;
+    if (!met_block_slabs(in, met, NULL, q, sizeof(unsigned short), (size_t) met->np, 0, 0.f, 0.f))
+      get_items(in, q, sizeof(unsigned short), n);
+  }
+  P->valid = 1;
+}
+
+/* ... and out of the float members of the met_t into a MET_TYPE 2 file: encoded on the device (mphip_pack_met) */
+static void met_pck_write_levels(FILE *out, met_t *met) {
+  const size_t n = (size_t) met->nx * (size_t) met->ny * (size_t) met->np;
+  unsigned short *q;
+  double *tab;
+  if ((q = malloc(MET_NLEVEL * n * sizeof(unsigned short))) == NULL || (tab = malloc(2 * MET_NLEVEL * EP * sizeof(double))) == NULL)
+    ERRMSG("Out of memory!");
+  need_ctx(NULL);
+  mphip_met_t in;
+  met_pack_base(met, &in);
+  mphip_met_packed_t pk;
+  memset(&pk, 0, sizeof(pk));
+  pk.base = in;
+  met_level_t level[MET_NLEVEL];
+  met_levels(met, level);
+  for (int k = 0; k < MET_NLEVEL; k++) {
+    in.f3[level[k].id] = level[k].field;
+    pk.q3[level[k].id] = q + (size_t) k * n;
+    pk.scl[level[k].id] = tab + (size_t) (2 * k) * EP;
+    pk.off[level[k].id] = tab + (size_t) (2 * k + 1) * EP;
+  }
+  HIP(mphip_pack_met(g_ctx, &in, &pk));
+  for (int k = 0; k < MET_NLEVEL; k++) {
+    put_items(out, tab + (size_t) (2 * k) * EP, sizeof(double), (size_t) met->np);
+    put_items(out, tab + (size_t) (2 * k + 1) * EP, sizeof(double), (size_t) met->np);
+    put_items(out, q + (size_t) k * n, sizeof(unsigned short), n);
+  }
+  free(tab);
+  free(q);
 }
 
 static int read_met_nc(const char *filename, const ctl_t *ctl, const clim_t *clim, met_t *met);
@@ -1458,14 +1630,19 @@ static int extent_from_file(FILE *in, const int max, const char *what) {
   return n;
 }
 
-/* MET_TYPE 1: [1] [104] time nx ny np lon[] lat[] p[] fields [999] (reference: read_met_bin, write_met_bin) */
+/* MET_TYPE 1: [1] [104] time nx ny np lon[] lat[] p[] fields [999] (reference: read_met_bin, write_met_bin); MET_TYPE 2:
+ * [2] [104] ..., the surface fields as floats, every level field as scl[np], off[np] and 16-bit codes (the definition:
+ * include/mptrac_hip.h, at mphip_met_packed_t) */
 int mptrac_read_met(const char *filename, const ctl_t *ctl, const clim_t *clim, met_t *met, dd_t *dd) {
   (void) dd;
   LOG(1, "Read meteo data: %s", filename);
+  if (met->packed)
+    ((met_packed_t *) met->packed)->valid = 0;     /* (the codes of an earlier read do not describe what is read now) */
   if (ctl->met_type == 0)
     return read_met_nc(filename, ctl, clim, met);
-  if (ctl->met_type != 1)
-    ERRMSG("This build reads MET_TYPE 0 (classic netCDF, grids without preprocessing) and 1 (raw binary) meteo files!");
+  if (ctl->met_type != 1 && ctl->met_type != 2)
+    ERRMSG("This build reads MET_TYPE 0 (classic netCDF, grids without preprocessing), 1 (raw binary) and 2 (16-bit packed "
+           "binary) meteo files!");
   FILE *in = fopen(filename, "r");
   if (!in) {
     WARN("Cannot open file!");
@@ -1483,10 +1660,25 @@ int mptrac_read_met(const char *filename, const ctl_t *ctl, const clim_t *clim, 
   get_items(in, met->lon, sizeof(double), (size_t) met->nx);
   get_items(in, met->lat, sizeof(double), (size_t) met->ny);
   get_items(in, met->p, sizeof(double), (size_t) met->np);
-  met_bin_body(in, 0, met);
+  if (ctl->met_type == 1)
+    met_bin_body(in, 0, met);
+  else {
+    float *buf;
+    if ((buf = malloc((size_t) met->nx * (size_t) met->ny * sizeof(float))) == NULL)
+      ERRMSG("Out of memory!");
+    met_bin_surface(in, 0, met, buf);
+    free(buf);
+    met_pck_read_levels(in, met);
+  }
   if (get_int(in) != 999)
     ERRMSG("Error while reading binary data!");
   fclose(in);
+  if (ctl->met_type == 2)
+    need_ctx(ctl);
+  if (ctl->met_type == 2 && !ctl->hip_met_packed) {
+    met_need_floats(met);     /* from here on the snapshot is what the MET_TYPE 1 reader leaves: floats in the members */
+    ((met_packed_t *) met->packed)->valid = 0;
+  }
   return 1;
 }
 
@@ -1494,12 +1686,15 @@ static void write_met_nc(const char *filename, const ctl_t *ctl, met_t *met);
 
 void mptrac_write_met(const char *filename, const ctl_t *ctl, met_t *met) {
   LOG(1, "Write meteo data: %s", filename);
+  if (met_is_packed(met) || ctl->met_type == 2)
+    need_ctx(ctl);
+  met_need_floats(met);
   if (ctl->met_type == 0) {
     write_met_nc(filename, ctl, met);
     return;
   }
-  if (ctl->met_type != 1)
-    ERRMSG("This build writes MET_TYPE 0 (netCDF, classic format) and 1 (raw binary) meteo files!");
+  if (ctl->met_type != 1 && ctl->met_type != 2)
+    ERRMSG("This build writes MET_TYPE 0 (netCDF, classic format), 1 (raw binary) and 2 (16-bit packed binary) meteo files!");
   FILE *out = fopen(filename, "w");
   REQUIRE(out, "Cannot create file!");
   const int head[2] = { ctl->met_type, 104 }, dims[3] = { met->nx, met->ny, met->np }, tail = 999;
@@ -1509,7 +1704,16 @@ void mptrac_write_met(const char *filename, const ctl_t *ctl, met_t *met) {
   put_items(out, met->lon, sizeof(double), (size_t) met->nx);
   put_items(out, met->lat, sizeof(double), (size_t) met->ny);
   put_items(out, met->p, sizeof(double), (size_t) met->np);
-  met_bin_body(out, 1, met);
+  if (ctl->met_type == 1)
+    met_bin_body(out, 1, met);
+  else {
+    float *buf;
+    if ((buf = malloc((size_t) met->nx * (size_t) met->ny * sizeof(float))) == NULL)
+      ERRMSG("Out of memory!");
+    met_bin_surface(out, 1, met, buf);
+    free(buf);
+    met_pck_write_levels(out, met);
+  }
   put_items(out, &tail, sizeof(int), 1);
   fclose(out);
 }
@@ -1971,7 +2175,8 @@ static void get_met_filename(const ctl_t *ctl, const double t, const int direct,
   else
     t6 = ceil(t / ctl->dt_met) * ctl->dt_met;
   jsec2time(t6, &year, &mon, &day, &hour, &min, &sec, &r);
-  sprintf(filename, "%s_%d_%02d_%02d_%02d.%s", ctl->metbase, year, mon, day, hour, ctl->met_type == 0 ? "nc" : "bin");
+  sprintf(filename, "%s_%d_%02d_%02d_%02d.%s", ctl->metbase, year, mon, day, hour,
+          ctl->met_type == 0 ? "nc" : ctl->met_type == 2 ? "pck" : "bin");
 }
 
 /* -------------------------------------------------------------------------- */
@@ -2136,8 +2341,25 @@ static void describe_met(met_t *met, mphip_met_t *out) {
   *out = m;
 }
 
+/* ... of a snapshot read from a MET_TYPE 2 file: every level field of the file that describe_met names goes as codes */
+static void describe_met_packed(met_t *met, mphip_met_packed_t *out) {
+  memset(out, 0, sizeof(*out));
+  describe_met(met, &out->base);
+  met_level_t level[MET_NLEVEL];
+  met_levels(met, level);
+  for (int k = 0; k < MET_NLEVEL; k++)
+    if (out->base.f3[level[k].id])
+      met_packed_field(met, k, out);
+}
+
 static void upload_met(met_t *met, int slot) {
   map_met_slot(met, slot);
+  if (met_is_packed(met)) {
+    mphip_met_packed_t pk;
+    describe_met_packed(met, &pk);
+    HIP(mphip_update_met_packed(g_ctx, slot, &pk));
+    return;
+  }
   mphip_met_t m;
   describe_met(met, &m);
   HIP(mphip_update_met(g_ctx, slot, &m));
@@ -2363,10 +2585,14 @@ static void poll_read_ahead(int wait) {
   pthread_join(g_ahead.thread, NULL);
   g_ahead.joined = 1;
   if (g_ahead.file_ok) {
-    mphip_met_t m;
-    describe_met(g_ahead.met, &m);
+    mphip_met_packed_t pk;
+    const int packed = met_is_packed(g_ahead.met);
+    if (packed)
+      describe_met_packed(g_ahead.met, &pk);
+    else
+      describe_met(g_ahead.met, &pk.base);
     flush_steps();
-    if (mphip_prefetch_met(g_ctx, &m) != 0) {
+    if ((packed ? mphip_prefetch_met_packed(g_ctx, &pk) : mphip_prefetch_met(g_ctx, &pk.base)) != 0) {
       WARN("Meteo read-ahead: %s", mphip_last_error(g_ctx));
     } else
       g_ahead.ok = 1;
@@ -2661,6 +2887,10 @@ static int grid_locate_irr(const double *xx, const int n, const double x) {
 
 double mptrac_amd_intpol_3d(const met_t *met0, const met_t *met1, size_t field_offset, const double ts,
                             const double p, const double lon, const double lat) {
+  /* (snapshots whose level fields are still codes: decoded now, once; the snapshots are the caller's met_t, const only
+   * in the reference's signature) */
+  met_need_floats((met_t *) met0);
+  met_need_floats((met_t *) met1);
   double lon2 = FMOD(lon, 360.);
   if (lon2 < met0->lon[0])
     lon2 += 360;

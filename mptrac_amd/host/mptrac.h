@@ -234,6 +234,9 @@ typedef struct {
                              values are refused */
   int hip_device_analysis;   /* HIP_DEVICE_ANALYSIS (default 1): the particle loops of the CSI, profile, sample and station
                                 outputs run on the device; 0: on particles downloaded in every time step */
+  int hip_met_packed;     /* HIP_MET_PACKED (default 1; read with MET_TYPE 2 only): the level fields of 16-bit packed meteo
+                             files go to the device as codes and are decoded there, the float members of met_t are filled
+                             on first use; 0: decoded into the members when the file is read, the MET_TYPE 1 path from there */
 } ctl_t;
 
 /* air parcels, as the reference (mptrac.h:3563-3583) */
@@ -323,6 +326,11 @@ typedef struct {
   float pl[EX][EY][EP], ul[EX][EY][EP], vl[EX][EY][EP], zetal[EX][EY][EP], zeta_dotl[EX][EY][EP];
   float wl[EX][EY][EP];   /* vertical velocity on model levels (ADVECT_VERT_COORD 2); with pl, ul, vl filled by the netCDF
                              reader from model-level files (MET_VERT_COORD 1) */
+  /* MET_TYPE 2: the level fields of the file as they were read -- 16-bit codes with their scales and offsets -- in a
+   * block this met_t owns (allocated by the first read, reused by the next read into the same met_t, freed by
+   * mptrac_free; NULL otherwise).  With HIP_MET_PACKED 1 the float level members above are filled from it on first use
+   * only (met_need_floats).  Appended: every earlier member keeps its offset. */
+  void *packed;
 } met_t;
 
 /* not used on the hot path; kept so that the reference's signatures hold */
@@ -405,6 +413,10 @@ long mptrac_amd_output_downloads(void);
  * intpol_met_time_3d returns (mptrac.c:3112-3137) -- for the few profile / sample points of the writers */
 double mptrac_amd_intpol_3d(const met_t *met0, const met_t *met1, size_t field_offset, double ts, double p,
                             double lon, double lat);
+/* The float level members (z, t, u, v, w, pv, h2o, o3, lwc, rwc, iwc, swc, cc) of a snapshot read from a MET_TYPE 2 file
+ * with HIP_MET_PACKED 1 are valid after this call: it decodes the codes on the device (mphip_unpack_met) the first time,
+ * and does nothing for any other snapshot.  Every host consumer of these members calls it first. */
+void met_need_floats(met_t *met);
 
 /* ---- one process per GPU (no reference counterpart) -------------------------- */
 /* The reference's driver binds MPI ranks to devices and gives every rank its own work directories
