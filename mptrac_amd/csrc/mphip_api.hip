@@ -15,6 +15,7 @@
 #include <thread>
 #include <vector>
 
+#include "mphip_buffers.hpp"
 #include "mphip_kernels.hpp"
 #include "mphip_metprep.hpp"
 #include "mphip_regrid.hpp"
@@ -43,8 +44,8 @@ const char *const kField3Name[MPHIP_N3D] = { "u", "v", "w", "t", "lwc", "rwc", "
 struct MetSlot {
   bool valid = false;
   double time = 0;
-  float *f3[MPHIP_N3D] = {};
-  float *f2[MPHIP_N2D] = {};
+  DevBuf<float> f3[MPHIP_N3D];
+  DevBuf<float> f2[MPHIP_N2D];
   bool has3[MPHIP_N3D] = {};
   bool has2[MPHIP_N2D] = {};
   std::vector<double> lon, lat, p;    // the snapshot's own axes: the reference interpolates on those of the current met0
@@ -65,26 +66,14 @@ struct MetSlot {
 struct PrepState {
   std::mutex lock;
   hipStream_t stream = nullptr;
-  int profile_phase = 0;              // option "derive_profile_phase": what mphip_profile_begin / _end time of a call
-  struct Buf {
-    char *p = nullptr;
-    size_t bytes = 0;
-  };
-  std::vector<Buf> pool;
+  std::vector<DevBuf<char>> pool;
   size_t taken = 0;                   // buffers of the pool the call in progress has taken
-  void release() {
-    for (Buf &b : pool)
-      if (b.p)
-        (void) hipFree(b.p);
-    pool.clear();
-    if (stream)
-      (void) hipStreamDestroy(stream);
-    stream = nullptr;
-  }
 };
 
 }   // namespace
 
+// Every device or page-locked array below is a DevBuf / PinnedBuf (mphip_buffers.hpp): it owns its memory and its
+// capacity, so `delete ctx` frees them all and no capacity is kept beside a pointer.
 struct mphip_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -93,16 +82,16 @@ struct mphip_ctx {
 
   mphip_ctl_t ctl;
   bool have_ctl = false;
-  DevClim *d_clim = nullptr;
+  DevBuf<DevClim> d_clim;
   DevClim h_clim = {};               // host copy of *d_clim (DevMet::strat_skip)
   bool have_clim = false;
-  double *d_zm[MPHIP_NZM] = {};      // zonal-mean climatologies: [time | p | lat | vmr] each
+  DevBuf<double> d_zm[MPHIP_NZM];    // zonal-mean climatologies: [time | p | lat | vmr] each
   DevZm zm[MPHIP_NZM] = {};
-  double *d_ts[MPHIP_NTR] = {};      // trace-gas time series: [time | vmr] each
+  DevBuf<double> d_ts[MPHIP_NTR];    // trace-gas time series: [time | vmr] each
   DevTracerSeries h_tracers = {};    // host copy of *d_tracers
-  DevTracerSeries *d_tracers = nullptr;
+  DevBuf<DevTracerSeries> d_tracers;
 
-  // meteo
+  // ---- meteo ----
   MetSlot slot[2];
   int flip = 0;                       // logical slot s lives in slot[s ^ flip]
   MetSlot next;                       // snapshot being uploaded ahead of time (mphip_prefetch_met)
@@ -112,177 +101,131 @@ struct mphip_ctx {
   hipEvent_t main_mark = nullptr;     // copies into `next` start after the kernels queued so far (they may read its arrays)
   // mphip_update_met_packed / mphip_prefetch_met_packed: where a field's {scl | off | codes} wait for met_unpack_kernel,
   // one buffer per stream ([0] stream, [1] copy_stream), sized for the largest field and reused in stream order; grow-only,
-  // freed with the slot arrays on a new grid and by mphip_destroy
-  struct CodeBuf {
-    char *p = nullptr;
-    size_t bytes = 0;
-  } codes[2];
-  // module_meteo only writes quantities nothing on the device reads: its launch is deferred until someone
-  // can see the result (a download, gridded output, a single-module call) or its inputs change; a pending
-  // launch that the next time step would overwrite unseen is dropped
-  bool fuse_sort = true;              // module_sort's gather of time, p, lon, lat inside the following step launch
-  const int *fused_perm = nullptr;    // set by do_sort, consumed by the next launch_step
-  bool fuse_quantities = true;        // ... which then moves the quantity arrays too (option fuse_sort_quantities)
-  bool fused_quantities = false;
-  const int *fold_perm = nullptr;     // the locality re-sort's permutation, handed to the multi-step launch that follows
-                                      // it inside one mphip_run_timesteps iteration (DevAtm::perm_all)
-  bool lazy_meteo = true;
-  bool meteo_pending = false;
-  bool pin_host_atm = false;          // page-lock the caller's particle arrays (persistent atm_t of a C caller only)
-  // One page-locked span of caller memory (option pin_host_atm: the particle arrays of a persistent atm_t,
-  // which lie next to each other in one allocation); released by mphip_destroy.
-  std::vector<std::pair<uintptr_t, uintptr_t>> pinned;
-  std::mutex pinned_lock;
+  // released with the slot arrays on a new grid
+  DevBuf<char> codes[2];
   std::thread uploader;               // mphip_prefetch_met: issues the (blocking, pageable) copies beside the stepping thread
   int uploader_rc = 0;
   std::atomic<bool> uploader_done{ false };
   std::string uploader_err;
   int nx = 0, ny = 0, npl = 0, coord_type = 0;   // npl: pressure levels (met_t::np)
   int nml = 0;                                    // model levels (met_t::npl), 0 = none uploaded
+  std::vector<double> h_lon, h_lat, h_p;
+  DevBuf<double> d_axes;              // axes blob (layout: DevMet::axes)
+  int lut_base = 0, lut_size = 0;
+  size_t axes_bytes = 0;
+  bool told_shortcuts_off = false;    // mphip_update_met's note about a nearly periodic longitude axis was printed
+  // module_meteo only writes quantities nothing on the device reads: its launch is deferred until someone
+  // can see the result (a download, gridded output, a single-module call) or its inputs change; a pending
+  // launch that the next time step would overwrite unseen is dropped
+  bool lazy_meteo = true;
+  bool meteo_pending = false;
+
+  // ---- packed grids ----
   // Packed two-snapshot grids (layouts: mphip_device.hpp).  `pk` is the set the kernels read; `pk_next` is
   // built beside the time steps from (met1, prefetched snapshot) on the copy stream and trades places with it
   // in mphip_commit_met, so that a hand-over costs the stepping stream nothing.
   struct PackedGrids {
-    float *wind = nullptr, *temp = nullptr, *h2o = nullptr;
-    float *mlw = nullptr, *zl2 = nullptr, *pl2 = nullptr;   // model levels: {ul,vl,zeta_dot|wl}, {zetal}, {pl} pairs
-    f32x4 *mx = nullptr, *mx2 = nullptr;                      // level / surface pair records of module_meteo
-    f32x4 *cloud = nullptr, *sfa = nullptr, *sfb = nullptr, *sfc = nullptr, *sfd = nullptr;
-    f32x4 *cp2 = nullptr;                                     // {cape,pel} pair records (module_convection)
-    int *ml_mono = nullptr;                                   // cleared by the pack kernel if a height column is not monotonic
+    DevBuf<float> wind, temp, h2o;
+    DevBuf<float> mlw, zl2, pl2;      // model levels: {ul,vl,zeta_dot|wl}, {zetal}, {pl} pairs
+    DevBuf<f32x4> mx, mx2;            // level / surface pair records of module_meteo
+    DevBuf<f32x4> cloud, sfa, sfb, sfc, sfd;
+    DevBuf<f32x4> cp2;                // {cape,pel} pair records (module_convection)
+    DevBuf<int> ml_mono;              // cleared by the pack kernel if a height column is not monotonic
     bool ml_monotonic = false;
     // module_diff_meso's wind deviations per raw cell (DevMet::meso), a function of `wind` alone: valid for exactly the
     // records it was built from (pack_launch, which writes `wind`, voids or rebuilds it; ensure_meso_table builds it for a
     // set packed while the module was off).  Allocated only in a context whose control parameters switch the module on.
-    float *meso = nullptr;
+    DevBuf<float> meso;
     bool meso_valid = false;
-    void release() {
-      for (void *q : { (void *) wind, (void *) temp, (void *) h2o, (void *) mlw, (void *) zl2, (void *) pl2, (void *) mx,
-                       (void *) mx2, (void *) cloud, (void *) sfa, (void *) sfb, (void *) sfc, (void *) sfd, (void *) cp2,
-                       (void *) ml_mono, (void *) meso })
-        if (q)
-          (void) hipFree(q);
-      *this = PackedGrids();
-    }
   };
   PackedGrids pk, pk_next;
   bool pk_next_valid = false;         // pk_next holds (met1, prefetched snapshot), packed with the control parameters of then
-  std::vector<double> h_lon, h_lat, h_p;
-  double *d_axes = nullptr;           // axes blob (layout: DevMet::axes)
-  int lut_base = 0, lut_size = 0;
-  size_t axes_bytes = 0;
   bool packed_dirty = true;
 
-  // particles
-  long long np = 0, ip0 = 0, np_total = 0, cap = 0;
+  // ---- particles ----
+  long long np = 0, ip0 = 0, np_total = 0;
   int nq = 0;
-  double *d_arr[4 + MPHIP_NQ_MAX] = {};   // time, p, lon, lat, q[*]
-  double *d_alt[4 + MPHIP_NQ_MAX] = {};   // gather targets (ping-pong)
-  float *d_uvwp[3] = {};
-  float *d_uvwp_alt[3] = {};
-  double *d_dt = nullptr;
-  double *d_dt_alt = nullptr;
+  DevBuf<double> d_arr[4 + MPHIP_NQ_MAX];   // time, p, lon, lat, q[*]
+  DevBuf<double> d_alt[4 + MPHIP_NQ_MAX];   // gather targets (ping-pong)
+  DevBuf<float> d_uvwp[3], d_uvwp_alt[3];
+  DevBuf<double> d_dt, d_dt_alt;
   uint64_t rng_ctr = 0;
-  double *d_iso = nullptr, *d_iso_alt = nullptr;   // cache->iso_var (allocated on first use)
-  int *d_kz = nullptr, *d_kz_alt = nullptr;        // model-level search hint per particle (allocated on first use)
-  double *d_iso_ts = nullptr, *d_iso_ps = nullptr; // balloon time series (ISOSURF 4)
+  DevBuf<double> d_iso, d_iso_alt;          // cache->iso_var (allocated on first use)
+  DevBuf<int> d_kz, d_kz_alt;               // model-level search hint per particle (allocated on first use)
+  DevBuf<double> d_iso_ts, d_iso_ps;        // balloon time series (ISOSURF 4)
   int iso_n = 0;
+  // One page-locked span of caller memory (option pin_host_atm: the particle arrays of a persistent atm_t,
+  // which lie next to each other in one allocation); released by mphip_destroy.
+  std::vector<std::pair<uintptr_t, uintptr_t>> pinned;
+  std::mutex pinned_lock;
 
+  // ---- locality order ----
   // internal locality order: particles are stored sorted by meteo grid cell;
   // d_ext[i] is the external slot (the reference's ip) of stored particle i
-  int *d_ext = nullptr, *d_ext_alt = nullptr;
+  DevBuf<int> d_ext, d_ext_alt;
   bool ext_identity = true;
-  int locality_interval = 60;         // re-sort every this many steps (0 = keep the caller's order)
-  double *d_rec = nullptr;            // mphip_grid_sums: the quantities as one record per particle (GridVals::rec)
-  size_t rec_cap = 0;
-  bool grid_records = true;
-  int chain_blocks = 0;               // workgroups of the chain walk of the ordered sums (0: default; tuning)
-  double *h_sums = nullptr;           // page-locked staging of mphip_grid_sums
-  size_t h_sums_cap = 0;
-  double *d_grid_kernel = nullptr;    // GRID_KERNEL: kz[nk] | kw[nk] (mphip_set_grid_kernel)
-  // analysis outputs (mphip_box_sums, mphip_sample_obs, mphip_station_hits)
-  double *d_ana_kernel = nullptr;     // the call's weighting function: kz[nk] | kw[nk]
-  size_t ana_kernel_cap = 0;
-  uint32_t *d_marks = nullptr;        // counts per external index (np + 1), then their scan; chunk offsets behind them
-  size_t marks_cap = 0;
-  int *d_slot_of = nullptr;           // station: where the particle of an external index is stored
-  size_t slot_of_cap = 0;
-  uint32_t *d_ana_flags = nullptr;    // [bad member | records (scan) | records (64-bit sum, 2 words)]
-  int grid_nk = 0;
-  bool locality_zorder = false;       // tiles of the locality key numbered along a Z-order curve instead of row by row
-  int locality_tile = 0;              // horizontal tile edge of the locality key (columns); 0 = 4, or 8 with model-level winds
-  int step_blocks = 8192;             // upper bound of the step kernel's grid
-  int step_blocks_multi = 32768;       // ... of a multi-step launch (mphip_run_timesteps)
-  int xcd_map = 1;
-  int big_grid = 0;                   // option "big_grid": take the 64-bit-offset (kBigGrid) instantiations on a grid that fits 32 bits too (tests)
-  int perm_records = 1;               // random permutations of the particle arrays through records (permute_random)
-  void *d_prec = nullptr;             // ... their buffer
-  size_t prec_cap = 0;
-  int multi_step = 64;                // mphip_run_timesteps: most time steps per launch (0 = always one by one)
-  bool fold_resort = true;            // ... and a launch that follows the locality re-sort does its gather (0: a pass of its own)
-  bool turb_strat = true;             // module_diff_turb's short path above every tropopause (DevMet::strat_skip; 0: never taken)
-  bool force_generic = false;
-  bool compact_depo = true;           // deposition-only launches through depo_kernel (0: the fused kernel's tail)
-  int sort_bits = 0;                  // digit width of the radix sort (0 = fewest passes; 8, 9, 10: tuning / tests)
   int steps_since_resort = 1 << 30;
+  const int *fold_perm = nullptr;     // the locality re-sort's permutation, handed to the multi-step launch that follows
+                                      // it inside one mphip_run_timesteps iteration (DevAtm::perm_all)
+  DevBuf<f32x4u> d_prec;              // permute_random: one record per particle (option perm_records)
 
-  // sort
-  uint32_t *d_keys[2] = {};
-  int *d_vals[2] = {};
-  uint32_t *d_counts = nullptr;
-  size_t counts_cap = 0;
+  // ---- sort / repair / sort ahead ----
+  DevBuf<uint32_t> d_keys[2];
+  DevBuf<int> d_vals[2];
+  DevBuf<uint32_t> d_counts;
   int sorted_buf = -1;                // which d_keys/d_vals pair holds the last result
+  const int *fused_perm = nullptr;    // set by do_sort, consumed by the next launch_step
+  bool fused_quantities = false;      // ... which then moves the quantity arrays too (option fuse_sort_quantities)
   // module_sort as a repair of the previous order (repair_* kernels): valid while the particles are stored in the order
   // of the last module_sort (stored_is_sorted) -- its sorted keys are then non-decreasing along the slots
-  // option "lds_tile": cells of the LDS wind tile of traj_tile_kernel (0: off); runs of pure trajectory steps only
-  int lds_tile = 0;
-  bool emit_keys = true;              // option "emit_keys": the launch that moves the particles writes the keys of the sort ahead
-  unsigned char *d_depo_busy = nullptr;   // EmitKeys::depo_busy (np bytes) ...
-  long long depo_busy_cap = 0;
-  bool told_shortcuts_off = false;    // mphip_update_met's note about a nearly periodic longitude axis was printed
-  bool depo_busy_valid = false;       // ... written by the last launch and not yet used by the deposition launch of its step
-  bool sort_repair = true;            // option "sort_repair"
-  bool ahead_priority = false;        // option "ahead_priority": the stream of the sort ahead at the highest priority (C5: no difference, profiles/r05_variants.txt item 3)
   bool stored_is_sorted = false;
   long long sorted_n = 0;
-  uint32_t *rep_sk = nullptr, *rep_mk[2] = {}, *rep_fk = nullptr, *rep_tiles = nullptr, *rep_nm = nullptr;
-  int *rep_si = nullptr, *rep_mi[2] = {}, *rep_fv = nullptr;
-  long long rep_cap = 0;
+  DevBuf<uint32_t> rep_sk, rep_mk[2], rep_fk, rep_tiles, rep_nm;
+  DevBuf<int> rep_si, rep_mi[2], rep_fv;
   // module_sort of the NEXT time step, started beside the rest of this one (option "sort_ahead"): once the launch
   // that moves the particles has run, their positions are final for this step -- module_mixing and the deposition
   // modules only change quantities -- so the keys and the radix sort of the next step's module_sort (and its
   // module_timesteps) can run on a second stream, into buffers of their own, while the main stream does the
   // rest of the step.  The next mphip_run_timestep takes the result if it is called with the expected time and
   // nothing touched the particles, the grids or the control parameters in between; otherwise it is dropped.
-  bool sort_ahead = true;
-  bool ahead_box = true;              // the key kernel of the sort ahead also writes module_mixing's box index (0: own kernel; 2.26 vs 2.29 ms on C5)
+  // The buffers trade places with d_keys / d_vals / d_counts / d_dt around the sort (ahead_swap_buffers).
   hipStream_t ahead_stream = nullptr;
   hipEvent_t ahead_mark = nullptr, ahead_done = nullptr;
-  uint32_t *ahead_keys[2] = {};
-  int *ahead_vals[2] = {};
-  uint32_t *ahead_counts = nullptr;
-  size_t ahead_counts_cap = 0;
-  double *ahead_dt = nullptr;
-  long long ahead_cap = 0;
+  DevBuf<uint32_t> ahead_keys[2];
+  DevBuf<int> ahead_vals[2];
+  DevBuf<uint32_t> ahead_counts;
+  DevBuf<double> ahead_dt;
   bool ahead_valid = false;
   double ahead_t = 0;
   int ahead_cur = 0;
+  DevBuf<unsigned char> d_depo_busy;               // EmitKeys::depo_busy (np bytes) ...
+  bool depo_busy_valid = false;                    // ... written by the last launch, not yet used by its step's deposition launch
+  const unsigned char *depo_busy_last = nullptr;   // ... as the step's deposition launch has just used it
+  unsigned depo_busy_last_mask = 0;                // ... and the deposition modules it was decided for
 
-  // mixing / grid sums
-  int *d_cell = nullptr;
-  double *d_sums = nullptr;
-  size_t sums_cap = 0;
+  // ---- mixing and sums ----
+  DevBuf<int> d_cell;
+  DevBuf<double> d_sums;
+  DevBuf<int> d_cnt;                  // particles per mixing cell (32-bit: the reference's `int count[]`)
+  DevBuf<unsigned long long> d_lists; // work space of the ordered sums (sequence, runs, sort buffers)
+  DevBuf<double> d_rec;               // mphip_grid_sums: the quantities as one record per particle (GridVals::rec)
+  PinnedBuf<double> h_sums;           // page-locked staging of mphip_grid_sums and of the analysis outputs
+  DevBuf<double> d_grid_kernel;       // GRID_KERNEL: kz[nk] | kw[nk] (mphip_set_grid_kernel)
+  int grid_nk = 0;
 
-  int *d_cnt = nullptr;               // particles per mixing cell (32-bit: the reference's `int count[]`)
+  // ---- chemistry ----
   // module_chem_grid: [press nz | area ny | lon nx | lat ny] of the chemistry grid, built by mphip_update_ctl with the
   // C library's exp and cos when the grid is due and valid (chemgrid_ok)
-  double *d_chemgrid = nullptr;
+  DevBuf<double> d_chemgrid;
   bool chemgrid_ok = false;
   double h2o2_low = 0;                // module_h2o2_chem: pow(1 / a, 1 / b) of the host's C library
   // module_tracer_chem: the photolysis rates, [p | sza | o3c | (pad) | PhotoRec rec[np][nsza][no3c]]
   // (mphip_update_clim_photo); photo_have[k]: the table of trace gas k (MPHIP_TR_CCL4 ... MPHIP_TR_N2O) was given
-  double *d_photo = nullptr;
+  DevBuf<double> d_photo;
   DevPhoto photo = {};
   bool photo_have[4] = {};
+
+  // ---- radio ----
   // module_radio_decay (mphip_set_radio_decay): the activities (-1: absent; module_mixing mixes the present ones) and the
   // switch of the time step
   RadioQnt radio = { { -1, -1, -1, -1, -1, -1 } };
@@ -292,36 +235,67 @@ struct mphip_ctx {
   // grid) and the time it is valid for (rdepo_have_t: one is known)
   bool rdepo_on = false;
   mphip_box_t rdepo_grid = {};
-  double *d_rdepo_inv = nullptr;
+  DevBuf<double> d_rdepo_inv;
   size_t rdepo_ntot = 0;
   bool rdepo_have_t = false;
   double rdepo_t = 0;
-  const unsigned char *depo_busy_last = nullptr;   // EmitKeys::depo_busy as the step's deposition launch has just used it
-  unsigned depo_busy_last_mask = 0;                // ... and the deposition modules it was decided for
-  // exchange of the occupied levels only (exchange_occupied_levels): per-level occupancy, the dense band, what was found
-  // option "mix_exchange_levels" (default 0): measured with a one-rank communicator, the band costs 0.14 ms per step (the
-  // host reads the occupancy: the one synchronisation in the step path; pack / unpack) against a MODELLED saving of
-  // 0.15-0.2 ms on eight GPUs -- undecidable without xGMI, so the whole-grid all-reduce stays the default
-  bool mix_exchange_levels = false;
-  double *d_occ = nullptr, *h_occ = nullptr, *d_band = nullptr;
-  int *d_band_cnt = nullptr;
-  size_t band_cap = 0;
-  int mix_band_lo = -1, mix_band_hi = -1;
-  size_t cnt_cap = 0;
-  int deterministic_sums = 1;         // cell sums in the reference's serial order (0: floating-point atomics)
-  int sum_path = 0;                   // ordered sums: 0 = by crowding, 1 = groups of cells per wave, 2 = a lane per (cell, value)
-  unsigned long long *d_lists = nullptr;   // work space of the ordered sums (sequence, runs, sort buffers)
-  size_t lists_cap = 0;
 
+  // ---- analysis outputs (mphip_box_sums, mphip_sample_obs, mphip_station_hits) ----
+  DevBuf<double> d_ana_kernel;        // the call's weighting function: kz[nk] | kw[nk]
+  DevBuf<uint32_t> d_marks;           // counts per external index (np + 1), then their scan; chunk offsets behind them
+  DevBuf<int> d_slot_of;              // station: where the particle of an external index is stored
+  DevBuf<uint32_t> d_ana_flags;       // [bad member | records (scan) | records (64-bit sum, 2 words)]
+
+  // ---- exchange ----
   mphip_allreduce_fn allreduce = nullptr;
   void *allreduce_user = nullptr;
   void *comm = nullptr;               // RCCL communicator (ncclComm_t) of mphip_comm_init, NULL = single rank / hook
   int comm_ranks = 1, comm_rank = 0;
+  // exchange of the occupied levels only (exchange_occupied_levels): per-level occupancy on the device and for the host,
+  // the dense band of the sums and of the counts, what was found
+  DevBuf<double> d_occ, d_band;
+  PinnedBuf<double> h_occ;
+  DevBuf<int> d_band_cnt;
+  int mix_band_lo = -1, mix_band_hi = -1;
 
-  // mphip_derive_met, mphip_regrid_met, mphip_detrend_met: their stream, lock and scratch (released by mphip_destroy)
+  // mphip_derive_met, mphip_regrid_met, mphip_detrend_met: their stream, lock and scratch
   PrepState prep;
 
-  // profiling of the fused step kernel
+  // ---- options (mphip_set_option; documented in include/mptrac_hip.h) ----
+  int locality_interval = 60;         // re-sort every this many steps (0 = keep the caller's order)
+  bool locality_zorder = false;       // tiles of the locality key numbered along a Z-order curve instead of row by row
+  int locality_tile = 0;              // horizontal tile edge of the locality key (columns); 0 = 4, or 8 with model-level winds
+  int step_blocks = 8192;             // upper bound of the step kernel's grid
+  int step_blocks_multi = 32768;      // ... of a multi-step launch (mphip_run_timesteps)
+  bool xcd_map = true;
+  bool big_grid = false;              // take the 64-bit-offset (kBigGrid) instantiations on a grid that fits 32 bits too (tests)
+  bool force_generic = false;         // "generic_kernel"
+  int multi_step = 64;                // mphip_run_timesteps: most time steps per launch (0 = always one by one)
+  bool fold_resort = true;            // ... and a launch that follows the locality re-sort does its gather (0: a pass of its own)
+  int lds_tile = 0;                   // cells of the LDS wind tile of traj_tile_kernel (0: off); runs of pure trajectory steps only
+  bool turb_strat = true;             // module_diff_turb's short path above every tropopause (DevMet::strat_skip; 0: never taken)
+  bool compact_depo = true;           // deposition-only launches through depo_kernel (0: the fused kernel's tail)
+  bool pin_host_atm = false;          // page-lock the caller's particle arrays (persistent atm_t of a C caller only)
+  bool perm_records = true;           // random permutations of the particle arrays through records (permute_random)
+  bool fuse_sort = true;              // module_sort's gather of time, p, lon, lat inside the following step launch
+  bool fuse_quantities = true;        // "fuse_sort_quantities": ... which then moves the quantity arrays too
+  int sort_bits = 0;                  // digit width of the radix sort (0 = fewest passes; 8, 9, 10: tuning / tests)
+  bool sort_repair = true;
+  bool sort_ahead = true;
+  bool ahead_box = true;              // the key kernel of the sort ahead also writes module_mixing's box index (0: own kernel; 2.26 vs 2.29 ms on C5)
+  bool ahead_priority = false;        // the stream of the sort ahead at the highest priority (C5: no difference, profiles/r05_variants.txt item 3)
+  bool emit_keys = true;              // the launch that moves the particles writes the keys of the sort ahead
+  int deterministic_sums = 1;         // cell sums in the reference's serial order (0: floating-point atomics)
+  int sum_path = 0;                   // ordered sums: 0 = by crowding, 1 = groups of cells per wave, 2 = a lane per (cell, value)
+  bool grid_records = true;
+  int chain_blocks = 0;               // workgroups of the chain walk of the ordered sums (0: default; tuning)
+  // (default 0): measured with a one-rank communicator, the band costs 0.14 ms per step (the host reads the occupancy:
+  // the one synchronisation in the step path; pack / unpack) against a MODELLED saving of 0.15-0.2 ms on eight GPUs --
+  // undecidable without xGMI, so the whole-grid all-reduce stays the default
+  bool mix_exchange_levels = false;
+  int derive_profile_phase = 0;       // what mphip_profile_begin / _end time of a preprocessing call
+
+  // ---- profiling of the fused step kernel ----
   bool prof = false;
   std::vector<hipEvent_t> ev;         // start/stop pairs
   size_t ev_used = 0;
@@ -344,22 +318,12 @@ int fail(mphip_ctx *ctx, const std::string &msg) {
       return fail(ctx, std::string(#call) + ": " + hipGetErrorString(e_));                   \
   } while (0)
 
+// the raw pointers of a pair of buffers, as radix_passes takes them
 template <typename T>
-int dev_alloc(mphip_ctx *ctx, T **p, size_t n) {
-  if (*p) {
-    HIPCHK(hipFree(*p));
-    *p = nullptr;
-  }
-  if (n) {
-    HIPCHK(hipMalloc((void **) p, n * sizeof(T)));
-  }
-  return 0;
-}
-
-void dev_free(void *p) {
-  if (p)
-    (void) hipFree(p);
-}
+struct RawPair {
+  T *q[2];
+  explicit RawPair(DevBuf<T> (&b)[2]) : q{ b[0].p, b[1].p } {}
+};
 
 int grid_for(long long n, int block = 256, int maxb = 8192) {
   long long b = (n + block - 1) / block;
@@ -372,37 +336,37 @@ int grid_for(long long n, int block = 256, int maxb = 8192) {
 
 DevAtm dev_atm(const mphip_ctx *c) {
   DevAtm a;
-  a.time = c->d_arr[0];
-  a.p = c->d_arr[1];
-  a.lon = c->d_arr[2];
-  a.lat = c->d_arr[3];
+  a.time = c->d_arr[0].p;
+  a.p = c->d_arr[1].p;
+  a.lon = c->d_arr[2].p;
+  a.lat = c->d_arr[3].p;
   for (int iq = 0; iq < MPHIP_NQ_MAX; iq++)
-    a.q[iq] = iq < c->nq ? c->d_arr[4 + iq] : nullptr;
-  a.up = c->d_uvwp[0];
-  a.vp = c->d_uvwp[1];
-  a.wp = c->d_uvwp[2];
-  a.dt = c->d_dt;
-  a.ext = c->ext_identity ? nullptr : c->d_ext;
-  a.iso = c->d_iso;
-  a.kz = c->d_kz;
-  a.iso_ts = c->d_iso_ts;
-  a.iso_ps = c->d_iso_ps;
+    a.q[iq] = iq < c->nq ? c->d_arr[4 + iq].p : nullptr;
+  a.up = c->d_uvwp[0].p;
+  a.vp = c->d_uvwp[1].p;
+  a.wp = c->d_uvwp[2].p;
+  a.dt = c->d_dt.p;
+  a.ext = c->ext_identity ? nullptr : c->d_ext.p;
+  a.iso = c->d_iso.p;
+  a.kz = c->d_kz.p;
+  a.iso_ts = c->d_iso_ts.p;
+  a.iso_ps = c->d_iso_ps.p;
   a.iso_n = c->iso_n;
   a.perm = c->fold_perm ? c->fold_perm : c->fused_perm;
-  a.s_time = c->d_alt[0];
-  a.s_p = c->d_alt[1];
-  a.s_lon = c->d_alt[2];
-  a.s_lat = c->d_alt[3];
+  a.s_time = c->d_alt[0].p;
+  a.s_p = c->d_alt[1].p;
+  a.s_lon = c->d_alt[2].p;
+  a.s_lat = c->d_alt[3].p;
   a.nq_perm = c->fold_perm || (c->fused_perm && c->fused_quantities) ? c->nq : 0;
   a.perm_all = c->fold_perm ? 1 : 0;   // (locality_sort_apply: the pre-sort arrays are the alternates)
-  a.s_up = c->d_uvwp_alt[0];
-  a.s_vp = c->d_uvwp_alt[1];
-  a.s_wp = c->d_uvwp_alt[2];
-  a.s_dt = c->d_dt_alt;
-  a.s_ext = c->d_ext_alt;
-  a.ext_out = c->d_ext;
+  a.s_up = c->d_uvwp_alt[0].p;
+  a.s_vp = c->d_uvwp_alt[1].p;
+  a.s_wp = c->d_uvwp_alt[2].p;
+  a.s_dt = c->d_dt_alt.p;
+  a.s_ext = c->d_ext_alt.p;
+  a.ext_out = c->d_ext.p;
   for (int iq = 0; iq < MPHIP_NQ_MAX; iq++)
-    a.s_q[iq] = iq < c->nq ? c->d_alt[4 + iq] : nullptr;
+    a.s_q[iq] = iq < c->nq ? c->d_alt[4 + iq].p : nullptr;
   a.np = c->np;
   a.ip0 = c->ip0;
   a.np_total = c->np_total;
@@ -451,29 +415,29 @@ static double clim_tropo_min(const DevClim &h) {
 
 DevMet dev_met(const mphip_ctx *c) {
   DevMet M;
-  M.wind = c->pk.wind;
-  M.temp = c->pk.temp;
-  M.cloud = c->pk.cloud;
-  M.mx = c->pk.mx;
-  M.mx2 = c->pk.mx2;
-  M.sfa = c->pk.sfa;
-  M.sfb = c->pk.sfb;
-  M.cp2 = c->pk.cp2;
-  M.sfc = c->pk.sfc;
-  M.sfd = c->pk.sfd;
-  M.h2o = c->pk.h2o;
-  M.mlw = c->pk.mlw;
-  M.zl2 = c->pk.zl2;
-  M.pl2 = c->pk.pl2;
-  M.meso = c->pk.meso_valid ? c->pk.meso : nullptr;
+  M.wind = c->pk.wind.p;
+  M.temp = c->pk.temp.p;
+  M.cloud = c->pk.cloud.p;
+  M.mx = c->pk.mx.p;
+  M.mx2 = c->pk.mx2.p;
+  M.sfa = c->pk.sfa.p;
+  M.sfb = c->pk.sfb.p;
+  M.cp2 = c->pk.cp2.p;
+  M.sfc = c->pk.sfc.p;
+  M.sfd = c->pk.sfd.p;
+  M.h2o = c->pk.h2o.p;
+  M.mlw = c->pk.mlw.p;
+  M.zl2 = c->pk.zl2.p;
+  M.pl2 = c->pk.pl2.p;
+  M.meso = c->pk.meso_valid ? c->pk.meso.p : nullptr;
   M.meso_nty = (c->ny + 2) / 4;   // (ny - 1 cells in bricks of four, rounded up)
   M.ml_monotonic = c->pk.ml_monotonic ? 1 : 0;
   for (int t = 0; t < 2; t++) {
-    M.zl[t] = c->slot[t ^ c->flip].f3[MPHIP_ZETAL];
-    M.pll[t] = c->slot[t ^ c->flip].f3[MPHIP_PL];
+    M.zl[t] = c->slot[t ^ c->flip].f3[MPHIP_ZETAL].p;
+    M.pll[t] = c->slot[t ^ c->flip].f3[MPHIP_PL].p;
   }
   M.npl = c->nml;
-  M.axes = c->d_axes;
+  M.axes = c->d_axes.p;
   M.lut_base = c->lut_base;
   M.lut_size = c->lut_size;
   M.lat_x0 = c->h_lat[0];
@@ -644,15 +608,14 @@ int upload_axes(mphip_ctx *ctx) {
     inv[nx + ny + i] = 1.0 / (ctx->h_p[i + 1] - ctx->h_p[i]);
   if (!lut.empty())
     memcpy(b + nd, lut.data(), lut.size() * sizeof(int16_t));
-  if (dev_alloc(ctx, &ctx->d_axes, blob.size()))
-    return 1;
-  HIPCHK(hipMemcpyAsync(ctx->d_axes, blob.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx->d_axes.resize(blob.size()));
+  HIPCHK(hipMemcpyAsync(ctx->d_axes.p, blob.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   ctx->axes_bytes = bytes;
   return 0;
 }
 
-// arrays of a packed set for the fields the two snapshots carry (allocated on first need; hipMalloc, so
+// arrays of a packed set for the fields the two snapshots carry (allocated on first need; an allocation, so
 // called from the stepping thread only)
 struct PackPlan {
   bool cloud = false, ml = false, pbl = false, mx = false, mx2 = false, ml_heights = false, coord2 = false;
@@ -698,35 +661,39 @@ PackPlan pack_plan(const mphip_ctx *ctx, const MetSlot &s0, const MetSlot &s1) {
 int pack_alloc(mphip_ctx *ctx, mphip_ctx::PackedGrids &K, const PackPlan &P) {
   const size_t ncell = (size_t) ctx->nx * ctx->ny * ctx->npl, ncol = (size_t) ctx->nx * ctx->ny;
   const size_t ncell_ml = (size_t) ctx->nx * ctx->ny * ctx->nml;
-  if (P.ml && !K.mlw
-      && (dev_alloc(ctx, &K.mlw, 6 * ncell_ml) || dev_alloc(ctx, &K.zl2, 2 * ncell_ml) || dev_alloc(ctx, &K.pl2, 2 * ncell_ml)))
-    return 1;
-  if (!K.ml_mono && dev_alloc(ctx, &K.ml_mono, 1))
-    return 1;
-  if (!K.wind && (dev_alloc(ctx, &K.wind, 6 * ncell) || dev_alloc(ctx, &K.temp, 2 * ncell)))
-    return 1;
-  if (P.meso && !K.meso && dev_alloc(ctx, &K.meso, meso_table_floats(ctx)))
-    return 1;
-  if (!K.cp2 && dev_alloc(ctx, &K.cp2, ncol))
-    return 1;
-  if (!K.sfa && (dev_alloc(ctx, &K.sfa, ncol) || dev_alloc(ctx, &K.sfb, 2 * ncol) || dev_alloc(ctx, &K.sfc, 2 * ncol)))
-    return 1;
-  if (P.cloud && !K.cloud && dev_alloc(ctx, &K.cloud, 2 * ncell))
-    return 1;
-  if (P.mx && !K.mx && dev_alloc(ctx, &K.mx, 2 * ncell))
-    return 1;
-  if (P.mx2 && !K.mx2 && dev_alloc(ctx, &K.mx2, 7 * ncol))
-    return 1;
-  if (P.pbl && !K.sfd && (dev_alloc(ctx, &K.sfd, 2 * ncol) || dev_alloc(ctx, &K.h2o, 2 * ncell)))
-    return 1;
+  // (a set is released on a new grid, so every size below is the only one its array ever has: reserve = first need)
+  if (P.ml) {
+    HIPCHK(K.mlw.reserve(6 * ncell_ml));
+    HIPCHK(K.zl2.reserve(2 * ncell_ml));
+    HIPCHK(K.pl2.reserve(2 * ncell_ml));
+  }
+  HIPCHK(K.ml_mono.reserve(1));
+  HIPCHK(K.wind.reserve(6 * ncell));
+  HIPCHK(K.temp.reserve(2 * ncell));
+  if (P.meso)
+    HIPCHK(K.meso.reserve(meso_table_floats(ctx)));
+  HIPCHK(K.cp2.reserve(ncol));
+  HIPCHK(K.sfa.reserve(ncol));
+  HIPCHK(K.sfb.reserve(2 * ncol));
+  HIPCHK(K.sfc.reserve(2 * ncol));
+  if (P.cloud)
+    HIPCHK(K.cloud.reserve(2 * ncell));
+  if (P.mx)
+    HIPCHK(K.mx.reserve(2 * ncell));
+  if (P.mx2)
+    HIPCHK(K.mx2.reserve(7 * ncol));
+  if (P.pbl) {
+    HIPCHK(K.sfd.reserve(2 * ncol));
+    HIPCHK(K.h2o.reserve(2 * ncell));
+  }
   return 0;
 }
 
-// the table of set K from its wind records, on `stream` (K.meso allocated; no hipMalloc, no use of ctx->err)
+// the table of set K from its wind records, on `stream` (K.meso allocated; no allocation, no use of ctx->err)
 int meso_table_launch(const mphip_ctx *ctx, mphip_ctx::PackedGrids &K, hipStream_t stream) {
   MesoTableArgs a;
-  a.wind = K.wind;
-  a.meso = K.meso;
+  a.wind = K.wind.p;
+  a.meso = K.meso.p;
   a.nx = ctx->nx;
   a.ny = ctx->ny;
   a.np = ctx->npl;
@@ -740,7 +707,7 @@ int meso_table_launch(const mphip_ctx *ctx, mphip_ctx::PackedGrids &K, hipStream
 }
 
 // build the packed set K from the staging copies of two snapshots on `stream` (arrays allocated: pack_alloc).
-// No hipMalloc, no use of ctx->err: also called by the uploader thread.  *mono_pending: the monotonicity flag of
+// No allocation, no use of ctx->err: also called by the uploader thread.  *mono_pending: the monotonicity flag of
 // the height columns has to be read back after the kernel (pack_finish).
 int pack_launch(mphip_ctx *ctx, mphip_ctx::PackedGrids &K, const PackPlan &P, const MetSlot &s0, const MetSlot &s1,
                 hipStream_t stream) {
@@ -749,31 +716,31 @@ int pack_launch(mphip_ctx *ctx, mphip_ctx::PackedGrids &K, const PackPlan &P, co
   const MetSlot *ss[2] = { &s0, &s1 };
   for (int t = 0; t < 2; t++) {
     for (int f = 0; f < MPHIP_N3D; f++)
-      a.f3[t][f] = ss[t]->has3[f] ? ss[t]->f3[f] : nullptr;
+      a.f3[t][f] = ss[t]->has3[f] ? ss[t]->f3[f].p : nullptr;
     for (int f = 0; f < MPHIP_N2D; f++)
-      a.f2[t][f] = ss[t]->has2[f] ? ss[t]->f2[f] : nullptr;
+      a.f2[t][f] = ss[t]->has2[f] ? ss[t]->f2[f].p : nullptr;
   }
   if (P.ml_heights) {
     const int one = 1;
-    if (hipMemcpyAsync(K.ml_mono, &one, sizeof(int), hipMemcpyHostToDevice, stream) != hipSuccess)
+    if (hipMemcpyAsync(K.ml_mono.p, &one, sizeof(int), hipMemcpyHostToDevice, stream) != hipSuccess)
       return 1;
   }
-  a.wind = K.wind;
-  a.temp = K.temp;
-  a.cloud = P.cloud ? K.cloud : nullptr;
-  a.mx = P.mx ? K.mx : nullptr;
-  a.mx2 = P.mx2 ? K.mx2 : nullptr;
-  a.sfa = K.sfa;
-  a.sfb = K.sfb;
-  a.cp2 = K.cp2;
-  a.sfc = K.sfc;
-  a.sfd = P.pbl ? K.sfd : nullptr;
-  a.h2o = P.pbl ? K.h2o : nullptr;
-  a.mlw = P.ml ? K.mlw : nullptr;
+  a.wind = K.wind.p;
+  a.temp = K.temp.p;
+  a.cloud = P.cloud ? K.cloud.p : nullptr;
+  a.mx = P.mx ? K.mx.p : nullptr;
+  a.mx2 = P.mx2 ? K.mx2.p : nullptr;
+  a.sfa = K.sfa.p;
+  a.sfb = K.sfb.p;
+  a.cp2 = K.cp2.p;
+  a.sfc = K.sfc.p;
+  a.sfd = P.pbl ? K.sfd.p : nullptr;
+  a.h2o = P.pbl ? K.h2o.p : nullptr;
+  a.mlw = P.ml ? K.mlw.p : nullptr;
   a.mlw_third = P.coord2 ? MPHIP_WL : MPHIP_ZETA_DOTL;
-  a.zl2 = P.ml_heights ? K.zl2 : nullptr;
-  a.pl2 = P.ml_heights ? K.pl2 : nullptr;
-  a.ml_mono = K.ml_mono;
+  a.zl2 = P.ml_heights ? K.zl2.p : nullptr;
+  a.pl2 = P.ml_heights ? K.pl2.p : nullptr;
+  a.ml_mono = K.ml_mono.p;
   a.nml = ctx->nml;
   a.ncell = ncell;
   a.ncol = ncol;
@@ -782,12 +749,12 @@ int pack_launch(mphip_ctx *ctx, mphip_ctx::PackedGrids &K, const PackPlan &P, co
   hipLaunchKernelGGL(pack_kernel, dim3(grid_for((long long) ncell)), dim3(256), 0, stream, a);
   if (hipGetLastError() != hipSuccess)
     return 1;
-  if (P.meso && K.meso && meso_table_launch(ctx, K, stream))
+  if (P.meso && K.meso.p && meso_table_launch(ctx, K, stream))
     return 1;
   K.ml_monotonic = false;
   if (P.ml_heights) {   // (model levels only) the fast kernel relies on monotonic height columns
     int mono = 0;
-    if (hipMemcpyAsync(&mono, K.ml_mono, sizeof(int), hipMemcpyDeviceToHost, stream) != hipSuccess
+    if (hipMemcpyAsync(&mono, K.ml_mono.p, sizeof(int), hipMemcpyDeviceToHost, stream) != hipSuccess
         || hipStreamSynchronize(stream) != hipSuccess)
       return 1;
     K.ml_monotonic = mono != 0;
@@ -841,12 +808,12 @@ bool both_have(const mphip_ctx *c, unsigned mask3, unsigned mask2 = 0) {
 
 // cache->iso_var lives on the device only while an isosurface mode needs it
 int ensure_iso(mphip_ctx *ctx) {
-  if (ctx->d_iso)
+  if (ctx->d_iso.p)
     return 0;
   const size_t n = (size_t) std::max<long long>(ctx->np, 1);
-  if (dev_alloc(ctx, &ctx->d_iso, n) || dev_alloc(ctx, &ctx->d_iso_alt, n))
-    return 1;
-  HIPCHK(hipMemsetAsync(ctx->d_iso, 0, n * sizeof(double), ctx->stream));   // calloc'ed cache_t
+  HIPCHK(ctx->d_iso.resize(n));
+  HIPCHK(ctx->d_iso_alt.resize(n));
+  HIPCHK(hipMemsetAsync(ctx->d_iso.p, 0, n * sizeof(double), ctx->stream));   // calloc'ed cache_t
   return 0;
 }
 
@@ -1091,8 +1058,7 @@ int ensure_meso_table(mphip_ctx *ctx) {
   mphip_ctx::PackedGrids &K = ctx->pk;
   if (K.meso_valid)
     return 0;
-  if (!K.meso && dev_alloc(ctx, &K.meso, meso_table_floats(ctx)))
-    return 1;
+  HIPCHK(K.meso.reserve(meso_table_floats(ctx)));
   if (meso_table_launch(ctx, K, ctx->stream))
     return fail(ctx, "building the table of the mesoscale wind deviations failed");
   return 0;
@@ -1106,12 +1072,12 @@ int launch_step(mphip_ctx *ctx, unsigned mask, double t, const RngCtr &rng = {},
     return 0;
   if (ensure_packed(ctx) || check_fields(ctx, mask))
     return 1;
-  if (ml_winds(ctx->ctl) && !ctx->d_kz) {
+  if (ml_winds(ctx->ctl) && !ctx->d_kz.p) {
     const size_t n = (size_t) std::max<long long>(ctx->np, 1);
-    if (dev_alloc(ctx, &ctx->d_kz, n) || dev_alloc(ctx, &ctx->d_kz_alt, n))
-      return 1;
+    HIPCHK(ctx->d_kz.resize(n));
+    HIPCHK(ctx->d_kz_alt.resize(n));
     std::vector<int> mid(n, std::max(ctx->nml / 2, 0));     // any level: the hint only shortens the search
-    HIPCHK(hipMemcpyAsync(ctx->d_kz, mid.data(), n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->d_kz.p, mid.data(), n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
   }
   StepParams S;
@@ -1122,8 +1088,8 @@ int launch_step(mphip_ctx *ctx, unsigned mask, double t, const RngCtr &rng = {},
   S.ctl = ctx->ctl;
   S.met = dev_met(ctx);
   S.atm = dev_atm(ctx);
-  S.clim = ctx->d_clim;
-  S.tracers = ctx->d_tracers;
+  S.clim = ctx->d_clim.p;
+  S.tracers = ctx->d_tracers.p;
   S.t = t;
   S.mask = mask;
   // every block walks a whole number of 256-particle rounds (no half-empty last round)
@@ -1163,7 +1129,7 @@ int launch_step(mphip_ctx *ctx, unsigned mask, double t, const RngCtr &rng = {},
   if (reads_meso_table(sel, mask)) {
     if (ensure_meso_table(ctx))
       return 1;
-    S.met.meso = ctx->pk.meso;
+    S.met.meso = ctx->pk.meso.p;
   }
   // module_wet_depo / module_dry_depo alone (the launch behind module_mixing): the kernel that packs the few
   // particles with anything to do into full waves
@@ -1171,7 +1137,7 @@ int launch_step(mphip_ctx *ctx, unsigned mask, double t, const RngCtr &rng = {},
   const size_t depo_lds = ((axes_lds_bytes(ctx) + 15) & ~(size_t) 15) + (size_t) per_block * sizeof(int);
   if (sel == kTailOnly && (mask & kDepo) && !(mask & ~kDepo) && ctx->compact_depo && !ctx->fused_perm
       && depo_lds <= 64 * 1024) {
-    S.depo_busy = ctx->depo_busy_valid ? ctx->d_depo_busy : nullptr;
+    S.depo_busy = ctx->depo_busy_valid ? ctx->d_depo_busy.p : nullptr;
     ctx->depo_busy_valid = false;
     ctx->depo_busy_last = S.depo_busy;      // (module_radio_depo behind this launch looks at the same particles)
     ctx->depo_busy_last_mask = mask;
@@ -1340,7 +1306,7 @@ int check_meteo(mphip_ctx *ctx) {
     { MPHIP_MQ_HNO3, MPHIP_ZM_HNO3, "HNO3" }, { MPHIP_MQ_TNAT, MPHIP_ZM_HNO3, "HNO3" }, { MPHIP_MQ_OH, MPHIP_ZM_OH, "OH" },
     { MPHIP_MQ_H2O2, MPHIP_ZM_H2O2, "H2O2" }, { MPHIP_MQ_HO2, MPHIP_ZM_HO2, "HO2" }, { MPHIP_MQ_O1D, MPHIP_ZM_O1D, "O1D" } };
   for (const auto &e : zmq)
-    if (c.qnt_met[e.q] >= 0 && !ctx->d_zm[e.zm])
+    if (c.qnt_met[e.q] >= 0 && !ctx->d_zm[e.zm].p)
       return fail(ctx, std::string("module_meteo: the ") + e.name + " climatology was not uploaded");
   if (c.qnt_met[MPHIP_MQ_TSTS] >= 0 && (c.qnt_met[MPHIP_MQ_TICE] < 0 || c.qnt_met[MPHIP_MQ_TNAT] < 0))
     return fail(ctx, "Need T_ice and T_NAT to calculate T_STS!");
@@ -1399,7 +1365,7 @@ int launch_oh(mphip_ctx *ctx) {
     return fail(ctx, "module_oh_chem: OH_CHEM_REACTION must be 1, 2 or 3");
   if (c.qnt_m < 0 && c.qnt_vmr < 0)
     return fail(ctx, "Module needs quantity mass or volume mixing ratio!");
-  if (!ctx->d_zm[MPHIP_ZM_OH])
+  if (!ctx->d_zm[MPHIP_ZM_OH].p)
     return fail(ctx, "module_oh_chem: the OH climatology was not uploaded");
   return launch_meteo_args(ctx, oh_chem_kernel, { { 1u << MPHIP_T, 0, "module_oh_chem: meteo field t was not uploaded" } },
                            1u << MPHIP_ZM_OH, MeteoDeps());
@@ -1418,7 +1384,7 @@ int launch_tracer_chem(mphip_ctx *ctx) {
   if (c.met_coord_type != 0)
     return fail(ctx, "module_tracer_chem: not implemented for MET_COORD_TYPE != 0 (the photolysis and O(1D) tables "
                      "are on latitude and longitude)");
-  if (!ctx->d_zm[MPHIP_ZM_O1D])
+  if (!ctx->d_zm[MPHIP_ZM_O1D].p)
     return fail(ctx, "module_tracer_chem: the O1D climatology was not uploaded");
   for (int k = 0; k < 4; k++)
     if (c.qnt_tracer[k] >= 0 && !ctx->photo_have[k])
@@ -1435,7 +1401,7 @@ int launch_h2o2(mphip_ctx *ctx) {
   const mphip_ctl_t &c = ctx->ctl;
   if (c.qnt_m < 0 && c.qnt_vmr < 0)
     return fail(ctx, "Module needs quantity mass or volume mixing ratio!");
-  if (!ctx->d_zm[MPHIP_ZM_H2O2])
+  if (!ctx->d_zm[MPHIP_ZM_H2O2].p)
     return fail(ctx, "module_h2o2_chem: the H2O2 climatology was not uploaded");
   return launch_meteo_args(ctx, h2o2_chem_kernel,
                            { { 1u << MPHIP_T | 1u << MPHIP_LWC | 1u << MPHIP_RWC, 0,
@@ -1484,26 +1450,26 @@ PermArgs perm_args(mphip_ctx *ctx, bool with_cache) {
   memset(&g, 0, sizeof(g));
   g.n8 = 4 + ctx->nq;
   for (int k = 0; k < g.n8; k++) {
-    g.in8[k] = ctx->d_arr[k];
-    g.out8[k] = ctx->d_alt[k];
+    g.in8[k] = ctx->d_arr[k].p;
+    g.out8[k] = ctx->d_alt[k].p;
   }
   if (with_cache) {
-    g.in8[g.n8] = ctx->d_dt;
-    g.out8[g.n8] = ctx->d_dt_alt;
+    g.in8[g.n8] = ctx->d_dt.p;
+    g.out8[g.n8] = ctx->d_dt_alt.p;
     g.n8++;
-    if (ctx->d_iso) {
-      g.in8[g.n8] = ctx->d_iso;
-      g.out8[g.n8] = ctx->d_iso_alt;
+    if (ctx->d_iso.p) {
+      g.in8[g.n8] = ctx->d_iso.p;
+      g.out8[g.n8] = ctx->d_iso_alt.p;
       g.n8++;
     }
     g.n4 = 3;
     for (int k = 0; k < 3; k++) {
-      g.in4[k] = ctx->d_uvwp[k];
-      g.out4[k] = ctx->d_uvwp_alt[k];
+      g.in4[k] = ctx->d_uvwp[k].p;
+      g.out4[k] = ctx->d_uvwp_alt[k].p;
     }
-    if (ctx->d_kz) {
-      g.in4[3] = (const float *) ctx->d_kz;
-      g.out4[3] = (float *) ctx->d_kz_alt;
+    if (ctx->d_kz.p) {
+      g.in4[3] = (const float *) ctx->d_kz.p;
+      g.out4[3] = (float *) ctx->d_kz_alt.p;
       g.n4 = 4;
     }
   }
@@ -1551,30 +1517,26 @@ int radix_passes(mphip_ctx *ctx, uint32_t *const keys[2], int *const vals[2], lo
   const int nchunks = (int) ((m + ((size_t) 1 << chunk_shift) - 1) >> chunk_shift);
   if (nchunks > kScanThreads)
     return fail(ctx, "too many particles for the two-level scan of the radix sort");
-  if (m + kScanThreads > ctx->counts_cap) {
-    if (dev_alloc(ctx, &ctx->d_counts, m + kScanThreads))   // counters + chunk totals
-      return 1;
-    ctx->counts_cap = m + kScanThreads;
-  }
-  uint32_t *d_chunks = ctx->d_counts + m;
+  HIPCHK(ctx->d_counts.reserve(m + kScanThreads));   // counters + chunk totals
+  uint32_t *d_chunks = ctx->d_counts.p + m;
   int cur = 0;
   for (int pass = 0; pass < passes; pass++) {
     const int shift = bits * pass;
     const int stride = packed_first && pass == 0 ? 2 : 1;
 #define SORT_PASS(B)                                                                                                   \
   hipLaunchKernelGGL(sort_hist_kernel<B>, dim3(ntiles), dim3(kSortThreads), 0, ctx->stream, keys[cur], n, shift,       \
-                     ntiles, ctx->d_counts, n_dev, stride);                                                            \
+                     ntiles, ctx->d_counts.p, n_dev, stride);                                                            \
   if (small)                                                                                                           \
     hipLaunchKernelGGL(sort_scan_local_kernel<kScanPerSmall>, dim3(nchunks), dim3(kScanThreads), 0, ctx->stream,       \
-                       ctx->d_counts, m, d_chunks, n_dev, 1 << B);                                                     \
+                       ctx->d_counts.p, m, d_chunks, n_dev, 1 << B);                                                     \
   else                                                                                                                 \
     hipLaunchKernelGGL(sort_scan_local_kernel<kScanPerLarge>, dim3(nchunks), dim3(kScanThreads), 0, ctx->stream,       \
-                       ctx->d_counts, m, d_chunks, n_dev, 1 << B);                                                     \
+                       ctx->d_counts.p, m, d_chunks, n_dev, 1 << B);                                                     \
   hipLaunchKernelGGL(sort_scan_chunks_kernel, dim3(1), dim3(kScanThreads), 0, ctx->stream, d_chunks, nchunks);         \
   hipLaunchKernelGGL(sort_scatter_kernel<B>, dim3(ntiles), dim3(kSortThreads), 0, ctx->stream, keys[cur],              \
                      index_sort && pass == 0 ? (const int *) nullptr                                                   \
                                              : (stride == 2 ? (const int *) keys[cur] + 1 : vals[cur]),                \
-                     keys[cur ^ 1], vals[cur ^ 1], n, shift, ntiles, ctx->d_counts, d_chunks, chunk_shift, n_dev, stride)
+                     keys[cur ^ 1], vals[cur ^ 1], n, shift, ntiles, ctx->d_counts.p, d_chunks, chunk_shift, n_dev, stride)
     if (bits == 8) {
       SORT_PASS(8);
     } else if (bits == 9) {
@@ -1639,11 +1601,11 @@ int sort_keys(mphip_ctx *ctx, int tile, const double *timestep_t, const BoxArgs 
   const bool lean = ctx->coord_type == 0 && ctx->lut_size > 0 && !ctx->force_generic;
   if (lean)
     hipLaunchKernelGGL(sort_key_kernel<true>, dim3(grid_for(ctx->np)), dim3(256), axes_lds_bytes(ctx), ctx->stream, M, a, tile,
-                       tile_zbits(ctx, tile), ctx->d_keys[0], (int *) nullptr, ts, timestep_t ? ctx->d_dt : nullptr,
+                       tile_zbits(ctx, tile), ctx->d_keys[0].p, (int *) nullptr, ts, timestep_t ? ctx->d_dt.p : nullptr,
                        box ? *box : none);
   else
     hipLaunchKernelGGL(sort_key_kernel<false>, dim3(grid_for(ctx->np)), dim3(256), axes_lds_bytes(ctx), ctx->stream, M, a, tile,
-                       tile_zbits(ctx, tile), ctx->d_keys[0], (int *) nullptr, ts, timestep_t ? ctx->d_dt : nullptr,
+                       tile_zbits(ctx, tile), ctx->d_keys[0].p, (int *) nullptr, ts, timestep_t ? ctx->d_dt.p : nullptr,
                        box ? *box : none);
   HIPCHK(hipGetLastError());
   return 0;
@@ -1652,37 +1614,39 @@ int sort_keys(mphip_ctx *ctx, int tile, const double *timestep_t, const BoxArgs 
 int sort_pairs(mphip_ctx *ctx, int tile, int *result_buf, const double *timestep_t) {
   if (sort_keys(ctx, tile, timestep_t, nullptr))
     return 1;
-  return radix_passes(ctx, ctx->d_keys, ctx->d_vals, ctx->np, bits_for(sort_key_range(ctx, tile)), result_buf, nullptr,
-                      true);
+  return radix_passes(ctx, RawPair<uint32_t>(ctx->d_keys).q, RawPair<int>(ctx->d_vals).q, ctx->np,
+                      bits_for(sort_key_range(ctx, tile)), result_buf, nullptr, true);
 }
 
 // ---- module_sort as a repair of the previous order ---------------------------------------------------------------
 // key_prev: the sorted keys of the module_sort whose order the particles are stored in; the new keys are in
 // ctx->d_keys[0] (sort_keys).  Leaves the sorted (key, slot) pairs in ctx->d_keys[0] / d_vals[0].
 int repair_sort(mphip_ctx *ctx, const uint32_t *key_prev, long long n, int key_bits, int *cur_out) {
-  if (n > ctx->rep_cap) {
-    const size_t m = (size_t) n;
-    if (dev_alloc(ctx, &ctx->rep_sk, m) || dev_alloc(ctx, &ctx->rep_si, m) || dev_alloc(ctx, &ctx->rep_fk, m)
-        || dev_alloc(ctx, &ctx->rep_fv, m) || dev_alloc(ctx, &ctx->rep_mk[0], m) || dev_alloc(ctx, &ctx->rep_mk[1], m)
-        || dev_alloc(ctx, &ctx->rep_mi[0], m) || dev_alloc(ctx, &ctx->rep_mi[1], m)
-        || dev_alloc(ctx, &ctx->rep_tiles, (m + kRepairTile - 1) / kRepairTile) || dev_alloc(ctx, &ctx->rep_nm, (size_t) 2))
-      return 1;
-    ctx->rep_cap = n;
+  const size_t m = (size_t) n;
+  HIPCHK(ctx->rep_sk.reserve(m));
+  HIPCHK(ctx->rep_si.reserve(m));
+  HIPCHK(ctx->rep_fk.reserve(m));
+  HIPCHK(ctx->rep_fv.reserve(m));
+  for (int k = 0; k < 2; k++) {
+    HIPCHK(ctx->rep_mk[k].reserve(m));
+    HIPCHK(ctx->rep_mi[k].reserve(m));
   }
+  HIPCHK(ctx->rep_tiles.reserve((m + kRepairTile - 1) / kRepairTile));
+  HIPCHK(ctx->rep_nm.reserve(2));
   const int ntiles = (int) ((n + kRepairTile - 1) / kRepairTile);
-  const uint32_t *key_new = ctx->d_keys[0];
-  hipLaunchKernelGGL(repair_count_kernel, dim3(ntiles), dim3(256), 0, ctx->stream, key_new, key_prev, n, ctx->rep_tiles);
-  hipLaunchKernelGGL(repair_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, ctx->rep_tiles, ntiles, n, ctx->rep_nm);
+  const uint32_t *key_new = ctx->d_keys[0].p;
+  hipLaunchKernelGGL(repair_count_kernel, dim3(ntiles), dim3(256), 0, ctx->stream, key_new, key_prev, n, ctx->rep_tiles.p);
+  hipLaunchKernelGGL(repair_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, ctx->rep_tiles.p, ntiles, n, ctx->rep_nm.p);
   hipLaunchKernelGGL(repair_split_kernel, dim3(ntiles), dim3(256), 0, ctx->stream, key_new, key_prev, n,
-                     (const uint32_t *) ctx->rep_tiles, ctx->rep_mk[0], ctx->rep_mi[0], ctx->rep_sk, ctx->rep_si);
+                     (const uint32_t *) ctx->rep_tiles.p, ctx->rep_mk[0].p, ctx->rep_mi[0].p, ctx->rep_sk.p, ctx->rep_si.p);
   HIPCHK(hipGetLastError());
   int mc = 0;     // the movers: the stable radix sort over as many pairs as there are (the count stays on the device)
-  if (radix_passes(ctx, ctx->rep_mk, ctx->rep_mi, n, key_bits, &mc, ctx->rep_nm))
+  if (radix_passes(ctx, RawPair<uint32_t>(ctx->rep_mk).q, RawPair<int>(ctx->rep_mi).q, n, key_bits, &mc, ctx->rep_nm.p))
     return 1;
   const int nmerge = (int) ((n + kMergeTile - 1) / kMergeTile);
-  hipLaunchKernelGGL(repair_merge_kernel, dim3(nmerge), dim3(256), 0, ctx->stream, (const uint32_t *) ctx->rep_sk,
-                     (const int *) ctx->rep_si, (const uint32_t *) ctx->rep_mk[mc], (const int *) ctx->rep_mi[mc],
-                     (const uint32_t *) ctx->rep_nm, n, ctx->rep_fk, ctx->rep_fv);
+  hipLaunchKernelGGL(repair_merge_kernel, dim3(nmerge), dim3(256), 0, ctx->stream, (const uint32_t *) ctx->rep_sk.p,
+                     (const int *) ctx->rep_si.p, (const uint32_t *) ctx->rep_mk[mc].p, (const int *) ctx->rep_mi[mc].p,
+                     (const uint32_t *) ctx->rep_nm.p, n, ctx->rep_fk.p, ctx->rep_fv.p);
   HIPCHK(hipGetLastError());
   std::swap(ctx->d_keys[0], ctx->rep_fk);
   std::swap(ctx->d_vals[0], ctx->rep_fv);
@@ -1699,7 +1663,6 @@ void ahead_swap_buffers(mphip_ctx *ctx) {
     std::swap(ctx->d_vals[k], ctx->ahead_vals[k]);
   }
   std::swap(ctx->d_counts, ctx->ahead_counts);
-  std::swap(ctx->counts_cap, ctx->ahead_counts_cap);
   std::swap(ctx->d_dt, ctx->ahead_dt);
 }
 
@@ -1732,14 +1695,11 @@ int ahead_ensure(mphip_ctx *ctx) {
     HIPCHK(hipEventCreateWithFlags(&ctx->ahead_mark, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&ctx->ahead_done, hipEventDisableTiming));
   }
-  if (n > ctx->ahead_cap) {
-    for (int k = 0; k < 2; k++)
-      if (dev_alloc(ctx, &ctx->ahead_keys[k], (size_t) n) || dev_alloc(ctx, &ctx->ahead_vals[k], (size_t) n))
-        return 1;
-    if (dev_alloc(ctx, &ctx->ahead_dt, (size_t) n))
-      return 1;
-    ctx->ahead_cap = n;
+  for (int k = 0; k < 2; k++) {
+    HIPCHK(ctx->ahead_keys[k].reserve((size_t) n));
+    HIPCHK(ctx->ahead_vals[k].reserve((size_t) n));
   }
+  HIPCHK(ctx->ahead_dt.reserve((size_t) n));
   return 0;
 }
 
@@ -1751,7 +1711,7 @@ int ahead_launch(mphip_ctx *ctx, double t_next, const BoxArgs *box = nullptr, bo
   // the particles are stored in the order of the last module_sort: its sorted keys (in the buffers of the context, which
   // the sort ahead does not touch) let this one repair that order instead of sorting from scratch
   const uint32_t *key_prev = ctx->sort_repair && ctx->stored_is_sorted && ctx->sorted_buf >= 0 && ctx->sorted_n == n
-    ? ctx->d_keys[ctx->sorted_buf] : nullptr;
+    ? ctx->d_keys[ctx->sorted_buf].p : nullptr;
   // the sort code runs as it is, on the other stream and the other buffers
   hipStream_t main_stream = ctx->stream;
   ahead_swap_buffers(ctx);
@@ -1766,7 +1726,8 @@ int ahead_launch(mphip_ctx *ctx, double t_next, const BoxArgs *box = nullptr, bo
     rc = sort_keys(ctx, 0, &t_next, nullptr);
   if (!rc)
     rc = key_prev ? repair_sort(ctx, key_prev, n, bits_for(sort_key_range(ctx, 0)), &cur)
-                  : radix_passes(ctx, ctx->d_keys, ctx->d_vals, n, bits_for(sort_key_range(ctx, 0)), &cur, nullptr, true);
+                  : radix_passes(ctx, RawPair<uint32_t>(ctx->d_keys).q, RawPair<int>(ctx->d_vals).q, n,
+                                 bits_for(sort_key_range(ctx, 0)), &cur, nullptr, true);
   ctx->stream = main_stream;
   ahead_swap_buffers(ctx);
   if (rc)
@@ -1793,20 +1754,8 @@ int permute_random(mphip_ctx *ctx, const PermArgs &g, const int *index, long lon
   for (int p = 0; p < 64 * rg.chunks; p++)
     if ((int) (((unsigned) p * (unsigned) rg.inv) >> 16) != p / rg.chunks)
       return fail(ctx, "internal: record piece index");
-  const size_t need = (size_t) n * (size_t) rg.chunks * 16;
-  bool records = ctx->perm_records && n >= 65536;
-  if (records && need > ctx->prec_cap) {
-    if (ctx->d_prec)
-      (void) hipFree(ctx->d_prec);
-    ctx->d_prec = nullptr;
-    ctx->prec_cap = 0;
-    if (hipMalloc(&ctx->d_prec, need) == hipSuccess)
-      ctx->prec_cap = need;
-    else {
-      (void) hipGetLastError();
-      records = false;
-    }
-  }
+  static_assert(sizeof(f32x4u) == 16, "a record piece is 16 bytes");
+  const bool records = ctx->perm_records && n >= 65536 && ctx->d_prec.try_reserve((size_t) n * (size_t) rg.chunks);
   if (!records) {
     if (scatter)
       hipLaunchKernelGGL(perm_scatter_kernel, dim3(pg.nblocks), dim3(256), 0, ctx->stream, g, index, n, pg);
@@ -1815,7 +1764,7 @@ int permute_random(mphip_ctx *ctx, const PermArgs &g, const int *index, long lon
     HIPCHK(hipGetLastError());
     return 0;
   }
-  f32x4u *rec = (f32x4u *) ctx->d_prec;
+  f32x4u *rec = ctx->d_prec.p;
   const size_t lds = (size_t) kRecordWaves * 64 * (size_t) rg.chunks * 16;
   hipLaunchKernelGGL(perm_pack_kernel, dim3(pg.nblocks), dim3(64 * kRecordWaves), lds, ctx->stream, g, rg,
                      scatter ? index : (const int *) nullptr, rec, n, pg);
@@ -1833,7 +1782,7 @@ int restore_external_order(mphip_ctx *ctx) {
   if (ahead_drop(ctx))
     return 1;
   PermArgs g = perm_args(ctx, true);
-  if (permute_random(ctx, g, ctx->d_ext, ctx->np, true))
+  if (permute_random(ctx, g, ctx->d_ext.p, ctx->np, true))
     return 1;
   perm_swap(ctx, true);
   ctx->stored_is_sorted = false;
@@ -1859,16 +1808,16 @@ int locality_sort_keys(mphip_ctx *ctx, int *cur) {
 // a re-sort only: `ext` composes with the one in place) and the caller clears the hand-over behind that launch.
 int locality_sort_apply(mphip_ctx *ctx, int cur, bool fold) {
   PermArgs g = perm_args(ctx, true);
-  g.ext_in = ctx->ext_identity ? nullptr : ctx->d_ext;
-  g.ext_out = ctx->d_ext_alt;
+  g.ext_in = ctx->ext_identity ? nullptr : ctx->d_ext.p;
+  g.ext_out = ctx->d_ext_alt.p;
   if (fold) {
-    ctx->fold_perm = ctx->d_vals[cur];
+    ctx->fold_perm = ctx->d_vals[cur].p;
   } else if (ctx->ext_identity) {   // out of the caller's order: a random permutation
-    if (permute_random(ctx, g, ctx->d_vals[cur], ctx->np, false))
+    if (permute_random(ctx, g, ctx->d_vals[cur].p, ctx->np, false))
       return 1;
   } else {                   // a re-sort: most particles stay where they are, the gathers hit the caches
     const PermGeom pg = perm_geom(ctx->np);
-    hipLaunchKernelGGL(perm_gather_kernel, dim3(pg.nblocks), dim3(256), 0, ctx->stream, g, ctx->d_vals[cur], ctx->np, pg);
+    hipLaunchKernelGGL(perm_gather_kernel, dim3(pg.nblocks), dim3(256), 0, ctx->stream, g, ctx->d_vals[cur].p, ctx->np, pg);
     HIPCHK(hipGetLastError());
   }
   perm_swap(ctx, true);
@@ -1917,21 +1866,21 @@ int do_sort(mphip_ctx *ctx, const double *timestep_t = nullptr) {
     memset(&g, 0, sizeof(g));
     g.n8 = ctx->nq;
     for (int k = 0; k < ctx->nq; k++) {
-      g.in8[k] = ctx->d_arr[4 + k];
-      g.out8[k] = ctx->d_alt[4 + k];
+      g.in8[k] = ctx->d_arr[4 + k].p;
+      g.out8[k] = ctx->d_alt[4 + k].p;
     }
     // ... or not even those: option fuse_sort_quantities (default) lets the step launch move them as well
     ctx->fused_quantities = ctx->fuse_quantities;
     if (ctx->nq > 0 && !ctx->fused_quantities) {
-      hipLaunchKernelGGL(perm_gather_kernel, dim3(pg.nblocks), dim3(256), 0, ctx->stream, g, ctx->d_vals[cur], n, pg);
+      hipLaunchKernelGGL(perm_gather_kernel, dim3(pg.nblocks), dim3(256), 0, ctx->stream, g, ctx->d_vals[cur].p, n, pg);
       HIPCHK(hipGetLastError());
     }
     for (int k = 0; k < 4 + ctx->nq; k++)
       std::swap(ctx->d_arr[k], ctx->d_alt[k]);   // d_alt[0..3] now hold the pre-sort time, p, lon, lat
-    ctx->fused_perm = ctx->d_vals[cur];
+    ctx->fused_perm = ctx->d_vals[cur].p;
   } else {
     PermArgs g = perm_args(ctx, false);
-    hipLaunchKernelGGL(perm_gather_kernel, dim3(pg.nblocks), dim3(256), 0, ctx->stream, g, ctx->d_vals[cur], n, pg);
+    hipLaunchKernelGGL(perm_gather_kernel, dim3(pg.nblocks), dim3(256), 0, ctx->stream, g, ctx->d_vals[cur].p, n, pg);
     HIPCHK(hipGetLastError());
     perm_swap(ctx, false);
   }
@@ -1939,12 +1888,10 @@ int do_sort(mphip_ctx *ctx, const double *timestep_t = nullptr) {
   return 0;
 }
 
-int ensure_sums(mphip_ctx *ctx, size_t n) {
-  if (n > ctx->sums_cap) {
-    if (dev_alloc(ctx, &ctx->d_sums, n))
-      return 1;
-    ctx->sums_cap = n;
-  }
+// grow-only with a hard failure, for the `||` chains of this file (a statement of its own: HIPCHK(buf.reserve(n)))
+template <typename B>
+int reserve(mphip_ctx *ctx, B &buf, size_t n) {
+  HIPCHK(buf.reserve(n));
   return 0;
 }
 
@@ -2109,12 +2056,8 @@ int ordered_cell_sums(mphip_ctx *ctx, const VALS &vals, int nv, int column, size
   const bool chains = ctx->sum_path == 2 || (ctx->sum_path == 0 && (double) n >= 16.0 * (double) ntot);
   if (chains && n > 0) {
     const size_t words32 = 4 * (size_t) n;
-    if ((words32 + 1) / 2 > ctx->lists_cap) {
-      if (dev_alloc(ctx, &ctx->d_lists, (words32 + 1) / 2))
-        return 1;
-      ctx->lists_cap = (words32 + 1) / 2;
-    }
-    uint32_t *base = (uint32_t *) ctx->d_lists;
+    HIPCHK(ctx->d_lists.reserve((words32 + 1) / 2));
+    uint32_t *base = (uint32_t *) ctx->d_lists.p;
     uint32_t *keys[2] = { base, base + 2 * n };
     int *slots[2] = { (int *) (base + n), (int *) (base + 3 * n) };
     // (cell, slot) pairs in external order, interleaved in the first half of the buffer; the first pass of the
@@ -2123,8 +2066,8 @@ int ordered_cell_sums(mphip_ctx *ctx, const VALS &vals, int nv, int column, size
     memset(&gb, 0, sizeof(gb));
     if (box)
       gb = *box;
-    hipLaunchKernelGGL(cell_slot_pairs_kernel, dim3(grid_for(n)), dim3(256), 0, ctx->stream, ctx->d_cell,
-                       ctx->ext_identity ? (const int *) nullptr : ctx->d_ext, n, (uint32_t) ntot, (uint2 *) base, gb,
+    hipLaunchKernelGGL(cell_slot_pairs_kernel, dim3(grid_for(n)), dim3(256), 0, ctx->stream, ctx->d_cell.p,
+                       ctx->ext_identity ? (const int *) nullptr : ctx->d_ext.p, n, (uint32_t) ntot, (uint2 *) base, gb,
                        box ? 1 : 0);
     int cur = 0;
     if (radix_passes(ctx, keys, slots, n, bits_for(ntot), &cur, nullptr, false, true))
@@ -2145,7 +2088,7 @@ int ordered_cell_sums(mphip_ctx *ctx, const VALS &vals, int nv, int column, size
   }
   if (box && n > 0)   // the other path works on ctx->d_cell
     hipLaunchKernelGGL(box_index_kernel, dim3(grid_for(n)), dim3(256), 0, ctx->stream, dev_atm(ctx), box->G, box->t0,
-                       box->t1, ctx->d_cell, (const double *) nullptr, 0);
+                       box->t1, ctx->d_cell.p, (const double *) nullptr, 0);
   if (every_cell) {
     HIPCHK(hipMemsetAsync(sums, 0, (size_t) nv * ntot * sizeof(double), ctx->stream));
     if (cnt)
@@ -2159,12 +2102,8 @@ int ordered_cell_sums(mphip_ctx *ctx, const VALS &vals, int nv, int column, size
   // (n + 1) | runs per tile (ntiles + 1) | overflow flag]
   const int ntiles = (int) ((n + kRunTile - 1) / kRunTile);
   const size_t words32 = 7 * (size_t) n + 1 + (size_t) ntiles + 1 + 1;
-  if ((words32 + 1) / 2 > ctx->lists_cap) {
-    if (dev_alloc(ctx, &ctx->d_lists, (words32 + 1) / 2))
-      return 1;
-    ctx->lists_cap = (words32 + 1) / 2;
-  }
-  uint32_t *base = (uint32_t *) ctx->d_lists;
+  HIPCHK(ctx->d_lists.reserve((words32 + 1) / 2));
+  uint32_t *base = (uint32_t *) ctx->d_lists.p;
   int *seq_cell = (int *) base, *seq_slot = (int *) (base + n);
   uint32_t *keys[2] = { base + 2 * n, base + 4 * n };
   int *ids[2] = { (int *) (base + 3 * n), (int *) (base + 5 * n) };
@@ -2183,7 +2122,7 @@ int ordered_cell_sums(mphip_ctx *ctx, const VALS &vals, int nv, int column, size
   };
 #define GROUPS(B, BYINDEX, SEQ, SLOT)                                                                                  \
   hipLaunchKernelGGL((cell_sum_groups_kernel<VALS, B, BYINDEX>), dim3(nblocks), dim3(256), 0, ctx->stream, vals,       \
-                     keys[cur], ids[cur], nruns_dev, (uint32_t) ngroups, run_start, SEQ, SLOT, ctx->d_ext, overflow, G, \
+                     keys[cur], ids[cur], nruns_dev, (uint32_t) ngroups, run_start, SEQ, SLOT, ctx->d_ext.p, overflow, G, \
                      ntot, sums, cnt, cnt_as_double)
 #define GROUPS_BY_WIDTH(BYINDEX, SEQ, SLOT)                                                                            \
   if (nv <= 1) {   /* values per pass: as many as there are, up to four */                                             \
@@ -2198,9 +2137,9 @@ int ordered_cell_sums(mphip_ctx *ctx, const VALS &vals, int nv, int column, size
   int cur = 0;
   if (ctx->ext_identity) {
     // the stored order is the external order (after module_sort): stream the groups as they come
-    if (sorted_runs(ctx->d_cell, nullptr, &cur))
+    if (sorted_runs(ctx->d_cell.p, nullptr, &cur))
       return 1;
-    GROUPS_BY_WIDTH(false, ctx->d_cell, (const int *) nullptr)
+    GROUPS_BY_WIDTH(false, ctx->d_cell.p, (const int *) nullptr)
   } else {
     // internal locality order: the runs of the STORED order are long; every wave puts its group into index
     // order in LDS.  A group that does not fit there raises the flag ...  (With hundreds of particles per
@@ -2209,13 +2148,13 @@ int ordered_cell_sums(mphip_ctx *ctx, const VALS &vals, int nv, int column, size
     const bool in_lds = (double) n / (double) ngroups <= 256.0;
     HIPCHK(hipMemsetAsync(overflow, in_lds ? 0 : 1, sizeof(int), ctx->stream));
     if (in_lds) {
-      if (sorted_runs(ctx->d_cell, nullptr, &cur))
+      if (sorted_runs(ctx->d_cell.p, nullptr, &cur))
         return 1;
-      GROUPS_BY_WIDTH(true, ctx->d_cell, (const int *) nullptr)
+      GROUPS_BY_WIDTH(true, ctx->d_cell.p, (const int *) nullptr)
     }
     // ... and the general pass runs: the whole sequence laid out in external order (one run per particle, the
     // permutation is random in the index), same kernels.  Without the flag its launches return at once.
-    hipLaunchKernelGGL(cell_pairs_kernel, dim3(grid_for(n)), dim3(256), 0, ctx->stream, ctx->d_cell, ctx->d_ext, n,
+    hipLaunchKernelGGL(cell_pairs_kernel, dim3(grid_for(n)), dim3(256), 0, ctx->stream, ctx->d_cell.p, ctx->d_ext.p, n,
                        seq_cell, seq_slot, overflow);
     if (sorted_runs(seq_cell, overflow, &cur))
       return 1;
@@ -2224,15 +2163,6 @@ int ordered_cell_sums(mphip_ctx *ctx, const VALS &vals, int nv, int column, size
 #undef GROUPS_BY_WIDTH
 #undef GROUPS
   HIPCHK(hipGetLastError());
-  return 0;
-}
-
-int ensure_cell_counts(mphip_ctx *ctx, size_t ntot) {
-  if (ntot > ctx->cnt_cap) {
-    if (dev_alloc(ctx, &ctx->d_cnt, ntot))
-      return 1;
-    ctx->cnt_cap = ntot;
-  }
   return 0;
 }
 
@@ -2278,7 +2208,7 @@ int mixing_plan(mphip_ctx *ctx, double t, MixPlan *P, bool *active) {
     return 0;
   // [sums of quantity 0 | 1 | 2 | scratch for a doubles-only all-reduce hook]
   const bool hook = !ctx->comm && ctx->allreduce;
-  if (ensure_sums(ctx, ((size_t) mq.n + (hook ? 1 : 0)) * ntot) || ensure_cell_counts(ctx, ntot))
+  if (reserve(ctx, ctx->d_sums, ((size_t) mq.n + (hook ? 1 : 0)) * ntot) || reserve(ctx, ctx->d_cnt, ntot))
     return 1;
   P->ntot = ntot;
   P->box.grid = BoxGrid{ c.mixing_lon0, c.mixing_lon1, c.mixing_lat0, c.mixing_lat1, c.mixing_z0, c.mixing_z1,
@@ -2296,7 +2226,7 @@ int mixing_cells(mphip_ctx *ctx, const MixPlan &P) {
     return 0;
   const MixGrid &h = P.box;
   hipLaunchKernelGGL(box_index_kernel, dim3(grid_for(ctx->np)), dim3(256), 0, ctx->stream, dev_atm(ctx), h.grid, h.t0, h.t1,
-                     ctx->d_cell, h.ens, h.ngrid);
+                     ctx->d_cell.p, h.ens, h.ngrid);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -2311,26 +2241,19 @@ int mixing_cells(mphip_ctx *ctx, const MixPlan &P) {
 // covers four fifths of it.
 int exchange_occupied_levels(mphip_ctx *ctx, int nq, size_t ntot, int nz) {
   const size_t ncol = ntot / (size_t) nz;
-  if (!ctx->d_occ || !ctx->h_occ) {      // (both: a failed host allocation must not leave the pair half made)
-    if (ctx->h_occ) {
-      (void) hipHostFree(ctx->h_occ);
-      ctx->h_occ = nullptr;
-    }
-    if (dev_alloc(ctx, &ctx->d_occ, (size_t) 256))
-      return 1;
-    HIPCHK(hipHostMalloc((void **) &ctx->h_occ, 256 * sizeof(double), hipHostMallocDefault));
-  }
-  HIPCHK(hipMemsetAsync(ctx->d_occ, 0, (size_t) nz * sizeof(double), ctx->stream));
+  HIPCHK(ctx->d_occ.reserve(256));   // (both or neither: a failure of either returns before any use)
+  HIPCHK(ctx->h_occ.reserve(256));
+  HIPCHK(hipMemsetAsync(ctx->d_occ.p, 0, (size_t) nz * sizeof(double), ctx->stream));
   hipLaunchKernelGGL(level_occupancy_kernel, dim3(std::min<size_t>(1024, (ntot + 255) / 256)), dim3(256), 0, ctx->stream,
-                     (const int *) ctx->d_cnt, ntot, nz, ctx->d_occ);
+                     (const int *) ctx->d_cnt.p, ntot, nz, ctx->d_occ.p);
   HIPCHK(hipGetLastError());
-  if (run_allreduce(ctx, ctx->d_occ, (size_t) nz))
+  if (run_allreduce(ctx, ctx->d_occ.p, (size_t) nz))
     return 1;
-  HIPCHK(hipMemcpyAsync(ctx->h_occ, ctx->d_occ, (size_t) nz * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(ctx->h_occ.p, ctx->d_occ.p, (size_t) nz * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   int lo = nz, hi = -1;
   for (int l = 0; l < nz; l++)
-    if (ctx->h_occ[l] > 0) {
+    if (ctx->h_occ.p[l] > 0) {
       lo = std::min(lo, l);
       hi = std::max(hi, l);
     }
@@ -2340,26 +2263,23 @@ int exchange_occupied_levels(mphip_ctx *ctx, int nq, size_t ntot, int nz) {
     return 0;
   const int nl = hi - lo + 1;
   if (5 * nl >= 4 * nz)
-    return run_allreduce(ctx, ctx->d_sums, (size_t) nq * ntot, ctx->d_cnt, ntot, ctx->d_sums + (size_t) nq * ntot);
+    return run_allreduce(ctx, ctx->d_sums.p, (size_t) nq * ntot, ctx->d_cnt.p, ntot, ctx->d_sums.p + (size_t) nq * ntot);
   const size_t per = ncol * (size_t) nl;
   // dense buffers: [sums of the quantities | scratch for a doubles-only hook] and the counts
-  if (((size_t) nq + 1) * per > ctx->band_cap) {
-    if (dev_alloc(ctx, &ctx->d_band, ((size_t) nq + 1) * per) || dev_alloc(ctx, &ctx->d_band_cnt, per))
-      return 1;
-    ctx->band_cap = ((size_t) nq + 1) * per;
-  }
+  HIPCHK(ctx->d_band.reserve(((size_t) nq + 1) * per));
+  HIPCHK(ctx->d_band_cnt.reserve(per));
   const int blocks = (int) std::min<size_t>(8192, ((size_t) nq * per + 255) / 256);
-  hipLaunchKernelGGL(pack_levels_kernel<double>, dim3(blocks), dim3(256), 0, ctx->stream, (const double *) ctx->d_sums,
-                     ctx->d_band, ncol, nz, lo, nl, nq, false, (double *) nullptr);
-  hipLaunchKernelGGL(pack_levels_kernel<int>, dim3(blocks), dim3(256), 0, ctx->stream, (const int *) ctx->d_cnt,
-                     ctx->d_band_cnt, ncol, nz, lo, nl, 1, false, (int *) nullptr);
+  hipLaunchKernelGGL(pack_levels_kernel<double>, dim3(blocks), dim3(256), 0, ctx->stream, (const double *) ctx->d_sums.p,
+                     ctx->d_band.p, ncol, nz, lo, nl, nq, false, (double *) nullptr);
+  hipLaunchKernelGGL(pack_levels_kernel<int>, dim3(blocks), dim3(256), 0, ctx->stream, (const int *) ctx->d_cnt.p,
+                     ctx->d_band_cnt.p, ncol, nz, lo, nl, 1, false, (int *) nullptr);
   HIPCHK(hipGetLastError());
-  if (run_allreduce(ctx, ctx->d_band, (size_t) nq * per, ctx->d_band_cnt, per, ctx->d_band + (size_t) nq * per))
+  if (run_allreduce(ctx, ctx->d_band.p, (size_t) nq * per, ctx->d_band_cnt.p, per, ctx->d_band.p + (size_t) nq * per))
     return 1;
   hipLaunchKernelGGL(pack_levels_kernel<double>, dim3(blocks), dim3(256), 0, ctx->stream, (const double *) nullptr,
-                     ctx->d_band, ncol, nz, lo, nl, nq, true, ctx->d_sums);
+                     ctx->d_band.p, ncol, nz, lo, nl, nq, true, ctx->d_sums.p);
   hipLaunchKernelGGL(pack_levels_kernel<int>, dim3(blocks), dim3(256), 0, ctx->stream, (const int *) nullptr,
-                     ctx->d_band_cnt, ncol, nz, lo, nl, 1, true, ctx->d_cnt);
+                     ctx->d_band_cnt.p, ncol, nz, lo, nl, 1, true, ctx->d_cnt.p);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -2371,16 +2291,16 @@ int mixing_sums(mphip_ctx *ctx, const MixPlan &P, bool every_cell = false) {
   if (ctx->deterministic_sums != 0) {
     MixVals vals = { mq };
     const bool exchanged = ctx->comm != nullptr || ctx->allreduce != nullptr;
-    if (ordered_cell_sums(ctx, vals, mq.n, P.box.grid.nz, ntot, ctx->d_sums, ctx->d_cnt, (double *) nullptr,
+    if (ordered_cell_sums(ctx, vals, mq.n, P.box.grid.nz, ntot, ctx->d_sums.p, ctx->d_cnt.p, (double *) nullptr,
                           exchanged || every_cell))
       return 1;
   } else {
-    HIPCHK(hipMemsetAsync(ctx->d_sums, 0, (size_t) mq.n * ntot * sizeof(double), ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->d_cnt, 0, ntot * sizeof(int), ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_sums.p, 0, (size_t) mq.n * ntot * sizeof(double), ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_cnt.p, 0, ntot * sizeof(int), ctx->stream));
     if (ctx->np) {
       const AccumGeom g = accum_geom(ctx, mq.n + 1);
-      hipLaunchKernelGGL(mix_accumulate_kernel, dim3(g.nblocks), dim3(256), g.lds, ctx->stream, dev_atm(ctx), ctx->d_cell,
-                         mq, ntot, ctx->d_sums, ctx->d_cnt, g.T, g.per_block);
+      hipLaunchKernelGGL(mix_accumulate_kernel, dim3(g.nblocks), dim3(256), g.lds, ctx->stream, dev_atm(ctx), ctx->d_cell.p,
+                         mq, ntot, ctx->d_sums.p, ctx->d_cnt.p, g.T, g.per_block);
       HIPCHK(hipGetLastError());
     }
   }
@@ -2389,14 +2309,14 @@ int mixing_sums(mphip_ctx *ctx, const MixPlan &P, bool every_cell = false) {
   const int nz = P.box.grid.nz;
   if (exchange && ctx->mix_exchange_levels && nz >= 8 && nz <= 256 && ntot >= ((size_t) 1 << 18))
     return exchange_occupied_levels(ctx, mq.n, ntot, nz);
-  return run_allreduce(ctx, ctx->d_sums, (size_t) mq.n * ntot, ctx->d_cnt, ntot, ctx->d_sums + (size_t) mq.n * ntot);
+  return run_allreduce(ctx, ctx->d_sums.p, (size_t) mq.n * ntot, ctx->d_cnt.p, ntot, ctx->d_sums.p + (size_t) mq.n * ntot);
 }
 
 int mixing_relax(mphip_ctx *ctx, const MixPlan &P) {
   if (ctx->np == 0)
     return 0;
-  hipLaunchKernelGGL(mix_relax_kernel, dim3(grid_for(ctx->np)), dim3(256), 0, ctx->stream, ctx->ctl, ctx->d_clim,
-                     dev_atm(ctx), ctx->d_cell, P.mq, P.ntot, ctx->d_sums, ctx->d_cnt);
+  hipLaunchKernelGGL(mix_relax_kernel, dim3(grid_for(ctx->np)), dim3(256), 0, ctx->stream, ctx->ctl, ctx->d_clim.p,
+                     dev_atm(ctx), ctx->d_cell.p, P.mq, P.ntot, ctx->d_sums.p, ctx->d_cnt.p);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -2459,12 +2379,12 @@ int do_chem_grid(mphip_ctx *ctx, double t) {
   P.box.ens = (c.nens > 0 && c.qnt_ens >= 0) ? a.q[c.qnt_ens] : nullptr;
   P.box.ngrid = (int) ngrid;
   const bool hook = !ctx->comm && ctx->allreduce;
-  if (ensure_sums(ctx, (1 + (hook ? 1 : 0)) * ntot) || ensure_cell_counts(ctx, ntot))
+  if (reserve(ctx, ctx->d_sums, (1 + (hook ? 1 : 0)) * ntot) || reserve(ctx, ctx->d_cnt, ntot))
     return 1;
   if (mixing_cells(ctx, P) || mixing_sums(ctx, P, true))
     return 1;
   ChemGridArgs C;
-  C.press = ctx->d_chemgrid;
+  C.press = ctx->d_chemgrid.p;
   C.area = C.press + c.chemgrid_nz;
   C.lon = C.area + c.chemgrid_ny;
   C.lat = C.lon + c.chemgrid_nx;
@@ -2476,14 +2396,14 @@ int do_chem_grid(mphip_ctx *ctx, double t) {
   C.nz = c.chemgrid_nz;
   C.ngrid = (int) ngrid;
   C.ntot = (long long) ntot;
-  C.val = ctx->d_sums;
-  C.cnt = ctx->d_cnt;
+  C.val = ctx->d_sums.p;
+  C.cnt = ctx->d_cnt.p;
   if (ctx->np == 0)   // (a rank without particles takes part in the all-reduce only)
     return 0;
   hipLaunchKernelGGL(chem_grid_table_kernel, dim3(grid_for((long long) ntot)), dim3(256), axes_lds_bytes(ctx), ctx->stream,
                      dev_met(ctx), C);
   hipLaunchKernelGGL(chem_grid_gather_kernel, dim3(grid_for(ctx->np)), dim3(256), 0, ctx->stream, a,
-                     (const int *) ctx->d_cell, (const double *) ctx->d_sums, c.qnt_Cx);
+                     (const int *) ctx->d_cell.p, (const double *) ctx->d_sums.p, c.qnt_Cx);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -2540,7 +2460,6 @@ bool step_chem_on(const mphip_ctl_t &c) {
 
 // ---- module_radio_depo ---------------------------------------------------------
 
-int ensure_rec(mphip_ctx *ctx, size_t need);   // (the record buffer of the analysis outputs, below)
 
 // the deposition modules the control parameters configure (the bits of the step's tail, plan_step)
 unsigned depo_bits(const mphip_ctl_t &c) {
@@ -2585,7 +2504,7 @@ std::string radio_depo_conflict(const mphip_ctl_t &c, const RadioQnt &r) {
 // busy: EmitKeys::depo_busy of the launch that moved the particles, if it holds for depo_bits' modules (NULL: the kernel
 // decides from p, time and dt itself).
 int launch_radio_depo(mphip_ctx *ctx, double t, const unsigned char *busy) {
-  if (!ctx->d_rdepo_inv)
+  if (!ctx->d_rdepo_inv.p)
     return fail(ctx, "module_radio_depo: no ground grid (mphip_set_radio_depo)");
   const std::string why = radio_depo_conflict(ctx->ctl, ctx->radio);
   if (!why.empty())
@@ -2617,17 +2536,17 @@ int launch_radio_depo(mphip_ctx *ctx, double t, const unsigned char *busy) {
     if (ctx->force_generic || !lean32_ok(ctx))
       return fail(ctx, "module_radio_depo: needs the lean deposition code (a regular longitude / latitude meteo grid with a "
                        "pressure look-up table, packed records within 32-bit offsets, option generic_kernel off)");
-    if (ensure_rec(ctx, (size_t) ctx->np * (size_t) nv) || ensure_sums(ctx, (size_t) nv * ntot))
+    if (reserve(ctx, ctx->d_rec, (size_t) ctx->np * (size_t) nv) || reserve(ctx, ctx->d_sums, (size_t) nv * ntot))
       return 1;
-    R.cell = ctx->d_cell;
-    R.val = ctx->d_rec;
+    R.cell = ctx->d_cell.p;
+    R.val = ctx->d_rec.p;
     StepParams S;
     memset(&S.emit, 0, sizeof(S.emit));
     S.ctl = c;
     S.met = dev_met(ctx);
     S.atm = dev_atm(ctx);
-    S.clim = ctx->d_clim;
-    S.tracers = ctx->d_tracers;
+    S.clim = ctx->d_clim.p;
+    S.tracers = ctx->d_tracers.p;
     S.t = t;
     S.mask = depo;
     // the partition of the deposition launch, with more blocks where the list of a block would not fit the LDS
@@ -2667,17 +2586,17 @@ int launch_radio_depo(mphip_ctx *ctx, double t, const unsigned char *busy) {
     HIPCHK(hipGetLastError());
     if (ctx->prof)
       HIPCHK(hipEventRecord(e1, ctx->stream));
-    const RecordVals vals = { ctx->d_rec, nv };
-    if (ordered_cell_sums(ctx, vals, nv, 1, ntot, ctx->d_sums, (int *) nullptr, (double *) nullptr, true))
+    const RecordVals vals = { ctx->d_rec.p, nv };
+    if (ordered_cell_sums(ctx, vals, nv, 1, ntot, ctx->d_sums.p, (int *) nullptr, (double *) nullptr, true))
       return 1;
-    step = ctx->d_sums;
+    step = ctx->d_sums.p;
   }
   // (behind the last refusal: a refused call leaves the inventory and its time as they were)
   ctx->rdepo_t = t;
   ctx->rdepo_have_t = true;
   if (D.ndep > 0) {
     hipLaunchKernelGGL(radio_depo_add_kernel, dim3(grid_for((long long) (2 * (size_t) D.ndep * ntot))), dim3(256), 0, ctx->stream,
-                       ctx->d_rdepo_inv, step, ntot, D);
+                       ctx->d_rdepo_inv.p, step, ntot, D);
     HIPCHK(hipGetLastError());
   }
   return 0;
@@ -2894,19 +2813,9 @@ size_t packed_block_bytes(const mphip_met_packed_t *pk) {
   return need;
 }
 
-// the code buffer of a stream, grown to `need` bytes (on the calling thread: nothing is queued on the stream that reads it)
-int reserve_codes(mphip_ctx *ctx, mphip_ctx::CodeBuf &B, size_t need) {
-  if (B.bytes >= need)
-    return 0;
-  B.bytes = 0;
-  if (dev_alloc(ctx, &B.p, need))
-    return 1;
-  B.bytes = need;
-  return 0;
-}
-
 // host -> device copies of one snapshot's fields into the staging arrays of slot S (asynchronous on `stream`); a field
-// that `pk` gives as codes goes into the block `codes` (reserve_codes) and is decoded from there behind its copy
+// that `pk` gives as codes goes into the block `codes` (mphip_ctx::codes, reserved by the caller) and is decoded from there
+// behind its copy
 int upload_fields(mphip_ctx *ctx, MetSlot &S, const mphip_met_t *met, bool new_grid, hipStream_t stream,
                   const mphip_met_packed_t *pk = nullptr, char *codes = nullptr) {
   const int nml = met->npl > 0 ? met->npl : 0;
@@ -2921,8 +2830,7 @@ int upload_fields(mphip_ctx *ctx, MetSlot &S, const mphip_met_t *met, bool new_g
       continue;
     const size_t n3 = (size_t) met->nx * met->ny * (size_t) nlev;
     if (new_grid || !S.f3[f])
-      if (dev_alloc(ctx, &S.f3[f], n3))
-        return 1;
+      HIPCHK(S.f3[f].resize(n3));
     if (coded) {
       const PackedField B = packed_field(n3, (int) nlev, pk->q3[f]);
       HIPCHK(hipMemcpyAsync(B.scl(codes), pk->scl[f], (size_t) nlev * sizeof(double), hipMemcpyHostToDevice, stream));
@@ -2930,13 +2838,13 @@ int upload_fields(mphip_ctx *ctx, MetSlot &S, const mphip_met_t *met, bool new_g
       HIPCHK(hipMemcpyAsync(B.q(codes), pk->q3[f], n3 * sizeof(unsigned short), hipMemcpyHostToDevice, stream));
       const PackStream P = pack_stream(B.q(codes), n3, (int) nlev);
       hipLaunchKernelGGL(P.table_in_lds ? met_unpack_kernel<true> : met_unpack_kernel<false>, P.grid, dim3(kPkThreads), P.lds,
-                         stream, B.q(codes), B.scl(codes), B.off(codes), S.f3[f], P.n, P.nlev, P.head, pk->lo[f], pk->hi[f]);
+                         stream, B.q(codes), B.scl(codes), B.off(codes), S.f3[f].p, P.n, P.nlev, P.head, pk->lo[f], pk->hi[f]);
       HIPCHK(hipGetLastError());
       continue;
     }
     if (!regrid_strides_ok(met->ny, (int) nlev, sx, sy))
       return fail(ctx, "unsupported 3-D meteo strides");
-    if (copy3(ctx, stream, S.f3[f], met->f3[f], met->nx, met->ny, (int) nlev, sx, sy, true))
+    if (copy3(ctx, stream, S.f3[f].p, met->f3[f], met->nx, met->ny, (int) nlev, sx, sy, true))
       return 1;
   }
   S.ps11 = met->f2[MPHIP_PS] ? met->f2[MPHIP_PS][(size_t) met->sx2 + 1] : 0.f;
@@ -2986,14 +2894,13 @@ int upload_fields(mphip_ctx *ctx, MetSlot &S, const mphip_met_t *met, bool new_g
     if (!S.has2[f])
       continue;
     if (new_grid || !S.f2[f])
-      if (dev_alloc(ctx, &S.f2[f], ncol))
-        return 1;
+      HIPCHK(S.f2[f].resize(ncol));
     if (met->sx2 == met->ny) {
-      HIPCHK(hipMemcpyAsync(S.f2[f], met->f2[f], ncol * sizeof(float), hipMemcpyHostToDevice, stream));
+      HIPCHK(hipMemcpyAsync(S.f2[f].p, met->f2[f], ncol * sizeof(float), hipMemcpyHostToDevice, stream));
     } else {
       if (met->sx2 < met->ny)
         return fail(ctx, "unsupported 2-D meteo stride");
-      HIPCHK(hipMemcpy2DAsync(S.f2[f], (size_t) met->ny * sizeof(float), met->f2[f], (size_t) met->sx2 * sizeof(float),
+      HIPCHK(hipMemcpy2DAsync(S.f2[f].p, (size_t) met->ny * sizeof(float), met->f2[f], (size_t) met->sx2 * sizeof(float),
                               (size_t) met->ny * sizeof(float), (size_t) met->nx, hipMemcpyHostToDevice, stream));
     }
   }
@@ -3037,20 +2944,14 @@ struct PrepCall {
   T *take(size_t n) {
     if (S.taken == S.pool.size())
       S.pool.emplace_back();
-    PrepState::Buf &b = S.pool[S.taken++];
-    if (b.bytes < n * sizeof(T)) {
-      b.bytes = 0;
-      if (dev_alloc(ctx, &b.p, n * sizeof(T)))
-        return nullptr;
-      b.bytes = n * sizeof(T);
-    }
-    return (T *) b.p;
+    DevBuf<char> &b = S.pool[S.taken++];
+    return reserve(ctx, b, n * sizeof(T)) ? nullptr : (T *) b.p;
   }
   // event pairs around every kernel (phase 0), around the uploads (1), around the downloads (2) or around the weight table
   // of mphip_detrend_met (3)
   int mark_begin(int phase) {
     ev_stop = nullptr;
-    if (!ctx->prof || S.profile_phase != phase)
+    if (!ctx->prof || ctx->derive_profile_phase != phase)
       return 0;
     while (ctx->ev_used + 2 > ctx->ev.size()) {
       hipEvent_t e;
@@ -3081,7 +2982,7 @@ struct PrepCall {
   // mphip_pack_met)
   template <typename K, typename... Args>
   int launch_as(int phase, K kernel, dim3 grid, dim3 block, size_t lds, Args... args) {
-    return mark_begin(S.profile_phase == phase ? phase : 0) || enqueue(kernel, grid, block, lds, args...) || mark_end();
+    return mark_begin(ctx->derive_profile_phase == phase ? phase : 0) || enqueue(kernel, grid, block, lds, args...) || mark_end();
   }
 };
 
@@ -3388,6 +3289,7 @@ int mphip_create(mphip_ctx **out, int device) {
   return 0;
 }
 
+// What is not memory ends here, every stream synchronised first; the buffers free themselves with the context.
 void mphip_destroy(mphip_ctx *ctx) {
   if (!ctx)
     return;
@@ -3397,96 +3299,19 @@ void mphip_destroy(mphip_ctx *ctx) {
     (void) rccl().CommDestroy(ctx->comm);
   if (ctx->uploader.joinable())
     ctx->uploader.join();
-  if (ctx->copy_stream) {
-    (void) hipStreamSynchronize(ctx->copy_stream);
-    (void) hipStreamDestroy(ctx->copy_stream);
-  }
-  if (ctx->next_ready)
-    (void) hipEventDestroy(ctx->next_ready);
-  if (ctx->main_mark)
-    (void) hipEventDestroy(ctx->main_mark);
-  unpin_all(ctx, ctx->pinned);
-  for (MetSlot *s : { &ctx->slot[0], &ctx->slot[1], &ctx->next }) {
-    for (auto p : s->f3)
-      dev_free(p);
-    for (auto p : s->f2)
-      dev_free(p);
-  }
-  for (auto &b : ctx->codes)
-    dev_free(b.p);
-  ctx->prep.release();
-  dev_free(ctx->d_clim);
-  for (auto p : ctx->d_zm)
-    dev_free(p);
-  for (auto p : ctx->d_ts)
-    dev_free(p);
-  dev_free(ctx->d_tracers);
-  dev_free(ctx->d_axes);
-  ctx->pk.release();
-  ctx->pk_next.release();
-  for (void *q : { (void *) ctx->rep_sk, (void *) ctx->rep_si, (void *) ctx->rep_fk, (void *) ctx->rep_fv, (void *) ctx->rep_mk[0],
-                   (void *) ctx->rep_mk[1], (void *) ctx->rep_mi[0], (void *) ctx->rep_mi[1], (void *) ctx->rep_tiles, (void *) ctx->rep_nm })
-    dev_free(q);
-  if (ctx->ahead_stream) {
-    (void) hipStreamSynchronize(ctx->ahead_stream);
-    (void) hipStreamDestroy(ctx->ahead_stream);
-    (void) hipEventDestroy(ctx->ahead_mark);
-    (void) hipEventDestroy(ctx->ahead_done);
-  }
-  for (int k = 0; k < 2; k++) {
-    dev_free(ctx->ahead_keys[k]);
-    dev_free(ctx->ahead_vals[k]);
-  }
-  dev_free(ctx->ahead_counts);
-  dev_free(ctx->ahead_dt);
-  for (auto p : ctx->d_arr)
-    dev_free(p);
-  for (auto p : ctx->d_alt)
-    dev_free(p);
-  for (auto p : ctx->d_uvwp)
-    dev_free(p);
-  for (auto p : ctx->d_uvwp_alt)
-    dev_free(p);
-  dev_free(ctx->d_dt);
-  dev_free(ctx->d_iso);
-  dev_free(ctx->d_iso_alt);
-  dev_free(ctx->d_kz);
-  dev_free(ctx->d_kz_alt);
-  dev_free(ctx->d_iso_ts);
-  dev_free(ctx->d_iso_ps);
-  dev_free(ctx->d_dt_alt);
-  dev_free(ctx->d_ext);
-  dev_free(ctx->d_ext_alt);
-  for (int k = 0; k < 2; k++) {
-    dev_free(ctx->d_keys[k]);
-    dev_free(ctx->d_vals[k]);
-  }
-  dev_free(ctx->d_counts);
-  dev_free(ctx->d_prec);
-  dev_free(ctx->d_cell);
-  dev_free(ctx->d_sums);
-  dev_free(ctx->d_chemgrid);
-  dev_free(ctx->d_photo);
-  dev_free(ctx->d_cnt);
-  dev_free(ctx->d_depo_busy);
-  dev_free(ctx->d_rdepo_inv);
-  dev_free(ctx->d_occ);
-  dev_free(ctx->d_band);
-  dev_free(ctx->d_band_cnt);
-  if (ctx->h_occ)
-    (void) hipHostFree(ctx->h_occ);
-  dev_free(ctx->d_lists);
-  dev_free(ctx->d_grid_kernel);
-  dev_free(ctx->d_ana_kernel);
-  dev_free(ctx->d_marks);
-  dev_free(ctx->d_slot_of);
-  dev_free(ctx->d_ana_flags);
-  dev_free(ctx->d_rec);
-  if (ctx->h_sums)
-    (void) hipHostFree(ctx->h_sums);
+  for (hipStream_t s : { ctx->copy_stream, ctx->ahead_stream, ctx->prep.stream })
+    if (s) {
+      (void) hipStreamSynchronize(s);
+      (void) hipStreamDestroy(s);
+    }
+  for (hipEvent_t e : { ctx->next_ready, ctx->main_mark, ctx->ahead_mark, ctx->ahead_done })
+    if (e)
+      (void) hipEventDestroy(e);
   for (auto e : ctx->ev)
     (void) hipEventDestroy(e);
+  unpin_all(ctx, ctx->pinned);
   (void) hipStreamDestroy(ctx->stream);
+  (void) hipSetDevice(ctx->device);
   delete ctx;
 }
 
@@ -3555,9 +3380,8 @@ int mphip_update_ctl(mphip_ctx *ctx, const mphip_ctl_t *ctl) {
     }
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(hipStreamSynchronize(ctx->stream));   // (the old tables may still be read)
-    if (dev_alloc(ctx, &ctx->d_chemgrid, tab.size()))
-      return 1;
-    HIPCHK(hipMemcpy(ctx->d_chemgrid, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(ctx->d_chemgrid.resize(tab.size()));
+    HIPCHK(hipMemcpy(ctx->d_chemgrid.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
     ctx->chemgrid_ok = true;
   }
   ctx->h2o2_low = pow(1. / kH2O2CorA, 1. / kH2O2CorB);
@@ -3588,9 +3412,8 @@ int mphip_update_clim(mphip_ctx *ctx, int ntime, int nlat, const double *tropo_t
     h.inv_dtime[i] = 1.0 / (h.time[i + 1] - h.time[i]);
   for (int j = 0; j + 1 < nlat; j++)
     h.inv_dlat[j] = 1.0 / (h.lat[j + 1] - h.lat[j]);
-  if (!ctx->d_clim)
-    HIPCHK(hipMalloc((void **) &ctx->d_clim, sizeof(DevClim)));
-  HIPCHK(hipMemcpyAsync(ctx->d_clim, &h, sizeof(DevClim), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx->d_clim.reserve(1));
+  HIPCHK(hipMemcpyAsync(ctx->d_clim.p, &h, sizeof(DevClim), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   ctx->h_clim = h;
   ctx->have_clim = true;
@@ -3605,8 +3428,7 @@ int mphip_update_clim_zm(mphip_ctx *ctx, int which, int ntime, int np, int nlat,
   if (flush_meteo(ctx))   // (a deferred module_meteo reads the tables of its own step)
     return 1;
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  dev_free(ctx->d_zm[which]);
-  ctx->d_zm[which] = nullptr;
+  ctx->d_zm[which].release();
   memset(&ctx->zm[which], 0, sizeof(DevZm));
   if (ntime == 0)
     return 0;
@@ -3619,10 +3441,8 @@ int mphip_update_clim_zm(mphip_ctx *ctx, int which, int ntime, int np, int nlat,
   if (!(lat[0] < lat[1]))
     return fail(ctx, "Latitude data are not ascending!");
   const size_t nv = (size_t) ntime * (size_t) np * (size_t) nlat, n = (size_t) ntime + np + nlat + nv;
-  double *d = nullptr;
-  if (dev_alloc(ctx, &d, n))
-    return 1;
-  ctx->d_zm[which] = d;
+  HIPCHK(ctx->d_zm[which].resize(n));
+  double *d = ctx->d_zm[which].p;
   HIPCHK(hipMemcpy(d, time, (size_t) ntime * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(d + ntime, p, (size_t) np * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(d + ntime + np, lat, (size_t) nlat * sizeof(double), hipMemcpyHostToDevice));
@@ -3646,8 +3466,7 @@ int mphip_update_clim_photo(mphip_ctx *ctx, int np, int nsza, int no3c, const do
   if (flush_meteo(ctx))
     return 1;
   HIPCHK(hipStreamSynchronize(ctx->stream));   // (kernels in flight may read the old tables)
-  dev_free(ctx->d_photo);
-  ctx->d_photo = nullptr;
+  ctx->d_photo.release();
   memset(&ctx->photo, 0, sizeof(DevPhoto));
   for (bool &h : ctx->photo_have)
     h = false;
@@ -3679,10 +3498,8 @@ int mphip_update_clim_photo(mphip_ctx *ctx, int np, int nsza, int no3c, const do
     if (rate[k])
       for (size_t j = 0; j < nrec; j++)
         h[naxes + 4 * j + k] = rate[k][j];
-  double *d = nullptr;
-  if (dev_alloc(ctx, &d, h.size()))
-    return 1;
-  ctx->d_photo = d;
+  HIPCHK(ctx->d_photo.resize(h.size()));
+  double *d = ctx->d_photo.p;
   HIPCHK(hipMemcpy(d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
   DevPhoto &ph = ctx->photo;
   ph.p = d;
@@ -3704,8 +3521,7 @@ int mphip_update_clim_ts(mphip_ctx *ctx, int which, int ntime, const double *tim
   if (ahead_drop(ctx))
     return 1;
   HIPCHK(hipStreamSynchronize(ctx->stream));   // kernels in flight may read the old series
-  dev_free(ctx->d_ts[which]);
-  ctx->d_ts[which] = nullptr;
+  ctx->d_ts[which].release();
   DevTracerSeries &h = ctx->h_tracers;
   h.time[which] = h.vmr[which] = nullptr;
   h.ntime[which] = 0;
@@ -3717,19 +3533,16 @@ int mphip_update_clim_ts(mphip_ctx *ctx, int which, int ntime, const double *tim
     for (int i = 1; i < ntime; i++)
       if (!(time[i] > time[i - 1]))
         return fail(ctx, "Time series must be ascending!");
-    double *d = nullptr;
-    if (dev_alloc(ctx, &d, 2 * (size_t) ntime))
-      return 1;
-    ctx->d_ts[which] = d;
+    HIPCHK(ctx->d_ts[which].resize(2 * (size_t) ntime));
+    double *d = ctx->d_ts[which].p;
     HIPCHK(hipMemcpy(d, time, (size_t) ntime * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d + ntime, vmr, (size_t) ntime * sizeof(double), hipMemcpyHostToDevice));
     h.time[which] = d;
     h.vmr[which] = d + ntime;
     h.ntime[which] = ntime;
   }
-  if (!ctx->d_tracers)
-    HIPCHK(hipMalloc((void **) &ctx->d_tracers, sizeof(DevTracerSeries)));
-  HIPCHK(hipMemcpy(ctx->d_tracers, &h, sizeof(DevTracerSeries), hipMemcpyHostToDevice));
+  HIPCHK(ctx->d_tracers.reserve(1));
+  HIPCHK(hipMemcpy(ctx->d_tracers.p, &h, sizeof(DevTracerSeries), hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -3767,22 +3580,16 @@ static int update_met_any(mphip_ctx *ctx, int slot, const mphip_met_t *met, cons
       ctx->uploader.join();
     if (ctx->copy_stream)
       HIPCHK(hipStreamSynchronize(ctx->copy_stream));
-    for (auto &q : ctx->next.f3) {
-      dev_free(q);
-      q = nullptr;
-    }
-    for (auto &q : ctx->next.f2) {
-      dev_free(q);
-      q = nullptr;
-    }
-    for (auto &b : ctx->codes) {   // (idle: every upload into a slot ends with its stream synchronised, the uploader was joined)
-      dev_free(b.p);
-      b = mphip_ctx::CodeBuf();
-    }
+    for (auto &q : ctx->next.f3)
+      q.release();
+    for (auto &q : ctx->next.f2)
+      q.release();
+    for (auto &b : ctx->codes)   // (idle: every upload into a slot ends with its stream synchronised, the uploader was joined)
+      b.release();
     ctx->next.valid = false;
     ctx->next_pending = false;
-    ctx->pk.release();
-    ctx->pk_next.release();
+    ctx->pk = mphip_ctx::PackedGrids();
+    ctx->pk_next = mphip_ctx::PackedGrids();
     ctx->pk_next_valid = false;
   }
   if (ctx->next_pending) {   // a snapshot uploaded now changes what the prefetched pair would have been packed from
@@ -3812,7 +3619,7 @@ static int update_met_any(mphip_ctx *ctx, int slot, const mphip_met_t *met, cons
               "the early exits of deposition, convection and turbulent diffusion are off (mphip_get_shortcuts)\n", first, last);
     }
   }
-  if (pk && reserve_codes(ctx, ctx->codes[0], packed_block_bytes(pk)))
+  if (pk && reserve(ctx, ctx->codes[0], packed_block_bytes(pk)))
     return 1;
   if (upload_fields(ctx, S, met, new_grid, ctx->stream, pk, ctx->codes[0].p))
     return 1;
@@ -3899,7 +3706,7 @@ static int prefetch_met_any(mphip_ctx *ctx, const mphip_met_t *met, const mphip_
   // page-locking arrays the caller owns is fragile (a copy has to lie inside one registration, arrays of
   // one allocation share pages, the caller may free them): an uploader thread of the library issues them
   // instead.  mphip_commit_met / mphip_discard_prefetch join it.
-  if (pk && reserve_codes(ctx, ctx->codes[1], packed_block_bytes(pk)))
+  if (pk && reserve(ctx, ctx->codes[1], packed_block_bytes(pk)))
     return 1;
   // (the uploader thread reads its own copy of the description: its base, and the packed one when there is one)
   mphip_met_packed_t desc_pk;
@@ -3926,7 +3733,7 @@ static int prefetch_met_any(mphip_ctx *ctx, const mphip_met_t *met, const mphip_
   bool pack_ahead = ctx->nml == 0;
   PackPlan plan;
   if (pack_ahead) {
-    MetSlot probe = ctx->next;   // (presence flags only)
+    MetSlot probe;   // (presence flags only)
     for (int f = 0; f < MPHIP_N3D; f++)
       probe.has3[f] = met->f3[f] != nullptr || (pk && pk->q3[f]);
     for (int f = 0; f < MPHIP_N2D; f++)
@@ -4250,7 +4057,7 @@ int mphip_derive_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const
   }
   if (what & MPHIP_PREP_CAPE) {
     const dim3 nb = blocks(c_cape);
-    if (call.launch(prep_cape_kernel, nb, lanes, lds_cape, G, O, ctx->d_clim, i3[MPHIP_T], i3[MPHIP_H2O], i2[MPHIP_PS],
+    if (call.launch(prep_cape_kernel, nb, lanes, lds_cape, G, O, ctx->d_clim.p, i3[MPHIP_T], i3[MPHIP_H2O], i2[MPHIP_PS],
                     o2[MPHIP_PLCL], o2[MPHIP_PLFC], o2[MPHIP_PEL], o2[MPHIP_CAPE], o2[MPHIP_CIN]))
       return 1;
   }
@@ -4276,7 +4083,7 @@ int mphip_derive_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const
     T.nprof = tropo_nprof;
     T.fine = tropo_fine;
     T.tab = d_tab;
-    if (call.launch(prep_tropo_kernel, nb, lanes, lds_tropo, G, O, T, ctx->d_clim, i3[MPHIP_T], i3[MPHIP_H2O], z_final,
+    if (call.launch(prep_tropo_kernel, nb, lanes, lds_tropo, G, O, T, ctx->d_clim.p, i3[MPHIP_T], i3[MPHIP_H2O], z_final,
                     T.mode == 5 ? pv_final : nullptr, o2[MPHIP_PT], o2[MPHIP_TT], o2[MPHIP_ZT], o2[MPHIP_H2OT]))
       return 1;
   }
@@ -4759,49 +4566,45 @@ int mphip_update_atm(mphip_ctx *ctx, long long np, long long ip0, long long np_t
   if (np && (!time || !p || !lon || !lat || (nq && !q)))
     return fail(ctx, "null particle array");
   HIPCHK(hipSetDevice(ctx->device));
-  const bool fresh = (np != ctx->np || nq != ctx->nq || !ctx->d_arr[0]);
+  const bool fresh = (np != ctx->np || nq != ctx->nq || !ctx->d_arr[0].p);
   if (fresh) {
     const size_t n = (size_t) std::max<long long>(np, 1);
     for (int k = 0; k < 4 + MPHIP_NQ_MAX; k++) {
       const size_t want = k < 4 + nq ? n : 0;
-      if (dev_alloc(ctx, &ctx->d_arr[k], want) || dev_alloc(ctx, &ctx->d_alt[k], want))
-        return 1;
+      HIPCHK(ctx->d_arr[k].resize(want));
+      HIPCHK(ctx->d_alt[k].resize(want));
     }
     for (int k = 0; k < 3; k++) {
-      if (dev_alloc(ctx, &ctx->d_uvwp[k], n) || dev_alloc(ctx, &ctx->d_uvwp_alt[k], n))
-        return 1;
-      HIPCHK(hipMemsetAsync(ctx->d_uvwp[k], 0, n * sizeof(float), ctx->stream));   // calloc'ed cache_t
+      HIPCHK(ctx->d_uvwp[k].resize(n));
+      HIPCHK(ctx->d_uvwp_alt[k].resize(n));
+      HIPCHK(hipMemsetAsync(ctx->d_uvwp[k].p, 0, n * sizeof(float), ctx->stream));   // calloc'ed cache_t
     }
-    if (dev_alloc(ctx, &ctx->d_dt, n) || dev_alloc(ctx, &ctx->d_dt_alt, n))
-      return 1;
-    HIPCHK(hipMemsetAsync(ctx->d_dt, 0, n * sizeof(double), ctx->stream));
-    if (dev_alloc(ctx, &ctx->d_ext, n) || dev_alloc(ctx, &ctx->d_ext_alt, n))
-      return 1;
-    for (int k = 0; k < 2; k++)
-      if (dev_alloc(ctx, &ctx->d_keys[k], n) || dev_alloc(ctx, &ctx->d_vals[k], n))
-        return 1;
-    if (dev_alloc(ctx, &ctx->d_cell, n))
-      return 1;
-    // the buffers of the sort that runs ahead trade places with d_keys / d_vals / d_dt when a sort is adopted,
-    // so after that they have whatever size those had: one capacity cannot describe them -- start over
-    for (int k = 0; k < 2; k++)
-      if (dev_alloc(ctx, &ctx->ahead_keys[k], 0) || dev_alloc(ctx, &ctx->ahead_vals[k], 0))
-        return 1;
-    if (dev_alloc(ctx, &ctx->ahead_dt, 0))
-      return 1;
-    ctx->ahead_cap = 0;
-    // ... and so do two buffers of the order repair (repair_sort swaps rep_fk / rep_fv with d_keys[0] / d_vals[0])
-    if (dev_alloc(ctx, &ctx->rep_sk, 0) || dev_alloc(ctx, &ctx->rep_si, 0) || dev_alloc(ctx, &ctx->rep_fk, 0)
-        || dev_alloc(ctx, &ctx->rep_fv, 0) || dev_alloc(ctx, &ctx->rep_mk[0], 0) || dev_alloc(ctx, &ctx->rep_mk[1], 0)
-        || dev_alloc(ctx, &ctx->rep_mi[0], 0) || dev_alloc(ctx, &ctx->rep_mi[1], 0))
-      return 1;
-    ctx->rep_cap = 0;
-    dev_free(ctx->d_iso);
-    dev_free(ctx->d_iso_alt);
-    ctx->d_iso = ctx->d_iso_alt = nullptr;
-    dev_free(ctx->d_kz);
-    dev_free(ctx->d_kz_alt);
-    ctx->d_kz = ctx->d_kz_alt = nullptr;
+    HIPCHK(ctx->d_dt.resize(n));
+    HIPCHK(ctx->d_dt_alt.resize(n));
+    HIPCHK(hipMemsetAsync(ctx->d_dt.p, 0, n * sizeof(double), ctx->stream));
+    HIPCHK(ctx->d_ext.resize(n));
+    HIPCHK(ctx->d_ext_alt.resize(n));
+    for (int k = 0; k < 2; k++) {
+      HIPCHK(ctx->d_keys[k].resize(n));
+      HIPCHK(ctx->d_vals[k].resize(n));
+    }
+    HIPCHK(ctx->d_cell.resize(n));
+    // the per-particle buffers of the sort ahead and of the order repair come back at the new count on first use
+    for (int k = 0; k < 2; k++) {
+      ctx->ahead_keys[k].release();
+      ctx->ahead_vals[k].release();
+      ctx->rep_mk[k].release();
+      ctx->rep_mi[k].release();
+    }
+    ctx->ahead_dt.release();
+    ctx->rep_sk.release();
+    ctx->rep_si.release();
+    ctx->rep_fk.release();
+    ctx->rep_fv.release();
+    ctx->d_iso.release();
+    ctx->d_iso_alt.release();
+    ctx->d_kz.release();
+    ctx->d_kz_alt.release();
     ctx->sorted_buf = -1;
     ctx->stored_is_sorted = false;
   }
@@ -4824,11 +4627,11 @@ int mphip_update_atm(mphip_ctx *ctx, long long np, long long ip0, long long np_t
     pin_host_span(ctx, all, 4 + nq, (size_t) np * sizeof(double));
   }
   for (int k = 0; k < 4 && np; k++)
-    HIPCHK(hipMemcpyAsync(ctx->d_arr[k], src[k], (size_t) np * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->d_arr[k].p, src[k], (size_t) np * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   for (int iq = 0; iq < nq && np; iq++) {
     if (!q[iq])
       return fail(ctx, "null quantity array");
-    HIPCHK(hipMemcpyAsync(ctx->d_arr[4 + iq], q[iq], (size_t) np * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->d_arr[4 + iq].p, q[iq], (size_t) np * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   }
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return 0;
@@ -4846,11 +4649,11 @@ int mphip_update_quantity(mphip_ctx *ctx, int iq, const double *q) {
     return 0;
   const size_t bytes = (size_t) ctx->np * sizeof(double);
   if (ctx->ext_identity) {
-    HIPCHK(hipMemcpyAsync(ctx->d_arr[4 + iq], q, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->d_arr[4 + iq].p, q, bytes, hipMemcpyHostToDevice, ctx->stream));
   } else {   // through the alternate buffer (free between two sorts), then into the stored order
-    HIPCHK(hipMemcpyAsync(ctx->d_alt[4 + iq], q, bytes, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(gather_by_ext_kernel, dim3(grid_for(ctx->np)), dim3(256), 0, ctx->stream, ctx->d_alt[4 + iq],
-                       ctx->d_ext, ctx->d_arr[4 + iq], ctx->np);
+    HIPCHK(hipMemcpyAsync(ctx->d_alt[4 + iq].p, q, bytes, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(gather_by_ext_kernel, dim3(grid_for(ctx->np)), dim3(256), 0, ctx->stream, ctx->d_alt[4 + iq].p,
+                       ctx->d_ext.p, ctx->d_arr[4 + iq].p, ctx->np);
     HIPCHK(hipGetLastError());
   }
   HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -4865,10 +4668,10 @@ int mphip_get_atm(mphip_ctx *ctx, double *time, double *p, double *lon, double *
     return 1;
   // The caller's order is produced in the alternate buffers (free between two sorts); the resident
   // arrays keep their internal order, so an output costs one scatter pass and no re-sort.
-  double *const *srcs = ctx->d_arr;
+  const DevBuf<double> *srcs = ctx->d_arr;
   if (!ctx->ext_identity && ctx->np) {
     PermArgs g = perm_args(ctx, false);
-    if (permute_random(ctx, g, ctx->d_ext, ctx->np, true))
+    if (permute_random(ctx, g, ctx->d_ext.p, ctx->np, true))
       return 1;
     srcs = ctx->d_alt;
   }
@@ -4881,10 +4684,10 @@ int mphip_get_atm(mphip_ctx *ctx, double *time, double *p, double *lon, double *
   }
   for (int k = 0; k < 4; k++)
     if (dst[k] && ctx->np)
-      HIPCHK(hipMemcpyAsync(dst[k], srcs[k], (size_t) ctx->np * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(hipMemcpyAsync(dst[k], srcs[k].p, (size_t) ctx->np * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   for (int iq = 0; iq < ctx->nq; iq++)
     if (q && q[iq] && ctx->np)
-      HIPCHK(hipMemcpyAsync(q[iq], srcs[4 + iq], (size_t) ctx->np * sizeof(double), hipMemcpyDeviceToHost,
+      HIPCHK(hipMemcpyAsync(q[iq], srcs[4 + iq].p, (size_t) ctx->np * sizeof(double), hipMemcpyDeviceToHost,
                             ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return 0;
@@ -4905,7 +4708,7 @@ int mphip_update_cache(mphip_ctx *ctx, const float *uvwp, const uint64_t *rng_ct
     for (int k = 0; k < 3; k++) {
       for (long long i = 0; i < ctx->np; i++)
         tmp[(size_t) i] = uvwp[3 * (size_t) i + k];
-      HIPCHK(hipMemcpy(ctx->d_uvwp[k], tmp.data(), tmp.size() * sizeof(float), hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(ctx->d_uvwp[k].p, tmp.data(), tmp.size() * sizeof(float), hipMemcpyHostToDevice));
     }
   }
   return 0;
@@ -4923,13 +4726,13 @@ int mphip_get_cache(mphip_ctx *ctx, float *uvwp, double *dt, uint64_t *rng_ctr) 
   if (uvwp && ctx->np) {
     std::vector<float> tmp((size_t) ctx->np);
     for (int k = 0; k < 3; k++) {
-      HIPCHK(hipMemcpy(tmp.data(), ctx->d_uvwp[k], tmp.size() * sizeof(float), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(tmp.data(), ctx->d_uvwp[k].p, tmp.size() * sizeof(float), hipMemcpyDeviceToHost));
       for (long long i = 0; i < ctx->np; i++)
         uvwp[3 * (size_t) i + k] = tmp[(size_t) i];
     }
   }
   if (dt && ctx->np)
-    HIPCHK(hipMemcpy(dt, ctx->d_dt, (size_t) ctx->np * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(dt, ctx->d_dt.p, (size_t) ctx->np * sizeof(double), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -4942,15 +4745,15 @@ int mphip_update_iso(mphip_ctx *ctx, const double *iso_var, const double *iso_ts
   if (iso_var && ctx->np) {
     if (restore_external_order(ctx) || ensure_iso(ctx))
       return 1;
-    HIPCHK(hipMemcpyAsync(ctx->d_iso, iso_var, (size_t) ctx->np * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->d_iso.p, iso_var, (size_t) ctx->np * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   }
   if (iso_ts && iso_ps) {
     if (iso_n < 1)
       return fail(ctx, "Could not read any data!");   // module_isosurf_init, mptrac.c:4943-4944
-    if (dev_alloc(ctx, &ctx->d_iso_ts, (size_t) iso_n) || dev_alloc(ctx, &ctx->d_iso_ps, (size_t) iso_n))
-      return 1;
-    HIPCHK(hipMemcpyAsync(ctx->d_iso_ts, iso_ts, (size_t) iso_n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(ctx->d_iso_ps, iso_ps, (size_t) iso_n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx->d_iso_ts.resize((size_t) iso_n));
+    HIPCHK(ctx->d_iso_ps.resize((size_t) iso_n));
+    HIPCHK(hipMemcpyAsync(ctx->d_iso_ts.p, iso_ts, (size_t) iso_n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->d_iso_ps.p, iso_ps, (size_t) iso_n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     ctx->iso_n = iso_n;
   }
   HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -4962,11 +4765,11 @@ int mphip_get_iso(mphip_ctx *ctx, double *iso_var) {
     return 1;
   HIPCHK(hipSetDevice(ctx->device));
   if (iso_var && ctx->np) {
-    if (!ctx->d_iso)
+    if (!ctx->d_iso.p)
       return fail(ctx, "cache->iso_var is not on the device (no isosurface mode has run)");
     if (restore_external_order(ctx))
       return 1;
-    HIPCHK(hipMemcpyAsync(iso_var, ctx->d_iso, (size_t) ctx->np * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(iso_var, ctx->d_iso.p, (size_t) ctx->np * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
   }
   return 0;
@@ -5058,9 +4861,9 @@ int mphip_run_timestep(mphip_ctx *ctx, double t) {
     if (mixing_plan(ctx, t, &plan, &act) || ahead_ensure(ctx))
       return 1;
     if (act) {
-      ek.keys = ctx->ahead_keys[0];
-      ek.dt_next = ctx->ahead_dt;
-      ek.cell = ctx->d_cell;
+      ek.keys = ctx->ahead_keys[0].p;
+      ek.dt_next = ctx->ahead_dt.p;
+      ek.cell = ctx->d_cell.p;
       ek.grid = plan.box.grid;
       ek.box_t0 = plan.box.t0;
       ek.box_t1 = plan.box.t1;
@@ -5073,12 +4876,8 @@ int mphip_run_timestep(mphip_ctx *ctx, double t) {
       constexpr unsigned kDepo = MPHIP_MOD_WET_DEPO | MPHIP_MOD_DRY_DEPO;
       // (the flags measured against a deposition launch that decides from dt, time, p itself: profiles/r06_ab_depo_flags.txt)
       if ((tail & kDepo) && !(tail & ~kDepo) && ctx->compact_depo) {   // the deposition launch behind module_mixing will be depo_kernel
-        if (ctx->np > ctx->depo_busy_cap) {
-          if (dev_alloc(ctx, &ctx->d_depo_busy, (size_t) ctx->np))
-            return 1;
-          ctx->depo_busy_cap = ctx->np;
-        }
-        ek.depo_busy = ctx->d_depo_busy;
+        HIPCHK(ctx->d_depo_busy.reserve((size_t) ctx->np));
+        ek.depo_busy = ctx->d_depo_busy.p;
         ek.depo_mask = tail;
       }
     }
@@ -5090,7 +4889,7 @@ int mphip_run_timestep(mphip_ctx *ctx, double t) {
     MixPlan plan;
     if (mixing_plan(ctx, t, &plan, &cells_ready))
       return 1;
-    const BoxArgs box = { ctx->d_cell, plan.box.grid, plan.box.t0, plan.box.t1, plan.box.ens, plan.box.ngrid };
+    const BoxArgs box = { ctx->d_cell.p, plan.box.grid, plan.box.t0, plan.box.t1, plan.box.ens, plan.box.ngrid };
     if (!ctx->ahead_box)
       cells_ready = false;
     if (ahead_launch(ctx, t_next, cells_ready ? &box : nullptr, emitted && cells_ready))
@@ -5154,7 +4953,7 @@ int mphip_run_timesteps(mphip_ctx *ctx, double t_first, int nsteps) {
     // instantiation: ruled out here, so that their due step goes to mphip_run_timestep without being planned twice)
     const bool fold = quiet && ctx->fold_resort && ctx->locality_interval > 0
       && ctx->steps_since_resort >= ctx->locality_interval && !ctx->ext_identity
-      && !ml_winds(c) && !ctx->d_iso && !ctx->d_kz && ctx->lds_tile <= 0;
+      && !ml_winds(c) && !ctx->d_iso.p && !ctx->d_kz.p && ctx->lds_tile <= 0;
     if (quiet) {
       batch = nsteps - done;
       if (ctx->locality_interval > 0)
@@ -5183,7 +4982,7 @@ int mphip_run_timesteps(mphip_ctx *ctx, double t_first, int nsteps) {
         return 1;
       P = plan_step(ctx, t);
       const unsigned sel = step_kernel_mask(ctx, P.mask | P.tail, batch);
-      if (sel == kNoStepKernel || (ml_winds(c) && !ctx->d_kz) || (fold && !step_kernel_stores_once(sel)))
+      if (sel == kNoStepKernel || (ml_winds(c) && !ctx->d_kz.p) || (fold && !step_kernel_stores_once(sel)))
         batch = 1;
     }
     if (batch < 2) {
@@ -5273,16 +5072,15 @@ int mphip_get_sort(mphip_ctx *ctx, double *keys, int *perm) {
   HIPCHK(hipSetDevice(ctx->device));
   const long long n = ctx->np;
   if (perm)
-    HIPCHK(hipMemcpyAsync(perm, ctx->d_vals[ctx->sorted_buf], (size_t) n * sizeof(int), hipMemcpyDeviceToHost,
+    HIPCHK(hipMemcpyAsync(perm, ctx->d_vals[ctx->sorted_buf].p, (size_t) n * sizeof(int), hipMemcpyDeviceToHost,
                           ctx->stream));
   if (keys) {
-    double *d_tmp = nullptr;
-    HIPCHK(hipMalloc((void **) &d_tmp, (size_t) n * sizeof(double)));
+    DevBuf<double> d_tmp;
+    HIPCHK(d_tmp.resize((size_t) n));
     hipLaunchKernelGGL(keys_to_double_kernel, dim3(grid_for(n)), dim3(256), 0, ctx->stream,
-                       ctx->d_keys[ctx->sorted_buf], d_tmp, n);
-    HIPCHK(hipMemcpyAsync(keys, d_tmp, (size_t) n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+                       ctx->d_keys[ctx->sorted_buf].p, d_tmp.p, n);
+    HIPCHK(hipMemcpyAsync(keys, d_tmp.p, (size_t) n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    HIPCHK(hipFree(d_tmp));
   }
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return 0;
@@ -5299,18 +5097,18 @@ int mphip_grid_sums(mphip_ctx *ctx, double t, int *cnt, double *mean, double *si
   const mphip_ctl_t &c = ctx->ctl;
   const size_t ncell = (size_t) c.grid_nx * c.grid_ny * c.grid_nz;
   const size_t total = ncell * (size_t) (1 + 2 * ctx->nq);
-  if (ensure_sums(ctx, total))
+  if (reserve(ctx, ctx->d_sums, total))
     return 1;
   const bool ordered = ctx->deterministic_sums != 0;
   const DevAtm a = dev_atm(ctx);
-  const GridKernel kern = { ctx->d_grid_kernel, ctx->d_grid_kernel ? ctx->d_grid_kernel + ctx->grid_nk : nullptr, a.p,
+  const GridKernel kern = { ctx->d_grid_kernel.p, ctx->d_grid_kernel.p ? ctx->d_grid_kernel.p + ctx->grid_nk : nullptr, a.p,
                             ctx->grid_nk };
   const BoxGrid G = { c.grid_lon0, c.grid_lon1, c.grid_lat0, c.grid_lat1, c.grid_z0, c.grid_z1, c.grid_nx, c.grid_ny,
                       c.grid_nz };
   const GridBoxArgs gbox = { G, t - 0.5 * c.dt_mod, t + 0.5 * c.dt_mod, a.time, a.lon, a.lat, a.p };
   if (ctx->np && !ordered)   // (the ordered sums compute the box index on their way)
     hipLaunchKernelGGL(box_index_kernel, dim3(grid_for(ctx->np)), dim3(256), 0, ctx->stream, a, G, gbox.t0, gbox.t1,
-                       ctx->d_cell, (const double *) nullptr, 0);
+                       ctx->d_cell.p, (const double *) nullptr, 0);
   if (ordered) {
     GridVals vals;
     for (int iq = 0; iq < ctx->nq; iq++)
@@ -5322,47 +5120,31 @@ int mphip_grid_sums(mphip_ctx *ctx, double t, int *cnt, double *mean, double *si
     // memory for it the sums gather from the arrays
     if (ctx->nq >= 2 && ctx->np > 0 && ctx->grid_records) {
       const size_t need = (size_t) ctx->np * (size_t) ctx->nq;
-      if (need > ctx->rec_cap) {
-        dev_free(ctx->d_rec);
-        ctx->d_rec = nullptr;
-        ctx->rec_cap = 0;
-        if (hipMalloc((void **) &ctx->d_rec, need * sizeof(double)) == hipSuccess)
-          ctx->rec_cap = need;
-        else
-          (void) hipGetLastError();
-      }
-      if (ctx->d_rec) {
-        hipLaunchKernelGGL(grid_records_kernel, dim3(grid_for(ctx->np)), dim3(256), 0, ctx->stream, vals, ctx->np, ctx->d_rec);
-        vals.rec = ctx->d_rec;
+      if (ctx->d_rec.try_reserve(need)) {
+        hipLaunchKernelGGL(grid_records_kernel, dim3(grid_for(ctx->np)), dim3(256), 0, ctx->stream, vals, ctx->np, ctx->d_rec.p);
+        vals.rec = ctx->d_rec.p;
       }
     }
     // [counts | sums of q | sums of q^2], as grid_accumulate_kernel
-    if (ordered_cell_sums(ctx, vals, 2 * ctx->nq, c.grid_nz, ncell, ctx->d_sums + ncell, (int *) nullptr, ctx->d_sums, true,
+    if (ordered_cell_sums(ctx, vals, 2 * ctx->nq, c.grid_nz, ncell, ctx->d_sums.p + ncell, (int *) nullptr, ctx->d_sums.p, true,
                           &gbox))
       return 1;
   } else {
-    HIPCHK(hipMemsetAsync(ctx->d_sums, 0, total * sizeof(double), ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_sums.p, 0, total * sizeof(double), ctx->stream));
     if (ctx->np) {
       const AccumGeom g = accum_geom(ctx, 1 + 2 * ctx->nq);
-      hipLaunchKernelGGL(grid_accumulate_kernel, dim3(g.nblocks), dim3(256), g.lds, ctx->stream, a, ctx->d_cell, ctx->nq,
-                         ncell, ctx->d_sums, g.T, g.per_block, kern);
+      hipLaunchKernelGGL(grid_accumulate_kernel, dim3(g.nblocks), dim3(256), g.lds, ctx->stream, a, ctx->d_cell.p, ctx->nq,
+                         ncell, ctx->d_sums.p, g.T, g.per_block, kern);
     }
   }
   HIPCHK(hipGetLastError());
-  if (run_allreduce(ctx, ctx->d_sums, total))
+  if (run_allreduce(ctx, ctx->d_sums.p, total))
     return 1;
   // through a page-locked staging buffer of the context: from pageable memory the 3.6 MB of a 360 x 180 grid
   // with three quantities took 0.3 ms of the output's 0.9
-  if (total > ctx->h_sums_cap) {
-    if (ctx->h_sums)
-      (void) hipHostFree(ctx->h_sums);
-    ctx->h_sums = nullptr;
-    ctx->h_sums_cap = 0;
-    HIPCHK(hipHostMalloc((void **) &ctx->h_sums, total * sizeof(double), hipHostMallocDefault));
-    ctx->h_sums_cap = total;
-  }
-  double *h = ctx->h_sums;
-  HIPCHK(hipMemcpyAsync(h, ctx->d_sums, total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx->h_sums.reserve(total));
+  double *h = ctx->h_sums.p;
+  HIPCHK(hipMemcpyAsync(h, ctx->d_sums.p, total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   for (size_t i = 0; i < ncell; i++)
     cnt[i] = (int) h[i];
@@ -5380,8 +5162,7 @@ int ana_common(mphip_ctx *ctx, const char *what) {
     return fail(ctx, "control parameters were not uploaded");
   if (ctx->ctl.met_coord_type != 0)
     return fail(ctx, std::string(what) + ": Only lat/lon grid supported");
-  if (!ctx->d_ana_flags && dev_alloc(ctx, &ctx->d_ana_flags, 8))
-    return 1;
+  HIPCHK(ctx->d_ana_flags.reserve(8));
   return 0;
 }
 
@@ -5403,41 +5184,17 @@ int ana_kernel_fn(mphip_ctx *ctx, int nk, const double *kz, const double *kw, Ke
   for (int k = 1; k < nk; k++)
     if (kz[k] < kz[k - 1])
       return fail(ctx, "height levels of the kernel function must be ascending");
-  if (2 * (size_t) nk > ctx->ana_kernel_cap) {
-    if (dev_alloc(ctx, &ctx->d_ana_kernel, 2 * (size_t) nk))
-      return 1;
-    ctx->ana_kernel_cap = 2 * (size_t) nk;
-  }
-  HIPCHK(hipMemcpyAsync(ctx->d_ana_kernel, kz, (size_t) nk * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(ctx->d_ana_kernel + nk, kw, (size_t) nk * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  K->kz = ctx->d_ana_kernel;
-  K->kw = ctx->d_ana_kernel + nk;
+  HIPCHK(ctx->d_ana_kernel.reserve(2 * (size_t) nk));
+  HIPCHK(hipMemcpyAsync(ctx->d_ana_kernel.p, kz, (size_t) nk * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(ctx->d_ana_kernel.p + nk, kw, (size_t) nk * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  K->kz = ctx->d_ana_kernel.p;
+  K->kw = ctx->d_ana_kernel.p + nk;
   K->nk = nk;
   return 0;
 }
 
-// a value per stored particle / per record (shares the record buffer of mphip_grid_sums)
-int ensure_rec(mphip_ctx *ctx, size_t need) {
-  if (need > ctx->rec_cap) {
-    ctx->rec_cap = 0;
-    if (dev_alloc(ctx, &ctx->d_rec, need))
-      return 1;
-    ctx->rec_cap = need;
-  }
-  return 0;
-}
-
-int ensure_h_sums(mphip_ctx *ctx, size_t total) {
-  if (total > ctx->h_sums_cap) {
-    if (ctx->h_sums)
-      (void) hipHostFree(ctx->h_sums);
-    ctx->h_sums = nullptr;
-    ctx->h_sums_cap = 0;
-    HIPCHK(hipHostMalloc((void **) &ctx->h_sums, total * sizeof(double), hipHostMallocDefault));
-    ctx->h_sums_cap = total;
-  }
-  return 0;
-}
+// (d_rec, a value per stored particle / per record, is the record buffer of mphip_grid_sums: there the gridded sums
+// do without it when it cannot be had; the analysis outputs need it, reserve(ctx, ctx->d_rec, ...))
 
 // Exclusive scan of the np + 1 counts in ctx->d_marks (the last one is zero): offset of element e afterwards =
 // d_marks[e] + chunk_off[e >> shift]; the total (offset of element np) goes to d_ana_flags[1].
@@ -5448,12 +5205,8 @@ struct MarkScan {
 
 int ensure_marks(mphip_ctx *ctx, MarkScan *M) {
   const size_t m = (size_t) ctx->np + 1;
-  if (m + kScanThreads > ctx->marks_cap) {
-    if (dev_alloc(ctx, &ctx->d_marks, m + kScanThreads))
-      return 1;
-    ctx->marks_cap = m + kScanThreads;
-  }
-  M->chunk_off = ctx->d_marks + m;
+  HIPCHK(ctx->d_marks.reserve(m + kScanThreads));
+  M->chunk_off = ctx->d_marks.p + m;
   M->shift = m <= (size_t) kScanThreads * kScanPerLarge * kScanThreads ? 14 : 16;
   if (((m + ((size_t) 1 << M->shift) - 1) >> M->shift) > (size_t) kScanThreads)
     return fail(ctx, "too many particles for the scan of the analysis outputs");
@@ -5464,14 +5217,14 @@ int scan_marks(mphip_ctx *ctx, const MarkScan &M) {
   const size_t m = (size_t) ctx->np + 1;
   const int nchunks = (int) ((m + ((size_t) 1 << M.shift) - 1) >> M.shift);
   if (M.shift == 14)
-    hipLaunchKernelGGL(sort_scan_local_kernel<kScanPerLarge>, dim3(nchunks), dim3(kScanThreads), 0, ctx->stream, ctx->d_marks,
+    hipLaunchKernelGGL(sort_scan_local_kernel<kScanPerLarge>, dim3(nchunks), dim3(kScanThreads), 0, ctx->stream, ctx->d_marks.p,
                        m, M.chunk_off, (const uint32_t *) nullptr, 0);
   else
-    hipLaunchKernelGGL(sort_scan_local_kernel<64>, dim3(nchunks), dim3(kScanThreads), 0, ctx->stream, ctx->d_marks, m,
+    hipLaunchKernelGGL(sort_scan_local_kernel<64>, dim3(nchunks), dim3(kScanThreads), 0, ctx->stream, ctx->d_marks.p, m,
                        M.chunk_off, (const uint32_t *) nullptr, 0);
   hipLaunchKernelGGL(sort_scan_chunks_kernel, dim3(1), dim3(kScanThreads), 0, ctx->stream, M.chunk_off, nchunks);
-  hipLaunchKernelGGL(scan_total_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->d_marks, M.chunk_off, M.shift, ctx->np,
-                     ctx->d_ana_flags + 1);
+  hipLaunchKernelGGL(scan_total_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->d_marks.p, M.chunk_off, M.shift, ctx->np,
+                     ctx->d_ana_flags.p + 1);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -5513,26 +5266,27 @@ int mphip_box_sums(mphip_ctx *ctx, const mphip_box_t *box, double t, int qnt, in
   B.qnt_member = qnt_member;
   B.nmember = nmember;
   B.ncell = (int) ncell;
-  if (ana_kernel_fn(ctx, nk, kz, kw, &B.K) || ensure_sums(ctx, ntot) || ensure_rec(ctx, (size_t) std::max<long long>(ctx->np, 1)))
+  if (ana_kernel_fn(ctx, nk, kz, kw, &B.K) || reserve(ctx, ctx->d_sums, ntot)
+      || reserve(ctx, ctx->d_rec, (size_t) std::max<long long>(ctx->np, 1)))
     return 1;
-  int *bad = (int *) ctx->d_ana_flags;
+  int *bad = (int *) ctx->d_ana_flags.p;
   HIPCHK(hipMemsetAsync(bad, 0x7f, sizeof(int), ctx->stream));   // 0x7f7f7f7f: above every index
-  hipLaunchKernelGGL(box_member_cell_kernel, dim3(grid_for(ctx->np)), dim3(256), 0, ctx->stream, dev_atm(ctx), B, ctx->d_cell,
-                     ctx->d_rec, bad);
+  hipLaunchKernelGGL(box_member_cell_kernel, dim3(grid_for(ctx->np)), dim3(256), 0, ctx->stream, dev_atm(ctx), B, ctx->d_cell.p,
+                     ctx->d_rec.p, bad);
   HIPCHK(hipGetLastError());
   int h_bad = 0;
   HIPCHK(hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   if (h_bad != 0x7f7f7f7f)
     return fail(ctx, "Ensemble ID out of range! (particle " + std::to_string(ctx->ip0 + h_bad) + ")");
-  const ArrayVals vals = { ctx->d_rec };
-  if (ordered_cell_sums(ctx, vals, 1, box->nz, ntot, ctx->d_sums, (int *) nullptr, (double *) nullptr, true))
+  const ArrayVals vals = { ctx->d_rec.p };
+  if (ordered_cell_sums(ctx, vals, 1, box->nz, ntot, ctx->d_sums.p, (int *) nullptr, (double *) nullptr, true))
     return 1;
-  if (run_allreduce(ctx, ctx->d_sums, ntot) || ensure_h_sums(ctx, ntot))
+  if (run_allreduce(ctx, ctx->d_sums.p, ntot) || reserve(ctx, ctx->h_sums, ntot))
     return 1;
-  HIPCHK(hipMemcpyAsync(ctx->h_sums, ctx->d_sums, ntot * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(ctx->h_sums.p, ctx->d_sums.p, ntot * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  memcpy(sum, ctx->h_sums, ntot * sizeof(double));
+  memcpy(sum, ctx->h_sums.p, ntot * sizeof(double));
   return 0;
 }
 
@@ -5559,7 +5313,8 @@ int mphip_sample_obs(mphip_ctx *ctx, double t0, double t1, int nobs, const doubl
   S.nobs = nobs;
   S.qnt_m = qnt_m;
   MarkScan M;
-  if (ana_kernel_fn(ctx, nk, kz, kw, &S.K) || ensure_sums(ctx, (size_t) (kObsFields + 2) * (size_t) nobs) || ensure_marks(ctx, &M))
+  if (ana_kernel_fn(ctx, nk, kz, kw, &S.K) || reserve(ctx, ctx->d_sums, (size_t) (kObsFields + 2) * (size_t) nobs)
+      || ensure_marks(ctx, &M))
     return 1;
   // the observations as the kernel stages them: centre, latitude, pressures of the top and the bottom of the layer
   std::vector<double> h_obs((size_t) kObsFields * (size_t) nobs);
@@ -5570,24 +5325,24 @@ int mphip_sample_obs(mphip_ctx *ctx, double t0, double t1, int nobs, const doubl
     o[4] = 1013.25 * exp(-(obs_z[i] + dz) / 7.0);
     o[5] = 1013.25 * exp(-(obs_z[i] - dz) / 7.0);
   }
-  double *d_obs = ctx->d_sums, *d_out = ctx->d_sums + (size_t) kObsFields * (size_t) nobs;
+  double *d_obs = ctx->d_sums.p, *d_out = ctx->d_sums.p + (size_t) kObsFields * (size_t) nobs;
   HIPCHK(hipMemcpyAsync(d_obs, h_obs.data(), h_obs.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemsetAsync(d_out, 0, 2 * (size_t) nobs * sizeof(double), ctx->stream));
   uint32_t nrec = 0;
   if (ctx->np > 0) {
     const DevAtm a = dev_atm(ctx);
     const int blocks = grid_for(ctx->np);
-    hipLaunchKernelGGL(sample_hits_kernel<false>, dim3(blocks), dim3(256), 0, ctx->stream, a, S, d_obs, ctx->d_marks,
+    hipLaunchKernelGGL(sample_hits_kernel<false>, dim3(blocks), dim3(256), 0, ctx->stream, a, S, d_obs, ctx->d_marks.p,
                        (const uint32_t *) nullptr, 0, (uint32_t *) nullptr, (double *) nullptr);
     HIPCHK(hipGetLastError());
     // the number of records: every particle's count is at most nobs, so 64 bits hold their sum; the scan works in 32
-    HIPCHK(hipMemsetAsync(ctx->d_ana_flags + 2, 0, 2 * sizeof(uint32_t), ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_ana_flags.p + 2, 0, 2 * sizeof(uint32_t), ctx->stream));
     hipLaunchKernelGGL(count_total_kernel, dim3(grid_for(ctx->np)), dim3(256), 0, ctx->stream,
-                       (const uint32_t *) ctx->d_marks, ctx->np, (unsigned long long *) (ctx->d_ana_flags + 2));
+                       (const uint32_t *) ctx->d_marks.p, ctx->np, (unsigned long long *) (ctx->d_ana_flags.p + 2));
     if (scan_marks(ctx, M))
       return 1;
     uint32_t h_flags[4] = { 0, 0, 0, 0 };
-    HIPCHK(hipMemcpyAsync(h_flags, ctx->d_ana_flags, sizeof(h_flags), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(h_flags, ctx->d_ana_flags.p, sizeof(h_flags), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     const unsigned long long total = ((unsigned long long) h_flags[3] << 32) | h_flags[2];
     if (total > 0x7fffffffULL || total != h_flags[1])
@@ -5595,35 +5350,31 @@ int mphip_sample_obs(mphip_ctx *ctx, double t0, double t1, int nobs, const doubl
     nrec = h_flags[1];
     if (nrec > 0) {
       const size_t words32 = 4 * (size_t) nrec;
-      if ((words32 + 1) / 2 > ctx->lists_cap) {
-        if (dev_alloc(ctx, &ctx->d_lists, (words32 + 1) / 2))
-          return 1;
-        ctx->lists_cap = (words32 + 1) / 2;
-      }
-      if (ensure_rec(ctx, nrec))
+      HIPCHK(ctx->d_lists.reserve((words32 + 1) / 2));
+      if (reserve(ctx, ctx->d_rec, nrec))
         return 1;
-      uint32_t *base = (uint32_t *) ctx->d_lists;
+      uint32_t *base = (uint32_t *) ctx->d_lists.p;
       uint32_t *keys[2] = { base, base + 2 * (size_t) nrec };
       int *ids[2] = { (int *) (base + (size_t) nrec), (int *) (base + 3 * (size_t) nrec) };
-      hipLaunchKernelGGL(sample_hits_kernel<true>, dim3(blocks), dim3(256), 0, ctx->stream, a, S, d_obs, ctx->d_marks,
-                         (const uint32_t *) M.chunk_off, M.shift, keys[0], ctx->d_rec);
+      hipLaunchKernelGGL(sample_hits_kernel<true>, dim3(blocks), dim3(256), 0, ctx->stream, a, S, d_obs, ctx->d_marks.p,
+                         (const uint32_t *) M.chunk_off, M.shift, keys[0], ctx->d_rec.p);
       HIPCHK(hipGetLastError());
       int cur = 0;
       if (radix_passes(ctx, keys, ids, nrec, bits_for((unsigned long long) (nobs - 1)), &cur, nullptr, true))
         return 1;
       hipLaunchKernelGGL(sample_sum_kernel, dim3(grid_for((long long) nobs * 64)), dim3(256), 0, ctx->stream, keys[cur],
-                         ids[cur], ctx->d_rec, nrec, nobs, d_out);
+                         ids[cur], ctx->d_rec.p, nrec, nobs, d_out);
       HIPCHK(hipGetLastError());
     }
   }
-  if (run_allreduce(ctx, d_out, 2 * (size_t) nobs) || ensure_h_sums(ctx, 2 * (size_t) nobs))
+  if (run_allreduce(ctx, d_out, 2 * (size_t) nobs) || reserve(ctx, ctx->h_sums, 2 * (size_t) nobs))
     return 1;
-  HIPCHK(hipMemcpyAsync(ctx->h_sums, d_out, 2 * (size_t) nobs * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(ctx->h_sums.p, d_out, 2 * (size_t) nobs * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   for (int i = 0; i < nobs; i++) {
-    count[i] = (int) ctx->h_sums[(size_t) nobs + (size_t) i];
+    count[i] = (int) ctx->h_sums.p[(size_t) nobs + (size_t) i];
     if (mass)
-      mass[i] = ctx->h_sums[i];
+      mass[i] = ctx->h_sums.p[i];
   }
   return 0;
 }
@@ -5654,21 +5405,17 @@ int mphip_station_hits(mphip_ctx *ctx, double t, double lon, double lat, double 
   geo2cart_host(lon, lat, S.centre);
   S.qnt_stat = qnt_stat < 0 ? -1 : qnt_stat;
   MarkScan M;
-  if (ensure_marks(ctx, &M) || ensure_rec(ctx, (size_t) ctx->np))
+  if (ensure_marks(ctx, &M) || reserve(ctx, ctx->d_rec, (size_t) ctx->np))
     return 1;
-  if ((size_t) ctx->np > ctx->slot_of_cap) {
-    if (dev_alloc(ctx, &ctx->d_slot_of, (size_t) ctx->np))
-      return 1;
-    ctx->slot_of_cap = (size_t) ctx->np;
-  }
+  HIPCHK(ctx->d_slot_of.reserve((size_t) ctx->np));
   const DevAtm a = dev_atm(ctx);
-  hipLaunchKernelGGL(station_mark_kernel, dim3(grid_for(ctx->np)), dim3(256), 0, ctx->stream, a, S, ctx->d_marks, ctx->d_slot_of,
-                     ctx->d_rec);
+  hipLaunchKernelGGL(station_mark_kernel, dim3(grid_for(ctx->np)), dim3(256), 0, ctx->stream, a, S, ctx->d_marks.p,
+                     ctx->d_slot_of.p, ctx->d_rec.p);
   HIPCHK(hipGetLastError());
   if (scan_marks(ctx, M))
     return 1;
   uint32_t total = 0;
-  HIPCHK(hipMemcpyAsync(&total, ctx->d_ana_flags + 1, sizeof(total), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(&total, ctx->d_ana_flags.p + 1, sizeof(total), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   *nhit = (int) total;
   if (total == 0)
@@ -5676,25 +5423,25 @@ int mphip_station_hits(mphip_ctx *ctx, double t, double lon, double lat, double 
   if (total > (uint32_t) cap) {   // the caller comes back with a larger buffer: nothing may have changed
     if (S.qnt_stat >= 0) {
       hipLaunchKernelGGL(station_restore_kernel, dim3(grid_for(ctx->np)), dim3(256), 0, ctx->stream, a, S.qnt_stat,
-                         (const uint32_t *) ctx->d_marks, (const uint32_t *) M.chunk_off, M.shift, (const int *) ctx->d_slot_of,
-                         (const double *) ctx->d_rec);
+                         (const uint32_t *) ctx->d_marks.p, (const uint32_t *) M.chunk_off, M.shift, (const int *) ctx->d_slot_of.p,
+                         (const double *) ctx->d_rec.p);
       HIPCHK(hipGetLastError());
       HIPCHK(hipStreamSynchronize(ctx->stream));
     }
     return 0;
   }
   const size_t width = 5 + (size_t) ctx->nq, words = (size_t) total * width;
-  if (ensure_sums(ctx, words) || ensure_h_sums(ctx, words))
+  if (reserve(ctx, ctx->d_sums, words) || reserve(ctx, ctx->h_sums, words))
     return 1;
   hipLaunchKernelGGL(station_rows_kernel, dim3(grid_for(ctx->np)), dim3(256), 0, ctx->stream, a, ctx->nq,
-                     (const uint32_t *) ctx->d_marks, (const uint32_t *) M.chunk_off, M.shift, (const int *) ctx->d_slot_of,
-                     ctx->d_sums);
+                     (const uint32_t *) ctx->d_marks.p, (const uint32_t *) M.chunk_off, M.shift, (const int *) ctx->d_slot_of.p,
+                     ctx->d_sums.p);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(ctx->h_sums, ctx->d_sums, words * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(ctx->h_sums.p, ctx->d_sums.p, words * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   for (size_t k = 0; k < total; k++) {
-    index[k] = (int) ctx->h_sums[k * width];
-    memcpy(rows + k * (width - 1), ctx->h_sums + k * width + 1, (width - 1) * sizeof(double));
+    index[k] = (int) ctx->h_sums.p[k * width];
+    memcpy(rows + k * (width - 1), ctx->h_sums.p + k * width + 1, (width - 1) * sizeof(double));
   }
   return 0;
 }
@@ -5755,14 +5502,13 @@ int mphip_set_radio_depo(mphip_ctx *ctx, int on, const mphip_box_t *grid) {
   HIPCHK(hipSetDevice(ctx->device));
   if (grid) {
     const mphip_box_t &g = ctx->rdepo_grid;
-    const bool same = ctx->d_rdepo_inv && g.nx == grid->nx && g.ny == grid->ny && g.lon0 == grid->lon0 && g.lon1 == grid->lon1
+    const bool same = ctx->d_rdepo_inv.p && g.nx == grid->nx && g.ny == grid->ny && g.lon0 == grid->lon0 && g.lon1 == grid->lon1
       && g.lat0 == grid->lat0 && g.lat1 == grid->lat1;
     if (!same) {   // a new inventory: zero, no time yet
       HIPCHK(hipStreamSynchronize(ctx->stream));
       ctx->rdepo_ntot = 0;
-      if (dev_alloc(ctx, &ctx->d_rdepo_inv, 2 * (size_t) MPHIP_NRADIO * ntot))
-        return 1;
-      HIPCHK(hipMemsetAsync(ctx->d_rdepo_inv, 0, 2 * (size_t) MPHIP_NRADIO * ntot * sizeof(double), ctx->stream));
+      HIPCHK(ctx->d_rdepo_inv.resize(2 * (size_t) MPHIP_NRADIO * ntot));
+      HIPCHK(hipMemsetAsync(ctx->d_rdepo_inv.p, 0, 2 * (size_t) MPHIP_NRADIO * ntot * sizeof(double), ctx->stream));
       ctx->rdepo_grid = *grid;
       ctx->rdepo_ntot = ntot;
       ctx->rdepo_have_t = false;
@@ -5776,24 +5522,24 @@ int mphip_set_radio_depo(mphip_ctx *ctx, int on, const mphip_box_t *grid) {
 int mphip_get_radio_depo(mphip_ctx *ctx, double *t_inv, double *wet, double *dry) {
   if (!ctx)
     return 1;
-  if (!ctx->d_rdepo_inv)
+  if (!ctx->d_rdepo_inv.p)
     return fail(ctx, "mphip_get_radio_depo: no inventory (mphip_set_radio_depo has not been called)");
   HIPCHK(hipSetDevice(ctx->device));
   const size_t plane = (size_t) MPHIP_NRADIO * ctx->rdepo_ntot, total = 2 * plane;
   // this rank's part, summed over the ranks in a copy (the inventory itself stays this rank's)
-  if (ensure_sums(ctx, total) || ensure_h_sums(ctx, total))
+  if (reserve(ctx, ctx->d_sums, total) || reserve(ctx, ctx->h_sums, total))
     return 1;
-  HIPCHK(hipMemcpyAsync(ctx->d_sums, ctx->d_rdepo_inv, total * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-  if (run_allreduce(ctx, ctx->d_sums, total))
+  HIPCHK(hipMemcpyAsync(ctx->d_sums.p, ctx->d_rdepo_inv.p, total * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+  if (run_allreduce(ctx, ctx->d_sums.p, total))
     return 1;
-  HIPCHK(hipMemcpyAsync(ctx->h_sums, ctx->d_sums, total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(ctx->h_sums.p, ctx->d_sums.p, total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   if (t_inv)
     *t_inv = ctx->rdepo_have_t ? ctx->rdepo_t : NAN;
   if (wet)
-    memcpy(wet, ctx->h_sums, plane * sizeof(double));
+    memcpy(wet, ctx->h_sums.p, plane * sizeof(double));
   if (dry)
-    memcpy(dry, ctx->h_sums + plane, plane * sizeof(double));
+    memcpy(dry, ctx->h_sums.p + plane, plane * sizeof(double));
   return 0;
 }
 
@@ -5807,12 +5553,11 @@ int mphip_set_grid_kernel(mphip_ctx *ctx, int nk, const double *kz, const double
       return fail(ctx, "height levels of the kernel function must be ascending");
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  if (dev_alloc(ctx, &ctx->d_grid_kernel, nk >= 2 ? 2 * (size_t) nk : 0))
-    return 1;
+  HIPCHK(ctx->d_grid_kernel.resize(nk >= 2 ? 2 * (size_t) nk : 0));
   ctx->grid_nk = nk >= 2 ? nk : 0;
   if (ctx->grid_nk) {
-    HIPCHK(hipMemcpy(ctx->d_grid_kernel, kz, (size_t) nk * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(ctx->d_grid_kernel + nk, kw, (size_t) nk * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ctx->d_grid_kernel.p, kz, (size_t) nk * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ctx->d_grid_kernel.p + nk, kw, (size_t) nk * sizeof(double), hipMemcpyHostToDevice));
   }
   return 0;
 }
@@ -5889,150 +5634,112 @@ int mphip_comm_query(mphip_ctx *ctx, int *nranks, int *rank) {
   return 0;
 }
 
+namespace {
+
+// mphip_set_option (documented in include/mptrac_hip.h) as a table: the name, the member it sets, which values are
+// accepted, the refusal, and for the few options with a side effect what runs before the store
+enum OptKind {
+  kFlag,          // value != 0
+  kRange,         // (int) value; refused if value < lo or value > hi
+  kZeroOrRange,   // (int) value; 0, or within [lo, hi]
+  kWhole          // one of the integers lo ... hi
+};
+
+struct Option {
+  const char *name;
+  bool mphip_ctx::*flag;     // kFlag
+  int mphip_ctx::*number;    // the other kinds
+  OptKind kind;
+  double lo, hi;
+  const char *refusal;
+  int (*before)(mphip_ctx *, double);
+};
+
+typedef int (*OptHook)(mphip_ctx *, double);
+
+constexpr Option flag(const char *name, bool mphip_ctx::*member, OptHook before = nullptr) {
+  return Option{ name, member, nullptr, kFlag, 0, 0, nullptr, before };
+}
+
+constexpr Option number(const char *name, int mphip_ctx::*member, OptKind kind, double lo, double hi, const char *refusal,
+                        OptHook before = nullptr) {
+  return Option{ name, nullptr, member, kind, lo, hi, refusal, before };
+}
+
+int flush_if_switched_off(mphip_ctx *ctx, double value) {
+  return value == 0 ? flush_meteo(ctx) : 0;
+}
+
+int drop_sort_ahead(mphip_ctx *ctx, double) {
+  return ahead_drop(ctx);
+}
+
+int resort_next_step(mphip_ctx *ctx, double) {
+  ctx->steps_since_resort = 1 << 30;
+  return 0;
+}
+
+const char *const kStepBlocksRefusal = "step_blocks must be in 8 ... 1048576";
+
+const Option kOptions[] = {
+  number("locality_sort_interval", &mphip_ctx::locality_interval, kRange, 0, HUGE_VAL, "locality_sort_interval must be >= 0"),
+  number("step_blocks", &mphip_ctx::step_blocks, kRange, 8, 1048576, kStepBlocksRefusal),
+  number("step_blocks_multi", &mphip_ctx::step_blocks_multi, kRange, 8, 1048576, kStepBlocksRefusal),
+  flag("fuse_sort", &mphip_ctx::fuse_sort),                   // 0: module_sort re-orders every array in its own pass
+  // 0: run module_meteo inside every time step that schedules it
+  flag("lazy_meteo", &mphip_ctx::lazy_meteo, flush_if_switched_off),
+  flag("pin_host_atm", &mphip_ctx::pin_host_atm),             // page-lock the arrays handed to mphip_update_atm / mphip_get_atm
+  // mphip_run_timesteps: most steps per launch, 0 = one launch per step
+  number("multi_step", &mphip_ctx::multi_step, kRange, 0, 4096, "multi_step must be in 0 ... 4096"),
+  flag("fold_resort", &mphip_ctx::fold_resort),               // 0: the locality re-sort always gathers in a pass of its own
+  flag("turb_strat", &mphip_ctx::turb_strat),                 // 0: module_diff_turb never takes its short path above the tropopause
+  flag("fuse_sort_quantities", &mphip_ctx::fuse_quantities),  // 0: module_sort moves the quantity arrays in a pass of its own
+  flag("perm_records", &mphip_ctx::perm_records),
+  flag("big_grid", &mphip_ctx::big_grid),
+  number("derive_profile_phase", &mphip_ctx::derive_profile_phase, kWhole, 0, 6,
+         "derive_profile_phase must be 0 (kernels), 1 (uploads), 2 (downloads), 3 (the weight table of "
+         "mphip_detrend_met) or 4, 5, 6 (the extremes, their reduction, the quantisation of mphip_pack_met)"),
+  flag("xcd_map", &mphip_ctx::xcd_map),
+  flag("generic_kernel", &mphip_ctx::force_generic),          // tuning aid: never pick a specialised instantiation
+  number("sort_bits", &mphip_ctx::sort_bits, kZeroOrRange, 8, kRadixMaxBits, "sort_bits must be 0 (automatic), 8, 9 or 10"),
+  flag("mix_exchange_levels", &mphip_ctx::mix_exchange_levels),   // 0: the exchange of a mixing step covers the whole grid
+  // cells of the LDS wind tile for runs of pure trajectory steps (24 bytes each; 0: off)
+  number("lds_tile", &mphip_ctx::lds_tile, kZeroOrRange, 64, 2400, "lds_tile must be 0 or 64 ... 2400 cells"),
+  flag("ahead_priority", &mphip_ctx::ahead_priority),         // (before the first sort ahead: the stream is created then)
+  flag("emit_keys", &mphip_ctx::emit_keys),                   // 0: the keys of the sort ahead come from a kernel of their own
+  flag("sort_repair", &mphip_ctx::sort_repair),               // 0: the module_sort that runs ahead always sorts from scratch
+  flag("compact_depo", &mphip_ctx::compact_depo),             // 0: deposition-only launches run the tail of the fused kernel
+  flag("ahead_box", &mphip_ctx::ahead_box),                   // tuning aid
+  flag("sort_ahead", &mphip_ctx::sort_ahead, drop_sort_ahead),   // 0: module_sort runs when mphip_run_timestep reaches it
+  // tests: force one of the ordered-sum algorithms (0: choose by crowding)
+  number("sum_path", &mphip_ctx::sum_path, kWhole, 0, 2, "sum_path must be 0, 1 or 2"),
+  // 1 (default): cell sums of module_mixing / the gridded output add in the reference's serial order;
+  // 0: floating-point atomics (order of arrival)
+  number("deterministic_sums", &mphip_ctx::deterministic_sums, kWhole, 0, 1, "deterministic_sums must be 0 or 1"),
+  flag("grid_records", &mphip_ctx::grid_records),             // tuning / tests: 0 = gather the gridded sums' values from the arrays
+  number("chain_blocks", &mphip_ctx::chain_blocks, kRange, -HUGE_VAL, HUGE_VAL, nullptr),   // (any value)
+  flag("locality_zorder", &mphip_ctx::locality_zorder, resort_next_step),
+  number("locality_tile", &mphip_ctx::locality_tile, kRange, 0, 64, "locality_tile must be in 0 ... 64", resort_next_step),
+};
+
+}   // namespace
+
 int mphip_set_option(mphip_ctx *ctx, const char *name, double value) {
   if (!ctx || !name)
     return 1;
-  if (strcmp(name, "locality_sort_interval") == 0) {
-    if (value < 0)
-      return fail(ctx, "locality_sort_interval must be >= 0");
-    ctx->locality_interval = (int) value;
-    return 0;
-  }
-  if (strcmp(name, "step_blocks") == 0 || strcmp(name, "step_blocks_multi") == 0) {
-    if (value < 8 || value > 1048576)
-      return fail(ctx, "step_blocks must be in 8 ... 1048576");
-    (strcmp(name, "step_blocks") == 0 ? ctx->step_blocks : ctx->step_blocks_multi) = (int) value;
-    return 0;
-  }
-  if (strcmp(name, "fuse_sort") == 0) {    // 0: module_sort re-orders every array in its own pass
-    ctx->fuse_sort = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "lazy_meteo") == 0) {   // 0: run module_meteo inside every time step that schedules it
-    if (value == 0 && flush_meteo(ctx))
+  for (const Option &o : kOptions) {
+    if (strcmp(name, o.name) != 0)
+      continue;
+    const bool inside = value >= o.lo && value <= o.hi;
+    if ((o.kind == kRange && (value < o.lo || value > o.hi)) || (o.kind == kZeroOrRange && !(value == 0 || inside))
+        || (o.kind == kWhole && !(inside && value == std::floor(value))))
+      return fail(ctx, o.refusal);
+    if (o.before && o.before(ctx, value))
       return 1;
-    ctx->lazy_meteo = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "pin_host_atm") == 0) {   // page-lock the arrays handed to mphip_update_atm / mphip_get_atm
-    ctx->pin_host_atm = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "multi_step") == 0) {   // mphip_run_timesteps: most steps per launch, 0 = one launch per step
-    if (value < 0 || value > 4096)
-      return fail(ctx, "multi_step must be in 0 ... 4096");
-    ctx->multi_step = (int) value;
-    return 0;
-  }
-  if (strcmp(name, "fold_resort") == 0) {   // 0: the locality re-sort always gathers in a pass of its own
-    ctx->fold_resort = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "turb_strat") == 0) {   // 0: module_diff_turb never takes its short path above the tropopause
-    ctx->turb_strat = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "fuse_sort_quantities") == 0) {   // 0: module_sort moves the quantity arrays in a pass of its own
-    ctx->fuse_quantities = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "perm_records") == 0) {
-    ctx->perm_records = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "big_grid") == 0) {
-    ctx->big_grid = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "derive_profile_phase") == 0) {
-    if (value != 0 && value != 1 && value != 2 && value != 3 && value != 4 && value != 5 && value != 6)
-      return fail(ctx, "derive_profile_phase must be 0 (kernels), 1 (uploads), 2 (downloads), 3 (the weight table of "
-                       "mphip_detrend_met) or 4, 5, 6 (the extremes, their reduction, the quantisation of mphip_pack_met)");
-    ctx->prep.profile_phase = (int) value;
-    return 0;
-  }
-  if (strcmp(name, "xcd_map") == 0) {
-    ctx->xcd_map = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "generic_kernel") == 0) {   // tuning aid: never pick a specialised instantiation
-    ctx->force_generic = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "sort_bits") == 0) {
-    if (!(value == 0 || (value >= 8 && value <= kRadixMaxBits)))
-      return fail(ctx, "sort_bits must be 0 (automatic), 8, 9 or 10");
-    ctx->sort_bits = (int) value;
-    return 0;
-  }
-  if (strcmp(name, "mix_exchange_levels") == 0) {   // 0: the exchange of a mixing step covers the whole grid
-    ctx->mix_exchange_levels = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "lds_tile") == 0) {   // cells of the LDS wind tile for runs of pure trajectory steps (24 bytes each; 0: off)
-    if (value != 0 && (value < 64 || value > 2400))
-      return fail(ctx, "lds_tile must be 0 or 64 ... 2400 cells");
-    ctx->lds_tile = (int) value;
-    return 0;
-  }
-  if (strcmp(name, "ahead_priority") == 0) {   // (before the first sort ahead: the stream is created then)
-    ctx->ahead_priority = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "emit_keys") == 0) {   // 0: the keys of the sort ahead always come from a kernel of their own
-    ctx->emit_keys = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "sort_repair") == 0) {   // 0: the module_sort that runs ahead always sorts from scratch
-    ctx->sort_repair = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "compact_depo") == 0) {   // 0: deposition-only launches run the tail of the fused kernel
-    ctx->compact_depo = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "ahead_box") == 0) {   // tuning aid
-    ctx->ahead_box = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "sort_ahead") == 0) {   // 0: module_sort runs when mphip_run_timestep reaches it
-    if (ahead_drop(ctx))
-      return 1;
-    ctx->sort_ahead = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "sum_path") == 0) {   // tests: force one of the two ordered-sum algorithms (0: choose by crowding)
-    if (!(value == 0 || value == 1 || value == 2))
-      return fail(ctx, "sum_path must be 0, 1 or 2");
-    ctx->sum_path = (int) value;
-    return 0;
-  }
-  if (strcmp(name, "deterministic_sums") == 0) {
-    // 1 (default): cell sums of module_mixing / the gridded output add in the reference's serial order;
-    // 0: floating-point atomics (order of arrival)
-    if (!(value == 0 || value == 1))
-      return fail(ctx, "deterministic_sums must be 0 or 1");
-    ctx->deterministic_sums = (int) value;
-    return 0;
-  }
-  if (strcmp(name, "grid_records") == 0) {   // tuning / tests: 0 = gather the gridded sums' values from the arrays
-    ctx->grid_records = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "chain_blocks") == 0) {
-    ctx->chain_blocks = (int) value;
-    return 0;
-  }
-  if (strcmp(name, "locality_zorder") == 0) {
-    ctx->locality_zorder = value != 0;
-    ctx->steps_since_resort = 1 << 30;
-    return 0;
-  }
-  if (strcmp(name, "locality_tile") == 0) {
-    if (value < 0 || value > 64)
-      return fail(ctx, "locality_tile must be in 0 ... 64");
-    ctx->locality_tile = (int) value;
-    ctx->steps_since_resort = 1 << 30;
+    if (o.kind == kFlag)
+      ctx->*o.flag = value != 0;
+    else
+      ctx->*o.number = (int) value;
     return 0;
   }
   return fail(ctx, std::string("unknown option ") + name);
@@ -6091,15 +5798,13 @@ int mphip_test_sincosf(mphip_ctx *ctx, uint32_t bits_first, uint32_t count, floa
   if (!ctx || !cos_out || !sin_out)
     return 1;
   HIPCHK(hipSetDevice(ctx->device));
-  float *dc = nullptr, *ds = nullptr;
-  HIPCHK(hipMalloc((void **) &dc, (size_t) count * sizeof(float)));
-  HIPCHK(hipMalloc((void **) &ds, (size_t) count * sizeof(float)));
-  hipLaunchKernelGGL(test_sincosf_kernel, dim3(grid_for(count)), dim3(256), 0, ctx->stream, bits_first, count, dc, ds);
-  HIPCHK(hipMemcpyAsync(cos_out, dc, (size_t) count * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipMemcpyAsync(sin_out, ds, (size_t) count * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  DevBuf<float> dc, ds;
+  HIPCHK(dc.resize(count));
+  HIPCHK(ds.resize(count));
+  hipLaunchKernelGGL(test_sincosf_kernel, dim3(grid_for(count)), dim3(256), 0, ctx->stream, bits_first, count, dc.p, ds.p);
+  HIPCHK(hipMemcpyAsync(cos_out, dc.p, (size_t) count * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(sin_out, ds.p, (size_t) count * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  HIPCHK(hipFree(dc));
-  HIPCHK(hipFree(ds));
   return 0;
 }
 
@@ -6107,23 +5812,20 @@ int mphip_test_libm(mphip_ctx *ctx, int op, const double *x, const double *y, lo
   if (!ctx || !x || !out || n < 0 || ((op & 15) == 2 && !y) || (op & ~31) || (op & 15) > 7)
     return 1;
   HIPCHK(hipSetDevice(ctx->device));
-  const size_t bytes = (size_t) std::max<long long>(n, 1) * sizeof(double);
-  double *dx = nullptr, *dy = nullptr, *dout = nullptr;
-  HIPCHK(hipMalloc((void **) &dx, bytes));
-  HIPCHK(hipMalloc((void **) &dout, bytes));
-  HIPCHK(hipMemcpyAsync(dx, x, (size_t) n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  const size_t count = (size_t) std::max<long long>(n, 1);
+  DevBuf<double> dx, dy, dout;
+  HIPCHK(dx.resize(count));
+  HIPCHK(dout.resize(count));
+  HIPCHK(hipMemcpyAsync(dx.p, x, (size_t) n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   if ((op & 15) == 2) {
-    HIPCHK(hipMalloc((void **) &dy, bytes));
-    HIPCHK(hipMemcpyAsync(dy, y, (size_t) n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(dy.resize(count));
+    HIPCHK(hipMemcpyAsync(dy.p, y, (size_t) n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   }
-  hipLaunchKernelGGL(test_libm_kernel, dim3(grid_for(std::max<long long>(n, 1))), dim3(256), 0, ctx->stream, op, dx, dy, n, dout);
+  hipLaunchKernelGGL(test_libm_kernel, dim3(grid_for(std::max<long long>(n, 1))), dim3(256), 0, ctx->stream, op, dx.p, dy.p, n,
+                     dout.p);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, dout, (size_t) n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(out, dout.p, (size_t) n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  HIPCHK(hipFree(dx));
-  HIPCHK(hipFree(dout));
-  if (dy)
-    HIPCHK(hipFree(dy));
   return 0;
 }
 
@@ -6141,8 +5843,8 @@ int mphip_test_piece(mphip_ctx *ctx, int piece, int reps, double *checksum) {
   S.ctl = ctx->ctl;
   S.met = dev_met(ctx);
   S.atm = dev_atm(ctx);
-  S.clim = ctx->d_clim;
-  S.tracers = ctx->d_tracers;
+  S.clim = ctx->d_clim.p;
+  S.tracers = ctx->d_tracers.p;
   S.t = 0;
   S.mask = 0;
   const BlockGeom geom = block_geom(ctx->np, ctx->step_blocks);
@@ -6159,10 +5861,11 @@ int mphip_test_piece(mphip_ctx *ctx, int piece, int reps, double *checksum) {
       return fail(ctx, "mphip_test_piece: piece 22 needs a grid the lean kernels with 32-bit offsets run on");
     if (ensure_meso_table(ctx))
       return 1;
-    S.met.meso = ctx->pk.meso;
+    S.met.meso = ctx->pk.meso.p;
   }
-  double *d = nullptr;
-  HIPCHK(hipMalloc((void **) &d, (size_t) ctx->np * sizeof(double)));
+  DevBuf<double> out;
+  HIPCHK(out.resize((size_t) ctx->np));
+  double *const d = out.p;
   const size_t lds = axes_lds_bytes(ctx) + sizeof(DevClim) + (size_t) kLibmLogExpDoubles * sizeof(double);
   switch (piece) {
 #define PIECE_CASE(K)                                                                                  \
@@ -6179,7 +5882,6 @@ int mphip_test_piece(mphip_ctx *ctx, int piece, int reps, double *checksum) {
 #endif
 #undef PIECE_CASE
   default:
-    (void) hipFree(d);
     return fail(ctx, "unknown piece");
   }
   HIPCHK(hipGetLastError());
@@ -6192,7 +5894,6 @@ int mphip_test_piece(mphip_ctx *ctx, int piece, int reps, double *checksum) {
       sum += v;
     *checksum = sum;
   }
-  HIPCHK(hipFree(d));
   return 0;
 }
 
@@ -6210,7 +5911,7 @@ int mphip_test_meso_table(mphip_ctx *ctx, float *out, size_t cells) {
   if (ensure_meso_table(ctx))
     return 1;
   std::vector<float> h(meso_table_floats(ctx));
-  HIPCHK(hipMemcpyAsync(h.data(), ctx->pk.meso, h.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(h.data(), ctx->pk.meso.p, h.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   const size_t nty = (size_t) (ctx->ny + 2) / 4;
   for (size_t ix = 0; ix < nx; ix++)
@@ -6227,13 +5928,12 @@ int mphip_test_rng(mphip_ctx *ctx, uint64_t ctr, long long n, int method, double
   if (!ctx || !out || n < 0)
     return 1;
   HIPCHK(hipSetDevice(ctx->device));
-  double *d = nullptr;
-  HIPCHK(hipMalloc((void **) &d, (size_t) std::max<long long>(n, 1) * sizeof(double)));
+  DevBuf<double> d;
+  HIPCHK(d.resize((size_t) std::max<long long>(n, 1)));
   hipLaunchKernelGGL(test_rng_kernel, dim3(grid_for(std::max<long long>(n, 1))), dim3(256), 0, ctx->stream, ctr, n,
-                     method, d);
-  HIPCHK(hipMemcpyAsync(out, d, (size_t) n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+                     method, d.p);
+  HIPCHK(hipMemcpyAsync(out, d.p, (size_t) n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  HIPCHK(hipFree(d));
   return 0;
 }
 
