@@ -577,6 +577,41 @@ int mphip_prefetch_met_packed(mphip_ctx *ctx, const mphip_met_packed_t *met);
 int mphip_unpack_met(mphip_ctx *ctx, const mphip_met_packed_t *in, const mphip_met_t *out);
 int mphip_pack_met(mphip_ctx *ctx, const mphip_met_t *in, const mphip_met_packed_t *out);
 
+/* intpol_met_time_3d / intpol_met_time_2d (mptrac.c:3112-3170) for n points of the caller: "what is field X at (t, p, lon,
+ * lat)?", answered from the resident meteo pair on the device.  time has ntime entries, ntime = 1 (one time for all
+ * points) or n; p, lon, lat have n; field[k] is MPHIP_U ... for a pressure-level field or MPHIP_INTPOL_2D | MPHIP_PS ...
+ * for a surface field; out is [nfield][n] doubles in host memory.  p may be NULL when only surface fields are asked for.
+ *   The snapshots are the resident pair as the next time step would see it: the current slots after any mphip_swap_met, a
+ * packed upload as decoded, and after mphip_commit_met the new pair; a prefetch in flight is not visible.  The call runs on
+ * the context's stream and belongs to the stepping thread.  It touches no particle, no packed record and no pending
+ * deferred module_meteo launch.  The points travel through two grow-only buffers of the context in chunks of the option
+ * "intpol_chunk" points, so device memory does not grow with n.  n = 0 succeeds and writes nothing.  Between
+ * mphip_profile_begin and mphip_profile_end every kernel launch of the call is one event pair (a phase of its own when
+ * only this call is made in between).
+ *
+ *   DEFINITION.  Per point, one index and weight set from the CURRENT met0's axes, shared by all fields (INTPOL_TIME_ALL,
+ * mptrac.h:1278-1318): the horizontal check by coord_type -- 0: lon2 = FMOD(lon, 360), plus 360 if below lon[0], else minus
+ * 360 if above lon[nx-1]; otherwise lon clamped to the axis; lat clamped to the axis --, ip = locate_irr(p), ix =
+ * locate_reg(lon2), iy = locate_irr(lat2), wp = (p[ip+1] - p) / (p[ip+1] - p[ip]) and wx, wy likewise: true divisions.
+ * Pressure-level field, on met0 and on met1 with met0's indices: vertical blend wp (a[ip] - a[ip+1]) + a[ip+1] at the four
+ * columns (the difference of the two floats is a float difference, as in the reference; everything else is double), then latitude, then longitude, then in time with wt = (time1 - t) / (time1 - time0): wt (v0 - v1) + v1.  Surface
+ * field: the same two horizontal blends if all four corners are finite, else the nearest corner (wx < 0.5 ? ix+1 : ix, wy <
+ * 0.5 ? iy+1 : iy); in time the blend if both values are finite, else the nearer snapshot (wt < 0.5 ? v1 : v0).  Every
+ * product and sum is rounded once and none is contracted, in BOTH libraries: the values are the reference's doubles bit for
+ * bit (tests/test_gpu_intpol.py, tests/test_gpu_intpol_exact.py), which is what lets a host writer switch to this call without
+ * a byte of its files changing.  Times outside [time0, time1] extrapolate as the formula gives.
+ *   Not-finite inputs (this project's definition: the reference's FMOD casts to int, which is undefined there): a point
+ * whose time, lon or lat -- or p, when a pressure-level field is requested -- is not finite, or whose |lon| > 1e9, gets NaN
+ * in every requested field.
+ *   Refused, nothing written to out, the cause in mphip_last_error: a slot without a snapshot; time0 == time1; n < 0; ntime
+ * not 1 or n; a NULL lon, lat, out, time or field; a NULL p with a pressure-level field; nfield outside 1 ... 32; a field
+ * index out of range; a model-level field (MPHIP_PL, UL, VL, WL, ZETAL, ZETA_DOTL: another level count, out of scope); a
+ * field that either resident snapshot was uploaded without (the message names the field); a grid whose three axes hold
+ * more than 4096 nodes together (the kernel keeps them in 64 KB of LDS, 16 bytes per node). */
+#define MPHIP_INTPOL_2D 256   /* flag bit above MPHIP_N3D */
+int mphip_intpol_met(mphip_ctx *ctx, long long n, const double *time, long long ntime, const double *p, const double *lon,
+                     const double *lat, int nfield, const int *field, double *out);
+
 /* mptrac_update_device(..., atm), mptrac.c:8050-8055.  This process owns the
  * particles [ip0, ip0 + np) of a simulation with np_total particles; random
  * numbers are drawn for the global index so results do not depend on the
@@ -828,7 +863,9 @@ int mphip_comm_query(mphip_ctx *ctx, int *nranks, int *rank);
  *     profiles does not step from another thread meanwhile); 3: the host's build of the weight table in
  *     mphip_detrend_met (the stream is idle meanwhile, so the pair of events brackets the host's time); 4, 5, 6: of the
  *     kernels of mphip_pack_met only the extremes, their reduction, the quantisation (mphip_unpack_met and mphip_pack_met
- *     are calls of the same family: 0, 1 and 2 hold for them as well). */
+ *     are calls of the same family: 0, 1 and 2 hold for them as well).
+ *   "intpol_chunk" (default 4194304 = 2^22; 64 ... 16777216 = 2^24): points per launch of mphip_intpol_met -- its two
+ *     device buffers hold 32 + 8 nfield bytes per point of a chunk.  Not observable. */
 int mphip_set_option(mphip_ctx *ctx, const char *name, double value);
 int mphip_synchronize(mphip_ctx *ctx);
 

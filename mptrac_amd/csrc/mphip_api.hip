@@ -21,6 +21,7 @@
 #include "mphip_regrid.hpp"
 #include "mphip_detrend.hpp"
 #include "mphip_pack.hpp"
+#include "mphip_intpol.hpp"
 
 using namespace mphip;
 
@@ -40,6 +41,8 @@ constexpr unsigned kParticleBits = 0x3fffu | MPHIP_MOD_ISOSURF | kBound | MPHIP_
 
 const char *const kField3Name[MPHIP_N3D] = { "u", "v", "w", "t", "lwc", "rwc", "iwc", "swc", "pl", "ul", "vl", "zetal",
                                              "zeta_dotl", "h2o", "z", "pv", "o3", "cc", "wl" };
+const char *const kField2Name[MPHIP_N2D] = { "ps", "pbl", "cape", "cin", "pel", "pct", "pcb", "cl", "ess", "nss", "shf", "ts",
+                                             "zs", "us", "vs", "lsm", "sst", "pt", "tt", "zt", "h2ot", "plcl", "plfc", "o3c" };
 
 struct MetSlot {
   bool valid = false;
@@ -261,6 +264,9 @@ struct mphip_ctx {
   // mphip_derive_met, mphip_regrid_met, mphip_detrend_met: their stream, lock and scratch
   PrepState prep;
 
+  // mphip_intpol_met: the points {time | p | lon | lat} and the values [nfield] of one chunk (grow-only)
+  DevBuf<double> d_ip_in, d_ip_out;
+
   // ---- options (mphip_set_option; documented in include/mptrac_hip.h) ----
   int locality_interval = 60;         // re-sort every this many steps (0 = keep the caller's order)
   bool locality_zorder = false;       // tiles of the locality key numbered along a Z-order curve instead of row by row
@@ -294,6 +300,7 @@ struct mphip_ctx {
   // undecidable without xGMI, so the whole-grid all-reduce stays the default
   bool mix_exchange_levels = false;
   int derive_profile_phase = 0;       // what mphip_profile_begin / _end time of a preprocessing call
+  int intpol_chunk = 1 << 22;         // points per launch of mphip_intpol_met: device memory does not grow with n
 
   // ---- profiling of the fused step kernel ----
   bool prof = false;
@@ -4555,6 +4562,105 @@ int mphip_prefetch_done(mphip_ctx *ctx) {
   return ctx->uploader_done && hipEventQuery(ctx->next_ready) == hipSuccess ? 1 : 0;
 }
 
+// intpol_met_time_3d / intpol_met_time_2d (mptrac.c:3112-3170) at the caller's points, from the resident pair
+int mphip_intpol_met(mphip_ctx *ctx, long long n, const double *time, long long ntime, const double *p, const double *lon,
+                     const double *lat, int nfield, const int *field, double *out) {
+  if (!ctx)
+    return 1;
+  const std::string who = "mphip_intpol_met: ";
+  if (n < 0)
+    return fail(ctx, who + "n < 0");
+  if (!lon || !lat || !out || !time || !field)
+    return fail(ctx, who + "a NULL lon, lat, out, time or field");
+  if (ntime != 1 && ntime != n)
+    return fail(ctx, who + "ntime must be 1 or n");
+  if (nfield < 1 || nfield > kIntpolMaxFields)
+    return fail(ctx, who + "nfield must be in 1 ... 32");
+  const MetSlot &s0 = ctx->slot[0 ^ ctx->flip], &s1 = ctx->slot[1 ^ ctx->flip];
+  if (!s0.valid || !s1.valid)
+    return fail(ctx, who + "a meteo slot without a snapshot");
+  if (s0.time == s1.time)
+    return fail(ctx, who + "time0 == time1");
+  IntpolArgs I = {};
+  for (int k = 0; k < nfield; k++) {
+    const bool is2 = (field[k] & MPHIP_INTPOL_2D) != 0;
+    const int f = field[k] & ~MPHIP_INTPOL_2D;
+    if (f < 0 || f >= (is2 ? (int) MPHIP_N2D : (int) MPHIP_N3D))
+      return fail(ctx, who + "field index " + std::to_string(field[k]) + " out of range");
+    const char *name = is2 ? kField2Name[f] : kField3Name[f];
+    if (!is2 && field_on_model_levels(f))
+      return fail(ctx, who + "model-level field " + name + " is out of scope");
+    if (!(is2 ? s0.has2[f] && s1.has2[f] : s0.has3[f] && s1.has3[f]))
+      return fail(ctx, who + "field " + name + " was not uploaded with both resident snapshots");
+    I.field[k] = is2 ? (f | kIntpol2D) : f;
+    I.f0[k] = is2 ? s0.f2[f].p : s0.f3[f].p;
+    I.f1[k] = is2 ? s1.f2[f].p : s1.f3[f].p;
+    I.need_p |= !is2;
+  }
+  if (I.need_p && !p)
+    return fail(ctx, who + "a NULL p with a pressure-level field");
+  // the kernel keeps the three axes and their reciprocal widths in LDS: 16 bytes per node, 64 KB per workgroup
+  if (2 * (size_t) (ctx->nx + ctx->ny + ctx->npl) * sizeof(double) > 64 * 1024)
+    return fail(ctx, who + "the axes of the meteo grid (" + std::to_string(ctx->nx + ctx->ny + ctx->npl)
+                + " nodes) do not fit 64 KB of LDS (at most 4096 nodes)");
+  if (n == 0)
+    return 0;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (axes_follow_met0(ctx))
+    return 1;
+  DevMet M = {};
+  M.axes = ctx->d_axes.p;
+  M.nx = ctx->nx;
+  M.ny = ctx->ny;
+  M.np = ctx->npl;
+  M.coord_type = ctx->coord_type;
+  M.time0 = s0.time;
+  M.time1 = s1.time;
+  M.lat_ascending = ctx->h_lat[(ctx->ny - 1) >> 1] < ctx->h_lat[((ctx->ny - 1) >> 1) + 1];
+  M.p_ascending = ctx->h_p[(ctx->npl - 1) >> 1] < ctx->h_p[((ctx->npl - 1) >> 1) + 1];
+  const size_t lds = 2 * (size_t) (M.nx + M.ny + M.np) * sizeof(double);   // (no pressure table: lut_size = 0)
+  const size_t chunk = (size_t) std::min<long long>(n, ctx->intpol_chunk);
+  HIPCHK(ctx->d_ip_in.reserve(4 * chunk));
+  HIPCHK(ctx->d_ip_out.reserve((size_t) nfield * chunk));
+  double *const d_time = ctx->d_ip_in.p, *const d_p = d_time + chunk, *const d_lon = d_p + chunk, *const d_lat = d_lon + chunk;
+  I.nfield = nfield;
+  I.time_all = time[0];
+  I.out = ctx->d_ip_out.p;
+  I.out_stride = (long long) chunk;
+  for (size_t first = 0; first < (size_t) n; first += chunk) {
+    const size_t m = std::min(chunk, (size_t) n - first), bytes = m * sizeof(double);
+    if (ntime == n)
+      HIPCHK(hipMemcpyAsync(d_time, time + first, bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (I.need_p)
+      HIPCHK(hipMemcpyAsync(d_p, p + first, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(d_lon, lon + first, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(d_lat, lat + first, bytes, hipMemcpyHostToDevice, ctx->stream));
+    I.time = ntime == n ? d_time : nullptr;
+    I.p = d_p;
+    I.lon = d_lon;
+    I.lat = d_lat;
+    I.n = (long long) m;
+    hipEvent_t e1 = nullptr;
+    if (ctx->prof) {   // (mphip_profile_begin / _end around calls of this function alone: the time of its kernel)
+      while (ctx->ev_used + 2 > ctx->ev.size()) {
+        hipEvent_t e;
+        HIPCHK(hipEventCreate(&e));
+        ctx->ev.push_back(e);
+      }
+      HIPCHK(hipEventRecord(ctx->ev[ctx->ev_used++], ctx->stream));
+      e1 = ctx->ev[ctx->ev_used++];
+    }
+    hipLaunchKernelGGL(intpol_points_kernel, dim3(grid_for((long long) m)), dim3(256), lds, ctx->stream, M, I);
+    HIPCHK(hipGetLastError());
+    if (e1)
+      HIPCHK(hipEventRecord(e1, ctx->stream));
+    HIPCHK(hipMemcpy2DAsync(out + first, (size_t) n * sizeof(double), ctx->d_ip_out.p, chunk * sizeof(double), bytes,
+                            (size_t) nfield, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
 int mphip_update_atm(mphip_ctx *ctx, long long np, long long ip0, long long np_total, int nq, const double *time,
                      const double *p, const double *lon, const double *lat, const double *const *q) {
   if (ctx && ahead_drop(ctx))
@@ -5720,6 +5826,8 @@ const Option kOptions[] = {
   number("chain_blocks", &mphip_ctx::chain_blocks, kRange, -HUGE_VAL, HUGE_VAL, nullptr),   // (any value)
   flag("locality_zorder", &mphip_ctx::locality_zorder, resort_next_step),
   number("locality_tile", &mphip_ctx::locality_tile, kRange, 0, 64, "locality_tile must be in 0 ... 64", resort_next_step),
+  // points per launch of mphip_intpol_met
+  number("intpol_chunk", &mphip_ctx::intpol_chunk, kRange, 64, 1 << 24, "intpol_chunk must be in 64 ... 16777216"),
 };
 
 }   // namespace

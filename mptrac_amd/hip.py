@@ -19,6 +19,7 @@ from .ctl import (HIP_CTL_FIELDS, RADIO_ACTIVITIES, TRACER_SERIES, ZONAL_MEANS, 
 from .synth import FIELDS_2D, FIELDS_3D, FIELDS_ML
 
 NQ_MAX = 16
+INTPOL_2D = 256     # MPHIP_INTPOL_2D: the field index of mphip_intpol_met names a surface field
 MOD = {
     "timesteps": 1 << 0, "position": 1 << 1, "advect": 1 << 2, "diff_turb": 1 << 3, "diff_meso": 1 << 4,
     "convection": 1 << 5, "sedi": 1 << 6, "position2": 1 << 7, "loss_zero": 1 << 8, "decay": 1 << 9,
@@ -196,6 +197,8 @@ def load(build=True):
         L.mphip_sizeof_met_packed.restype = C.c_size_t
         if L.mphip_sizeof_met_packed() != C.sizeof(MphipMetPacked):
             raise MphipError("mphip_met_packed_t layout mismatch between header and Python mirror")
+    if hasattr(L, "mphip_intpol_met"):      # (absent from libraries built before the point interpolation: A/B runs through MPHIP_LIB)
+        L.mphip_intpol_met.argtypes = [C.c_void_p, C.c_longlong, _dp, C.c_longlong, _dp, _dp, _dp, C.c_int, C.POINTER(C.c_int), _dp]
     if hasattr(L, "mphip_sizeof_prep"):     # (absent from libraries built before pv and the tropopause: they read the old members)
         L.mphip_sizeof_prep.restype = C.c_size_t
         if L.mphip_sizeof_prep() != C.sizeof(MphipPrep):
@@ -655,6 +658,37 @@ class Simulation:
 
     def prefetch_done(self):
         return bool(self.L.mphip_prefetch_done(self.h))
+
+    def intpol_met(self, time, p, lon, lat, fields):
+        """The resident meteo pair interpolated at the caller's points (mphip_intpol_met: intpol_met_time_3d / _2d of the
+        reference, its doubles bit for bit in both libraries).  `fields`: names of FIELDS_3D (pressure-level fields) and
+        FIELDS_2D (surface fields), any order, repeats allowed; a scalar `time` holds for all points; `p` may be None
+        when only surface fields are asked for.  Returns {name: float64 array [n]} (a name given twice: its last row)."""
+        return dict(zip(fields, self.intpol_met_rows(time, p, lon, lat, fields)))
+
+    def intpol_met_rows(self, time, p, lon, lat, fields, out=None):
+        """intpol_met as the array [nfield][n], rows in the order of `fields` (`out`: such an array to write into)."""
+        lon, lat = (np.ascontiguousarray(np.atleast_1d(a), dtype=np.float64) for a in (lon, lat))
+        n = len(lon)
+        time = np.ascontiguousarray(np.atleast_1d(time), dtype=np.float64)
+        if np.ndim(p) == 0 and p is not None:
+            p = np.full(n, p)
+        p = None if p is None else np.ascontiguousarray(p, dtype=np.float64)
+        assert len(lat) == n and (p is None or len(p) == n)
+        ids = (C.c_int * max(len(fields), 1))()
+        for k, name in enumerate(fields):
+            if name in FIELDS_2D:
+                ids[k] = INTPOL_2D | FIELDS_2D.index(name)
+            elif name in FIELDS_3D:
+                ids[k] = FIELDS_3D.index(name)
+            else:
+                raise TypeError(f"unknown field {name}")
+        if out is None:
+            out = np.empty((len(fields), n), dtype=np.float64)
+        assert out.dtype == np.float64 and out.shape == (len(fields), n) and out.flags["C_CONTIGUOUS"]
+        self._chk(self.L.mphip_intpol_met(self.h, n, _ptr(time, _dp), len(time), None if p is None else _ptr(p, _dp),
+                                          _ptr(lon, _dp), _ptr(lat, _dp), len(fields), ids, _ptr(out, _dp)))
+        return out
 
     def update_atm(self, atm):
         sl = slice(0, self.n) if self.atm_is_local else slice(self.lo, self.hi)

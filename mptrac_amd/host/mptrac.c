@@ -24,6 +24,11 @@
 static mphip_ctx *g_ctx;
 static int g_prep_ready;               /* met_derive has set up this context (HIP_MET_PREP) */
 static const met_t *g_met_host[2];     /* host snapshots mirrored in device slots met0 / met1 */
+static double g_met_time[2];           /* ... and their times when they were uploaded (NAN: no upload known) */
+static int g_met_o3[2];                /* ... and whether o3 went up with them (describe_met: o3_described) */
+static int g_ahead_o3;                 /* ... and with the snapshot of the read-ahead */
+static int g_intpol_o3;                /* HIP_DEVICE_INTPOL 1 with PROF_BASENAME: upload o3 for write_prof's device values */
+static long g_decodes, g_host_points, g_device_points;   /* mptrac_amd_intpol_stats */
 /* meteo read-ahead (HIP_MET_PREFETCH), see start_read_ahead() */
 static struct {
   met_t *met;              /* the spare buffer */
@@ -374,7 +379,8 @@ static const char *unsupported_qnt[] = {
   I(hip_locality_interval, "HIP_LOCALITY_SORT_INTERVAL", "60") \
   I(hip_met_prefetch, "HIP_MET_PREFETCH", "0") \
   I(hip_met_prep, "HIP_MET_PREP", "0") \
-  I(hip_device_analysis, "HIP_DEVICE_ANALYSIS", "1")
+  I(hip_device_analysis, "HIP_DEVICE_ANALYSIS", "1") \
+  I(hip_device_intpol, "HIP_DEVICE_INTPOL", "0")
 
 void mptrac_read_ctl(const char *filename, int argc, char *argv[], ctl_t *ctl) {
   LOG(1, "\nMassive-Parallel Trajectory Calculations (MPTRAC), MI355X build (%s)\n", mphip_version());
@@ -457,6 +463,7 @@ void mptrac_read_ctl(const char *filename, int argc, char *argv[], ctl_t *ctl) {
   /* 16-bit packed files: the codes go to the device as they are (1, the default) or are decoded when the file is read */
   ctl->hip_met_packed = ctl->met_type == 2 ? (int) scan_ctl(filename, argc, argv, "HIP_MET_PACKED", -1, "1", NULL) : 0;
   REQUIRE(ctl->hip_met_packed == 0 || ctl->hip_met_packed == 1, "Set HIP_MET_PACKED to 0 or 1!");
+  REQUIRE(ctl->hip_device_intpol == 0 || ctl->hip_device_intpol == 1, "Set HIP_DEVICE_INTPOL to 0 or 1!");
   if (ctl->met_type == 0) {
     /* netCDF input is taken as stored: no hybrid-coefficient levels (mptrac.c:7770-7830) ... */
     static const struct {
@@ -1560,6 +1567,7 @@ void met_need_floats(met_t *met) {
   if (mphip_unpack_met(g_ctx, &in, &out) != 0)
     ERRMSG("HIP back end: %s", mphip_last_error(g_ctx));
   ((met_packed_t *) met->packed)->floats = 1;
+  __atomic_add_fetch(&g_decodes, 1, __ATOMIC_RELAXED);   /* (the read-ahead thread decodes too, with HIP_MET_PACKED 0) */
   LOG(2, "Decoded on the device: %d level fields of %d x %d x %d", MET_NLEVEL, met->nx, met->ny, met->np);
 }
 
@@ -2238,6 +2246,7 @@ static void to_device_ctl(const ctl_t *c, mphip_ctl_t *d) {
   for (int k = 0; k < MPHIP_NMQ; k++)
     if (d->qnt_met[k] >= 0)
       g_meteo_fields = 1;
+  g_intpol_o3 = c->hip_device_intpol && c->prof_basename[0] != '-';
   for (int k = 0; k < 2; k++) {
     d->wet_depo_pre[k] = c->wet_depo_pre[k];
     d->wet_depo_ic_h[k] = c->wet_depo_ic_h[k];
@@ -2268,9 +2277,22 @@ static void map_met_slot(const met_t *host, int slot) {
     const met_t *tmp = g_met_host[0];
     g_met_host[0] = g_met_host[1];
     g_met_host[1] = tmp;
+    const double time = g_met_time[0];
+    g_met_time[0] = g_met_time[1];
+    g_met_time[1] = time;
+    const int o3 = g_met_o3[0];
+    g_met_o3[0] = g_met_o3[1];
+    g_met_o3[1] = o3;
     return;
   }
   g_met_host[slot] = host;
+  g_met_time[slot] = NAN;      /* (until upload_met has handed it over) */
+  g_met_o3[slot] = 0;
+}
+
+/* does describe_met name o3 (with a module_meteo quantity, or for write_prof's device values)? */
+static int o3_described(void) {
+  return g_meteo_fields || g_intpol_o3;
 }
 
 static void describe_met(met_t *met, mphip_met_t *out) {
@@ -2338,6 +2360,8 @@ static void describe_met(met_t *met, mphip_met_t *out) {
     m.f2[MPHIP_PLFC] = &met->plfc[0][0];
     m.f2[MPHIP_O3C] = &met->o3c[0][0];
   }
+  if (g_intpol_o3)
+    m.f3[MPHIP_O3] = &met->o3[0][0][0];
   *out = m;
 }
 
@@ -2358,11 +2382,15 @@ static void upload_met(met_t *met, int slot) {
     mphip_met_packed_t pk;
     describe_met_packed(met, &pk);
     HIP(mphip_update_met_packed(g_ctx, slot, &pk));
+    g_met_time[slot] = met->time;
+    g_met_o3[slot] = o3_described();
     return;
   }
   mphip_met_t m;
   describe_met(met, &m);
   HIP(mphip_update_met(g_ctx, slot, &m));
+  g_met_time[slot] = met->time;
+  g_met_o3[slot] = o3_described();
 }
 
 /* HIP_MET_PREP 1 or 2: the fields of the reference's meteo preprocessing that the file's own fields allow (2: potential
@@ -2594,8 +2622,10 @@ static void poll_read_ahead(int wait) {
     flush_steps();
     if ((packed ? mphip_prefetch_met_packed(g_ctx, &pk) : mphip_prefetch_met(g_ctx, &pk.base)) != 0) {
       WARN("Meteo read-ahead: %s", mphip_last_error(g_ctx));
-    } else
+    } else {
       g_ahead.ok = 1;
+      g_ahead_o3 = o3_described();
+    }
   }
 }
 
@@ -2626,6 +2656,10 @@ static int take_read_ahead(const char *filename, met_t **met0, met_t **met1) {
   g_ahead.met = old0;
   HIP(mphip_commit_met(g_ctx));
   LOG(1, "Meteo data from the read-ahead: %s", filename);
+  g_met_time[0] = g_met_host[1] == *met0 ? g_met_time[1] : NAN;
+  g_met_time[1] = (*met1)->time;
+  g_met_o3[0] = g_met_host[1] == *met0 ? g_met_o3[1] : 0;
+  g_met_o3[1] = g_ahead_o3;
   g_met_host[0] = *met0;
   g_met_host[1] = *met1;
   return 1;
@@ -2924,6 +2958,44 @@ double mptrac_amd_intpol_3d(const met_t *met0, const met_t *met1, size_t field_o
   return wt * (v[0] - v[1]) + v[1];
 }
 
+void mptrac_amd_intpol_points(const ctl_t *ctl, const met_t *met0, const met_t *met1, const size_t n, const double *time,
+                              const size_t ntime, const double *p, const double *lon, const double *lat, const int nfield,
+                              const size_t *field_offset, double *out) {
+  if (n == 0)
+    return;
+  /* the device answers from its resident pair: only when that is the pair the writer was handed, and only for fields it
+   * holds for both snapshots -- t and h2o always, o3 where it went up with both (a snapshot uploaded before the control
+   * parameters asked for o3 has none); anything else takes the host path below */
+  int on_device = ctl->hip_device_intpol && g_ctx && met0 && met1 && met0 == g_met_host[0] && met1 == g_met_host[1]
+    && met0->time == g_met_time[0] && met1->time == g_met_time[1] && nfield <= 3;
+  int field[3];
+  for (int k = 0; on_device && k < nfield; k++) {
+    if (field_offset[k] == offsetof(met_t, t))
+      field[k] = MPHIP_T;
+    else if (field_offset[k] == offsetof(met_t, h2o))
+      field[k] = MPHIP_H2O;
+    else if (field_offset[k] == offsetof(met_t, o3) && g_met_o3[0] && g_met_o3[1])
+      field[k] = MPHIP_O3;
+    else
+      on_device = 0;
+  }
+  if (on_device) {
+    HIP(mphip_intpol_met(g_ctx, (long long) n, time, (long long) ntime, p, lon, lat, nfield, field, out));
+    g_device_points += (long) n;
+    return;
+  }
+  for (int k = 0; k < nfield; k++)
+    for (size_t i = 0; i < n; i++)
+      out[(size_t) k * n + i] = mptrac_amd_intpol_3d(met0, met1, field_offset[k], time[ntime == 1 ? 0 : i], p[i], lon[i], lat[i]);
+  g_host_points += (long) n;
+}
+
+void mptrac_amd_intpol_stats(long *decodes, long *host_points, long *device_points) {
+  *decodes = __atomic_load_n(&g_decodes, __ATOMIC_RELAXED);
+  *host_points = g_host_points;
+  *device_points = g_device_points;
+}
+
 /* what write_grid derives per box from the device's sums: column density, implicit volume mixing ratio, number of
  * particles, mean (and standard deviation) of every quantity -- then laid out as text or as netCDF */
 typedef struct {
@@ -3057,8 +3129,9 @@ void write_grid(const char *filename, const ctl_t *ctl, met_t *met0, met_t *met1
   /* Binning and sums on the device (mphip_grid_sums; mptrac.c:13815-13872),
    * post-processing as mptrac.c:13875-13918, layout as write_grid_asc / write_grid_nc;
    * the implicit volume mixing ratio (MOLMASS set, mass quantity present) uses
-   * the temperature at the cell centre, interpolated on the host as in the
-   * reference. */
+   * the temperature at the centres of the cells that hold mass: collected and
+   * interpolated in one call -- on the host as in the reference, or with
+   * HIP_DEVICE_INTPOL 1 on the device (mptrac_amd_intpol_points). */
   (void) atm;
   if (ctl->met_coord_type != 0)
     ERRMSG("Only lat/lon grid supported");
@@ -3099,6 +3172,36 @@ void write_grid(const char *filename, const ctl_t *ctl, met_t *met0, met_t *met1
     g.lat[j] = ctl->grid_lat0 + g.step_lat * (j + 0.5);
     g.area[j] = g.step_lat * g.step_lon * SQR(RE * M_PI / 180.) * cos(DEG2RAD(g.lat[j]));
   }
+  /* the temperature at the centres of the cells that hold mass, for the implicit volume mixing ratio: the points are
+   * collected first and interpolated in one call (mptrac_amd_intpol_points: on the host, or on the device) */
+  double *temp = NULL;
+  size_t *temp_of = NULL;      /* cell -> index into temp */
+  if (ctl->qnt_m >= 0 && ctl->molmass > 0 && met0 && met1) {
+    size_t n = 0;
+    double *pt_p, *pt_lon, *pt_lat;
+    ALLOC(temp_of, size_t, g.ncell);
+    ALLOC(pt_p, double, g.ncell);
+    ALLOC(pt_lon, double, g.ncell);
+    ALLOC(pt_lat, double, g.ncell);
+    for (int i = 0; i < ctl->grid_nx; i++)
+      for (int j = 0; j < ctl->grid_ny; j++)
+        for (int k = 0; k < ctl->grid_nz; k++) {
+          const size_t cell = (size_t) ARRAY_3D(i, j, ctl->grid_ny, k, ctl->grid_nz);
+          if (g.mean[(size_t) ctl->qnt_m * g.ncell + cell] > 0) {
+            temp_of[cell] = n;
+            pt_p[n] = P(g.z[k]);
+            pt_lon[n] = g.lon[i];
+            pt_lat[n] = g.lat[j];
+            n++;
+          }
+        }
+    ALLOC(temp, double, n + 1);
+    const size_t offset = offsetof(met_t, t);
+    mptrac_amd_intpol_points(ctl, met0, met1, n, &t, 1, pt_p, pt_lon, pt_lat, 1, &offset, temp);
+    free(pt_p);
+    free(pt_lon);
+    free(pt_lat);
+  }
   for (int i = 0; i < ctl->grid_nx; i++)
     for (int j = 0; j < ctl->grid_ny; j++)
       for (int k = 0; k < ctl->grid_nz; k++) {
@@ -3111,8 +3214,7 @@ void write_grid(const char *filename, const ctl_t *ctl, met_t *met0, met_t *met1
           g.vmr_impl[cell] = 0;
           if (mass > 0) {
             const double press = P(g.z[k]);
-            const double temp = mptrac_amd_intpol_3d(met0, met1, offsetof(met_t, t), t, press, g.lon[i], g.lat[j]);
-            g.vmr_impl[cell] = MA / ctl->molmass * g.cd[cell] / (100. * press / (RA * temp) * g.step_z * 1e3);
+            g.vmr_impl[cell] = MA / ctl->molmass * g.cd[cell] / (100. * press / (RA * temp[temp_of[cell]]) * g.step_z * 1e3);
           }
         }
         /* sums -> mean and standard deviation (after the column density: it uses the summed mass) */
@@ -3126,6 +3228,8 @@ void write_grid(const char *filename, const ctl_t *ctl, met_t *met0, met_t *met1
             *mean = *sigma = NAN;
         }
       }
+  free(temp);
+  free(temp_of);
   if (ctl->grid_type == 0)
     write_grid_asc(filename, ctl, &g, t);
   else

@@ -237,6 +237,10 @@ typedef struct {
   int hip_met_packed;     /* HIP_MET_PACKED (default 1; read with MET_TYPE 2 only): the level fields of 16-bit packed meteo
                              files go to the device as codes and are decoded there, the float members of met_t are filled
                              on first use; 0: decoded into the members when the file is read, the MET_TYPE 1 path from there */
+  int hip_device_intpol;  /* HIP_DEVICE_INTPOL (default 0): 1: the meteo values of the grid, profile and sample outputs come
+                             from the resident snapshots on the device (mphip_intpol_met, one call per output; the same
+                             doubles, so the same files), packed snapshots stay codes, and o3 is uploaded with
+                             PROF_BASENAME; 0: interpolated on the host; other values are refused */
 } ctl_t;
 
 /* air parcels, as the reference (mptrac.h:3563-3583) */
@@ -413,6 +417,17 @@ long mptrac_amd_output_downloads(void);
  * intpol_met_time_3d returns (mptrac.c:3112-3137) -- for the few profile / sample points of the writers */
 double mptrac_amd_intpol_3d(const met_t *met0, const met_t *met1, size_t field_offset, double ts, double p,
                             double lon, double lat);
+/* The same for n points and nfield level fields at once, for a writer that has collected its points: out[k * n + i] is
+ * field k (its offset in met_t: t, h2o or o3) at point i; time has ntime = 1 or n entries.  With HIP_DEVICE_INTPOL 1, and
+ * met0 / met1 the two snapshots last uploaded as the resident pair (same objects, same times), one mphip_intpol_met call
+ * -- no met_need_floats, no host arithmetic --; otherwise (other snapshots, another field than t, h2o, o3, more than three
+ * fields, or o3 asked for where a resident snapshot was uploaded without it) mptrac_amd_intpol_3d per point and field.
+ * Same doubles either way. */
+void mptrac_amd_intpol_points(const ctl_t *ctl, const met_t *met0, const met_t *met1, size_t n, const double *time,
+                              size_t ntime, const double *p, const double *lon, const double *lat, int nfield,
+                              const size_t *field_offset, double *out);
+/* for the driver's closing summary: met_need_floats calls that decoded, points interpolated on the host / on the device */
+void mptrac_amd_intpol_stats(long *decodes, long *host_points, long *device_points);
 /* The float level members (z, t, u, v, w, pv, h2o, o3, lwc, rwc, iwc, swc, cc) of a snapshot read from a MET_TYPE 2 file
  * with HIP_MET_PACKED 1 are valid after this call: it decodes the codes on the device (mphip_unpack_met) the first time,
  * and does nothing for any other snapshot.  Every host consumer of these members calls it first. */

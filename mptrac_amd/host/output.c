@@ -596,28 +596,53 @@ void write_prof(const char *filename, const ctl_t *ctl, met_t *met0, met_t *met1
     prof_loop_host(ctl, atm, &grid, &now, mass);
   else
     prof_loop_device(ctl, &grid, t, mass);
+  /* the box centres of the columns that will be printed: collected, then interpolated in one call for t, h2o and o3
+   * (mptrac_amd_intpol_points: on the host, or on the device) */
+  size_t npt = 0;
+  double *pt_p, *pt_lon, *pt_lat, *val;
+  ALLOC(pt_p, double, ncol * (size_t) grid.nz);
+  ALLOC(pt_lon, double, ncol * (size_t) grid.nz);
+  ALLOC(pt_lat, double, ncol * (size_t) grid.nz);
   for (size_t c = 0; c < ncol; c++) {
     if (ocount[c] <= 0)
       continue;
     int loaded = 0;
     for (int iz = 0; iz < grid.nz && !loaded; iz++)
       loaded = mass[c * (size_t) grid.nz + (size_t) iz] > 0;
-    if (!loaded)
+    if (!loaded) {
+      ocount[c] = 0;     /* (not printed) */
+      continue;
+    }
+    const int ix = (int) (c / (size_t) grid.ny), iy = (int) (c % (size_t) grid.ny);
+    for (int iz = 0; iz < grid.nz; iz++, npt++) {
+      pt_p[npt] = P(grid.z0 + grid.dz * (iz + 0.5));
+      pt_lon[npt] = grid.lon0 + grid.dlon * (ix + 0.5);
+      pt_lat[npt] = grid.lat0 + grid.dlat * (iy + 0.5);
+    }
+  }
+  ALLOC(val, double, 3 * npt + 1);
+  const size_t offsets[3] = { offsetof(met_t, t), offsetof(met_t, h2o), offsetof(met_t, o3) };
+  mptrac_amd_intpol_points(ctl, met0, met1, npt, &t, 1, pt_p, pt_lon, pt_lat, 3, offsets, val);
+  size_t pt = 0;
+  for (size_t c = 0; c < ncol; c++) {
+    if (ocount[c] <= 0)
       continue;
     const int ix = (int) (c / (size_t) grid.ny), iy = (int) (c % (size_t) grid.ny);
     const double lon = grid.lon0 + grid.dlon * (ix + 0.5), lat = grid.lat0 + grid.dlat * (iy + 0.5);
     fputc('\n', out);
-    for (int iz = 0; iz < grid.nz; iz++) {
+    for (int iz = 0; iz < grid.nz; iz++, pt++) {
       const double z = grid.z0 + grid.dz * (iz + 0.5), press = P(z);
-      const double temp = mptrac_amd_intpol_3d(met0, met1, offsetof(met_t, t), t, press, lon, lat);
-      const double h2o = mptrac_amd_intpol_3d(met0, met1, offsetof(met_t, h2o), t, press, lon, lat);
-      const double o3 = mptrac_amd_intpol_3d(met0, met1, offsetof(met_t, o3), t, press, lon, lat);
+      const double temp = val[pt], h2o = val[npt + pt], o3 = val[2 * npt + pt];
       const double air = 100. * press / (RA * temp);   /* density [kg/m^3] */
       const double vmr = MA / ctl->molmass * mass[c * (size_t) grid.nz + (size_t) iz] / (air * grid.area[iy] * grid.dz * 1e9);
       fprintf(out, "%.2f %g %g %g %g %g %g %g %g %g %d\n", t, z, lon, lat, press, temp, vmr, h2o, o3,
               osum[c] / ocount[c], ocount[c]);
     }
   }
+  free(pt_p);
+  free(pt_lon);
+  free(pt_lat);
+  free(val);
   free(mass);
   free(osum);
   free(ocount);
@@ -706,12 +731,28 @@ void write_sample(const char *filename, const ctl_t *ctl, met_t *met0, met_t *me
   double *dev_mass = NULL;
   if (!atm)
     sample_loop_device(ctl, &obs, t0, t1, kz, kw, nk, &first, &dev_count, &dev_mass);
-  for (int i = 0; i < obs.n && obs.t[i] < t1; i++) {
-    if (obs.t[i] < t0)
-      continue;
+  /* count and mass around every observation of the step; the observations that hold mass are collected and their
+   * temperatures interpolated in one call (mptrac_amd_intpol_points: on the host, or on the device) */
+  int begin = 0, nstep = 0;
+  while (begin < obs.n && obs.t[begin] < t0)
+    begin++;
+  while (begin + nstep < obs.n && obs.t[begin + nstep] < t1)
+    nstep++;
+  double *mass_of, *pt_t, *pt_p, *pt_lon, *pt_lat, *temp;
+  int *count_of;
+  ALLOC(mass_of, double, nstep + 1);
+  ALLOC(count_of, int, nstep + 1);
+  ALLOC(pt_t, double, nstep + 1);
+  ALLOC(pt_p, double, nstep + 1);
+  ALLOC(pt_lon, double, nstep + 1);
+  ALLOC(pt_lat, double, nstep + 1);
+  ALLOC(temp, double, nstep + 1);
+  const int want_temp = ctl->molmass > 0 && ctl->sample_dz > 0;
+  size_t npt = 0;
+  for (int i = begin; i < begin + nstep; i++) {
     double centre[3];
     geo2cart(0, obs.lon[i], obs.lat[i], centre);
-    const double p_obs = P(obs.z[i]), p_top = P(obs.z[i] + ctl->sample_dz), p_bottom = P(obs.z[i] - ctl->sample_dz);
+    const double p_top = P(obs.z[i] + ctl->sample_dz), p_bottom = P(obs.z[i] - ctl->sample_dz);
     double mass = 0;
     int count = 0;
     if (atm)
@@ -720,18 +761,38 @@ void write_sample(const char *filename, const ctl_t *ctl, met_t *met0, met_t *me
       mass = dev_mass[i - first];
       count = dev_count[i - first];
     }
+    mass_of[i - begin] = mass;
+    count_of[i - begin] = count;
+    if (want_temp && mass > 0) {
+      pt_t[npt] = obs.t[i];
+      pt_p[npt] = P(obs.z[i]);
+      pt_lon[npt] = obs.lon[i];
+      pt_lat[npt] = obs.lat[i];
+      npt++;
+    }
+  }
+  const size_t offset = offsetof(met_t, t);
+  mptrac_amd_intpol_points(ctl, met0, met1, npt, pt_t, npt, pt_p, pt_lon, pt_lat, 1, &offset, temp);
+  size_t pt = 0;
+  for (int i = begin; i < begin + nstep; i++) {
+    const double p_obs = P(obs.z[i]), mass = mass_of[i - begin];
     const double cd = mass / (1e6 * area);
     double vmr = NAN;
-    if (ctl->molmass > 0 && ctl->sample_dz > 0) {
+    if (want_temp) {
       vmr = 0;
-      if (mass > 0) {
-        const double temp = mptrac_amd_intpol_3d(met0, met1, offsetof(met_t, t), obs.t[i], p_obs, obs.lon[i], obs.lat[i]);
-        vmr = MA / ctl->molmass * cd / (100. * p_obs / (RA * temp) * ctl->sample_dz * 1e3);
-      }
+      if (mass > 0)
+        vmr = MA / ctl->molmass * cd / (100. * p_obs / (RA * temp[pt++]) * ctl->sample_dz * 1e3);
     }
     fprintf(out, "%.2f %g %g %g %g %g %d %g %g %g\n", obs.t[i], obs.z[i], obs.lon[i], obs.lat[i], area, ctl->sample_dz,
-            count, cd, vmr, obs.val[i]);
+            count_of[i - begin], cd, vmr, obs.val[i]);
   }
+  free(mass_of);
+  free(count_of);
+  free(pt_t);
+  free(pt_p);
+  free(pt_lon);
+  free(pt_lat);
+  free(temp);
   free(dev_count);
   free(dev_mass);
   if (t == ctl->t_stop) {

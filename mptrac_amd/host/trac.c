@@ -119,6 +119,13 @@ int main(int argc, char *argv[]) {
     LOG(1, "TIMER_UPDATE_HOST = %.3f s    (rest of the queue + final download)", w1 - a4);
     LOG(1, "PARTICLE_DOWNLOADS = %ld    (by mptrac_write_output in %ld calls; the final download not counted)",
         mptrac_amd_output_downloads(), nsteps);
+    {
+      long decodes, host_points, device_points;
+      mptrac_amd_intpol_stats(&decodes, &host_points, &device_points);
+      LOG(1, "MET_DECODES = %ld    (met_need_floats calls that decoded a packed snapshot for the host)", decodes);
+      LOG(1, "INTPOL_POINTS = %ld host, %ld device    (meteo values of the grid, profile and sample outputs)", host_points,
+          device_points);
+    }
     LOG(1, "TIMER_WITHOUT_MET_AND_OUTPUT = %.3f s    (%.3e particle-steps/s)", w1 - w0 - w_met - w_out,
         nsteps > 1 && w1 - w0 - w_met - w_out > 0 ? (double) atm->np * (double) (nsteps - 1) / (w1 - w0 - w_met - w_out) : 0.0);
 
