@@ -12,8 +12,17 @@ import numpy as np
 RE, H0, P0 = 6367.421, 7.0, 1013.25
 
 
+def _libm(f, x, at_zero=math.nan):
+    """f(x) of the C library where Python's math module raises instead: cos / sin of an infinity and the logarithm of a
+    negative number are NaN, log(+-0) is -inf.  Every other argument goes through math's call of libm unchanged."""
+    try:
+        return f(x)
+    except ValueError:
+        return at_zero if x == 0 else math.nan
+
+
 def Z(p):
-    return H0 * math.log(P0 / p)
+    return H0 * _libm(math.log, P0 / p, -math.inf)
 
 
 def P(z):
@@ -22,7 +31,8 @@ def P(z):
 
 def geo2cart(z, lon, lat):
     r, phi, lam = RE + z, lat * (math.pi / 180.0), lon * (math.pi / 180.0)
-    return (r * math.cos(phi) * math.cos(lam), r * math.cos(phi) * math.sin(lam), r * math.sin(phi))
+    cos_phi, sin_phi, cos_lam, sin_lam = _libm(math.cos, phi), _libm(math.sin, phi), _libm(math.cos, lam), _libm(math.sin, lam)
+    return (r * cos_phi * cos_lam, r * cos_phi * sin_lam, r * sin_phi)
 
 
 def kernel_weight(kz, kw, p):
@@ -41,7 +51,10 @@ def kernel_weight(kz, kw, p):
             hi = mid
         else:
             lo = mid
-    return kw[lo] + (kw[lo + 1] - kw[lo]) / (kz[lo + 1] - kz[lo]) * (z - kz[lo])
+    # (C's division: a repeated node gives +-inf or NaN where Python's / raises; the same bits everywhere else)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        slope = float(np.float64(kw[lo + 1] - kw[lo]) / np.float64(kz[lo + 1] - kz[lo]))
+    return kw[lo] + slope * (z - kz[lo])
 
 
 def box_cell(box, lon, lat, z):
