@@ -525,6 +525,81 @@ typedef struct {
 size_t mphip_sizeof_detrend(void);      /* sizeof(mphip_detrend_t), for mirrors of the structure in other languages */
 int mphip_detrend_met(mphip_ctx *ctx, const mphip_met_t *in, const mphip_detrend_t *opt, const mphip_regrid_out_t *out);
 
+/* Ingest: what lies between the values a netCDF file (MET_TYPE 0) stores and a met_t -- decoding of packed shorts, the
+ * fill / missing-value mask, the unit scale, the re-ordering from the file's [level][y][x] to met_t's [x][y][level], the
+ * surface pressure from its logarithm, the extrapolation below the lowest valid level, the pole rows of the winds and
+ * the periodic longitude column.  The call keeps the contract of mphip_derive_met / mphip_regrid_met /
+ * mphip_detrend_met: the same stream and lock, the same scratch pool (grow-only, freed by mphip_destroy), no meteo slot,
+ * no prefetch state and no particle touched, callable from a file-reader thread while another thread steps; a refused
+ * call writes nothing and its message starts with "mphip_ingest_met: ".  Every input is uploaded before any output is
+ * copied back, so met-order outputs may alias met-order inputs (the host layer works on its met_t in place).
+ *   `what` is an OR of MPHIP_INGEST_* bits; the stages always run in the order DECODE, EXTRAPOLATE, POLAR, PERIODIC.
+ *   Input.  The axes (lon, lat, p), the extents nx, ny, np (npl: the levels of the model-level slots MPHIP_PL, UL, VL,
+ * ZETAL, ZETA_DOTL, WL) and coord_type come from `in`.  With DECODE a slot whose descriptor in `raw` has a type other than
+ * 0 is read from that descriptor: `data` in file order, [nlev][ny][nx] or [ny][nx], host-endian.  Every other slot, and
+ * every slot without DECODE (`raw` may be NULL then), is read from in->f3 / in->f2 in met order, strided as for
+ * mphip_detrend_met (sx_ml, sy_ml for the model-level slots).  The second form is what a model-level file needs, where
+ * mphip_regrid_met(ML2PL) runs between DECODE and the other stages.
+ *   Output.  `out` names its arrays, their strides (sy >= the levels of every field named, sx a multiple of sy and >= ny
+ * sy, sx2 >= ny; the model-level slots use sx, sy as well) and the axes: lon gets nx2 values, lat ny, p np; an axis that is
+ * NULL is skipped.  A slot that is absent on the input side or NULL in `out` is skipped.  Every slot present on both
+ * sides is written, with nx2 columns, whichever stages run.
+ *
+ *   DEFINITIONS, transcribed from the host loops of read_met_nc in mptrac_amd/host/mptrac.c (nc_field, the lnsp
+ * conversion, the extrapolation loop behind "Pressure levels must be descending", met_polar_winds /
+ * pole_row_from_neighbour, met_periodic), which tests/test_ingest_cpu.py pins to the restatement tests/refingest.py.
+ * Every operation is the IEEE operation on the named type, rounded once and never contracted, in BOTH libraries; NAN is
+ * the quiet NaN 0x7fc00000; exp, cos and sin are the C library's (mphip_libm.h on the device).
+ *   DECODE, MPHIP_RAW_SHORT (shorts are always packed; an unpacked short variable stays the reader's float conversion):
+ * float v = (float) raw * scale_factor + add_offset, a float product and then a float sum; keep = (fill_s == 0 || raw !=
+ * fill_s) && (miss_s == 0 || raw != miss_s) && fabsf(v) < 1e14f; out = keep ? scl * v : NAN.  fill and miss are already
+ * converted to the stored type, 0 meaning "none", exactly as nc_field forms fillval / missval.
+ *   DECODE, MPHIP_RAW_FLOAT: the same with v the stored value and float comparisons against fill_f, miss_f.  A NaN or
+ * infinite stored value therefore gives NAN, and a NaN fill masks nothing.
+ *   DECODE, lnsp (MPHIP_PS only): after the above (the reader passes scl = 1), ps = (float) (exp((double) out) / 100.).
+ *   DECODE, placement: the value of file index (k, j, i) lands at [i][j][k].
+ *   EXTRAPOLATE.  Per column, low = the largest level index at which t, u, v or w is not finite, or -1; a field of the
+ * four that is absent counts as finite.  Every present level field of t, u, v, w, h2o, o3, lwc, rwc, iwc, swc, cc gets f[k]
+ * = f[low + 1] for k <= low; bits are copied, so NaN payloads survive.  If low == np - 1 the column is filled with 0.f.
+ * (This is this project's definition.  The host loop reads element np of the fixed-extent array [EP] there -- zero in a
+ * fresh met_t, whatever an earlier and larger file left there otherwise -- or 0.f when np == EP.  The host loop is left
+ * as it is.)
+ *   POLAR.  Runs only if coord_type == 0, |lat[0]| >= 89.999 and |lat[ny-1]| >= 89.999, and u and v are both present.  Per
+ * pole row the tables c[ix] = cos(turn lon[ix] (M_PI / 180.0)), s[ix] = sin(turn lon[ix] (M_PI / 180.0)) with turn =
+ * lat[pole] < 0 ? -1 : 1 are built by the host inside the call.  Per pole and level the double sums run over ix = 0 ...
+ * nx-1 in that order: mx += (u c - v s) / nx, my += (u s + v c) / nx with u, v of the neighbour row -- two products, one
+ * difference or sum and one true division by (double) nx each --, then u = (float) (mx c + my s), v = (float) (my c - mx
+ * s) on the pole row.  The rows are done in the order {0 from 1}, {ny-1 from ny-2}: with ny == 2 the second reads what the
+ * first wrote.  nx is the extent before the periodic column is added.
+ *   PERIODIC.  Runs only if coord_type == 0 and fabs(lon[nx-1] - lon[0] + lon[1] - lon[0] - 360) < 0.01.  nx2 = nx + 1,
+ * lon[nx] = lon[nx-1] + lon[1] - lon[0], and column nx of every present field, the model-level slots included, is a copy
+ * of column 0.  Otherwise nx2 = nx.  mphip_ingest_shape answers nx2 without a context (non-zero where the call would
+ * refuse the grid or `what`).  A caller with arrays of a fixed extent checks nx2 against it before the call.
+ *   Refused: a NULL argument (raw with DECODE) or a missing axis (lon, lat, p); nx < 2, ny < 2, np < 2; nx2 ny >= 2^24 or
+ * nx2 ny nlev >= 2^31; input strides that do not hold a met-order field that is read; output strides that do not hold ny
+ * and the levels; a descriptor with a type other than 0, MPHIP_RAW_FLOAT, MPHIP_RAW_SHORT; a descriptor with NULL data
+ * for a field that `out` names; DECODE with a field given both raw and in in->f3 / in->f2; a `what` outside the four
+ * bits, or 0; lnsp on a slot other than MPHIP_PS; a model-level slot with npl < 1; no field present on both sides. */
+enum { MPHIP_INGEST_DECODE = 1, MPHIP_INGEST_EXTRAPOLATE = 2, MPHIP_INGEST_POLAR = 4, MPHIP_INGEST_PERIODIC = 8 };
+enum { MPHIP_RAW_FLOAT = 1, MPHIP_RAW_SHORT = 2 };
+typedef struct {
+  const void *data;                     /* float or short values in file order; NULL with type 0 */
+  int type;                             /* 0: the slot is not given raw */
+  int lnsp;                             /* MPHIP_PS only: the values are the logarithm of the surface pressure in Pa */
+  float scale_factor, add_offset;       /* MPHIP_RAW_SHORT */
+  float fill_f, miss_f;                 /* MPHIP_RAW_FLOAT: _FillValue, missing_value as floats (0: none) */
+  short fill_s, miss_s;                 /* MPHIP_RAW_SHORT: ... as shorts (0: none) */
+  float scl;                            /* the unit scale */
+} mphip_raw_t;
+typedef struct {
+  mphip_raw_t f3[MPHIP_N3D];
+  mphip_raw_t f2[MPHIP_N2D];
+} mphip_ingest_raw_t;
+size_t mphip_sizeof_ingest_raw(void);   /* sizeof(mphip_ingest_raw_t), for mirrors of the structure in other languages */
+int mphip_ingest_shape(const mphip_met_t *in, unsigned what, int *nx2);
+int mphip_ingest_met(mphip_ctx *ctx, const mphip_met_t *in, const mphip_ingest_raw_t *raw, unsigned what,
+                     const mphip_regrid_out_t *out);
+
 /* 16-bit packed level fields (the reference's MET_TYPE 2 files): every level field as unsigned 16-bit codes with one scale
  * and one offset per level -- half the bytes on disk and over PCIe.  The codes travel to the device as they are and become
  * floats there (2 bytes read and 4 written per value, once per snapshot); no arithmetic on meteo values on the host.

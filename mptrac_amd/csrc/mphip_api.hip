@@ -20,6 +20,7 @@
 #include "mphip_metprep.hpp"
 #include "mphip_regrid.hpp"
 #include "mphip_detrend.hpp"
+#include "mphip_ingest.hpp"
 #include "mphip_pack.hpp"
 #include "mphip_intpol.hpp"
 
@@ -4317,6 +4318,216 @@ int mphip_detrend_met(mphip_ctx *ctx, const mphip_met_t *in, const mphip_detrend
   if (call.mark_end())
     return 1;
   return call.close();
+}
+
+// ---- mphip_ingest_met (mphip_ingest.hpp) -------------------------------------------------------------------------------
+size_t mphip_sizeof_ingest_raw(void) {
+  return sizeof(mphip_ingest_raw_t);
+}
+
+// what mphip_ingest_shape and mphip_ingest_met refuse of the grid and of `what`, and which of POLAR and PERIODIC act;
+// NULL = accepted
+struct IngestPlan {
+  int nx, ny, np, nx2;
+  bool polar, periodic;
+};
+
+static const char *ingest_plan(const mphip_met_t *in, unsigned what, IngestPlan *P) {
+  const unsigned all = MPHIP_INGEST_DECODE | MPHIP_INGEST_EXTRAPOLATE | MPHIP_INGEST_POLAR | MPHIP_INGEST_PERIODIC;
+  if (!what || (what & ~all))
+    return "`what` must be an OR of MPHIP_INGEST_* bits";
+  if (!in->lon || !in->lat || !in->p)
+    return "the input axes are missing";
+  if (const char *why = grid_refusal(in->nx, in->ny, in->np))
+    return why;
+  if (const char *why = grid_size_refusal(in->nx, in->ny, std::max(in->np, in->npl)))
+    return why;
+  P->nx = in->nx;
+  P->ny = in->ny;
+  P->np = in->np;
+  const double *lon = in->lon, *lat = in->lat;
+  P->polar = (what & MPHIP_INGEST_POLAR) && in->coord_type == 0 && fabs(lat[0]) >= 89.999 && fabs(lat[in->ny - 1]) >= 89.999;
+  P->periodic = (what & MPHIP_INGEST_PERIODIC) && in->coord_type == 0
+    && fabs(lon[in->nx - 1] - lon[0] + lon[1] - lon[0] - 360) < 0.01;
+  P->nx2 = in->nx + (P->periodic ? 1 : 0);
+  return grid_size_refusal(P->nx2, in->ny, std::max(in->np, in->npl));
+}
+
+int mphip_ingest_shape(const mphip_met_t *in, unsigned what, int *nx2) {
+  IngestPlan P;
+  if (!in || !nx2 || ingest_plan(in, what, &P))
+    return 1;
+  *nx2 = P.nx2;
+  return 0;
+}
+
+int mphip_ingest_met(mphip_ctx *ctx, const mphip_met_t *in, const mphip_ingest_raw_t *raw, unsigned what,
+                     const mphip_regrid_out_t *out) {
+  const bool decode = what & MPHIP_INGEST_DECODE;
+  if (!ctx || !in || !out || (decode && !raw))
+    return fail(ctx, "mphip_ingest_met: null argument");
+  IngestPlan P;
+  if (const char *why = ingest_plan(in, what, &P))
+    return fail(ctx, std::string("mphip_ingest_met: ") + why);
+  // the fields of this call: given raw or in met order, and named in `out`
+  struct Field {
+    bool is3;
+    int f, nlev;
+    const mphip_raw_t *raw;     // NULL: in met order
+    const float *src;
+    float *dst, *dev;
+    long long sx, sy;           // of src (3-D)
+  } fld[MPHIP_N3D + MPHIP_N2D];
+  int nf = 0;
+  for (int i = 0; i < MPHIP_N3D + MPHIP_N2D; i++) {
+    const bool is3 = i < MPHIP_N3D;
+    const int f = is3 ? i : i - MPHIP_N3D;
+    const char *name = is3 ? kField3Name[f] : kField2Name[f];
+    const mphip_raw_t *r = decode ? (is3 ? &raw->f3[f] : &raw->f2[f]) : nullptr;
+    const float *src = is3 ? in->f3[f] : in->f2[f];
+    float *dst = is3 ? out->f3[f] : out->f2[f];
+    if (r && r->type == 0)
+      r = nullptr;
+    if (r) {
+      if (r->type != MPHIP_RAW_FLOAT && r->type != MPHIP_RAW_SHORT)
+        return fail(ctx, std::string("mphip_ingest_met: field ") + name + " has a raw descriptor of unknown type");
+      if (src)
+        return fail(ctx, std::string("mphip_ingest_met: field ") + name + " is given both raw and in met order");
+      if (r->lnsp && (is3 || f != MPHIP_PS))
+        return fail(ctx, std::string("mphip_ingest_met: field ") + name + ": lnsp belongs to the surface pressure alone");
+      if (dst && !r->data)
+        return fail(ctx, std::string("mphip_ingest_met: field ") + name + " has a raw descriptor without data");
+    }
+    if ((!r && !src) || !dst)
+      continue;
+    const bool is_ml = is3 && field_on_model_levels(f);
+    if (is_ml && in->npl < 1)
+      return fail(ctx, std::string("mphip_ingest_met: field ") + name + " is on model levels and npl < 1");
+    const int nlev = !is3 ? 1 : is_ml ? in->npl : in->np;
+    if (!r && (is3 ? !regrid_strides_ok(P.ny, nlev, is_ml ? in->sx_ml : in->sx, is_ml ? in->sy_ml : in->sy) : in->sx2 < P.ny))
+      return fail(ctx, "mphip_ingest_met: unsupported meteo strides");
+    if (is3 ? !regrid_strides_ok(P.ny, nlev, out->sx, out->sy) : out->sx2 < P.ny)
+      return fail(ctx, "mphip_ingest_met: the output strides do not hold the grid");
+    fld[nf++] = Field{ is3, f, nlev, r, src, dst, nullptr, is_ml ? in->sx_ml : in->sx, is_ml ? in->sy_ml : in->sy };
+  }
+  if (!nf)
+    return fail(ctx, "mphip_ingest_met: no field is given in `in` or `raw` and named in `out`");
+
+  // the axes of the output and the frames of the two poles are taken before anything is written (`out` may alias `in`)
+  const int nx = P.nx, ny = P.ny, np = P.np, nx2 = P.nx2;
+  std::vector<double> lon2(in->lon, in->lon + nx), lat2(in->lat, in->lat + ny), p2(in->p, in->p + np);
+  if (P.periodic)
+    lon2.push_back(in->lon[nx - 1] + in->lon[1] - in->lon[0]);
+  const int pole_rows[2][2] = { { 0, 1 }, { ny - 1, ny - 2 } };   // { pole row, its neighbour }
+  std::vector<double> cs;       // [pole][c, s][nx]
+  if (P.polar) {
+    cs.resize((size_t) 4 * nx);
+    for (int k = 0; k < 2; k++) {
+      const double turn = in->lat[pole_rows[k][0]] < 0 ? -1 : 1;
+      for (int ix = 0; ix < nx; ix++) {
+        const double a = turn * (in->lon[ix] * (M_PI / 180.0));
+        cs[((size_t) 2 * k) * nx + ix] = cos(a);
+        cs[((size_t) 2 * k + 1) * nx + ix] = sin(a);
+      }
+    }
+  }
+
+  PrepCall call(ctx);
+  if (call.open())
+    return 1;
+  hipStream_t st = call.st;
+  const size_t ncol = (size_t) nx * ny;
+  void *d_raw[MPHIP_N3D + MPHIP_N2D] = {};
+  double *d_cs = nullptr;
+  if (call.mark_begin(1))
+    return 1;
+  if (P.polar) {
+    if (!(d_cs = call.take<double>(cs.size())))
+      return 1;
+    HIPCHK(hipMemcpyAsync(d_cs, cs.data(), cs.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  }
+  for (int i = 0; i < nf; i++) {
+    Field &F = fld[i];
+    const size_t n = ncol * F.nlev;
+    if (!(F.dev = call.take<float>((size_t) nx2 * ny * F.nlev)))
+      return 1;
+    if (F.raw) {
+      const size_t bytes = n * (F.raw->type == MPHIP_RAW_SHORT ? sizeof(short) : sizeof(float));
+      if (!(d_raw[i] = call.take<char>(bytes)))
+        return 1;
+      HIPCHK(hipMemcpyAsync(d_raw[i], F.raw->data, bytes, hipMemcpyHostToDevice, st));
+    } else if (F.is3 ? copy3(ctx, st, F.dev, F.src, nx, ny, F.nlev, F.sx, F.sy, true)
+                     : copy2(ctx, st, F.dev, F.src, nx, ny, in->sx2, true)) {
+      return 1;
+    }
+  }
+  if (call.mark_end())
+    return 1;
+  // (an aliased input must have been read before the first download overwrites it: the uploads are complete here)
+  HIPCHK(hipStreamSynchronize(st));
+
+  float *dev3[MPHIP_N3D] = {};
+  for (int i = 0; i < nf; i++) {
+    const Field &F = fld[i];
+    if (F.is3)
+      dev3[F.f] = F.dev;
+    if (!F.raw)
+      continue;
+    const mphip_raw_t &r = *F.raw;
+    const IngestRaw R = { r.scale_factor, r.add_offset, r.fill_f, r.miss_f, r.fill_s, r.miss_s, r.scl, r.lnsp };
+    // (a surface field: its y axis in the place of the level)
+    const int rows = F.is3 ? ny : 1, lev = F.is3 ? F.nlev : ny;
+    const dim3 grid((unsigned) ((nx + kIgTile - 1) / kIgTile), (unsigned) rows, (unsigned) ((lev + kIgTile - 1) / kIgTile));
+    if (r.type == MPHIP_RAW_SHORT
+          ? call.launch(ingest_decode_kernel<short>, grid, dim3(kIgThreads), 0, (const short *) d_raw[i], F.dev, nx, rows, lev, R)
+          : call.launch(ingest_decode_kernel<float>, grid, dim3(kIgThreads), 0, (const float *) d_raw[i], F.dev, nx, rows, lev, R))
+      return 1;
+  }
+  if (what & MPHIP_INGEST_EXTRAPOLATE) {
+    IngestColumns C;
+    bool any = false;
+    for (int i = 0; i < kIgFields; i++)
+      any |= (C.f[i] = dev3[kRegridMl[i]]) != nullptr;
+    constexpr int per = kIgThreads / 64;
+    if (any && call.launch(ingest_extrapolate_kernel, dim3((unsigned) ((ncol + per - 1) / per)), dim3(kIgThreads), 0, C, (int) ncol, np))
+      return 1;
+  }
+  if (P.polar && dev3[MPHIP_U] && dev3[MPHIP_V])
+    for (int k = 0; k < 2; k++)
+      if (call.launch(ingest_polar_kernel, dim3((unsigned) ((np + 63) / 64)), dim3(64), 0, dev3[MPHIP_U], dev3[MPHIP_V], nx, ny, np,
+                      pole_rows[k][0], pole_rows[k][1], (const double *) (d_cs + (size_t) 2 * k * nx),
+                      (const double *) (d_cs + ((size_t) 2 * k + 1) * nx)))
+        return 1;
+  if (P.periodic) {
+    IngestCopy C;
+    memset(&C, 0, sizeof(C));
+    unsigned most = 0;
+    for (int i = 0; i < nf; i++) {
+      C.p[i] = fld[i].dev;
+      C.n[i] = (unsigned) ((size_t) ny * fld[i].nlev);
+      most = std::max(most, C.n[i]);
+    }
+    const unsigned blocks = std::min<unsigned>((most + kIgThreads - 1) / kIgThreads, 1024);
+    if (call.launch(ingest_periodic_kernel, dim3(blocks, (unsigned) nf), dim3(kIgThreads), 0, C, nx))
+      return 1;
+  }
+  if (call.mark_begin(2))
+    return 1;
+  for (int i = 0; i < nf; i++) {
+    const Field &F = fld[i];
+    if (F.is3 ? copy3(ctx, st, F.dev, F.dst, nx2, ny, F.nlev, out->sx, out->sy, false)
+              : copy2(ctx, st, F.dev, F.dst, nx2, ny, out->sx2, false))
+      return 1;
+  }
+  if (call.mark_end() || call.close())
+    return 1;
+  if (out->lon)
+    memcpy(out->lon, lon2.data(), lon2.size() * sizeof(double));
+  if (out->lat)
+    memcpy(out->lat, lat2.data(), lat2.size() * sizeof(double));
+  if (out->p)
+    memcpy(out->p, p2.data(), p2.size() * sizeof(double));
+  return 0;
 }
 
 size_t mphip_sizeof_met_packed(void) {

@@ -84,6 +84,23 @@ class MphipDetrend(C.Structure):
 
 DETREND_FIELDS = ("t", "u", "v", "w")
 
+INGEST = {"decode": 1, "extrapolate": 2, "polar": 4, "periodic": 8}
+INGEST_ALL = 15
+RAW_FLOAT, RAW_SHORT = 1, 2       # MPHIP_RAW_FLOAT, MPHIP_RAW_SHORT
+
+
+class MphipRaw(C.Structure):
+    """mphip_raw_t: one field as a netCDF file stores it."""
+    _fields_ = [("data", C.c_void_p), ("type", C.c_int), ("lnsp", C.c_int), ("scale_factor", C.c_float),
+                ("add_offset", C.c_float), ("fill_f", C.c_float), ("miss_f", C.c_float), ("fill_s", C.c_short),
+                ("miss_s", C.c_short), ("scl", C.c_float)]
+
+
+class MphipIngestRaw(C.Structure):
+    """mphip_ingest_raw_t: the raw descriptors of mphip_ingest_met, one per field slot."""
+    _fields_ = [("f3", MphipRaw * len(FIELDS_3D)), ("f2", MphipRaw * len(FIELDS_2D))]
+
+
 _up = C.POINTER(C.c_ushort)
 
 
@@ -189,6 +206,13 @@ def load(build=True):
         L.mphip_sizeof_detrend.restype = C.c_size_t
         if L.mphip_sizeof_detrend() != C.sizeof(MphipDetrend):
             raise MphipError("mphip_detrend_t layout mismatch between header and Python mirror")
+    if hasattr(L, "mphip_ingest_met"):      # (absent from libraries built before the ingest: A/B runs through MPHIP_LIB)
+        L.mphip_ingest_met.argtypes = [C.c_void_p, C.POINTER(MphipMet), C.POINTER(MphipIngestRaw), C.c_uint,
+                                       C.POINTER(MphipRegridOut)]
+        L.mphip_ingest_shape.argtypes = [C.POINTER(MphipMet), C.c_uint, C.POINTER(C.c_int)]
+        L.mphip_sizeof_ingest_raw.restype = C.c_size_t
+        if L.mphip_sizeof_ingest_raw() != C.sizeof(MphipIngestRaw):
+            raise MphipError("mphip_ingest_raw_t layout mismatch between header and Python mirror")
     if hasattr(L, "mphip_update_met_packed"):      # (absent from libraries built before the packed files: A/B runs through MPHIP_LIB)
         L.mphip_update_met_packed.argtypes = [C.c_void_p, C.c_int, C.POINTER(MphipMetPacked)]
         L.mphip_prefetch_met_packed.argtypes = [C.c_void_p, C.POINTER(MphipMetPacked)]
@@ -531,6 +555,114 @@ class Simulation:
             if k in DETREND_FIELDS and k not in names:
                 m.f3[i] = None
         self._chk(self.L.mphip_detrend_met(self.h, C.byref(m), C.byref(o), C.byref(mo)))
+        return res
+
+    # -- netCDF values to a met_t (mphip_ingest_met) ---------------------------
+    @staticmethod
+    def _ingest_bits(what):
+        if isinstance(what, str):
+            what = (what,)
+        return what if isinstance(what, int) else sum(INGEST[w] for w in set(what))
+
+    def ingest_shape(self, axes, what):
+        """nx2 of mphip_ingest_met for the axes of `axes` (lon, lat, p, coord_type) and the stages `what`: nx + 1 where the
+        periodic column is added, else nx (mphip_ingest_shape; needs no device).  Raises where the call would refuse the
+        grid or `what`."""
+        m = self._met_struct(axes)
+        n = C.c_int(0)
+        if self.L.mphip_ingest_shape(C.byref(m), self._ingest_bits(what), C.byref(n)):
+            raise MphipError("mphip_ingest_shape: the grid or `what` is refused")
+        return n.value
+
+    def ingest_met(self, *args, out=None, out_strides=None):
+        """From a netCDF file's values to a met_t's on the device (mphip_ingest_met), in two forms.
+        ingest_met(raw, axes, what): `raw` = {name: (array, dict(scale_factor=..., add_offset=..., fill=..., miss=...,
+        scl=..., lnsp=...))} with the arrays in file order, float32 or int16 (packed), [nlev][ny][nx] or [ny][nx],
+        C-contiguous (None: a descriptor without data, which the library refuses; `type` in the dict overrides the type
+        the array's dtype gives); fill / miss are already of the stored type, 0 = none; `axes`: an object with lon, lat, p,
+        coord_type (and nx, ny, np, npl) -- its f3 / f2, if any, are further inputs in met order.
+        ingest_met(met, what): the met-order form, every field from met.f3 / met.f2 (the conventions of derive_met).
+        `what`: names among decode, extrapolate, polar, periodic (or the OR of their MPHIP_INGEST_* bits).  `out`: {name:
+        float32 array [nx2][ny][nlev] / [nx2][ny] to write into, or None to leave a field out} -- an input array itself
+        for in-place use; views into larger arrays name their strides in floats as `out_strides` = (sx, sy, sx2), which
+        then hold for every output array; by default new compact arrays.  Returns a Snapshot with nx2 longitudes."""
+        if isinstance(args[0], dict):
+            raw, met, what = args
+        else:
+            (met, what), raw = args, {}
+        bits = self._ingest_bits(what)
+        if not hasattr(met, "f3"):
+            met = Snapshot(getattr(met, "time", 0.0), met.coord_type, met.lon, met.lat, met.p, {}, {})
+        m = self._met_struct(met)
+        if any(k in FIELDS_ML for k in list(raw) + list(met.f3)):
+            m.npl = met.npl
+        r = MphipIngestRaw()
+        keep = []
+        for name, (a, o) in raw.items():
+            three = name in FIELDS_3D
+            d = r.f3[FIELDS_3D.index(name)] if three else r.f2[FIELDS_2D.index(name)]
+            o = dict(o)
+            if a is not None:
+                nlev = met.npl if name in FIELDS_ML else met.np
+                assert a.dtype in (np.float32, np.int16) and a.flags["C_CONTIGUOUS"], name
+                assert a.shape == ((nlev, met.ny, met.nx) if three else (met.ny, met.nx)), name
+                keep.append(a)
+                d.data = a.ctypes.data
+            short = a is not None and a.dtype == np.int16
+            d.type = int(o.pop("type", RAW_SHORT if short else RAW_FLOAT))
+            d.lnsp = int(o.pop("lnsp", 0))
+            d.scale_factor, d.add_offset = float(o.pop("scale_factor", 1.0)), float(o.pop("add_offset", 0.0))
+            fill, miss = o.pop("fill", 0), o.pop("miss", 0)
+            if short:
+                d.fill_s, d.miss_s = int(fill), int(miss)
+            else:
+                d.fill_f, d.miss_f = float(fill), float(miss)
+            d.scl = float(o.pop("scl", 1.0))
+            if o:
+                raise TypeError(f"unknown raw options {sorted(o)}")
+        mo = MphipRegridOut()
+        out = dict(out or {})
+        n = C.c_int(0)
+        if self.L.mphip_ingest_shape(C.byref(m), bits, C.byref(n)):
+            mo.sx, mo.sy, mo.sx2 = out_strides or (0, 0, 0)
+            for f, a in out.items():        # (the caller's arrays all the same: a refused call writes nothing)
+                if a is not None and f in FIELDS_3D:
+                    mo.f3[FIELDS_3D.index(f)] = _ptr(a, _fp)
+                elif a is not None:
+                    mo.f2[FIELDS_2D.index(f)] = _ptr(a, _fp)
+            self._chk(self.L.mphip_ingest_met(self.h, C.byref(m), C.byref(r), bits, C.byref(mo)))     # (refused: its message)
+            raise MphipError("mphip_ingest_shape refused what mphip_ingest_met accepts")
+        nx2 = n.value
+        mo.sx, mo.sy, mo.sx2 = out_strides or (met.ny * max(met.np, m.npl), max(met.np, m.npl), met.ny)
+        lon, lat, p = (np.empty(k, dtype=np.float64) for k in (nx2, met.ny, met.np))
+        mo.lon, mo.lat, mo.p = _ptr(lon, _dp), _ptr(lat, _dp), _ptr(p, _dp)
+        f3, f2 = {}, {}
+        for f in FIELDS_3D:
+            if f in out or f in raw or f in met.f3:
+                nlev = met.npl if f in FIELDS_ML else met.np
+                if f in out:
+                    a = out[f]
+                else:
+                    a = np.empty((nx2, mo.sx // mo.sy, mo.sy), dtype=np.float32)[:, :met.ny, :nlev]
+                if a is None:
+                    continue
+                assert a.dtype == np.float32 and a.shape == (nx2, met.ny, nlev) and a.strides == (4 * mo.sx, 4 * mo.sy, 4), f
+                mo.f3[FIELDS_3D.index(f)] = _ptr(a, _fp)
+                if f in raw or f in met.f3:
+                    f3[f] = a
+        for f in FIELDS_2D:
+            if f in out or f in raw or f in met.f2:
+                a = out[f] if f in out else np.empty((nx2, mo.sx2), dtype=np.float32)[:, :met.ny]
+                if a is None:
+                    continue
+                assert a.dtype == np.float32 and a.shape == (nx2, met.ny) and a.strides == (4 * mo.sx2, 4), f
+                mo.f2[FIELDS_2D.index(f)] = _ptr(a, _fp)
+                if f in raw or f in met.f2:
+                    f2[f] = a
+        self._chk(self.L.mphip_ingest_met(self.h, C.byref(m), C.byref(r) if raw or bits & INGEST["decode"] else None, bits,
+                                          C.byref(mo)))
+        res = Snapshot(getattr(met, "time", 0.0), met.coord_type, lon, lat, p, f3, f2, out_strides)
+        res.npl = met.npl
         return res
 
     # -- 16-bit packed level fields (MET_TYPE 2) ------------------------------

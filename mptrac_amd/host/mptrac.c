@@ -380,7 +380,8 @@ static const char *unsupported_qnt[] = {
   I(hip_met_prefetch, "HIP_MET_PREFETCH", "0") \
   I(hip_met_prep, "HIP_MET_PREP", "0") \
   I(hip_device_analysis, "HIP_DEVICE_ANALYSIS", "1") \
-  I(hip_device_intpol, "HIP_DEVICE_INTPOL", "0")
+  I(hip_device_intpol, "HIP_DEVICE_INTPOL", "0") \
+  I(hip_met_ingest, "HIP_MET_INGEST", "0")
 
 void mptrac_read_ctl(const char *filename, int argc, char *argv[], ctl_t *ctl) {
   LOG(1, "\nMassive-Parallel Trajectory Calculations (MPTRAC), MI355X build (%s)\n", mphip_version());
@@ -464,6 +465,7 @@ void mptrac_read_ctl(const char *filename, int argc, char *argv[], ctl_t *ctl) {
   ctl->hip_met_packed = ctl->met_type == 2 ? (int) scan_ctl(filename, argc, argv, "HIP_MET_PACKED", -1, "1", NULL) : 0;
   REQUIRE(ctl->hip_met_packed == 0 || ctl->hip_met_packed == 1, "Set HIP_MET_PACKED to 0 or 1!");
   REQUIRE(ctl->hip_device_intpol == 0 || ctl->hip_device_intpol == 1, "Set HIP_DEVICE_INTPOL to 0 or 1!");
+  REQUIRE(ctl->hip_met_ingest == 0 || ctl->hip_met_ingest == 1, "Set HIP_MET_INGEST to 0 or 1!");
   if (ctl->met_type == 0) {
     /* netCDF input is taken as stored: no hybrid-coefficient levels (mptrac.c:7770-7830) ... */
     static const struct {
@@ -1843,6 +1845,11 @@ typedef struct {
   const ctl_t *ctl;
   const met_t *met;
   int nc_scale;
+  /* HIP_MET_INGEST 1: nc_field only reads -- the stored values into buffers of the reader, their description into `raw`
+   * (mphip_ingest_met decodes them on the device) */
+  mphip_ingest_raw_t *raw;
+  void *bufs[MPHIP_N3D + MPHIP_N2D];
+  int nbufs;
 } nc_reader;
 
 static int nc_lookup(const nc_reader *r, const char *const *names) {
@@ -1854,9 +1861,10 @@ static int nc_lookup(const nc_reader *r, const char *const *names) {
   return -1;
 }
 
-/* one level field ([np][ny][nx] in the file) or surface field (nlev = 0: [ny][nx]) into dest[(ix * EY + iy) * stride + ip] */
-static int nc_field(const nc_reader *r, const char *const *names, const int nlev, const float scl, float *dest,
-                    const size_t stride) {
+/* one level field ([np][ny][nx] in the file) or surface field (nlev = 0: [ny][nx]) into dest[(ix * EY + iy) * stride + ip];
+ * `slot`: its MPHIP_* index, where the description goes when the device decodes (r->raw) */
+static int nc_field(nc_reader *r, const char *const *names, const int nlev, const float scl, float *dest,
+                    const size_t stride, const int slot) {
   const int var = nc_lookup(r, names);
   if (var < 0)
     return 0;
@@ -1872,6 +1880,29 @@ static int nc_field(const nc_reader *r, const char *const *names, const int nlev
   const int has_miss = ncc_get_att(r->nc, var, "missing_value", &miss);
   const int packed = r->nc_scale && ncc_get_att(r->nc, var, "add_offset", &offset)
     && ncc_get_att(r->nc, var, "scale_factor", &scale);
+  if (r->raw) {
+    mphip_raw_t *d = nlev > 0 ? &r->raw->f3[slot] : &r->raw->f2[slot];
+    memset(d, 0, sizeof(*d));
+    void *buf = malloc((size_t) n * (packed ? sizeof(short) : sizeof(float)));
+    if (!buf)
+      ERRMSG("Out of memory!");
+    if (!(packed ? ncc_read_short(r->nc, var, 0, 0, n, (short *) buf) : ncc_read_float(r->nc, var, 0, 0, n, (float *) buf)))
+      ERRMSG("netCDF: %s", ncc_error(r->nc));
+    r->bufs[r->nbufs++] = buf;
+    d->data = buf;
+    d->type = packed ? MPHIP_RAW_SHORT : MPHIP_RAW_FLOAT;
+    d->scale_factor = (float) scale;
+    d->add_offset = (float) offset;
+    if (packed) {
+      d->fill_s = has_fill ? (short) fill : 0;
+      d->miss_s = has_miss ? (short) miss : 0;
+    } else {
+      d->fill_f = has_fill ? (float) fill : 0.f;
+      d->miss_f = has_miss ? (float) miss : 0.f;
+    }
+    d->scl = scl;
+    return 1;
+  }
   float *help;
   ALLOC(help, float, (size_t) n);
   if (packed) {
@@ -1905,8 +1936,8 @@ static int nc_field(const nc_reader *r, const char *const *names, const int nlev
 }
 
 #define NAMES(...) ((const char *const[]) { __VA_ARGS__, NULL })
-#define NC_3D(field, scl, ...) nc_field(&r, NAMES(__VA_ARGS__), met->np, scl, &met->field[0][0][0], EP)
-#define NC_2D(field, scl, ...) nc_field(&r, NAMES(__VA_ARGS__), 0, scl, &met->field[0][0], 1)
+#define NC_3D(field, slot, scl, ...) nc_field(&r, NAMES(__VA_ARGS__), met->np, scl, &met->field[0][0][0], EP, slot)
+#define NC_2D(field, slot, scl, ...) nc_field(&r, NAMES(__VA_ARGS__), 0, scl, &met->field[0][0], 1, slot)
 
 /* The wind at a pole has no direction of its own.  On a grid that reaches both poles (read_met_polar_winds,
  * mptrac.c:11775-11833) each pole row gets the mean wind vector of the row next to it: averaged in a frame fixed
@@ -1979,6 +2010,7 @@ typedef struct {
 static unsigned met_derive(const ctl_t *ctl, const clim_t *clim, met_t *met, const nc_have_t *have);
 static void met_regrid(const ctl_t *ctl, met_t *met, unsigned what);
 static void met_detrend(const ctl_t *ctl, met_t *met);
+static void met_ingest(const ctl_t *ctl, met_t *met, const mphip_ingest_raw_t *raw, int ps_on_host, unsigned what);
 
 static int read_met_nc(const char *filename, const ctl_t *ctl, const clim_t *clim, met_t *met) {
   char err[256];
@@ -1991,7 +2023,18 @@ static int read_met_nc(const char *filename, const ctl_t *ctl, const clim_t *cli
     ERRMSG("%s: %s", filename, err);
   }
   met->coord_type = ctl->met_coord_type;
-  nc_reader r = { nc, ctl, met, ctl->met_nc_scale };
+  nc_reader r;
+  memset(&r, 0, sizeof(r));
+  r.nc = nc;
+  r.ctl = ctl;
+  r.met = met;
+  r.nc_scale = ctl->met_nc_scale;
+  mphip_ingest_raw_t *raw = NULL;   /* HIP_MET_INGEST 1: what nc_field found, for mphip_ingest_met */
+  int ps_on_host = 0;
+  if (ctl->hip_met_ingest) {
+    ALLOC(raw, mphip_ingest_raw_t, 1);
+    r.raw = raw;
+  }
 
   /* time from the file name: ..._YYYY_MM_DD_HH.nc */
   const size_t len = strlen(filename);
@@ -2047,48 +2090,60 @@ static int read_met_nc(const char *filename, const ctl_t *ctl, const clim_t *cli
   }
 
   /* surface fields */
-  if (NC_2D(ps, 1.0f, "lnsp", "LNSP")) {   /* logarithm of the surface pressure in Pa */
-    EACH_COLUMN(met, i, j)
-      met->ps[i][j] = (float) (exp(met->ps[i][j]) / 100.);
-  } else if (!NC_2D(ps, 0.01f, "ps", "PS", "sp", "SP")) {
+  if (NC_2D(ps, MPHIP_PS, 1.0f, "lnsp", "LNSP")) {   /* logarithm of the surface pressure in Pa */
+    if (raw)
+      raw->f2[MPHIP_PS].lnsp = 1;
+    else
+      EACH_COLUMN(met, i, j)
+        met->ps[i][j] = (float) (exp(met->ps[i][j]) / 100.);
+  } else if (!NC_2D(ps, MPHIP_PS, 0.01f, "ps", "PS", "sp", "SP")) {
     WARN("Cannot not read surface pressure data (use lowest level)!");
     EACH_COLUMN(met, i, j)
       met->ps[i][j] = (float) met->p[0];
+    ps_on_host = 1;
   }
   nc_have_t have;
   memset(&have, 0, sizeof(have));
-  have.zs = NC_2D(zs, (float) (1. / (1000. * 9.80665)), "z", "Z");
-  have.ts = NC_2D(ts, 1.0f, "t2m", "T2M", "2t", "2T", "t2", "T2");
-  have.us = NC_2D(us, 1.0f, "u10m", "U10M", "10u", "10U", "u10", "U10");
-  have.vs = NC_2D(vs, 1.0f, "v10m", "V10M", "10v", "10V", "v10", "V10");
-  (void) NC_2D(ess, 1.0f, "iews", "IEWS");
-  (void) NC_2D(nss, 1.0f, "inss", "INSS");
-  (void) NC_2D(shf, 1.0f, "ishf", "ISHF");
-  (void) NC_2D(lsm, 1.0f, "lsm", "LSM");
-  (void) NC_2D(sst, 1.0f, "sstk", "SSTK", "sst", "SST");
-  const int have_pbl = ctl->met_pbl == 0 && NC_2D(pbl, 0.01f, "blp", "BLP");
-  const int have_cape = ctl->met_cape == 0 && NC_2D(cape, 1.0f, "cape", "CAPE") && NC_2D(cin, 1.0f, "cin", "CIN");
+  have.zs = NC_2D(zs, MPHIP_ZS, (float) (1. / (1000. * 9.80665)), "z", "Z");
+  have.ts = NC_2D(ts, MPHIP_TS, 1.0f, "t2m", "T2M", "2t", "2T", "t2", "T2");
+  have.us = NC_2D(us, MPHIP_US, 1.0f, "u10m", "U10M", "10u", "10U", "u10", "U10");
+  have.vs = NC_2D(vs, MPHIP_VS, 1.0f, "v10m", "V10M", "10v", "10V", "v10", "V10");
+  (void) NC_2D(ess, MPHIP_ESS, 1.0f, "iews", "IEWS");
+  (void) NC_2D(nss, MPHIP_NSS, 1.0f, "inss", "INSS");
+  (void) NC_2D(shf, MPHIP_SHF, 1.0f, "ishf", "ISHF");
+  (void) NC_2D(lsm, MPHIP_LSM, 1.0f, "lsm", "LSM");
+  (void) NC_2D(sst, MPHIP_SST, 1.0f, "sstk", "SSTK", "sst", "SST");
+  const int have_pbl = ctl->met_pbl == 0 && NC_2D(pbl, MPHIP_PBL, 0.01f, "blp", "BLP");
+  const int have_cape = ctl->met_cape == 0 && NC_2D(cape, MPHIP_CAPE, 1.0f, "cape", "CAPE") && NC_2D(cin, MPHIP_CIN, 1.0f, "cin", "CIN");
 
   /* level fields */
-  REQUIRE(NC_3D(t, 1.0f, "t", "T", "temp", "TEMP"), "Cannot read temperature!");
-  REQUIRE(NC_3D(u, 1.0f, "u", "U"), "Cannot read zonal wind!");
-  REQUIRE(NC_3D(v, 1.0f, "v", "V"), "Cannot read meridional wind!");
-  if (!NC_3D(w, 0.01f, "w", "W", "omega", "OMEGA"))   /* Pa/s -> hPa/s */
+  REQUIRE(NC_3D(t, MPHIP_T, 1.0f, "t", "T", "temp", "TEMP"), "Cannot read temperature!");
+  REQUIRE(NC_3D(u, MPHIP_U, 1.0f, "u", "U"), "Cannot read zonal wind!");
+  REQUIRE(NC_3D(v, MPHIP_V, 1.0f, "v", "V"), "Cannot read meridional wind!");
+  if (!NC_3D(w, MPHIP_W, 0.01f, "w", "W", "omega", "OMEGA"))   /* Pa/s -> hPa/s */
     WARN("Cannot read vertical velocity!");
-  if (!(have.h2o = NC_3D(h2o, (float) (MA / MH2O), "q", "Q", "sh", "SH")))   /* mass -> volume mixing ratio */
+  if (!(have.h2o = NC_3D(h2o, MPHIP_H2O, (float) (MA / MH2O), "q", "Q", "sh", "SH")))   /* mass -> volume mixing ratio */
     WARN("Cannot read specific humidity!");
-  if (!(have.o3 = NC_3D(o3, (float) (MA / MO3), "o3", "O3")))
+  if (!(have.o3 = NC_3D(o3, MPHIP_O3, (float) (MA / MO3), "o3", "O3")))
     WARN("Cannot read ozone data!");
-  have.lwc = NC_3D(lwc, 1.0f, "clwc", "CLWC");
-  have.rwc = NC_3D(rwc, 1.0f, "crwc", "CRWC");
-  have.iwc = NC_3D(iwc, 1.0f, "ciwc", "CIWC");
-  have.swc = NC_3D(swc, 1.0f, "cswc", "CSWC");
+  have.lwc = NC_3D(lwc, MPHIP_LWC, 1.0f, "clwc", "CLWC");
+  have.rwc = NC_3D(rwc, MPHIP_RWC, 1.0f, "crwc", "CRWC");
+  have.iwc = NC_3D(iwc, MPHIP_IWC, 1.0f, "ciwc", "CIWC");
+  have.swc = NC_3D(swc, MPHIP_SWC, 1.0f, "cswc", "CSWC");
   have.pbl = have_pbl;
-  (void) NC_3D(cc, 1.0f, "cc", "CC");
+  (void) NC_3D(cc, MPHIP_CC, 1.0f, "cc", "CC");
   if (model_levels)
-    REQUIRE(NC_3D(pl, 0.01f, "pl", "PL", "pressure", "PRESSURE", "press", "PRESS"),   /* Pa -> hPa */
+    REQUIRE(NC_3D(pl, MPHIP_PL, 0.01f, "pl", "PL", "pressure", "PRESSURE", "press", "PRESS"),   /* Pa -> hPa */
             "MET_VERT_COORD 1: cannot read the 3-D pressure (pl, pressure or press)!");
   ncc_close(nc);
+  /* HIP_MET_INGEST 1: the stored values become the met_t's on the device -- all four stages in one call for a
+   * pressure-level file; for a model-level file the decoding alone, the other three stages behind ML2PL below */
+  if (raw)
+    met_ingest(ctl, met, raw, ps_on_host,
+               model_levels ? MPHIP_INGEST_DECODE
+                            : MPHIP_INGEST_DECODE | MPHIP_INGEST_EXTRAPOLATE | MPHIP_INGEST_POLAR | MPHIP_INGEST_PERIODIC);
+  for (int k = 0; k < r.nbufs; k++)
+    free(r.bufs[k]);
   if (model_levels) {
     /* the winds stay on the file's levels for ADVECT_VERT_COORD 2; everything else goes to the levels MET_P on the
      * device, and from here on this is an ordinary pressure-level snapshot */
@@ -2105,23 +2160,29 @@ static int read_met_nc(const char *filename, const ctl_t *ctl, const clim_t *cli
   for (int k = 1; k < met->np; k++)
     REQUIRE(met->p[k - 1] >= met->p[k], "Pressure levels must be descending!");
 
-  /* below the lowest level with valid t, u, v, w every level field continues with that level's value
-   * (reference: read_met_extrapolate) */
-  EACH_COLUMN(met, i, j) {
-    int low = met->np - 1;
-    while (low >= 0 && isfinite(met->t[i][j][low]) && isfinite(met->u[i][j][low]) && isfinite(met->v[i][j][low])
-           && isfinite(met->w[i][j][low]))
-      low--;
-    float (*f3[11])[EY][EP] = { met->t, met->u, met->v, met->w, met->h2o, met->o3, met->lwc, met->rwc, met->iwc,
-      met->swc, met->cc };
-    for (int k = low; k >= 0; k--)
-      for (int f = 0; f < 11; f++)
-        f3[f][i][j][k] = k + 1 < EP ? f3[f][i][j][k + 1] : 0.f;
-  }
+  if (raw) {
+    if (model_levels)
+      met_ingest(ctl, met, raw, 1, MPHIP_INGEST_EXTRAPOLATE | MPHIP_INGEST_POLAR | MPHIP_INGEST_PERIODIC);
+    free(raw);
+  } else {
+    /* below the lowest level with valid t, u, v, w every level field continues with that level's value
+     * (reference: read_met_extrapolate) */
+    EACH_COLUMN(met, i, j) {
+      int low = met->np - 1;
+      while (low >= 0 && isfinite(met->t[i][j][low]) && isfinite(met->u[i][j][low]) && isfinite(met->v[i][j][low])
+             && isfinite(met->w[i][j][low]))
+        low--;
+      float (*f3[11])[EY][EP] = { met->t, met->u, met->v, met->w, met->h2o, met->o3, met->lwc, met->rwc, met->iwc,
+        met->swc, met->cc };
+      for (int k = low; k >= 0; k--)
+        for (int f = 0; f < 11; f++)
+          f3[f][i][j][k] = k + 1 < EP ? f3[f][i][j][k + 1] : 0.f;
+    }
 
-  if (met->coord_type == 0) {
-    met_polar_winds(met);
-    met_periodic(met);
+    if (met->coord_type == 0) {
+      met_polar_winds(met);
+      met_periodic(met);
+    }
   }
   /* down-sampling with smoothing (read_met_sample): the derived fields below are those of the sampled grid */
   if (ctl->met_dx != 1 || ctl->met_dy != 1 || ctl->met_dp != 1 || ctl->met_sx != 1 || ctl->met_sy != 1 || ctl->met_sp != 1)
@@ -2568,6 +2629,70 @@ static void met_detrend(const ctl_t *ctl, met_t *met) {
   if (mphip_detrend_met(g_ctx, &in, &opt, &out) != 0)
     ERRMSG("HIP back end: %s", mphip_last_error(g_ctx));
   LOG(2, "Detrended on the device: t, u, v, w minus a background of %g km", ctl->met_detrend);
+}
+
+/* HIP_MET_INGEST 1: from the values the netCDF reader found (`raw`, in file order) to the met_t on the device
+ * (mphip_ingest_met), the met_t's own arrays being the output.  With MPHIP_INGEST_DECODE every field the file gave is
+ * decoded (`ps_on_host`: the file had no surface pressure and the reader has filled met->ps itself); without it the call
+ * works in place on the met_t, on every field the file gave and the kept model-level fields -- the form a model-level file
+ * needs behind ML2PL.  The periodic column must fit the fixed extent, which is checked here as met_periodic checks it.
+ * Like met_derive it may run on the read-ahead thread; the context exists by then. */
+static void met_ingest(const ctl_t *ctl, met_t *met, const mphip_ingest_raw_t *raw, const int ps_on_host, const unsigned what) {
+  need_ctx(ctl);
+  const int decode = (what & MPHIP_INGEST_DECODE) != 0;
+  mphip_met_t all, in;
+  describe_met(met, &all);
+  all.f3[MPHIP_O3] = &met->o3[0][0][0];
+  all.f3[MPHIP_CC] = &met->cc[0][0][0];
+  all.f3[MPHIP_PL] = &met->pl[0][0][0];
+  float *const s2[] = { &met->ps[0][0], &met->zs[0][0], &met->ts[0][0], &met->us[0][0], &met->vs[0][0], &met->ess[0][0],
+    &met->nss[0][0], &met->shf[0][0], &met->lsm[0][0], &met->sst[0][0], &met->pbl[0][0], &met->cape[0][0], &met->cin[0][0] };
+  const int i2[] = { MPHIP_PS, MPHIP_ZS, MPHIP_TS, MPHIP_US, MPHIP_VS, MPHIP_ESS, MPHIP_NSS, MPHIP_SHF, MPHIP_LSM, MPHIP_SST,
+    MPHIP_PBL, MPHIP_CAPE, MPHIP_CIN };
+  memset(all.f2, 0, sizeof(all.f2));
+  for (size_t k = 0; k < sizeof(i2) / sizeof(i2[0]); k++)
+    all.f2[i2[k]] = s2[k];
+  in = all;
+  memset(in.f3, 0, sizeof(in.f3));
+  memset(in.f2, 0, sizeof(in.f2));
+  mphip_regrid_out_t out;
+  memset(&out, 0, sizeof(out));
+  out.sx = all.sx;
+  out.sy = all.sy;
+  out.sx2 = all.sx2;
+  out.lon = met->lon;
+  if (decode) {
+    in.npl = met->np;       /* (a model-level file's pl has the levels of every other field) */
+    for (int f = 0; f < MPHIP_N3D; f++)
+      if (raw->f3[f].type)
+        out.f3[f] = (float *) all.f3[f];
+    for (int f = 0; f < MPHIP_N2D; f++)
+      if (raw->f2[f].type)
+        out.f2[f] = (float *) all.f2[f];
+    if (ps_on_host) {
+      in.f2[MPHIP_PS] = all.f2[MPHIP_PS];
+      out.f2[MPHIP_PS] = (float *) all.f2[MPHIP_PS];
+    }
+  } else {
+    /* in place: what the file gave, on the pressure levels by now, and the model-level fields met_periodic copies */
+    for (int f = 0; f < MPHIP_N3D; f++)
+      if ((raw->f3[f].type && f != MPHIP_PL)
+          || (met->npl > 0 && (f == MPHIP_PL || f == MPHIP_UL || f == MPHIP_VL || f == MPHIP_WL)))
+        in.f3[f] = all.f3[f], out.f3[f] = (float *) all.f3[f];
+    for (int f = 0; f < MPHIP_N2D; f++)
+      if (raw->f2[f].type || (f == MPHIP_PS && ps_on_host))
+        in.f2[f] = all.f2[f], out.f2[f] = (float *) all.f2[f];
+  }
+  int nx2 = met->nx;
+  (void) mphip_ingest_shape(&in, what, &nx2);
+  if (nx2 >= EX)
+    ERRMSG("Cannot create periodic boundary conditions!");
+  /* (not through HIP(): that macro first submits the main thread's queued time steps) */
+  if (mphip_ingest_met(g_ctx, &in, decode ? raw : NULL, what, &out) != 0)
+    ERRMSG("HIP back end: %s", mphip_last_error(g_ctx));
+  met->nx = nx2;
+  LOG(2, "Ingested on the device:%s%s%s%s", decode ? " decoding" : "", what & MPHIP_INGEST_EXTRAPOLATE ? " extrapolation" : "",
+      what & MPHIP_INGEST_POLAR ? " polar winds" : "", what & MPHIP_INGEST_PERIODIC ? " periodic column" : "");
 }
 
 /* Read-ahead of the next meteo file (HIP_MET_PREFETCH 1, forward runs): while the time steps of the current

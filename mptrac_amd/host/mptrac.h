@@ -241,6 +241,10 @@ typedef struct {
                              from the resident snapshots on the device (mphip_intpol_met, one call per output; the same
                              doubles, so the same files), packed snapshots stay codes, and o3 is uploaded with
                              PROF_BASENAME; 0: interpolated on the host; other values are refused */
+  int hip_met_ingest;     /* HIP_MET_INGEST (default 0): 1: the netCDF reader (MET_TYPE 0) only reads; decoding, the mask,
+                             the unit scales, the re-ordering into met_t, the extrapolation below the lowest valid level,
+                             the polar winds and the periodic column happen on the device (mphip_ingest_met; the same
+                             bits, so the same files); 0: in the reader's own loops; other values are refused */
 } ctl_t;
 
 /* air parcels, as the reference (mptrac.h:3563-3583) */
