@@ -648,7 +648,11 @@ int mphip_prefetch_met_packed(mphip_ctx *ctx, const mphip_met_packed_t *met);
  *   mphip_unpack_met writes out->f3[f] for every field that `in` gives as codes and `out` names (base.f3 of `in` and the
  * surface fields are ignored).  mphip_pack_met encodes in->f3[f] into the arrays out->q3[f], out->scl[f], out->off[f]
  * point to, for every field present in both (a NULL q3[f] skips the field; out->base.f3, lo and hi are ignored); a value
- * that is not finite refuses the call with the field's name and the level.  Messages start with the call's name. */
+ * that is not finite refuses the call with the field's name and the level.  mphip_pack_met takes up to 16383 levels: a
+ * column of a field is staged in 64 KB of LDS at the pitch nlev | 1 floats, and a field with more levels is refused ("too
+ * many levels for one column in 64 KB of LDS") before anything is written; mphip_unpack_met and the two uploads have no
+ * such limit (their scales and offsets are read from LDS up to 4096 levels and from global memory above).  Messages start
+ * with the call's name. */
 int mphip_unpack_met(mphip_ctx *ctx, const mphip_met_packed_t *in, const mphip_met_t *out);
 int mphip_pack_met(mphip_ctx *ctx, const mphip_met_t *in, const mphip_met_packed_t *out);
 

@@ -1,9 +1,11 @@
 """Seeded cases of the 16-bit packed level fields, shared by tests/test_pack_cpu.py and tests/test_gpu_pack*.py.
 
-Grids (nx, ny, nlev), the smallest at which the kernels can still go wrong: 9 x 7 x 20; 37 x 19 x 137 (703 columns: several
-workgroups of the extremes kernel with a ragged last one, and 137 is no multiple of 8); 5 x 5 x 3 (75 values: the 8-wide
-path has a tail, and a lane's 8 values wrap the level more than once); 2 x 2 x 2; 2 x 2 x 4099 (a tall axis past the LDS
-table of 4096 levels).
+Grids (nx, ny, nlev), small ones at which the arithmetic of a value can go wrong: 9 x 7 x 20; 37 x 19 x 137 (703 columns:
+several workgroups of the extremes kernel with a ragged last one, and 137 is no multiple of 8); 5 x 5 x 3 (75 values: the
+8-wide path has a tail, and a lane's 8 values wrap the level more than once); 2 x 2 x 2; 2 x 2 x 4099 (a tall axis past the
+LDS table of 4096 levels).  None of them reaches the grid stride of the streaming kernels, a second partial in a slice of
+the reduction, more than two alignments of the code array, one level or the LDS limits themselves: those cases are in
+tests/pack_edge_cases.py.
 
 ENCODE: name -> float32 field, all finite.  DECODE: name -> (codes, scl, off, lo, hi), codes chosen by hand, scl / off also
 NaN and infinite.  NOT_FINITE: name -> (field, first level that is not finite)."""
