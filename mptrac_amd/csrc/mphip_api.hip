@@ -62,11 +62,12 @@ struct MetSlot {
   double ps_max = HUGE_VAL, pbl_min = -HUGE_VAL, pbl_max = HUGE_VAL, pel_min = -HUGE_VAL;
 };
 
-// What mphip_derive_met, mphip_regrid_met and mphip_detrend_met share (PrepCall below is one call's view of it): a stream
-// of their own, so that a file-reader thread may call them while another thread steps; the lock that serialises their
-// callers; and the scratch of the call in progress.  No buffer carries a value from one call to the next, so the pool
-// hands its buffers out from the first again at every call (PrepCall::take); a buffer grows when a call needs more than
-// it holds and is kept otherwise, so a repeating sequence of calls allocates nothing after its first round.
+// What mphip_derive_met, mphip_regrid_met, mphip_detrend_met, mphip_ingest_met, mphip_unpack_met and mphip_pack_met share
+// (PrepCall below is one call's view of it): a stream of their own, so that a file-reader thread may call them while
+// another thread steps; the lock that serialises their callers; and the scratch of the call in progress.  No buffer
+// carries a value from one call to the next, so the pool hands its buffers out from the first again at every call
+// (PrepCall::take); a buffer grows when a call needs more than it holds and is kept otherwise, so a repeating sequence of
+// calls allocates nothing after its first round.
 struct PrepState {
   std::mutex lock;
   hipStream_t stream = nullptr;
@@ -325,6 +326,22 @@ int fail(mphip_ctx *ctx, const std::string &msg) {
     if (e_ != hipSuccess)                                                                    \
       return fail(ctx, std::string(#call) + ": " + hipGetErrorString(e_));                   \
   } while (0)
+
+// One start/stop pair of what mphip_profile_begin / _end time: the start event is recorded on `stream` here, *stop is for
+// the caller to record behind what the pair brackets (NULL: nothing is being profiled).  ctx->ev grows as needed.
+int prof_pair(mphip_ctx *ctx, hipStream_t stream, hipEvent_t *stop) {
+  *stop = nullptr;
+  if (!ctx->prof)
+    return 0;
+  while (ctx->ev_used + 2 > ctx->ev.size()) {
+    hipEvent_t e;
+    HIPCHK(hipEventCreate(&e));
+    ctx->ev.push_back(e);
+  }
+  HIPCHK(hipEventRecord(ctx->ev[ctx->ev_used++], stream));
+  *stop = ctx->ev[ctx->ev_used++];
+  return 0;
+}
 
 // the raw pointers of a pair of buffers, as radix_passes takes them
 template <typename T>
@@ -1120,19 +1137,9 @@ int launch_step(mphip_ctx *ctx, unsigned mask, double t, const RngCtr &rng = {},
   S.ctr_stride = ctr_stride;
   // axes, climatological tropopause, the tables of log and exp (+ pow's for the instantiations with the closure, below)
   size_t lds = axes_lds_bytes(ctx) + sizeof(DevClim) + (size_t) kLibmLogExpDoubles * sizeof(double);
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (ctx->prof) {
-    if (ctx->ev_used + 2 > ctx->ev.size()) {
-      for (int k = 0; k < 2; k++) {
-        hipEvent_t e;
-        HIPCHK(hipEventCreate(&e));
-        ctx->ev.push_back(e);
-      }
-    }
-    e0 = ctx->ev[ctx->ev_used++];
-    e1 = ctx->ev[ctx->ev_used++];
-    HIPCHK(hipEventRecord(e0, ctx->stream));
-  }
+  hipEvent_t e1 = nullptr;
+  if (prof_pair(ctx, ctx->stream, &e1))
+    return 1;
   unsigned sel = step_kernel_mask(ctx, mask, nsteps);
   if (reads_meso_table(sel, mask)) {
     if (ensure_meso_table(ctx))
@@ -2578,18 +2585,9 @@ int launch_radio_depo(mphip_ctx *ctx, double t, const unsigned char *busy) {
     S.nsteps = 1;
     S.t_stride = 0;
     S.ctr_stride = 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (ctx->prof) {   // (mphip_profile_begin / _end: the kernel counts as a launch of the step)
-      if (ctx->ev_used + 2 > ctx->ev.size())
-        for (int k = 0; k < 2; k++) {
-          hipEvent_t e;
-          HIPCHK(hipEventCreate(&e));
-          ctx->ev.push_back(e);
-        }
-      e0 = ctx->ev[ctx->ev_used++];
-      e1 = ctx->ev[ctx->ev_used++];
-      HIPCHK(hipEventRecord(e0, ctx->stream));
-    }
+    hipEvent_t e1 = nullptr;
+    if (prof_pair(ctx, ctx->stream, &e1))   // (mphip_profile_begin / _end: the kernel counts as a launch of the step)
+      return 1;
     hipLaunchKernelGGL(radio_depo_kernel, dim3(geom.nblocks_logical), dim3(256), lds, ctx->stream, S, R);
     HIPCHK(hipGetLastError());
     if (ctx->prof)
@@ -2710,9 +2708,16 @@ bool regrid_strides_ok(int ny, int np, long long sx, long long sy) {
   return sy >= np && sx >= sy * ny && sx % sy == 0;
 }
 
-// a level field of nx x ny x np values between such a host array and a compact device array (asynchronous on `stream`)
-int copy3(mphip_ctx *ctx, hipStream_t stream, float *dev, const float *host, int nx, int ny, int np, long long sx, long long sy,
-          bool to_device) {
+// levels of a level field and the strides of the host array that holds it
+struct LevelField {
+  int nlev;
+  long long sx, sy;
+};
+
+// a level field of nx x ny x L.nlev values between such a host array and a compact device array (asynchronous on `stream`)
+int copy3(mphip_ctx *ctx, hipStream_t stream, float *dev, const float *host, int nx, int ny, const LevelField &L, bool to_device) {
+  const int np = L.nlev;
+  const long long sx = L.sx, sy = L.sy;
   if (sy == np && sx == (long long) ny * np) {
     const size_t bytes = (size_t) nx * ny * np * sizeof(float);
     if (to_device)
@@ -2767,6 +2772,14 @@ const char *packed_refusal(const mphip_met_packed_t *pk, std::string &why) {
   return nullptr;
 }
 
+// LevelField of field f of a snapshot: npl levels (none if npl < 1) at sx_ml, sy_ml on model levels, else np at sx, sy;
+// the strides are those of `arrays` where given (mphip_unpack_met: the grid is its input's, the arrays are its output's)
+LevelField level_field(const mphip_met_t *met, int f, const mphip_met_t *arrays = nullptr) {
+  const bool is_ml = field_on_model_levels(f);
+  const mphip_met_t *a = arrays ? arrays : met;
+  return LevelField{ is_ml ? std::max(met->npl, 0) : met->np, is_ml ? a->sx_ml : a->sx, is_ml ? a->sy_ml : a->sy };
+}
+
 // One field on the device on its way through a streaming kernel: {scl[nlev] | off[nlev]} doubles, then the codes, which
 // keep their host array's offset from a 16-byte boundary (`shift` codes: the copy moves aligned runs to aligned runs, and
 // the kernels' vector path starts where the codes are aligned).
@@ -2775,17 +2788,19 @@ struct PackedField {
   int nlev;
   size_t shift;            // codes in front of the first one, 0 ... 7
   size_t bytes;            // of the whole block
-  double *scl(char *blk) const { return (double *) blk; }
-  double *off(char *blk) const { return (double *) blk + nlev; }
-  unsigned short *q(char *blk) const { return (unsigned short *) (blk + 2 * (size_t) nlev * sizeof(double)) + shift; }
+  char *blk;               // the block on the device, once its owner has one of `bytes` bytes
+  double *scl() const { return (double *) blk; }
+  double *off() const { return (double *) blk + nlev; }
+  unsigned short *q() const { return (unsigned short *) (blk + 2 * (size_t) nlev * sizeof(double)) + shift; }
 };
 
-PackedField packed_field(size_t n, int nlev, const void *host_codes) {
+PackedField packed_field(size_t n, int nlev, const void *host_codes, char *blk = nullptr) {
   PackedField B;
   B.n = n;
   B.nlev = nlev;
   B.shift = ((uintptr_t) host_codes & 15) / sizeof(unsigned short);
   B.bytes = 2 * (size_t) nlev * sizeof(double) + (n + 2 * kPkVec) * sizeof(unsigned short);
+  B.blk = blk;
   return B;
 }
 
@@ -2809,12 +2824,30 @@ PackStream pack_stream(const unsigned short *q, size_t n, int nlev) {
   return P;
 }
 
+// the host's scales, offsets and codes of field f into its block B (asynchronous on `stream`)
+int upload_packed(mphip_ctx *ctx, hipStream_t stream, const PackedField &B, const mphip_met_packed_t *pk, int f) {
+  HIPCHK(hipMemcpyAsync(B.scl(), pk->scl[f], (size_t) B.nlev * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemcpyAsync(B.off(), pk->off[f], (size_t) B.nlev * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemcpyAsync(B.q(), pk->q3[f], B.n * sizeof(unsigned short), hipMemcpyHostToDevice, stream));
+  return 0;
+}
+
+// met_unpack_kernel of field f from its block B into dst; `launch` takes (kernel, grid, block, lds, arguments ...) and
+// puts the kernel on its caller's stream in its caller's way
+template <typename L>
+int unpack_packed(const PackedField &B, const mphip_met_packed_t *pk, int f, float *dst, L launch) {
+  const PackStream P = pack_stream(B.q(), B.n, B.nlev);
+  return launch(P.table_in_lds ? met_unpack_kernel<true> : met_unpack_kernel<false>, P.grid, dim3(kPkThreads), P.lds,
+                (const unsigned short *) B.q(), (const double *) B.scl(), (const double *) B.off(), dst, P.n, P.nlev, P.head,
+                pk->lo[f], pk->hi[f]);
+}
+
 // the largest block a packed snapshot's fields need (0: no field is given as codes)
 size_t packed_block_bytes(const mphip_met_packed_t *pk) {
   const mphip_met_t *met = &pk->base;
   size_t need = 0;
   for (int f = 0; f < MPHIP_N3D; f++) {
-    const int nlev = field_on_model_levels(f) ? std::max(met->npl, 0) : met->np;
+    const int nlev = level_field(met, f).nlev;
     if (pk->q3[f] && nlev > 0)
       need = std::max(need, packed_field((size_t) met->nx * met->ny * (size_t) nlev, nlev, pk->q3[f]).bytes);
   }
@@ -2826,33 +2859,30 @@ size_t packed_block_bytes(const mphip_met_packed_t *pk) {
 // behind its copy
 int upload_fields(mphip_ctx *ctx, MetSlot &S, const mphip_met_t *met, bool new_grid, hipStream_t stream,
                   const mphip_met_packed_t *pk = nullptr, char *codes = nullptr) {
-  const int nml = met->npl > 0 ? met->npl : 0;
-  const size_t ncell = (size_t) met->nx * met->ny * met->np, ncol = (size_t) met->nx * met->ny;
+  const size_t ncol = (size_t) met->nx * met->ny;
+  auto launch = [&](auto kernel, dim3 grid, dim3 block, size_t lds, auto... args) {
+    hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+    HIPCHK(hipGetLastError());
+    return 0;
+  };
   for (int f = 0; f < MPHIP_N3D; f++) {
-    const bool is_ml = field_on_model_levels(f);
-    const long long nlev = is_ml ? nml : met->np;
-    const long long sx = is_ml ? met->sx_ml : met->sx, sy = is_ml ? met->sy_ml : met->sy;
+    const LevelField L = level_field(met, f);
     const bool coded = pk && pk->q3[f];
-    S.has3[f] = (met->f3[f] != nullptr || coded) && nlev > 0;
+    S.has3[f] = (met->f3[f] != nullptr || coded) && L.nlev > 0;
     if (!S.has3[f])
       continue;
-    const size_t n3 = (size_t) met->nx * met->ny * (size_t) nlev;
+    const size_t n3 = ncol * (size_t) L.nlev;
     if (new_grid || !S.f3[f])
       HIPCHK(S.f3[f].resize(n3));
     if (coded) {
-      const PackedField B = packed_field(n3, (int) nlev, pk->q3[f]);
-      HIPCHK(hipMemcpyAsync(B.scl(codes), pk->scl[f], (size_t) nlev * sizeof(double), hipMemcpyHostToDevice, stream));
-      HIPCHK(hipMemcpyAsync(B.off(codes), pk->off[f], (size_t) nlev * sizeof(double), hipMemcpyHostToDevice, stream));
-      HIPCHK(hipMemcpyAsync(B.q(codes), pk->q3[f], n3 * sizeof(unsigned short), hipMemcpyHostToDevice, stream));
-      const PackStream P = pack_stream(B.q(codes), n3, (int) nlev);
-      hipLaunchKernelGGL(P.table_in_lds ? met_unpack_kernel<true> : met_unpack_kernel<false>, P.grid, dim3(kPkThreads), P.lds,
-                         stream, B.q(codes), B.scl(codes), B.off(codes), S.f3[f].p, P.n, P.nlev, P.head, pk->lo[f], pk->hi[f]);
-      HIPCHK(hipGetLastError());
+      const PackedField B = packed_field(n3, L.nlev, pk->q3[f], codes);
+      if (upload_packed(ctx, stream, B, pk, f) || unpack_packed(B, pk, f, S.f3[f].p, launch))
+        return 1;
       continue;
     }
-    if (!regrid_strides_ok(met->ny, (int) nlev, sx, sy))
+    if (!regrid_strides_ok(met->ny, L.nlev, L.sx, L.sy))
       return fail(ctx, "unsupported 3-D meteo strides");
-    if (copy3(ctx, stream, S.f3[f].p, met->f3[f], met->nx, met->ny, (int) nlev, sx, sy, true))
+    if (copy3(ctx, stream, S.f3[f].p, met->f3[f], met->nx, met->ny, L, true))
       return 1;
   }
   S.ps11 = met->f2[MPHIP_PS] ? met->f2[MPHIP_PS][(size_t) met->sx2 + 1] : 0.f;
@@ -2915,8 +2945,10 @@ int upload_fields(mphip_ctx *ctx, MetSlot &S, const mphip_met_t *met, bool new_g
   return 0;
 }
 
-// ---- mphip_derive_met, mphip_regrid_met, mphip_detrend_met: what a call of the three shares ------------------------
-// One call, from open() to the end of its scope: it holds the lock, hands out the scratch (PrepState), brackets what
+// ---- mphip_derive_met, mphip_regrid_met, mphip_detrend_met, mphip_ingest_met, mphip_unpack_met, mphip_pack_met: what a
+// ---- call of the six shares ----------------------------------------------------------------------------------------
+// One call, from open() to the end of its scope: it holds the lock, hands out the scratch (PrepState), stages fields
+// between the caller's arrays and that scratch (upload3 ... download2, uploads_complete), brackets what
 // mphip_profile_begin / _end time with event pairs (tools/gpu_*_cost.py; a caller that profiles does not step from another
 // thread) and, however the call ends, leaves nothing queued on the stream.  A copy may read the call's own vectors: those
 // are declared before the PrepCall, so that they are destroyed after it.
@@ -2940,8 +2972,10 @@ struct PrepCall {
     S.taken = 0;
     return 0;
   }
-  // the end of an accepted call: its results are in the caller's arrays
+  // the end of an accepted call and of the event pair around its downloads: its results are in the caller's arrays
   int close() {
+    if (mark_end())
+      return 1;
     const hipStream_t s = st;
     st = nullptr;
     HIPCHK(hipStreamSynchronize(s));
@@ -2955,24 +2989,48 @@ struct PrepCall {
     DevBuf<char> &b = S.pool[S.taken++];
     return reserve(ctx, b, n * sizeof(T)) ? nullptr : (T *) b.p;
   }
+  // A field between the caller's array and a compact device array, on the call's stream: a level field of nx x ny columns
+  // (L: its levels and the host array's strides) or a surface field (row stride sx2).  upload: into the next buffer of the
+  // pool, which holds `room` values where that is more than the field's (mphip_ingest_met: the periodic column); NULL:
+  // it failed.  to_device3: into a buffer taken earlier (the order of the takes decides which buffer serves what).
+  float *upload3(const float *host, int nx, int ny, LevelField L, size_t room = 0) {
+    float *const dev = take<float>(std::max(room, (size_t) nx * ny * L.nlev));
+    return dev && !to_device3(dev, host, nx, ny, L) ? dev : nullptr;
+  }
+  float *upload2(const float *host, int nx, int ny, long long sx2, size_t room = 0) {
+    float *const dev = take<float>(std::max(room, (size_t) nx * ny));
+    return dev && !copy2(ctx, st, dev, host, nx, ny, sx2, true) ? dev : nullptr;
+  }
+  int to_device3(float *dev, const float *host, int nx, int ny, LevelField L) { return copy3(ctx, st, dev, host, nx, ny, L, true); }
+  int download3(float *dev, float *host, int nx, int ny, LevelField L) { return copy3(ctx, st, dev, host, nx, ny, L, false); }
+  int download2(float *dev, float *host, int nx, int ny, long long sx2) { return copy2(ctx, st, dev, host, nx, ny, sx2, false); }
+  // The uploads are complete behind this.  With pageable memory the copies have read the caller's arrays when they
+  // return; the synchronisation makes that hold for pinned arrays too, before the first download overwrites an input
+  // that an output aliases, and it covers the call's own vectors that a copy reads.
+  int uploads_complete() {
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+  }
+  // the axes of the output grid (taken before anything was written: `out` may alias `in`) into `out`, behind close()
+  static void write_axes(const mphip_regrid_out_t *out, const std::vector<double> &lon2, const std::vector<double> &lat2,
+                         const std::vector<double> &p2) {
+    if (out->lon)
+      memcpy(out->lon, lon2.data(), lon2.size() * sizeof(double));
+    if (out->lat)
+      memcpy(out->lat, lat2.data(), lat2.size() * sizeof(double));
+    if (out->p)
+      memcpy(out->p, p2.data(), p2.size() * sizeof(double));
+  }
   // event pairs around every kernel (phase 0), around the uploads (1), around the downloads (2) or around the weight table
   // of mphip_detrend_met (3)
   int mark_begin(int phase) {
     ev_stop = nullptr;
-    if (!ctx->prof || ctx->derive_profile_phase != phase)
-      return 0;
-    while (ctx->ev_used + 2 > ctx->ev.size()) {
-      hipEvent_t e;
-      HIPCHK(hipEventCreate(&e));
-      ctx->ev.push_back(e);
-    }
-    HIPCHK(hipEventRecord(ctx->ev[ctx->ev_used++], st));
-    ev_stop = ctx->ev[ctx->ev_used++];
-    return 0;
+    return ctx->derive_profile_phase == phase ? prof_pair(ctx, st, &ev_stop) : 0;
   }
   int mark_end() {
     if (ev_stop)
       HIPCHK(hipEventRecord(ev_stop, st));
+    ev_stop = nullptr;
     return 0;
   }
   template <typename K, typename... Args>
@@ -3006,7 +3064,7 @@ int columns_per_workgroup(F lds_of, size_t *lds) {
   return 0;
 }
 
-// the refusals every call of the three makes of a grid; NULL = accepted
+// the refusals every call of the six makes of a grid; NULL = accepted
 const char *grid_dims_refusal(int nx, int ny, bool axes_given = true) {
   return nx < 2 || ny < 2 || !axes_given ? "meteo grid dimensions out of range" : nullptr;
 }
@@ -3989,14 +4047,13 @@ int mphip_derive_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const
     HIPCHK(hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, st));
   }
   float *i3[MPHIP_N3D] = {}, *i2[MPHIP_N2D] = {}, *o2[MPHIP_N2D] = {};
+  const LevelField L = { np, in->sx, in->sy };
   for (int f = 0; f < MPHIP_N3D; f++)
-    if (need3[f])
-      if (!(i3[f] = call.take<float>(ncell)) || copy3(ctx, st, i3[f], in->f3[f], nx, ny, np, in->sx, in->sy, true))
-        return 1;
+    if (need3[f] && !(i3[f] = call.upload3(in->f3[f], nx, ny, L)))
+      return 1;
   for (int f = 0; f < MPHIP_N2D; f++) {
-    if (need2[f])
-      if (!(i2[f] = call.take<float>(ncol)) || copy2(ctx, st, i2[f], in->f2[f], nx, ny, in->sx2, true))
-        return 1;
+    if (need2[f] && !(i2[f] = call.upload2(in->f2[f], nx, ny, in->sx2)))
+      return 1;
     if (give2[f] && !(o2[f] = call.take<float>(ncol)))
       return 1;
   }
@@ -4097,15 +4154,13 @@ int mphip_derive_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const
   }
   if (call.mark_begin(2))
     return 1;
-  if (do_pv && copy3(ctx, st, pv, out->f3[MPHIP_PV], nx, ny, np, in->sx, in->sy, false))
+  if (do_pv && call.download3(pv, out->f3[MPHIP_PV], nx, ny, L))
     return 1;
-  if (geopot && copy3(ctx, st, z_final, out->f3[MPHIP_Z], nx, ny, np, in->sx, in->sy, false))
+  if (geopot && call.download3(z_final, out->f3[MPHIP_Z], nx, ny, L))
     return 1;
   for (int f = 0; f < MPHIP_N2D; f++)
-    if (give2[f] && copy2(ctx, st, o2[f], out->f2[f], nx, ny, in->sx2, false))
+    if (give2[f] && call.download2(o2[f], out->f2[f], nx, ny, in->sx2))
       return 1;
-  if (call.mark_end())
-    return 1;
   return call.close();
 }
 
@@ -4161,7 +4216,7 @@ int mphip_regrid_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const
     return 1;
   hipStream_t st = call.st;
   const size_t ncol = (size_t) P.nx * P.ny, ncol2 = (size_t) P.nx2 * P.ny2;
-  const size_t ncell0 = ncol * P.np0, ncell1 = ncol * P.np1, ncell2 = ncol2 * P.np2;
+  const size_t ncell1 = ncol * P.np1, ncell2 = ncol2 * P.np2;
   // the axes of the output are taken before anything is written (`out` may alias `in`)
   std::vector<double> lon2(P.nx2), lat2(P.ny2), p2(P.np2);
   const int ddx = sample ? opt->met_dx : 1, ddy = sample ? opt->met_dy : 1, ddp = sample ? opt->met_dp : 1;
@@ -4182,11 +4237,11 @@ int mphip_regrid_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const
     if (!(d_metp = call.take<double>((size_t) opt->met_np)))
       return 1;
     HIPCHK(hipMemcpyAsync(d_metp, opt->met_p, (size_t) opt->met_np * sizeof(double), hipMemcpyHostToDevice, st));
-    if (!(d_pl = call.take<float>(ncell0)) || copy3(ctx, st, d_pl, in->f3[MPHIP_PL], P.nx, P.ny, P.np0, in->sx_ml, in->sy_ml, true))
+    if (!(d_pl = call.upload3(in->f3[MPHIP_PL], P.nx, P.ny, LevelField{ P.np0, in->sx_ml, in->sy_ml })))
       return 1;
   }
   for (int i = 0; i < n3; i++) {
-    if (!(in3[i] = call.take<float>(ncell0)) || copy3(ctx, st, in3[i], in->f3[f3[i]], P.nx, P.ny, P.np0, in->sx, in->sy, true))
+    if (!(in3[i] = call.upload3(in->f3[f3[i]], P.nx, P.ny, LevelField{ P.np0, in->sx, in->sy })))
       return 1;
     if (ml && !(mid3[i] = call.take<float>(ncell1)))
       return 1;
@@ -4194,16 +4249,13 @@ int mphip_regrid_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const
       return 1;
   }
   for (int i = 0; i < n2; i++) {
-    if (!(in2[i] = call.take<float>(ncol)) || copy2(ctx, st, in2[i], in->f2[f2[i]], P.nx, P.ny, in->sx2, true))
+    if (!(in2[i] = call.upload2(in->f2[f2[i]], P.nx, P.ny, in->sx2)))
       return 1;
     if (sample && !(out2[i] = call.take<float>(ncol2)))
       return 1;
   }
-  if (call.mark_end())
+  if (call.mark_end() || call.uploads_complete())
     return 1;
-  // (pageable memory: the copies above have read the caller's arrays when they return; the synchronisation makes that
-  // hold for pinned arrays too, before the first download below overwrites an aliased input)
-  HIPCHK(hipStreamSynchronize(st));
 
   if (ml && n3 > 0) {
     RegridFields F;
@@ -4229,19 +4281,14 @@ int mphip_regrid_met(mphip_ctx *ctx, const mphip_met_t *in, unsigned what, const
   if (call.mark_begin(2))
     return 1;
   for (int i = 0; i < n3; i++)
-    if (copy3(ctx, st, sample ? out3[i] : mid3[i], out->f3[f3[i]], P.nx2, P.ny2, P.np2, out->sx, out->sy, false))
+    if (call.download3(sample ? out3[i] : mid3[i], out->f3[f3[i]], P.nx2, P.ny2, LevelField{ P.np2, out->sx, out->sy }))
       return 1;
   for (int i = 0; i < n2; i++)
-    if (copy2(ctx, st, sample ? out2[i] : in2[i], out->f2[f2[i]], P.nx2, P.ny2, out->sx2, false))
+    if (call.download2(sample ? out2[i] : in2[i], out->f2[f2[i]], P.nx2, P.ny2, out->sx2))
       return 1;
-  if (call.mark_end() || call.close())
+  if (call.close())
     return 1;
-  if (out->lon)
-    memcpy(out->lon, lon2.data(), lon2.size() * sizeof(double));
-  if (out->lat)
-    memcpy(out->lat, lat2.data(), lat2.size() * sizeof(double));
-  if (out->p)
-    memcpy(out->p, p2.data(), p2.size() * sizeof(double));
+  call.write_axes(out, lon2, lat2, p2);
   return 0;
 }
 
@@ -4296,16 +4343,13 @@ int mphip_detrend_met(mphip_ctx *ctx, const mphip_met_t *in, const mphip_detrend
   for (int i = 0; i < nf; i++) {
     float *const d_in = call.take<float>(ncell);
     if (!d_in || !(res[i] = call.take<float>(ncell))
-        || copy3(ctx, st, d_in, in->f3[fld[i]], P.nx, P.ny, P.np, in->sx, in->sy, true))
+        || call.to_device3(d_in, in->f3[fld[i]], P.nx, P.ny, LevelField{ P.np, in->sx, in->sy }))
       return 1;
     F.in[i] = d_in;
     F.out[i] = res[i];
   }
-  if (call.mark_end())
+  if (call.mark_end() || call.uploads_complete())     // (the table and the row records are this call's own vectors)
     return 1;
-  // (the table and the row records are this call's own vectors, and an aliased input must have been read before the
-  // first download overwrites it: the uploads are complete here)
-  HIPCHK(hipStreamSynchronize(st));
 
   if (call.launch(detrend_kernel, dim3((unsigned) ((long long) P.nchunk * P.ny), (unsigned) nf), dim3(kDtThreads), 0, P.nx, P.ny,
                   P.np, d_rows, d_w, F))
@@ -4313,10 +4357,8 @@ int mphip_detrend_met(mphip_ctx *ctx, const mphip_met_t *in, const mphip_detrend
   if (call.mark_begin(2))
     return 1;
   for (int i = 0; i < nf; i++)
-    if (copy3(ctx, st, res[i], out->f3[fld[i]], P.nx, P.ny, P.np, out->sx, out->sy, false))
+    if (call.download3(res[i], out->f3[fld[i]], P.nx, P.ny, LevelField{ P.np, out->sx, out->sy }))
       return 1;
-  if (call.mark_end())
-    return 1;
   return call.close();
 }
 
@@ -4376,7 +4418,7 @@ int mphip_ingest_met(mphip_ctx *ctx, const mphip_met_t *in, const mphip_ingest_r
     const mphip_raw_t *raw;     // NULL: in met order
     const float *src;
     float *dst, *dev;
-    long long sx, sy;           // of src (3-D)
+    LevelField L;               // of src (3-D)
   } fld[MPHIP_N3D + MPHIP_N2D];
   int nf = 0;
   for (int i = 0; i < MPHIP_N3D + MPHIP_N2D; i++) {
@@ -4400,15 +4442,14 @@ int mphip_ingest_met(mphip_ctx *ctx, const mphip_met_t *in, const mphip_ingest_r
     }
     if ((!r && !src) || !dst)
       continue;
-    const bool is_ml = is3 && field_on_model_levels(f);
-    if (is_ml && in->npl < 1)
+    if (is3 && field_on_model_levels(f) && in->npl < 1)
       return fail(ctx, std::string("mphip_ingest_met: field ") + name + " is on model levels and npl < 1");
-    const int nlev = !is3 ? 1 : is_ml ? in->npl : in->np;
-    if (!r && (is3 ? !regrid_strides_ok(P.ny, nlev, is_ml ? in->sx_ml : in->sx, is_ml ? in->sy_ml : in->sy) : in->sx2 < P.ny))
+    const LevelField L = is3 ? level_field(in, f) : LevelField{ 1, 0, 0 };
+    if (!r && (is3 ? !regrid_strides_ok(P.ny, L.nlev, L.sx, L.sy) : in->sx2 < P.ny))
       return fail(ctx, "mphip_ingest_met: unsupported meteo strides");
-    if (is3 ? !regrid_strides_ok(P.ny, nlev, out->sx, out->sy) : out->sx2 < P.ny)
+    if (is3 ? !regrid_strides_ok(P.ny, L.nlev, out->sx, out->sy) : out->sx2 < P.ny)
       return fail(ctx, "mphip_ingest_met: the output strides do not hold the grid");
-    fld[nf++] = Field{ is3, f, nlev, r, src, dst, nullptr, is_ml ? in->sx_ml : in->sx, is_ml ? in->sy_ml : in->sy };
+    fld[nf++] = Field{ is3, f, L.nlev, r, src, dst, nullptr, L };
   }
   if (!nf)
     return fail(ctx, "mphip_ingest_met: no field is given in `in` or `raw` and named in `out`");
@@ -4448,23 +4489,18 @@ int mphip_ingest_met(mphip_ctx *ctx, const mphip_met_t *in, const mphip_ingest_r
   }
   for (int i = 0; i < nf; i++) {
     Field &F = fld[i];
-    const size_t n = ncol * F.nlev;
-    if (!(F.dev = call.take<float>((size_t) nx2 * ny * F.nlev)))
-      return 1;
+    const size_t n = ncol * F.nlev, room = (size_t) nx2 * ny * F.nlev;     // (room: with the periodic column)
     if (F.raw) {
       const size_t bytes = n * (F.raw->type == MPHIP_RAW_SHORT ? sizeof(short) : sizeof(float));
-      if (!(d_raw[i] = call.take<char>(bytes)))
+      if (!(F.dev = call.take<float>(room)) || !(d_raw[i] = call.take<char>(bytes)))
         return 1;
       HIPCHK(hipMemcpyAsync(d_raw[i], F.raw->data, bytes, hipMemcpyHostToDevice, st));
-    } else if (F.is3 ? copy3(ctx, st, F.dev, F.src, nx, ny, F.nlev, F.sx, F.sy, true)
-                     : copy2(ctx, st, F.dev, F.src, nx, ny, in->sx2, true)) {
+    } else if (!(F.dev = F.is3 ? call.upload3(F.src, nx, ny, F.L, room) : call.upload2(F.src, nx, ny, in->sx2, room))) {
       return 1;
     }
   }
-  if (call.mark_end())
+  if (call.mark_end() || call.uploads_complete())
     return 1;
-  // (an aliased input must have been read before the first download overwrites it: the uploads are complete here)
-  HIPCHK(hipStreamSynchronize(st));
 
   float *dev3[MPHIP_N3D] = {};
   for (int i = 0; i < nf; i++) {
@@ -4515,18 +4551,13 @@ int mphip_ingest_met(mphip_ctx *ctx, const mphip_met_t *in, const mphip_ingest_r
     return 1;
   for (int i = 0; i < nf; i++) {
     const Field &F = fld[i];
-    if (F.is3 ? copy3(ctx, st, F.dev, F.dst, nx2, ny, F.nlev, out->sx, out->sy, false)
-              : copy2(ctx, st, F.dev, F.dst, nx2, ny, out->sx2, false))
+    if (F.is3 ? call.download3(F.dev, F.dst, nx2, ny, LevelField{ F.nlev, out->sx, out->sy })
+              : call.download2(F.dev, F.dst, nx2, ny, out->sx2))
       return 1;
   }
-  if (call.mark_end() || call.close())
+  if (call.close())
     return 1;
-  if (out->lon)
-    memcpy(out->lon, lon2.data(), lon2.size() * sizeof(double));
-  if (out->lat)
-    memcpy(out->lat, lat2.data(), lat2.size() * sizeof(double));
-  if (out->p)
-    memcpy(out->p, p2.data(), p2.size() * sizeof(double));
+  call.write_axes(out, lon2, lat2, p2);
   return 0;
 }
 
@@ -4552,16 +4583,16 @@ int mphip_unpack_met(mphip_ctx *ctx, const mphip_met_packed_t *in, const mphip_m
   std::string msg;
   if (packed_refusal(in, msg))
     return fail(ctx, "mphip_unpack_met: " + msg);
-  int fld[MPHIP_N3D], nlev[MPHIP_N3D], nf = 0;
+  int fld[MPHIP_N3D], nf = 0;
+  LevelField lev[MPHIP_N3D];      // the levels of the input's grid at the strides of the output's arrays
   for (int f = 0; f < MPHIP_N3D; f++) {
-    const bool is_ml = field_on_model_levels(f);
-    const int nl = is_ml ? std::max(m->npl, 0) : m->np;
-    if (!in->q3[f] || !out->f3[f] || nl < 1)
+    const LevelField L = level_field(m, f, out);
+    if (!in->q3[f] || !out->f3[f] || L.nlev < 1)
       continue;
-    if (!regrid_strides_ok(m->ny, nl, is_ml ? out->sx_ml : out->sx, is_ml ? out->sy_ml : out->sy))
+    if (!regrid_strides_ok(m->ny, L.nlev, L.sx, L.sy))
       return fail(ctx, "mphip_unpack_met: the output strides do not hold the grid");
     fld[nf] = f;
-    nlev[nf++] = nl;
+    lev[nf++] = L;
   }
   if (!nf)
     return fail(ctx, "mphip_unpack_met: no field is given as codes in `in` and named in `out`");
@@ -4569,43 +4600,27 @@ int mphip_unpack_met(mphip_ctx *ctx, const mphip_met_packed_t *in, const mphip_m
   PrepCall call(ctx);
   if (call.open())
     return 1;
-  hipStream_t st = call.st;
   const size_t ncol = (size_t) m->nx * m->ny;
-  char *blk[MPHIP_N3D];
+  PackedField B[MPHIP_N3D];
   float *res[MPHIP_N3D];
   if (call.mark_begin(1))
     return 1;
   for (int i = 0; i < nf; i++) {
-    const int f = fld[i];
-    const PackedField B = packed_field(ncol * nlev[i], nlev[i], in->q3[f]);
-    if (!(blk[i] = call.take<char>(B.bytes)) || !(res[i] = call.take<float>(B.n)))
+    B[i] = packed_field(ncol * lev[i].nlev, lev[i].nlev, in->q3[fld[i]]);
+    if (!(B[i].blk = call.take<char>(B[i].bytes)) || !(res[i] = call.take<float>(B[i].n))
+        || upload_packed(ctx, call.st, B[i], in, fld[i]))
       return 1;
-    HIPCHK(hipMemcpyAsync(B.scl(blk[i]), in->scl[f], (size_t) nlev[i] * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(B.off(blk[i]), in->off[f], (size_t) nlev[i] * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(B.q(blk[i]), in->q3[f], B.n * sizeof(unsigned short), hipMemcpyHostToDevice, st));
   }
-  if (call.mark_end())
+  if (call.mark_end() || call.uploads_complete())
     return 1;
-  HIPCHK(hipStreamSynchronize(st));     // (an output may lie where an input does: the uploads are complete here)
-  for (int i = 0; i < nf; i++) {
-    const int f = fld[i];
-    const PackedField B = packed_field(ncol * nlev[i], nlev[i], in->q3[f]);
-    const PackStream P = pack_stream(B.q(blk[i]), B.n, nlev[i]);
-    if (call.launch(P.table_in_lds ? met_unpack_kernel<true> : met_unpack_kernel<false>, P.grid, dim3(kPkThreads), P.lds,
-                    (const unsigned short *) B.q(blk[i]), (const double *) B.scl(blk[i]), (const double *) B.off(blk[i]), res[i],
-                    P.n, P.nlev, P.head, in->lo[f], in->hi[f]))
+  for (int i = 0; i < nf; i++)
+    if (unpack_packed(B[i], in, fld[i], res[i], [&](auto... launch) { return call.launch(launch...); }))
       return 1;
-  }
   if (call.mark_begin(2))
     return 1;
-  for (int i = 0; i < nf; i++) {
-    const bool is_ml = field_on_model_levels(fld[i]);
-    if (copy3(ctx, st, res[i], out->f3[fld[i]], m->nx, m->ny, nlev[i], is_ml ? out->sx_ml : out->sx,
-              is_ml ? out->sy_ml : out->sy, false))
+  for (int i = 0; i < nf; i++)
+    if (call.download3(res[i], (float *) out->f3[fld[i]], m->nx, m->ny, lev[i]))
       return 1;
-  }
-  if (call.mark_end())
-    return 1;
   return call.close();
 }
 
@@ -4614,20 +4629,18 @@ int mphip_pack_met(mphip_ctx *ctx, const mphip_met_t *in, const mphip_met_packed
     return fail(ctx, "mphip_pack_met: null argument");
   if (const char *why = pack_grid_refusal(in))
     return fail(ctx, std::string("mphip_pack_met: ") + why);
-  int fld[MPHIP_N3D], nlev[MPHIP_N3D], nf = 0, nlev_max = 0, nlev_sum = 0;
+  int fld[MPHIP_N3D], nlev[MPHIP_N3D], nf = 0, nlev_sum = 0;
   for (int f = 0; f < MPHIP_N3D; f++) {
-    const bool is_ml = field_on_model_levels(f);
-    const int nl = is_ml ? std::max(in->npl, 0) : in->np;
-    if (!in->f3[f] || !out->q3[f] || nl < 1)
+    const LevelField L = level_field(in, f);
+    if (!in->f3[f] || !out->q3[f] || L.nlev < 1)
       continue;
     if (!out->scl[f] || !out->off[f])
       return fail(ctx, std::string("mphip_pack_met: field ") + kField3Name[f] + " is given as codes without scl or off");
-    if (!regrid_strides_ok(in->ny, nl, is_ml ? in->sx_ml : in->sx, is_ml ? in->sy_ml : in->sy))
+    if (!regrid_strides_ok(in->ny, L.nlev, L.sx, L.sy))
       return fail(ctx, "mphip_pack_met: unsupported meteo strides");
     fld[nf] = f;
-    nlev[nf++] = nl;
-    nlev_max = std::max(nlev_max, nl);
-    nlev_sum += nl;
+    nlev[nf++] = L.nlev;
+    nlev_sum += L.nlev;
   }
   if (!nf)
     return fail(ctx, "mphip_pack_met: no field is present in `in` and named as codes in `out`");
@@ -4650,15 +4663,13 @@ int mphip_pack_met(mphip_ctx *ctx, const mphip_met_t *in, const mphip_met_packed
     return 1;
   hipStream_t st = call.st;
   float *x[MPHIP_N3D];
-  char *blk[MPHIP_N3D];
+  PackedField B[MPHIP_N3D];
   if (call.mark_begin(1))
     return 1;
   for (int i = 0; i < nf; i++) {
-    const bool is_ml = field_on_model_levels(fld[i]);
-    const PackedField B = packed_field((size_t) ncol * nlev[i], nlev[i], out->q3[fld[i]]);
-    if (!(x[i] = call.take<float>(B.n)) || !(blk[i] = call.take<char>(B.bytes))
-        || copy3(ctx, st, x[i], in->f3[fld[i]], in->nx, in->ny, nlev[i], is_ml ? in->sx_ml : in->sx, is_ml ? in->sy_ml : in->sy,
-                 true))
+    B[i] = packed_field((size_t) ncol * nlev[i], nlev[i], out->q3[fld[i]]);
+    if (!(x[i] = call.take<float>(B[i].n)) || !(B[i].blk = call.take<char>(B[i].bytes))
+        || call.to_device3(x[i], in->f3[fld[i]], in->nx, in->ny, level_field(in, fld[i])))
       return 1;
   }
   if (call.mark_end())
@@ -4666,17 +4677,15 @@ int mphip_pack_met(mphip_ctx *ctx, const mphip_met_t *in, const mphip_met_packed
   // the partials of one field at a time (the stream's order), and the flags of every level of every field
   float *const pmin = call.take<float>(npart), *const pmax = pmin ? call.take<float>(npart) : nullptr;
   int *const pbad = pmax ? call.take<int>(npart) : nullptr, *const d_bad = pbad ? call.take<int>((size_t) nlev_sum) : nullptr;
-  if (!d_bad)
+  if (!d_bad || call.uploads_complete())
     return 1;
-  HIPCHK(hipStreamSynchronize(st));     // (an output may lie where an input does: the uploads are complete here)
   for (int i = 0, at = 0; i < nf; at += nlev[i], i++) {
-    const PackedField B = packed_field((size_t) ncol * nlev[i], nlev[i], out->q3[fld[i]]);
     const int pitch = nlev[i] | 1;
     if (call.launch_as(4, met_pack_extremes_kernel, dim3((unsigned) nblk[i]), dim3(kPkThreads),
                        (size_t) cpb[i] * pitch * sizeof(float), (const float *) x[i], ncol, nlev[i], cpb[i], pitch, pmin, pmax, pbad)
         || call.launch_as(5, met_pack_reduce_kernel, dim3((unsigned) ((nlev[i] + kPkRedLevels - 1) / kPkRedLevels)),
                           dim3(kPkRedThreads), 0, (const float *) pmin, (const float *) pmax, (const int *) pbad, nblk[i], nlev[i],
-                          B.scl(blk[i]), B.off(blk[i]), d_bad + at))
+                          B[i].scl(), B[i].off(), d_bad + at))
       return 1;
   }
   // a level with a value that is not finite has no code: refused before anything is written
@@ -4688,24 +4697,20 @@ int mphip_pack_met(mphip_ctx *ctx, const mphip_met_t *in, const mphip_met_packed
         return fail(ctx, std::string("mphip_pack_met: field ") + kField3Name[fld[i]] + " holds a value that is not finite at level "
                            + std::to_string(k));
   for (int i = 0; i < nf; i++) {
-    const PackedField B = packed_field((size_t) ncol * nlev[i], nlev[i], out->q3[fld[i]]);
-    const PackStream P = pack_stream(B.q(blk[i]), B.n, nlev[i]);
+    const PackStream P = pack_stream(B[i].q(), B[i].n, B[i].nlev);
     if (call.launch_as(6, P.table_in_lds ? met_pack_quantise_kernel<true> : met_pack_quantise_kernel<false>, P.grid,
-                       dim3(kPkThreads), P.lds, (const float *) x[i], (const double *) B.scl(blk[i]),
-                       (const double *) B.off(blk[i]), B.q(blk[i]), P.n, P.nlev, P.head))
+                       dim3(kPkThreads), P.lds, (const float *) x[i], (const double *) B[i].scl(),
+                       (const double *) B[i].off(), B[i].q(), P.n, P.nlev, P.head))
       return 1;
   }
   if (call.mark_begin(2))
     return 1;
   for (int i = 0; i < nf; i++) {
     const int f = fld[i];
-    const PackedField B = packed_field((size_t) ncol * nlev[i], nlev[i], out->q3[fld[i]]);
-    HIPCHK(hipMemcpyAsync((void *) out->scl[f], B.scl(blk[i]), (size_t) nlev[i] * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync((void *) out->off[f], B.off(blk[i]), (size_t) nlev[i] * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync((void *) out->q3[f], B.q(blk[i]), B.n * sizeof(unsigned short), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync((void *) out->scl[f], B[i].scl(), (size_t) B[i].nlev * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync((void *) out->off[f], B[i].off(), (size_t) B[i].nlev * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync((void *) out->q3[f], B[i].q(), B[i].n * sizeof(unsigned short), hipMemcpyDeviceToHost, st));
   }
-  if (call.mark_end())
-    return 1;
   return call.close();
 }
 
@@ -4851,16 +4856,9 @@ int mphip_intpol_met(mphip_ctx *ctx, long long n, const double *time, long long 
     I.lon = d_lon;
     I.lat = d_lat;
     I.n = (long long) m;
-    hipEvent_t e1 = nullptr;
-    if (ctx->prof) {   // (mphip_profile_begin / _end around calls of this function alone: the time of its kernel)
-      while (ctx->ev_used + 2 > ctx->ev.size()) {
-        hipEvent_t e;
-        HIPCHK(hipEventCreate(&e));
-        ctx->ev.push_back(e);
-      }
-      HIPCHK(hipEventRecord(ctx->ev[ctx->ev_used++], ctx->stream));
-      e1 = ctx->ev[ctx->ev_used++];
-    }
+    hipEvent_t e1 = nullptr;   // (mphip_profile_begin / _end around calls of this function alone: the time of its kernel)
+    if (prof_pair(ctx, ctx->stream, &e1))
+      return 1;
     hipLaunchKernelGGL(intpol_points_kernel, dim3(grid_for((long long) m)), dim3(256), lds, ctx->stream, M, I);
     HIPCHK(hipGetLastError());
     if (e1)

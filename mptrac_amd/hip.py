@@ -280,6 +280,24 @@ def _ptr(a, t):
     return a.ctypes.data_as(t)
 
 
+def _bits(table, what):
+    """`what` of a meteo call: a name of `table`, several of them, or the OR of their bits itself."""
+    if isinstance(what, str):
+        what = (what,)
+    return what if isinstance(what, int) else sum(table[w] for w in set(what))
+
+
+def _name_out(mo, f, a, shape=None, strides=None, check=True):
+    """Name the array `a` as field f of the out-structure `mo` (f3 or f2 by the field's kind).  Checked first, unless the
+    call is made for its refusal alone: float32 and, where given, the shape and the strides in bytes."""
+    if check:
+        assert a.dtype == np.float32 and shape in (None, a.shape) and strides in (None, a.strides), f
+    if f in FIELDS_3D:
+        mo.f3[FIELDS_3D.index(f)] = _ptr(a, _fp)
+    else:
+        mo.f2[FIELDS_2D.index(f)] = _ptr(a, _fp)
+
+
 def shard_range(n, rank, world):
     """Contiguous index range [lo, hi) of rank `rank`."""
     return (n * rank) // world, (n * (rank + 1)) // world
@@ -420,6 +438,16 @@ class Simulation:
             m.f2[i] = _ptr(met.f2[k], _fp) if k in met.f2 else None
         return m
 
+    def _shape_refused(self, which, mo, out, out_strides, call):
+        """mphip_<which>_shape refused the grid or `what`: `call`, the mphip_<which>_met of the same arguments, is made for
+        its message, with the caller's arrays all the same (a refused call writes nothing)."""
+        mo.sx, mo.sy, mo.sx2 = out_strides or (0, 0, 0)
+        for f, a in (out or {}).items():
+            if a is not None:
+                _name_out(mo, f, a, check=False)
+        self._chk(call())
+        raise MphipError(f"mphip_{which}_shape refused what mphip_{which}_met accepts")
+
     def derive_met(self, met, what, out=None, **opts):
         """The derived fields of the meteo preprocessing (mphip_derive_met).  `met`: a snapshot as synthetic_met returns
         it, or a strided view -- any object with its attributes whose f3 / f2 arrays are NumPy views [nx][ny][np] /
@@ -429,9 +457,7 @@ class Simulation:
         automatic), met_cloud_min (0), met_tropo (3), met_tropo_pv (3.5), met_tropo_theta (380), met_tropo_spline (1).
         `out`: {name: float32 array with the strides of the input} to write into (tests); by default new arrays.  Returns
         {name: array} of the fields of the requested bits."""
-        if isinstance(what, str):
-            what = (what,)
-        bits = what if isinstance(what, int) else sum(PREP[w] for w in set(what))
+        bits = _bits(PREP, what)
         o = MphipPrep(int(opts.pop("met_pbl", 3)), float(opts.pop("met_pbl_min", 0.1)), float(opts.pop("met_pbl_max", 5.0)),
                       int(opts.pop("met_geopot_sx", -1)), int(opts.pop("met_geopot_sy", -1)), float(opts.pop("met_cloud_min", 0.0)),
                       int(opts.pop("met_tropo", 3)), float(opts.pop("met_tropo_pv", 3.5)), float(opts.pop("met_tropo_theta", 380.)),
@@ -457,13 +483,9 @@ class Simulation:
                     a = np.empty((met.nx, m.sx // m.sy, m.sy), dtype=np.float32)[:, :met.ny, :met.np]
                 else:
                     a = np.empty((met.nx, m.sx2), dtype=np.float32)[:, :met.ny]
-                assert a.dtype == np.float32 and a.strides == like.strides, f
+                _name_out(mo, f, a, strides=like.strides)
                 if bits & PREP[name]:
                     res[f] = a
-                if three:
-                    mo.f3[FIELDS_3D.index(f)] = _ptr(a, _fp)
-                else:
-                    mo.f2[FIELDS_2D.index(f)] = _ptr(a, _fp)
         self._chk(self.L.mphip_derive_met(self.h, C.byref(m), bits, C.byref(o), C.byref(mo)))
         return res
 
@@ -475,9 +497,7 @@ class Simulation:
         met_sy, met_sp (1).  `out`: {name: float32 array of the new shape to write into, or None to leave a field out}
         -- views into larger arrays name their strides in floats as `out_strides` = (sx, sy, sx2), which then hold for
         every output array (tests; in-place use); by default new compact arrays.  Returns a Snapshot of the new shape."""
-        if isinstance(what, str):
-            what = (what,)
-        bits = what if isinstance(what, int) else sum(REGRID[w] for w in set(what))
+        bits = _bits(REGRID, what)
         met_p = np.ascontiguousarray(opts.pop("met_p", ()), dtype=np.float64)
         o = MphipRegrid(len(met_p), _ptr(met_p, _dp) if len(met_p) else None,
                         *(int(opts.pop(k, 1)) for k in ("met_dx", "met_dy", "met_dp", "met_sx", "met_sy", "met_sp")))
@@ -489,14 +509,8 @@ class Simulation:
         mo = MphipRegridOut()
         n = [C.c_int(0) for _ in range(3)]
         if self.L.mphip_regrid_shape(C.byref(m), bits, C.byref(o), *(C.byref(k) for k in n)):
-            mo.sx, mo.sy, mo.sx2 = out_strides or (0, 0, 0)
-            for f, a in (out or {}).items():        # (the caller's arrays all the same: a refused call writes nothing)
-                if a is not None and f in FIELDS_3D:
-                    mo.f3[FIELDS_3D.index(f)] = _ptr(a, _fp)
-                elif a is not None:
-                    mo.f2[FIELDS_2D.index(f)] = _ptr(a, _fp)
-            self._chk(self.L.mphip_regrid_met(self.h, C.byref(m), bits, C.byref(o), C.byref(mo)))     # (refused: its message)
-            raise MphipError("mphip_regrid_shape refused what mphip_regrid_met accepts")
+            self._shape_refused("regrid", mo, out, out_strides,
+                                lambda: self.L.mphip_regrid_met(self.h, C.byref(m), bits, C.byref(o), C.byref(mo)))
         nx2, ny2, np2 = (k.value for k in n)
         mo.sx, mo.sy, mo.sx2 = out_strides or (ny2 * np2, np2, ny2)
         lon, lat, p = (np.empty(k, dtype=np.float64) for k in (nx2, ny2, np2))
@@ -508,8 +522,7 @@ class Simulation:
                 a = out[f] if f in out else np.empty((nx2, ny2, np2), dtype=np.float32)
                 if a is None:
                     continue
-                assert a.dtype == np.float32 and a.shape == (nx2, ny2, np2) and a.strides == (4 * mo.sx, 4 * mo.sy, 4), f
-                mo.f3[FIELDS_3D.index(f)] = _ptr(a, _fp)
+                _name_out(mo, f, a, (nx2, ny2, np2), (4 * mo.sx, 4 * mo.sy, 4))
                 if f in met.f3:
                     f3[f] = a
         for f in FIELDS_2D:
@@ -517,8 +530,7 @@ class Simulation:
                 a = out[f] if f in out else np.empty((nx2, ny2), dtype=np.float32)
                 if a is None:
                     continue
-                assert a.dtype == np.float32 and a.shape == (nx2, ny2) and a.strides == (4 * mo.sx2, 4), f
-                mo.f2[FIELDS_2D.index(f)] = _ptr(a, _fp)
+                _name_out(mo, f, a, (nx2, ny2), (4 * mo.sx2, 4))
                 if f in met.f2:
                     f2[f] = a
         self._chk(self.L.mphip_regrid_met(self.h, C.byref(m), bits, C.byref(o), C.byref(mo)))
@@ -547,8 +559,7 @@ class Simulation:
                 a = np.empty((met.nx, met.ny, met.np), dtype=np.float32)
             else:
                 continue
-            assert a.dtype == np.float32 and a.shape == (met.nx, met.ny, met.np) and a.strides == (4 * mo.sx, 4 * mo.sy, 4), f
-            mo.f3[FIELDS_3D.index(f)] = _ptr(a, _fp)
+            _name_out(mo, f, a, (met.nx, met.ny, met.np), (4 * mo.sx, 4 * mo.sy, 4))
             if f in met.f3 and f in DETREND_FIELDS:
                 res[f] = a
         for i, k in enumerate(FIELDS_3D):       # (a field that was not asked for is not passed: NULL on the input side too)
@@ -558,19 +569,13 @@ class Simulation:
         return res
 
     # -- netCDF values to a met_t (mphip_ingest_met) ---------------------------
-    @staticmethod
-    def _ingest_bits(what):
-        if isinstance(what, str):
-            what = (what,)
-        return what if isinstance(what, int) else sum(INGEST[w] for w in set(what))
-
     def ingest_shape(self, axes, what):
         """nx2 of mphip_ingest_met for the axes of `axes` (lon, lat, p, coord_type) and the stages `what`: nx + 1 where the
         periodic column is added, else nx (mphip_ingest_shape; needs no device).  Raises where the call would refuse the
         grid or `what`."""
         m = self._met_struct(axes)
         n = C.c_int(0)
-        if self.L.mphip_ingest_shape(C.byref(m), self._ingest_bits(what), C.byref(n)):
+        if self.L.mphip_ingest_shape(C.byref(m), _bits(INGEST, what), C.byref(n)):
             raise MphipError("mphip_ingest_shape: the grid or `what` is refused")
         return n.value
 
@@ -590,7 +595,7 @@ class Simulation:
             raw, met, what = args
         else:
             (met, what), raw = args, {}
-        bits = self._ingest_bits(what)
+        bits = _bits(INGEST, what)
         if not hasattr(met, "f3"):
             met = Snapshot(getattr(met, "time", 0.0), met.coord_type, met.lon, met.lat, met.p, {}, {})
         m = self._met_struct(met)
@@ -624,14 +629,8 @@ class Simulation:
         out = dict(out or {})
         n = C.c_int(0)
         if self.L.mphip_ingest_shape(C.byref(m), bits, C.byref(n)):
-            mo.sx, mo.sy, mo.sx2 = out_strides or (0, 0, 0)
-            for f, a in out.items():        # (the caller's arrays all the same: a refused call writes nothing)
-                if a is not None and f in FIELDS_3D:
-                    mo.f3[FIELDS_3D.index(f)] = _ptr(a, _fp)
-                elif a is not None:
-                    mo.f2[FIELDS_2D.index(f)] = _ptr(a, _fp)
-            self._chk(self.L.mphip_ingest_met(self.h, C.byref(m), C.byref(r), bits, C.byref(mo)))     # (refused: its message)
-            raise MphipError("mphip_ingest_shape refused what mphip_ingest_met accepts")
+            self._shape_refused("ingest", mo, out, out_strides,
+                                lambda: self.L.mphip_ingest_met(self.h, C.byref(m), C.byref(r), bits, C.byref(mo)))
         nx2 = n.value
         mo.sx, mo.sy, mo.sx2 = out_strides or (met.ny * max(met.np, m.npl), max(met.np, m.npl), met.ny)
         lon, lat, p = (np.empty(k, dtype=np.float64) for k in (nx2, met.ny, met.np))
@@ -646,8 +645,7 @@ class Simulation:
                     a = np.empty((nx2, mo.sx // mo.sy, mo.sy), dtype=np.float32)[:, :met.ny, :nlev]
                 if a is None:
                     continue
-                assert a.dtype == np.float32 and a.shape == (nx2, met.ny, nlev) and a.strides == (4 * mo.sx, 4 * mo.sy, 4), f
-                mo.f3[FIELDS_3D.index(f)] = _ptr(a, _fp)
+                _name_out(mo, f, a, (nx2, met.ny, nlev), (4 * mo.sx, 4 * mo.sy, 4))
                 if f in raw or f in met.f3:
                     f3[f] = a
         for f in FIELDS_2D:
@@ -655,8 +653,7 @@ class Simulation:
                 a = out[f] if f in out else np.empty((nx2, mo.sx2), dtype=np.float32)[:, :met.ny]
                 if a is None:
                     continue
-                assert a.dtype == np.float32 and a.shape == (nx2, met.ny) and a.strides == (4 * mo.sx2, 4), f
-                mo.f2[FIELDS_2D.index(f)] = _ptr(a, _fp)
+                _name_out(mo, f, a, (nx2, met.ny), (4 * mo.sx2, 4))
                 if f in raw or f in met.f2:
                     f2[f] = a
         self._chk(self.L.mphip_ingest_met(self.h, C.byref(m), C.byref(r) if raw or bits & INGEST["decode"] else None, bits,
@@ -716,12 +713,11 @@ class Simulation:
             nlev = met.npl if name in FIELDS_ML else met.np
             a = np.empty((met.nx, met.ny, nlev), dtype=np.float32) if out is None else out[name]
             sx, sy = out_strides or (met.ny * nlev, nlev)
-            assert a.dtype == np.float32 and a.shape == (met.nx, met.ny, nlev) and a.strides == (4 * sx, 4 * sy, 4), name
+            _name_out(mo, name, a, (met.nx, met.ny, nlev), (4 * sx, 4 * sy, 4))
             if name in FIELDS_ML:
                 mo.sx_ml, mo.sy_ml = sx, sy
             else:
                 mo.sx, mo.sy = sx, sy
-            mo.f3[FIELDS_3D.index(name)] = _ptr(a, _fp)
             res[name] = a
         mo.sx2 = met.ny
         self._chk(self.L.mphip_unpack_met(self.h, C.byref(m), C.byref(mo)))

@@ -1,12 +1,19 @@
 """The result of a preprocessing call does not depend on which preprocessing calls its context has served before.
 
-mphip_derive_met, mphip_regrid_met and mphip_detrend_met take their device scratch from one pool that hands its buffers
-out from the first again at every call: a buffer may have served a call of another kind, with
-another element type and another size.  One context runs a sequence that mixes the three kinds, small after large and
-large after small, with a refused call in between; every accepted call is compared bit for bit (int32 views) with the
-same call made alone on a context created just for it, by the same library in the same process.  Equality is exact:
-the code and the inputs are the same.  That the values are the right ones is what tests/test_gpu_metprep.py,
-test_gpu_pv_tropo.py, test_gpu_regrid.py and test_gpu_detrend.py assert.
+mphip_derive_met, mphip_regrid_met, mphip_detrend_met, mphip_ingest_met, mphip_unpack_met and mphip_pack_met take their
+device scratch from one pool that hands its buffers out from the first again at every call: a buffer
+may have served a call of another kind, with another element type (floats, doubles, row records, raw shorts, blocks of
+scales, offsets and codes) and another size.  One context runs a sequence that mixes the six kinds, small after large and
+large after small, with a refused call in between; every accepted call is compared bit for bit (integer views of the
+element's width) with the same call made alone on a context created just for it, by the same library in the same
+process.  Equality is exact: the code and the inputs are the same.  That the values are the right ones is what
+tests/test_gpu_metprep.py, test_gpu_pv_tropo.py, test_gpu_regrid.py, test_gpu_detrend.py, test_gpu_ingest.py and
+test_gpu_pack.py assert.
+
+The ingest, unpack and pack rows are the smallest cases of tests/ingest_cases.py and tests/pack_cases.py (2 x 2 x 2) that
+give a periodic column from two longitudes, both poles, and a field of two levels with distinct ranges; for each,
+tests/refingest.py and tests/refpack.py alone give two distinct finite values or more in every returned array, the
+per-level scl and off included.
 
 The derive bits are those that need no climatology.  MPHIP_PREP_PV is refused below five rows, so on 5 x 4 x 137 the call
 leaves it out and a call on 5 x 5 x 137 with every bit follows.  A process loads one library: each runs in a child (as
@@ -24,6 +31,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import detrend_cases as D       # noqa: E402
+import ingest_cases as I        # noqa: E402
+import pack_cases as Q          # noqa: E402
 import refmetprep as M          # noqa: E402
 import regrid_cases as K        # noqa: E402
 from test_gpu_regrid import bare_context, sentinel_like, untouched      # noqa: E402
@@ -70,6 +79,34 @@ def regrid_smallest(sim):
     return _fields(sim.regrid_met(met, "sample", met_dx=d[0], met_dy=d[1], met_dp=d[2], met_sx=s[0], met_sy=s[1], met_sp=s[2]))
 
 
+def ingest_all_stages(sim):
+    """Decode (raw shorts), extrapolate, both poles and the periodic column in one call on 2 x 2 x 2."""
+    from mptrac_amd.hip import Snapshot
+    c = I.CASES["shape_2x2x2_short"]
+    axes = Snapshot(0.0, c["coord_type"], np.ascontiguousarray(c["lon"]), np.ascontiguousarray(c["lat"]),
+                    np.ascontiguousarray(c["p"]), {}, {})
+    got = sim.ingest_met(c["raw"], axes, ("decode", "extrapolate", "polar", "periodic"))
+    assert got.f3["u"].shape == (3, 2, 2) and got.lat[0] == 90.0 and got.lat[-1] == -90.0
+    return _fields(got)
+
+
+def _grid_2x2x2():
+    from mptrac_amd.hip import Snapshot
+    return Snapshot(0.0, 0, np.arange(2, dtype=np.float64), np.arange(2, dtype=np.float64), np.arange(2, 0, -1.0), {}, {})
+
+
+def unpack_hand(sim):
+    return sim.unpack_met(_grid_2x2x2(), {"t": Q.DECODE["hand_2x2x2"]})
+
+
+def pack_smooth(sim):
+    """Two levels of distinct ranges: the codes, and scl and off per level."""
+    met = _grid_2x2x2()
+    met.f3["t"] = Q.ENCODE["smooth_2x2x2"]
+    codes, scl, off = sim.pack_met(met)["t"]
+    return dict(t_codes=codes, t_scl=scl, t_off=off)
+
+
 def refused(sim):
     """A detrending with a NaN scale: refused, and its outputs stay as they are."""
     from mptrac_amd import hip
@@ -85,9 +122,12 @@ def refused(sim):
 # (name, call); None: the refused call
 SEQUENCE = [("detrend_smallest", detrend("smallest")),
             ("derive_37x19x20", derive(37, 19, 20)),
+            ("ingest_all_stages_2x2x2_short", ingest_all_stages),
             ("regrid_ml2pl_sample_19x11x20", regrid_both),
             ("derive_5x4x137", derive(5, 4, 137, tuple(b for b in BITS if b != "pv"))),
+            ("unpack_hand_2x2x2", unpack_hand),
             ("derive_5x5x137", derive(5, 5, 137)),
+            ("pack_smooth_2x2x2", pack_smooth),
             ("detrend_two_workgroups", detrend("two_workgroups")),
             ("regrid_sx_minus_1_is_nx", regrid_smallest),
             ("refused", None),
@@ -113,7 +153,7 @@ def child():
         fields = {}
         for f in got:
             a, b = np.ascontiguousarray(got[f]), np.ascontiguousarray(alone[f])
-            bits = "i%d" % a.itemsize            # (float32 fields, float64 axes)
+            bits = "i%d" % a.itemsize            # (float32 fields, float64 axes, scl and off, uint16 codes)
             fields[f] = dict(differ=int((a.view(bits) != b.view(bits)).sum()) if a.shape == b.shape else -1,
                              distinct=int(len(np.unique(b[np.isfinite(b)]))))
         rows.append(dict(name=name, fields=fields))
