@@ -749,6 +749,12 @@ int mphip_module(mphip_ctx *ctx, unsigned modules, double t);
 /* Keys (as the reference's double keys) and permutation of the last
  * module_sort call, for order checks. */
 int mphip_get_sort(mphip_ctx *ctx, double *keys, int *perm);
+/* How the module_sort calls of this context were answered so far: *repaired by the repair of the previous order
+ * (option "sort_repair": the sort ahead of a step whose particles are stored in the order of the last module_sort),
+ * *scratch by the radix sort of all pairs; *undone (may be NULL): those of *scratch that found the particles stored in
+ * the internal locality order and restored the caller's order first.  Host counters, read-only; calls on an empty
+ * particle set count as none of them. */
+int mphip_get_sort_counts(mphip_ctx *ctx, long long *repaired, long long *scratch, long long *undone);
 
 /* write_grid's binning loop (mptrac.c:13815-13872) on the device: cnt[ncell],
  * mean[nq][ncell], sigma[nq][ncell] raw sums (added in ascending particle index like the reference's loop,

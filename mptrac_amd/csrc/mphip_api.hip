@@ -203,6 +203,9 @@ struct mphip_ctx {
   bool ahead_valid = false;
   double ahead_t = 0;
   int ahead_cur = 0;
+  bool ahead_repaired = false;                     // the sort ahead repaired the previous order (it did not sort from scratch)
+  long long sorts_repaired = 0, sorts_scratch = 0; // module_sort calls answered by the repair / sorted from scratch (mphip_get_sort_counts)
+  long long sorts_undone = 0;                      // ... of the latter, those that found the internal locality order and undid it first
   DevBuf<unsigned char> d_depo_busy;               // EmitKeys::depo_busy (np bytes) ...
   bool depo_busy_valid = false;                    // ... written by the last launch, not yet used by its step's deposition launch
   const unsigned char *depo_busy_last = nullptr;   // ... as the step's deposition launch has just used it
@@ -1751,6 +1754,7 @@ int ahead_launch(mphip_ctx *ctx, double t_next, const BoxArgs *box = nullptr, bo
   ctx->ahead_valid = true;
   ctx->ahead_t = t_next;
   ctx->ahead_cur = cur;
+  ctx->ahead_repaired = key_prev != nullptr;
   return 0;
 }
 
@@ -1864,11 +1868,15 @@ int do_sort(mphip_ctx *ctx, const double *timestep_t = nullptr) {
     ahead_swap_buffers(ctx);
     ctx->ahead_valid = false;
     cur = ctx->ahead_cur;
+    (ctx->ahead_repaired ? ctx->sorts_repaired : ctx->sorts_scratch)++;
   } else {
+    const bool internal = !ctx->ext_identity;   // stored in the internal locality order: undone first
     if (ahead_drop(ctx) || ensure_packed(ctx) || restore_external_order(ctx))
       return 1;
     if (sort_pairs(ctx, 0, &cur, timestep_t))   // with timestep_t: module_timesteps in the key kernel
       return 1;
+    ctx->sorts_scratch++;
+    ctx->sorts_undone += internal;
   }
   ctx->sorted_buf = cur;
   ctx->stored_is_sorted = true;      // (once the gather below -- or the step launch that carries it -- has run)
@@ -5398,6 +5406,16 @@ int mphip_get_sort(mphip_ctx *ctx, double *keys, int *perm) {
     HIPCHK(hipStreamSynchronize(ctx->stream));
   }
   HIPCHK(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+int mphip_get_sort_counts(mphip_ctx *ctx, long long *repaired, long long *scratch, long long *undone) {
+  if (!ctx || !repaired || !scratch)
+    return fail(ctx, "null argument");
+  *repaired = ctx->sorts_repaired;
+  *scratch = ctx->sorts_scratch;
+  if (undone)
+    *undone = ctx->sorts_undone;
   return 0;
 }
 

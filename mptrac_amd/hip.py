@@ -239,6 +239,8 @@ def load(build=True):
     L.mphip_run_timesteps.argtypes = [C.c_void_p, C.c_double, C.c_int]
     L.mphip_module.argtypes = [C.c_void_p, C.c_uint, C.c_double]
     L.mphip_get_sort.argtypes = [C.c_void_p, _dp, C.POINTER(C.c_int)]
+    if hasattr(L, "mphip_get_sort_counts"):      # (absent from libraries built before the sort counters: Simulation._sort_counts says so)
+        L.mphip_get_sort_counts.argtypes = [C.c_void_p] + [C.POINTER(C.c_longlong)] * 3
     L.mphip_grid_sums.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int), _dp, _dp]
     L.mphip_set_grid_kernel.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
     _ip = C.POINTER(C.c_int)
@@ -913,6 +915,21 @@ class Simulation:
         perm = np.empty(self.n, dtype=np.int32)
         self._chk(self.L.mphip_get_sort(self.h, _ptr(keys, _dp), _ptr(perm, C.POINTER(C.c_int))))
         return keys, perm
+
+    def sort_counts(self):
+        """(module_sort calls answered by the repair of the previous order, calls sorted from scratch) of this context"""
+        return self._sort_counts()[:2]
+
+    def sorts_undone(self):
+        """module_sort calls that found the particles in the internal locality order and restored the caller's first"""
+        return self._sort_counts()[2]
+
+    def _sort_counts(self):
+        if not hasattr(self.L, "mphip_get_sort_counts"):
+            raise MphipError(f"{self.L._name} has no mphip_get_sort_counts: the library was built before the sort counters")
+        repaired, scratch, undone = C.c_longlong(), C.c_longlong(), C.c_longlong()
+        self._chk(self.L.mphip_get_sort_counts(self.h, C.byref(repaired), C.byref(scratch), C.byref(undone)))
+        return repaired.value, scratch.value, undone.value
 
     def grid_sums(self, t, out=None):
         """Counts, sums of q and of q^2 per output cell (mphip_grid_sums).  `out` = (cnt, mean, sigma) of an
