@@ -884,6 +884,12 @@ int mphip_comm_query(mphip_ctx *ctx, int *nranks, int *rank);
  *   that order (tile, then level, then column within the tile).
  *   "step_blocks" (default 8192): upper bound of the step kernel's grid;
  *   "xcd_map" (default 1): give each XCD one contiguous eighth of the particles;
+ *   "step_queue" (default 1): the step kernel runs as a grid that is resident at once (at most step_blocks /
+ *   step_blocks_multi workgroups) whose waves claim chunks of 64 particles from one queue per XCD ("xcd_map" 0: from
+ *   one queue) and, once their own is used up, from the others -- in launches with 16 chunks or more per wave of
+ *   that grid (4.2 million particles on an MI355X: below, the queues' fixed cost per launch outweighs the shorter
+ *   tail); 2 = in every launch; 0 = never: every workgroup walks its fixed share of the particles.  Results do not
+ *   depend on the value;
  *   "lazy_meteo" (default 1): module_meteo (mptrac.c:7921-7924) writes quantities
  *   no module reads, so the launch a time step schedules is held back until
  *   its result can be seen -- mphip_get_atm, mphip_grid_sums, mphip_module --

@@ -10,6 +10,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <map>
 #include <string>
 #include <mutex>
 #include <thread>
@@ -180,6 +181,10 @@ struct mphip_ctx {
   DevBuf<uint32_t> d_counts;
   int sorted_buf = -1;                // which d_keys/d_vals pair holds the last result
   const int *fused_perm = nullptr;    // set by do_sort, consumed by the next launch_step
+  // the counters of the step kernel's chunk queues (kQueueInts; zero between launches: the kernel's last wave zeroes
+  // them) and the workgroups of an instantiation that a CU holds at a time, by kernel and dynamic LDS size
+  DevBuf<int> d_step_queue;
+  std::map<std::pair<const void *, size_t>, int> step_resident;
   bool fused_quantities = false;      // ... which then moves the quantity arrays too (option fuse_sort_quantities)
   // module_sort as a repair of the previous order (repair_* kernels): valid while the particles are stored in the order
   // of the last module_sort (stored_is_sorted) -- its sorted keys are then non-decreasing along the slots
@@ -279,6 +284,9 @@ struct mphip_ctx {
   int step_blocks = 8192;             // upper bound of the step kernel's grid
   int step_blocks_multi = 32768;      // ... of a multi-step launch (mphip_run_timesteps)
   bool xcd_map = true;
+  // the step kernel's waves claim 64-particle chunks from queues (step_queue_grid): 1 = where a launch has 16 chunks
+  // or more per wave of the resident grid, 2 = in every launch (tests), 0 = never (the static partition of block_geom)
+  int step_queue = 1;
   bool big_grid = false;              // take the 64-bit-offset (kBigGrid) instantiations on a grid that fits 32 bits too (tests)
   bool force_generic = false;         // "generic_kernel"
   int multi_step = 64;                // mphip_run_timesteps: most time steps per launch (0 = always one by one)
@@ -1092,6 +1100,47 @@ int ensure_meso_table(mphip_ctx *ctx) {
   return 0;
 }
 
+// The chunk queues of a step_kernel launch (option step_queue; the kernel's chunk_claim).  The grid is what the GPU
+// holds at a time -- the workgroups of this instantiation with this much dynamic LDS per CU, asked once per context,
+// times the CUs -- or the option's bound `blocks` (step_blocks, step_blocks_multi) if that is less, a multiple of 8:
+// every workgroup fills its LDS tables once and its waves then claim chunks until none is left, so the launch ends
+// within one chunk's time of its last wave, not one block's.  The queues have a price per launch that does not depend
+// on the particle count: at its end every wave finds up to eight queues used up and adds to the counter of finished
+// waves, 4 096 waves x 9 returning atomics on nine words, 30-50 us measured (C3 at 10^6 particles, one launch per step:
+// 0.194 -> 0.224 ms; C2: 0.078 -> 0.130 ms; at 10^7 particles the same launches gain 0.07 ms,
+// profiles/r10_step_queue_ab.txt).  So step_queue 1 takes them from kQueueChunksPerWave chunks per wave of the grid on
+// -- 65 536 chunks, 4.2 million particles, at 256 CUs with four workgroups each -- and keeps the static partition
+// below; between 10^6 and 10^7 particles nothing was measured.  Fills S.queue* and *grid; leaves both alone where the
+// static partition stays.
+constexpr int kQueueChunksPerWave = 16;
+int step_queue_grid(mphip_ctx *ctx, void (*kernel)(const StepParams), size_t lds, int blocks, StepParams &S, int *grid) {
+  if (ctx->step_queue == 0)
+    return 0;
+  const auto key = std::make_pair((const void *) kernel, lds);
+  auto it = ctx->step_resident.find(key);
+  if (it == ctx->step_resident.end()) {
+    int per_cu = 0, cus = 0;
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, lds));
+    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    it = ctx->step_resident.emplace(key, std::max(per_cu, 1) * std::max(cus, 1)).first;
+  }
+  const long long nchunks = (ctx->np + 63) / 64;
+  long long g = std::max<long long>(8, std::min(it->second, blocks) & ~7);
+  if (nchunks > 0x7fffffffll || (ctx->step_queue == 1 && nchunks < (long long) kQueueChunksPerWave * kStepWaves * g))
+    return 0;
+  g = std::min(g, ((nchunks + kStepWaves - 1) / kStepWaves + 7) & ~7ll);   // (no more waves than chunks, in whole eights)
+  if (!ctx->d_step_queue.p) {
+    HIPCHK(ctx->d_step_queue.resize(kQueueInts));
+    HIPCHK(hipMemsetAsync(ctx->d_step_queue.p, 0, kQueueInts * sizeof(int), ctx->stream));
+  }
+  S.queue = ctx->d_step_queue.p;
+  S.queue_n = ctx->xcd_map ? 8 : 1;
+  S.queue_chunks = (int) ((nchunks + S.queue_n - 1) / S.queue_n);
+  S.queue_waves = (int) g * kStepWaves;
+  *grid = (int) g;
+  return 0;
+}
+
 // nsteps > 1: that many consecutive time steps in one launch, time and counters advancing by t_stride and ctr_stride
 // (kMultiStep instantiations: step_kernel_mask says whether one exists for the module set)
 int launch_step(mphip_ctx *ctx, unsigned mask, double t, const RngCtr &rng = {}, int nsteps = 1, double t_stride = 0,
@@ -1120,10 +1169,13 @@ int launch_step(mphip_ctx *ctx, unsigned mask, double t, const RngCtr &rng = {},
   S.tracers = ctx->d_tracers.p;
   S.t = t;
   S.mask = mask;
-  // every block walks a whole number of 256-particle rounds (no half-empty last round)
-  // (multi-step launches: more, shorter blocks -- a thread that takes 20 steps per particle should not also walk
-  // five particles; measured on C3, alternating in one process: 0.744-0.781 / 0.738-0.757 / 0.729-0.747 ms per step
-  // with 8 192 / 16 384 / 32 768 logical blocks)
+  // The static partition (step_queue 0, launches below step_queue_grid's threshold, and the kernels other than
+  // step_kernel): every block walks a whole number of 256-particle rounds (no half-empty last round).  block_geom
+  // rounds per_block up to a multiple of 256, so the option is an upper bound: 10^7 particles make 7 813 blocks of 1 280
+  // under step_blocks 8 192, and 19 532 blocks of 512 under step_blocks_multi 32 768.
+  // (multi-step launches: more, shorter blocks -- a launch ends one block's time after its last block starts, and a
+  // block that takes 20 steps per particle lasts long; measured on C3 at 20 steps per launch, alternating in one
+  // process: 0.744-0.781 / 0.738-0.757 / 0.729-0.747 ms per step with bounds of 8 192 / 16 384 / 32 768 blocks)
   const BlockGeom geom = block_geom(ctx->np, nsteps > 1 ? ctx->step_blocks_multi : ctx->step_blocks);
   const int nb = geom.nblocks_logical;
   const long long per_block = geom.per_block;
@@ -1138,6 +1190,8 @@ int launch_step(mphip_ctx *ctx, unsigned mask, double t, const RngCtr &rng = {},
   S.nsteps = nsteps;
   S.t_stride = t_stride;
   S.ctr_stride = ctr_stride;
+  S.queue = nullptr;   // (the static partition; step_queue_grid below)
+  S.queue_n = S.queue_chunks = S.queue_waves = 0;
   // axes, climatological tropopause, the tables of log and exp (+ pow's for the instantiations with the closure, below)
   size_t lds = axes_lds_bytes(ctx) + sizeof(DevClim) + (size_t) kLibmLogExpDoubles * sizeof(double);
   hipEvent_t e1 = nullptr;
@@ -1196,10 +1250,11 @@ int launch_step(mphip_ctx *ctx, unsigned mask, double t, const RngCtr &rng = {},
   if (step_kernel_parks(sel))   // + the thread-private parking area in front of them (step_kernel: park_slot)
     lds += kParkBytes;
   // (-DMPHIP_QUICK: only the instantiations step_kernel_mask selects in that build)
+  void (*kernel)(const StepParams) = nullptr;
   switch (sel) {
 #define STEP_CASE(M)                                                                                  \
   case M:                                                                                             \
-    hipLaunchKernelGGL(step_kernel<M>, dim3(nb), dim3(256), lds, ctx->stream, S);                     \
+    kernel = step_kernel<M>;                                                                          \
     break;
 #ifdef MPHIP_QUICK
 #define STEP_CASE_REST(M)
@@ -1254,6 +1309,10 @@ int launch_step(mphip_ctx *ctx, unsigned mask, double t, const RngCtr &rng = {},
   default:   // kNoStepKernel
     return fail(ctx, "internal: no multi-step instantiation for this module set");
   }
+  int grid = nb;
+  if (step_queue_grid(ctx, kernel, lds, nsteps > 1 ? ctx->step_blocks_multi : ctx->step_blocks, S, &grid))
+    return 1;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, ctx->stream, S);
   HIPCHK(hipGetLastError());
   ctx->fused_perm = nullptr;   // module_sort's gather, if one was pending, has happened in this launch
   if (ctx->prof)
@@ -2593,6 +2652,8 @@ int launch_radio_depo(mphip_ctx *ctx, double t, const unsigned char *busy) {
     S.nsteps = 1;
     S.t_stride = 0;
     S.ctr_stride = 0;
+    S.queue = nullptr;
+    S.queue_n = S.queue_chunks = S.queue_waves = 0;
     hipEvent_t e1 = nullptr;
     if (prof_pair(ctx, ctx->stream, &e1))   // (mphip_profile_begin / _end: the kernel counts as a launch of the step)
       return 1;
@@ -6033,6 +6094,8 @@ const Option kOptions[] = {
          "derive_profile_phase must be 0 (kernels), 1 (uploads), 2 (downloads), 3 (the weight table of "
          "mphip_detrend_met) or 4, 5, 6 (the extremes, their reduction, the quantisation of mphip_pack_met)"),
   flag("xcd_map", &mphip_ctx::xcd_map),
+  // the step kernel's chunk queues: 0 = the static partition, 1 = launches of 16 chunks per resident wave or more, 2 = all
+  number("step_queue", &mphip_ctx::step_queue, kWhole, 0, 2, "step_queue must be 0, 1 or 2"),
   flag("generic_kernel", &mphip_ctx::force_generic),          // tuning aid: never pick a specialised instantiation
   number("sort_bits", &mphip_ctx::sort_bits, kZeroOrRange, 8, kRadixMaxBits, "sort_bits must be 0 (automatic), 8, 9 or 10"),
   flag("mix_exchange_levels", &mphip_ctx::mix_exchange_levels),   // 0: the exchange of a mixing step covers the whole grid
@@ -6191,6 +6254,8 @@ int mphip_test_piece(mphip_ctx *ctx, int piece, int reps, double *checksum) {
   S.ctr_meso = 5000;
   S.ctr_conv = 9000;
   S.ctr_pbl = 0;
+  S.queue = nullptr;
+  S.queue_n = S.queue_chunks = S.queue_waves = 0;
   if (piece == 22) {   // (diff_meso_fast reads the table)
     if (!lean32_ok(ctx))
       return fail(ctx, "mphip_test_piece: piece 22 needs a grid the lean kernels with 32-bit offsets run on");

@@ -145,6 +145,11 @@ struct StepParams {
   int nsteps;
   double t_stride;
   uint64_t ctr_stride;
+  // step_kernel's chunk queues (chunk_claim; option step_queue): queue_n = 0 -- the static partition above;
+  // else 8 (xcd_map) or 1 queues of queue_chunks 64-particle chunks each, their counters in `queue`; queue_waves: the
+  // waves of the grid
+  int *queue;
+  int queue_n, queue_chunks, queue_waves;
 };
 
 // the running workgroup's particles [first, last) of a launch with StepParams' or MeteoArgs' partition
@@ -157,6 +162,93 @@ __device__ __forceinline__ void block_range(const Params &G, long long np, long 
   last = first + G.per_block;
   if (last > np)
     last = np;
+}
+
+// ---- step_kernel's walk over 64-particle chunks ----
+// A wave takes its particles a chunk at a time: chunk c is the particles 64 c ... 64 c + 63, lane l the particle
+// 64 c + l.  Which chunk comes next is wave-uniform (scalar registers, one branch for the whole wave), in one of two ways.
+//   Static partition (queue_n = 0): the chunks of the workgroup's block_range, wave w the ones w, w + 4, ... of it --
+//     thread t of the block walks first + t, first + t + 256, ..., the partition of every other per-particle kernel.
+//   Queues (queue_n = 8 with xcd_map, else 1): queue k holds the k-th contiguous part of the chunk range, queue_chunks
+//     chunks, and hands them out in ascending order -- lane 0 adds 1 to the queue's counter, the value it gets back is
+//     the chunk.  Workgroup b starts at queue b % queue_n (with 8: the XCD it runs on, so that an XCD's waves work on
+//     neighbouring chunks); a wave that finds a queue used up moves on to the next one and never comes back (the
+//     counters only grow), and leaves the loop behind the last.  A counter may run past its range: such a claim is no
+//     chunk.  No wave ever waits for another one.
+// The counters are zero in front of every launch: the wave that finishes last -- told by the counter of finished waves,
+// which every wave of the grid adds to once, behind its last claim -- stores the zeros for the next launch on the stream.
+// All of it is returning agent-scope atomics, which execute at the memory side and in the program order of the wave
+// (each value is used before the next one is issued): no payload travels between waves, so no fence is needed.
+constexpr int kQueueStride = 32;   // ints from one counter to the next: a 128-byte line each
+constexpr int kQueueDone = 8;      // the counter of finished waves, behind those of the (at most) 8 queues
+constexpr int kQueueInts = (kQueueDone + 1) * kQueueStride;
+constexpr int kStepWaves = 4;      // waves per workgroup of a step_kernel launch (256 threads)
+
+__device__ __forceinline__ const StepParams &step_kernarg() {   // (scalar loads at the point of use: step_kernel's loop)
+  auto kp = (const __attribute__((address_space(4))) StepParams *) __builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(kp));
+  return *(const StepParams *) kp;
+}
+// the lane's number in its wave (volatile: counted where it is used -- as a loop invariant the compiler would keep it,
+// and what it is compared with, in registers across the whole step body)
+__device__ __forceinline__ int wave_lane() {
+  int lane;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
+  return lane;
+}
+// What a wave keeps from one chunk to the next is one scalar register: bits 31-30 its index in the workgroup
+// (park_slot); below them the end of its block (static partition: a chunk index, below 2^30), or (queues) in bits 3-0
+// how many queues it has found used up and in bits 6-4 the queue its workgroup starts at.
+typedef unsigned ChunkWalk;
+// the next chunk of the queues, or -1
+__device__ __forceinline__ int chunk_claim(ChunkWalk &walk) {
+  const StepParams &S = step_kernarg();
+  const int nq = S.queue_n, per = S.queue_chunks;
+  const int nchunks = (int) ((S.atm.np + 63) >> 6);
+  for (; (int) (walk & 15u) < nq; walk++) {
+    const int q = (int) (((walk >> 4) + walk) & (unsigned) (nq - 1));   // (start + used up, modulo nq: nq is 1 or 8)
+    const int begin = q * per;
+    const int n = nchunks - begin < per ? nchunks - begin : per;   // (<= 0: nothing in this queue at this particle count)
+    if (n <= 0)
+      continue;
+    int c = 0;
+    if (wave_lane() == 0)
+      c = atomicAdd(S.queue + q * kQueueStride, 1);
+    c = __builtin_amdgcn_readfirstlane(c);
+    if (c < n)
+      return begin + c;
+  }
+  return -1;
+}
+// the wave's first chunk, or -1
+__device__ __forceinline__ int chunk_first(ChunkWalk &walk) {
+  const StepParams &S = step_kernarg();
+  const unsigned wave = (unsigned) __builtin_amdgcn_readfirstlane((int) threadIdx.x) >> 6;
+  if (S.queue_n) {
+    walk = wave << 30 | (blockIdx.x & 7u) << 4;
+    return chunk_claim(walk);
+  }
+  long long first, last;
+  block_range(S, S.atm.np, first, last);   // (first is a multiple of 256; last < first in a block behind the last particle)
+  const int end = (int) ((last + 63) >> 6);
+  walk = wave << 30 | (unsigned) end;
+  const int c = (int) (first >> 6) + (int) wave;
+  return c < end ? c : -1;
+}
+// the chunk behind the one of particle i (of any lane)
+__device__ __forceinline__ int chunk_next(long long i, ChunkWalk &walk) {
+  if (step_kernarg().queue_n)
+    return chunk_claim(walk);
+  const int c = __builtin_amdgcn_readfirstlane((int) (i >> 6)) + kStepWaves;
+  return c < (int) (walk & 0x3fffffffu) ? c : -1;
+}
+// behind a wave's last chunk: the last wave of the grid zeroes the counters
+__device__ __forceinline__ void chunk_walk_end() {
+  const StepParams &S = step_kernarg();
+  if (S.queue_n && wave_lane() == 0
+      && atomicAdd(S.queue + kQueueDone * kQueueStride, 1) == S.queue_waves - 1)
+    for (int q = 0; q <= kQueueDone; q++)
+      __hip_atomic_store(S.queue + q * kQueueStride, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 constexpr unsigned kMaskGeneric = 0xffffffffu;     // every module, module set taken from StepParams::mask
@@ -525,9 +617,10 @@ __device__ __forceinline__ void emit_sort_keys(const EmitKeys &E, const mphip_ct
 // q[qnt_rhop] -- is loaded once per particle and parked there, structure of arrays (slot[k][threadIdx.x]: a wave's
 // reads hit consecutive banks).  A slot belongs to one thread (no barrier); a thread that walks several particles
 // reuses it.  The area lies at the START of the dynamic LDS block, in front of the axes (the issue of a slot's address
-// is then a constant offset on the lane's), and the lane is taken from the particle index where a slot is used
-// (every block's range starts at a multiple of 256 -- block_geom --, so i & 255 == threadIdx.x): no register holds
-// an address across the steps.  No module that runs in these launches writes the two quantities: module_bound_cond
+// is then a constant offset on the lane's), and the thread index is put together where a slot is used, from the particle
+// index (a chunk starts at a multiple of 64, so i & 63 is the lane) and the wave's index in the workgroup, which the
+// scalar register of the chunk walk holds (ChunkWalk): no vector register holds an address across the steps.  No
+// module that runs in these launches writes the two quantities: module_bound_cond
 // writes m, vmr, the trace gases and aoa, the decay and deposition modules m, vmr, loss_rate and mloss_*,
 // module_radio_decay its nuclides -- indices of other quantity names.  The instantiations with the boundary-layer
 // closure keep their per-step loads: with pow's tables their LDS has no room left under the 40 KiB that let four
@@ -571,8 +664,9 @@ constexpr int kParkDoubles = 256 * 2 + 128;   // rp[256], rhop[256], ext[256] (i
 constexpr size_t kParkBytes = kParkDoubles * sizeof(double);
 enum { kParkRp = 0, kParkRhop = 256, kParkExt = 512 };   // (offsets in doubles)
 template <class T>
-__device__ __forceinline__ T *park_slot(double *area, int slot, long long i) {
-  unsigned lane = (unsigned) i & 255u;
+__device__ __forceinline__ T *park_slot(double *area, int slot, ChunkWalk walk, long long i) {
+  asm volatile("" : "+s"(walk));   // (nor does a scalar one hold 64 times the wave's index)
+  unsigned lane = ((unsigned) i & 63u) | ((walk >> 24) & 0xc0u);
   asm volatile("" : "+v"(lane));   // (the address is formed here, not once in front of the step loop)
   return (T *) (area + slot) + lane;
 }
@@ -615,10 +709,14 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
   }
   __syncthreads();
 
-  long long first, last;
-  block_range(S, a.np, first, last);
-
-  for (long long i = first + threadIdx.x; i < last; i += (park ? 256 : blockDim.x)) {   // (256: the launch's block size)
+  // the wave's chunks, one after the other (chunk_first / chunk_next: wave-uniform, so every lane is there when the
+  // next one is claimed; nothing in the loop needs a barrier)
+  ChunkWalk walk;
+  long long i;
+  for (int chunk = chunk_first(walk); chunk >= 0; chunk = chunk_next(i, walk)) {
+    i = 64ll * chunk + wave_lane();
+    if (i >= step_kernarg().atm.np)   // (the last chunk may be a part of one)
+      continue;
     // re-read the launch parameters from the kernarg segment in every iteration (scalar loads at
     // the point of use) instead of keeping all of them live across the loop, which spills SGPRs
     auto kp = (const __attribute__((address_space(4))) StepParams *) __builtin_amdgcn_kernarg_segment_ptr();
@@ -670,7 +768,7 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
           // (with module_diff_meso the store behind the last step writes uvwp)
           const PermRest r = perm_rest(a, i, src, !(mask & MPHIP_MOD_DIFF_MESO));
           if constexpr (park)
-            *park_slot<int>(s_lds, kParkExt, i) = r.ext;
+            *park_slot<int>(s_lds, kParkExt, walk, i) = r.ext;
           up = r.up;
           vp = r.vp;
           wp = r.wp;
@@ -689,10 +787,10 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
     }
     if constexpr (park) {   // (behind the gather of module_sort, which writes a.q[k][i])
       if (a.ext && !perm_all)
-        *park_slot<int>(s_lds, kParkExt, i) = a.ext[i];
+        *park_slot<int>(s_lds, kParkExt, walk, i) = a.ext[i];
       if (((CT & kGated) ? mask & S.mask : mask) & MPHIP_MOD_SEDI) {
-        *park_slot<double>(s_lds, kParkRp, i) = a.q[ctl.qnt_rp][i];
-        *park_slot<double>(s_lds, kParkRhop, i) = a.q[ctl.qnt_rhop][i];
+        *park_slot<double>(s_lds, kParkRp, walk, i) = a.q[ctl.qnt_rp][i];
+        *park_slot<double>(s_lds, kParkRhop, walk, i) = a.q[ctl.qnt_rhop][i];
       }
     }
     }
@@ -742,7 +840,7 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
     const uint64_t g_held = park ? 0 : (uint64_t) (a.ip0 + (a.ext ? (long long) a.ext[i] : i));
     auto g_now = [&]() -> uint64_t {
       if constexpr (park)
-        return (uint64_t) (a.ip0 + (a.ext ? (long long) *park_slot<int>(s_lds, kParkExt, i) : i));
+        return (uint64_t) (a.ip0 + (a.ext ? (long long) *park_slot<int>(s_lds, kParkExt, walk, i) : i));
       else
         return g_held;
     };
@@ -845,8 +943,8 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
       if (opt & (MPHIP_MOD_CONVECTION | MPHIP_MOD_SEDI)) {
         const bool sedi_on = (opt & MPHIP_MOD_SEDI) != 0;
         conv_sedi_fast<kBig<CT>>(ctl, M, A, P, opt, c_conv, g_now(),
-                       !sedi_on ? 0.0 : park ? *park_slot<double>(s_lds, kParkRp, i) : a.q[ctl.qnt_rp][i],
-                       !sedi_on ? 0.0 : park ? *park_slot<double>(s_lds, kParkRhop, i) : a.q[ctl.qnt_rhop][i], ltab);
+                       !sedi_on ? 0.0 : park ? *park_slot<double>(s_lds, kParkRp, walk, i) : a.q[ctl.qnt_rp][i],
+                       !sedi_on ? 0.0 : park ? *park_slot<double>(s_lds, kParkRhop, walk, i) : a.q[ctl.qnt_rhop][i], ltab);
       }
     } else {
       if (opt & MPHIP_MOD_CONVECTION)
@@ -931,6 +1029,7 @@ __global__ __launch_bounds__(256, kLeanML<CT> ? MPHIP_ML_WAVES_PER_SIMD : !kRunt
       }
     }
   }
+  chunk_walk_end();
 }
 
 // ---------------------------------------------------------------------------
