@@ -807,6 +807,42 @@ int mphip_sample_obs(mphip_ctx *ctx, double t0, double t1, int nobs, const doubl
  * particles): refused with a communicator or an index range that is not the whole simulation. */
 int mphip_station_hits(mphip_ctx *ctx, double t, double lon, double lat, double r, double stat_t0, double stat_t1,
                        int qnt_stat, int cap, int *nhit, int *index, double *rows);
+/* A read-only selection of the resident particles in the caller's (external) order: what a strided, windowed or boxed
+ * writer needs of mphip_get_atm without taking all of it (write_atm_asc with ATM_STRIDE / ATM_FILTER 2, write_vtk).
+ *   An external index e (rank-local, as in mphip_get_atm) is a candidate when first <= e <= last and
+ * (e - first) % stride == 0; a candidate is selected when no enabled criterion rejects it (all criteria are ANDed).
+ * Every test has the negated-or form written beside the members below, the form of write_atm_asc and of the box test of
+ * the analysis outputs: a NaN coordinate therefore PASSES the range it is tested against (and the distance test).  A
+ * caller who wants `time >= t0 && time <= t1` drops the NaN times from the few rows it gets back.  Z(p) is the
+ * log-pressure height of mptrac.h:2243 with the C library's log (restated on the device; both libraries decide alike);
+ * the distance test is the station loop's: geo2cart of the particle at the surface against that of the centre (the
+ * host's C library), squared distance against near_r^2.  Longitudes are compared as stored, without wrapping. */
+typedef struct {
+  long long first, last;   /* external (caller-order, rank-local) indices considered: first <= e <= last;
+                              last < 0 or last >= np: np - 1 */
+  long long stride;        /* >= 1; e is a candidate when (e - first) % stride == 0 */
+  int use_time, use_z, use_lon, use_lat, use_near;
+  double t0, t1;           /* rejected when time < t0 || time > t1 */
+  double z0, z1;           /* rejected when Z(p) < z0 || Z(p) > z1, Z as in mptrac.h:2243 */
+  double lon0, lon1;       /* rejected when lon < lon0 || lon > lon1 (stored longitude, no wrap) */
+  double lat0, lat1;       /* rejected when lat < lat0 || lat > lat1 */
+  double near_lon, near_lat, near_r;   /* km; rejected when |geo2cart(0, lon, lat) - geo2cart(0, near_lon, near_lat)|^2 > near_r^2 */
+} mphip_select_t;
+/* The selected particles in ascending external index: *nsel of them, index[k] the external index, time[k], p[k], lon[k],
+ * lat[k], q[iq][k] its values -- the bits mphip_get_atm delivers at that index.  Any output pointer, q itself and any
+ * q[iq] may be NULL: that row is neither gathered nor copied.  Every array given holds cap elements.  *nsel > cap:
+ * nothing but *nsel is written and the call returns 0; call again with larger arrays (cap = 0 counts only).  np == 0 or
+ * first > last: *nsel = 0.
+ *   The call only reads: a pending deferred module_meteo is flushed first, as in mphip_get_atm, and neither the stored
+ * order nor any particle value changes, so a time loop with calls in between has the bits of one without.  It works on a
+ * context that is one rank of several; nothing is reduced.  Beyond the marks (4 bytes per particle, twice) device memory
+ * grows with *nsel only: the two lists and two rows of doubles, whatever nq is.
+ *   Refused, with a message that names the call and nothing written: NULL ctx, sel or nsel; stride < 1, first < 0,
+ * cap < 0; an enabled range with a NaN bound or a lower bound above the upper; near_r negative or not finite; use_lon,
+ * use_lat or use_near on a Cartesian grid (met_coord_type != 0; use_time and use_z work there, as write_atm_asc does);
+ * control parameters not uploaded. */
+int mphip_select_atm(mphip_ctx *ctx, const mphip_select_t *sel, long long cap, long long *nsel, int *index, double *time,
+                     double *p, double *lon, double *lat, double *const *q);
 /* module_radio_decay (RADIO_DECAY): qnt[MPHIP_RN_*] is the quantity index of each activity [Bq] (-1: absent).  The
  * registered activities are mixed by module_mixing whether or not the module is on.  on != 0: mphip_run_timestep(s)
  * decay them after module_decay, module_mixing and the chemistry and before module_wet_depo, in the step kernel's tail
@@ -956,7 +992,13 @@ int mphip_comm_query(mphip_ctx *ctx, int *nranks, int *rank);
  *     kernels of mphip_pack_met only the extremes, their reduction, the quantisation (mphip_unpack_met and mphip_pack_met
  *     are calls of the same family: 0, 1 and 2 hold for them as well).
  *   "intpol_chunk" (default 4194304 = 2^22; 64 ... 16777216 = 2^24): points per launch of mphip_intpol_met -- its two
- *     device buffers hold 32 + 8 nfield bytes per point of a chunk.  Not observable. */
+ *     device buffers hold 32 + 8 nfield bytes per point of a chunk.  Not observable.
+ *   "select_direct" (default 0): mphip_select_atm copies every gathered row straight into the caller's array (page-locked
+ *     in one span under "pin_host_atm", as mphip_get_atm has them) instead of through the context's two page-locked rows.
+ *     Not observable.
+ *   "select_profile_phase" (default 0; 1 ... 5): measurement -- what mphip_profile_begin / _end time of a
+ *     mphip_select_atm call: every kernel (0), or only the mark kernel (1), the scan (2), the list kernel (3), the row
+ *     gathers (4), the copies to the host (5). */
 int mphip_set_option(mphip_ctx *ctx, const char *name, double value);
 int mphip_synchronize(mphip_ctx *ctx);
 

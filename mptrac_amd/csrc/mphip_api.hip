@@ -258,6 +258,12 @@ struct mphip_ctx {
   DevBuf<uint32_t> d_marks;           // counts per external index (np + 1), then their scan; chunk offsets behind them
   DevBuf<int> d_slot_of;              // station: where the particle of an external index is stored
   DevBuf<uint32_t> d_ana_flags;       // [bad member | records (scan) | records (64-bit sum, 2 words)]
+  // mphip_select_atm: [slot | external index] of the selected particles by rank, the two rows in flight on the device and
+  // their page-locked landing places, the events behind the copies into those
+  DevBuf<int> d_sel_list;
+  DevBuf<double> d_sel_rows;
+  PinnedBuf<double> h_sel_rows;
+  hipEvent_t sel_copied[2] = { nullptr, nullptr };
 
   // ---- exchange ----
   mphip_allreduce_fn allreduce = nullptr;
@@ -314,6 +320,8 @@ struct mphip_ctx {
   bool mix_exchange_levels = false;
   int derive_profile_phase = 0;       // what mphip_profile_begin / _end time of a preprocessing call
   int intpol_chunk = 1 << 22;         // points per launch of mphip_intpol_met: device memory does not grow with n
+  bool select_direct = false;         // mphip_select_atm copies into the caller's arrays (0: through the page-locked rows)
+  int select_profile_phase = 0;       // what mphip_profile_begin / _end time of mphip_select_atm
 
   // ---- profiling of the fused step kernel ----
   bool prof = false;
@@ -3439,7 +3447,7 @@ void mphip_destroy(mphip_ctx *ctx) {
       (void) hipStreamSynchronize(s);
       (void) hipStreamDestroy(s);
     }
-  for (hipEvent_t e : { ctx->next_ready, ctx->main_mark, ctx->ahead_mark, ctx->ahead_done })
+  for (hipEvent_t e : { ctx->next_ready, ctx->main_mark, ctx->ahead_mark, ctx->ahead_done, ctx->sel_copied[0], ctx->sel_copied[1] })
     if (e)
       (void) hipEventDestroy(e);
   for (auto e : ctx->ev)
@@ -5840,6 +5848,184 @@ int mphip_station_hits(mphip_ctx *ctx, double t, double lon, double lat, double 
   return 0;
 }
 
+namespace {
+
+// an enabled range of mphip_select_atm: no NaN bound, lower <= upper
+bool select_range_ok(int use, double lo, double hi) {
+  return !use || lo <= hi;
+}
+
+// One start/stop pair around a stage of mphip_select_atm when that stage is what is being timed (option
+// "select_profile_phase": 0 every kernel, 1 mark, 2 scan, 3 list, 4 the row gathers, 5 the copies to the host).
+int select_prof(mphip_ctx *ctx, int phase, bool kernel, hipEvent_t *stop) {
+  *stop = nullptr;
+  if (ctx->select_profile_phase == phase || (ctx->select_profile_phase == 0 && kernel))
+    return prof_pair(ctx, ctx->stream, stop);
+  return 0;
+}
+
+int select_prof_stop(mphip_ctx *ctx, hipEvent_t stop) {
+  if (stop)
+    HIPCHK(hipEventRecord(stop, ctx->stream));
+  return 0;
+}
+
+}   // namespace
+
+int mphip_select_atm(mphip_ctx *ctx, const mphip_select_t *sel, long long cap, long long *nsel, int *index, double *time,
+                     double *p, double *lon, double *lat, double *const *q) {
+  if (!ctx || !sel || !nsel)
+    return fail(ctx, "mphip_select_atm: null argument");
+  if (!ctx->have_ctl)
+    return fail(ctx, "mphip_select_atm: control parameters were not uploaded");
+  if (sel->stride < 1)
+    return fail(ctx, "mphip_select_atm: stride must be >= 1");
+  if (sel->first < 0)
+    return fail(ctx, "mphip_select_atm: first must be >= 0");
+  if (cap < 0)
+    return fail(ctx, "mphip_select_atm: cap must be >= 0");
+  if (!select_range_ok(sel->use_time, sel->t0, sel->t1))
+    return fail(ctx, "mphip_select_atm: bad time range (a bound is NaN or t0 > t1)");
+  if (!select_range_ok(sel->use_z, sel->z0, sel->z1))
+    return fail(ctx, "mphip_select_atm: bad height range (a bound is NaN or z0 > z1)");
+  if (!select_range_ok(sel->use_lon, sel->lon0, sel->lon1))
+    return fail(ctx, "mphip_select_atm: bad longitude range (a bound is NaN or lon0 > lon1)");
+  if (!select_range_ok(sel->use_lat, sel->lat0, sel->lat1))
+    return fail(ctx, "mphip_select_atm: bad latitude range (a bound is NaN or lat0 > lat1)");
+  if (sel->use_near && !(sel->near_r >= 0 && std::isfinite(sel->near_r)))
+    return fail(ctx, "mphip_select_atm: near_r must be finite and >= 0");
+  if ((sel->use_lon || sel->use_lat || sel->use_near) && ctx->ctl.met_coord_type != 0)
+    return fail(ctx, "mphip_select_atm: lon, lat and near need a lat/lon grid (MET_COORD_TYPE 0)");
+  HIPCHK(hipSetDevice(ctx->device));
+  if (flush_meteo(ctx))   // (the rows deliver every quantity)
+    return 1;
+  const long long np = ctx->np;
+  const long long last = sel->last < 0 || sel->last >= np ? np - 1 : sel->last;
+  if (np == 0 || sel->first > last) {
+    *nsel = 0;
+    return 0;
+  }
+  SelectArgs S;
+  memset(&S, 0, sizeof(S));
+  S.first = (uint32_t) sel->first;
+  S.last = (uint32_t) last;
+  S.stride = (uint32_t) std::min<long long>(sel->stride, 0x7fffffffLL);   // (np < 2^31: beyond it only `first` is a candidate)
+  S.use_time = sel->use_time != 0;
+  S.use_z = sel->use_z != 0;
+  S.use_lon = sel->use_lon != 0;
+  S.use_lat = sel->use_lat != 0;
+  S.use_near = sel->use_near != 0;
+  S.t0 = sel->t0, S.t1 = sel->t1;
+  S.z0 = sel->z0, S.z1 = sel->z1;
+  S.lon0 = sel->lon0, S.lon1 = sel->lon1;
+  S.lat0 = sel->lat0, S.lat1 = sel->lat1;
+  if (S.use_near) {
+    S.reach2 = sel->near_r * sel->near_r;
+    geo2cart_host(sel->near_lon, sel->near_lat, S.centre);
+  }
+  MarkScan M;
+  if (ensure_marks(ctx, &M))
+    return 1;
+  HIPCHK(ctx->d_ana_flags.reserve(8));
+  HIPCHK(ctx->d_slot_of.reserve((size_t) np));
+  const DevAtm a = dev_atm(ctx);
+  hipEvent_t stop = nullptr;
+  if (select_prof(ctx, 1, true, &stop))
+    return 1;
+  hipLaunchKernelGGL(select_mark_kernel, dim3(grid_for(np)), dim3(256), 0, ctx->stream, a, S, ctx->d_marks.p, ctx->d_slot_of.p);
+  HIPCHK(hipGetLastError());
+  if (select_prof_stop(ctx, stop) || select_prof(ctx, 2, true, &stop) || scan_marks(ctx, M) || select_prof_stop(ctx, stop))
+    return 1;
+  uint32_t total = 0;
+  HIPCHK(hipMemcpyAsync(&total, ctx->d_ana_flags.p + 1, sizeof(total), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  *nsel = (long long) total;
+  if (total == 0 || (long long) total > cap)   // (too small a buffer: the count only; the caller comes back with a larger one)
+    return 0;
+  double *const dst[4] = { time, p, lon, lat };
+  int nrows = index ? 1 : 0;
+  for (int k = 0; k < 4 + ctx->nq; k++)
+    nrows += (k < 4 ? dst[k] : q ? q[k - 4] : nullptr) != nullptr;
+  if (nrows == 0)
+    return 0;
+  // the two lists by rank, then row after row through two device rows: the copy of one overlaps the gather of the next
+  const size_t n = total;
+  HIPCHK(ctx->d_sel_list.reserve(2 * n));
+  HIPCHK(ctx->d_sel_rows.reserve(2 * n));
+  int *const sel_slot = ctx->d_sel_list.p, *const sel_index = ctx->d_sel_list.p + n;
+  if (select_prof(ctx, 3, true, &stop))
+    return 1;
+  hipLaunchKernelGGL(select_list_kernel, dim3(grid_for(np)), dim3(256), 0, ctx->stream, np, (const uint32_t *) ctx->d_marks.p,
+                     (const uint32_t *) M.chunk_off, M.shift, (const int *) ctx->d_slot_of.p, sel_slot, sel_index);
+  HIPCHK(hipGetLastError());
+  if (select_prof_stop(ctx, stop))
+    return 1;
+  // To the caller's arrays: through two page-locked rows of the context and a memcpy that runs beside the next row's
+  // gather and copy (the default), or -- option "select_direct" -- straight into the caller's arrays, page-locked in one
+  // span under option pin_host_atm as mphip_get_atm has them.
+  const bool direct = ctx->select_direct;
+  if (direct) {
+    const void *all[4 + MPHIP_NQ_MAX] = { time, p, lon, lat };
+    for (int iq = 0; iq < ctx->nq; iq++)
+      all[4 + iq] = q ? q[iq] : nullptr;
+    pin_host_span(ctx, all, 4 + ctx->nq, n * sizeof(double));
+  } else {
+    HIPCHK(ctx->h_sel_rows.reserve(2 * n));
+    for (hipEvent_t &e : ctx->sel_copied)
+      if (!e)
+        HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  }
+  struct Pending {
+    void *to;
+    size_t bytes;
+  } pending[2] = { { nullptr, 0 }, { nullptr, 0 } };
+  int turn = 0;
+  auto land = [&](int b) -> int {   // the staged row of buffer b reaches the caller
+    if (!pending[b].to)
+      return 0;
+    HIPCHK(hipEventSynchronize(ctx->sel_copied[b]));
+    memcpy(pending[b].to, ctx->h_sel_rows.p + (size_t) b * n, pending[b].bytes);
+    pending[b].to = nullptr;
+    return 0;
+  };
+  auto send = [&](const void *d_src, void *to, size_t bytes) -> int {   // a finished device row on its way to `to`
+    const int b = turn;
+    if (select_prof(ctx, 5, false, &stop))
+      return 1;
+    if (direct) {
+      HIPCHK(hipMemcpyAsync(to, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    } else {
+      HIPCHK(hipMemcpyAsync(ctx->h_sel_rows.p + (size_t) b * n, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(hipEventRecord(ctx->sel_copied[b], ctx->stream));
+      pending[b].to = to;
+      pending[b].bytes = bytes;
+    }
+    if (select_prof_stop(ctx, stop))
+      return 1;
+    turn ^= 1;
+    return direct ? 0 : land(turn);   // (the buffer the next row will use: its copy was queued a whole row ago)
+  };
+  if (index && send(sel_index, index, n * sizeof(int)))
+    return 1;
+  for (int k = 0; k < 4 + ctx->nq; k++) {
+    double *const to = k < 4 ? dst[k] : q ? q[k - 4] : nullptr;
+    if (!to)
+      continue;
+    double *const row = ctx->d_sel_rows.p + (size_t) turn * n;
+    if (select_prof(ctx, 4, true, &stop))
+      return 1;
+    hipLaunchKernelGGL(select_row_kernel, dim3(grid_for((long long) n)), dim3(256), 0, ctx->stream,
+                       (const double *) ctx->d_arr[k].p, (const int *) sel_slot, (long long) n, row);
+    HIPCHK(hipGetLastError());
+    if (select_prof_stop(ctx, stop) || send(row, to, n * sizeof(double)))
+      return 1;
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (!direct && (land(0) || land(1)))
+    return 1;
+  return 0;
+}
+
 int mphip_set_radio_decay(mphip_ctx *ctx, int on, const int qnt[MPHIP_NRADIO]) {
   if (ctx && ahead_drop(ctx))
     return 1;
@@ -6118,6 +6304,10 @@ const Option kOptions[] = {
   number("locality_tile", &mphip_ctx::locality_tile, kRange, 0, 64, "locality_tile must be in 0 ... 64", resort_next_step),
   // points per launch of mphip_intpol_met
   number("intpol_chunk", &mphip_ctx::intpol_chunk, kRange, 64, 1 << 24, "intpol_chunk must be in 64 ... 16777216"),
+  // mphip_select_atm: 1 = rows are copied straight into the caller's arrays (page-locked under pin_host_atm)
+  flag("select_direct", &mphip_ctx::select_direct),
+  number("select_profile_phase", &mphip_ctx::select_profile_phase, kWhole, 0, 5,
+         "select_profile_phase must be 0 (kernels), 1 (mark), 2 (scan), 3 (list), 4 (row gathers) or 5 (copies)"),
 };
 
 }   // namespace

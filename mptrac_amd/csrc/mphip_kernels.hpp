@@ -3599,6 +3599,76 @@ __global__ __launch_bounds__(256) void station_restore_kernel(DevAtm a, int qnt_
   }
 }
 
+// ---- mphip_select_atm --------------------------------------------------------------------------------------------------
+// The same three stages for a caller's own question.  select_mark_kernel decides for every stored particle and leaves
+// 0 / 1 at its external index (and where it is stored); the scan numbers the selected ones in ascending external index;
+// select_list_kernel turns the scanned marks into the two lists {slot, external index} by rank -- the one further pass
+// over np; select_row_kernel then gathers a requested row with lanes over the rank (coalesced stores, gathered loads).
+struct SelectArgs {
+  double t0, t1, z0, z1, lon0, lon1, lat0, lat1;
+  double reach2;          // near_r^2
+  double centre[3];       // geo2cart of (near_lon, near_lat)
+  uint32_t first, last;   // external indices considered (first <= last < np)
+  uint32_t stride;        // (a stride beyond the index range selects `first` alone: any value above last - first does)
+  int use_time, use_z, use_lon, use_lat, use_near;
+};
+
+__global__ __launch_bounds__(256) void select_mark_kernel(DevAtm a, SelectArgs S, uint32_t *__restrict__ mark,
+                                                          int *__restrict__ slot_of) {
+#pragma clang fp contract(off)
+  for (long long i = blockIdx.x * (long long) blockDim.x + threadIdx.x; i < a.np; i += (long long) gridDim.x * blockDim.x) {
+    const uint32_t e = a.ext ? (uint32_t) a.ext[i] : (uint32_t) i;
+    bool hit = e >= S.first && e <= S.last && (S.stride == 1u || (e - S.first) % S.stride == 0u);
+    // every test in the negated-or form of the host loops: a NaN coordinate passes
+    if (hit && S.use_time) {
+      const double tp = a.time[i];
+      hit = !(tp < S.t0 || tp > S.t1);
+    }
+    if (hit && S.use_lon) {
+      const double lon = a.lon[i];
+      hit = !(lon < S.lon0 || lon > S.lon1);
+    }
+    if (hit && S.use_lat) {
+      const double lat = a.lat[i];
+      hit = !(lat < S.lat0 || lat > S.lat1);
+    }
+    if (hit && S.use_z) {
+      const double z = zfromp(a.p[i]);
+      hit = !(z < S.z0 || z > S.z1);
+    }
+    if (hit && S.use_near) {
+      double x[3];
+      geo2cart_surface(a.lon[i], a.lat[i], x);
+      hit = !(dist2_exact(S.centre, x) > S.reach2);
+    }
+    mark[e] = hit ? 1u : 0u;
+    if (hit)
+      slot_of[e] = (int) i;
+    if (i == 0)
+      mark[a.np] = 0;
+  }
+}
+
+// (mark holds the scanned marks: external index e is selected when its offset differs from the next one's)
+__global__ __launch_bounds__(256) void select_list_kernel(long long np, const uint32_t *__restrict__ mark,
+                                                          const uint32_t *__restrict__ chunk_off, int chunk_shift,
+                                                          const int *__restrict__ slot_of, int *__restrict__ sel_slot,
+                                                          int *__restrict__ sel_index) {
+  for (long long e = blockIdx.x * (long long) blockDim.x + threadIdx.x; e < np; e += (long long) gridDim.x * blockDim.x) {
+    const uint32_t at = mark[e] + chunk_off[e >> chunk_shift], next = mark[e + 1] + chunk_off[(e + 1) >> chunk_shift];
+    if (next == at)
+      continue;
+    sel_slot[at] = slot_of[e];
+    sel_index[at] = (int) e;
+  }
+}
+
+__global__ __launch_bounds__(256) void select_row_kernel(const double *__restrict__ src, const int *__restrict__ sel_slot,
+                                                         long long nsel, double *__restrict__ out) {
+  for (long long r = blockIdx.x * (long long) blockDim.x + threadIdx.x; r < nsel; r += (long long) gridDim.x * blockDim.x)
+    out[r] = src[sel_slot[r]];
+}
+
 // *total (64 bits, cleared by the caller) += the n counts: the check on the 32-bit scan
 __global__ __launch_bounds__(256) void count_total_kernel(const uint32_t *__restrict__ cnt, long long n,
                                                           unsigned long long *__restrict__ total) {

@@ -141,6 +141,15 @@ class MphipBox(C.Structure):
                 ("ny", C.c_int), ("z0", C.c_double), ("z1", C.c_double), ("nz", C.c_int)]
 
 
+class MphipSelect(C.Structure):
+    """mphip_select_t: which particles mphip_select_atm returns (index range and stride, ANDed range and distance tests)."""
+    _fields_ = [("first", C.c_longlong), ("last", C.c_longlong), ("stride", C.c_longlong),
+                ("use_time", C.c_int), ("use_z", C.c_int), ("use_lon", C.c_int), ("use_lat", C.c_int), ("use_near", C.c_int),
+                ("t0", C.c_double), ("t1", C.c_double), ("z0", C.c_double), ("z1", C.c_double),
+                ("lon0", C.c_double), ("lon1", C.c_double), ("lat0", C.c_double), ("lat1", C.c_double),
+                ("near_lon", C.c_double), ("near_lat", C.c_double), ("near_r", C.c_double)]
+
+
 class MphipError(RuntimeError):
     pass
 
@@ -249,6 +258,9 @@ def load(build=True):
                                    C.c_int, _dp, _dp, _ip, _dp]
     L.mphip_station_hits.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                      C.c_int, C.c_int, _ip, _ip, _dp]
+    if hasattr(L, "mphip_select_atm"):      # (absent from libraries built before the selection: A/B runs through MPHIP_LIB)
+        L.mphip_select_atm.argtypes = [C.c_void_p, C.POINTER(MphipSelect), C.c_longlong, C.POINTER(C.c_longlong), _ip,
+                                       _dp, _dp, _dp, _dp, C.POINTER(_dp)]
     L.mphip_set_radio_decay.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     if hasattr(L, "mphip_set_radio_depo"):      # (absent from libraries built before module_radio_depo: A/B runs through MPHIP_LIB)
         L.mphip_set_radio_depo.argtypes = [C.c_void_p, C.c_int, C.POINTER(MphipBox)]
@@ -994,6 +1006,60 @@ class Simulation:
         if n.value > cap:
             return n.value, None, None
         return n.value, index[:n.value].copy(), rows[:n.value].copy()
+
+    def select_atm(self, stride=1, first=0, last=-1, time=None, z=None, lon=None, lat=None, near=None,
+                   rows=("time", "p", "lon", "lat", "q"), cap=None):
+        """The particles with external index first, first + stride, ... <= last that no given criterion rejects, in
+        ascending index, without downloading the others (mphip_select_atm).  `time`, `z`, `lon`, `lat`: (lo, hi) or None;
+        `near`: (lon, lat, r_km).  Returns {"n", "index", the requested rows cut to n, "q" of shape (nq, n)}; `rows` names
+        the rows wanted ("q": all quantities, or "q0", "q1", ... for single ones -- the others stay NaN in "q").
+        cap=None: the number of candidates, which always suffices; an explicit cap below n: {"n": n} with None for the
+        rows, and nothing was copied."""
+        s = MphipSelect()
+        s.first, s.last, s.stride = int(first), int(last), int(stride)
+        for name, pair, lo, hi in (("time", time, "t0", "t1"), ("z", z, "z0", "z1"), ("lon", lon, "lon0", "lon1"),
+                                   ("lat", lat, "lat0", "lat1")):
+            if pair is not None:
+                setattr(s, "use_" + name, 1)
+                setattr(s, lo, float(pair[0]))
+                setattr(s, hi, float(pair[1]))
+        if near is not None:
+            s.use_near = 1
+            s.near_lon, s.near_lat, s.near_r = (float(v) for v in near)
+        if cap is None:
+            end = self.n - 1 if last < 0 or last >= self.n else int(last)
+            cap = (end - int(first)) // int(stride) + 1 if stride >= 1 and 0 <= first <= end else 0
+        cap = int(cap)
+        m = max(cap, 1)
+        rows = tuple(rows)
+        unknown = [r for r in rows if r not in ("index", "time", "p", "lon", "lat", "q")
+                   and not (r[:1] == "q" and r[1:].isdigit() and int(r[1:]) < self.nq)]
+        if unknown:
+            raise KeyError(f"not a row of select_atm: {unknown}")
+        want_q = [("q" in rows or f"q{iq}" in rows) for iq in range(self.nq)]
+        out = {k: np.empty(m) for k in ("time", "p", "lon", "lat") if k in rows}
+        index = np.empty(m, dtype=np.int32)
+        q = np.full((self.nq, m), np.nan) if any(want_q) else None
+        qp = (_dp * NQ_MAX)()
+        for iq in range(self.nq):
+            if want_q[iq]:
+                qp[iq] = _ptr(q[iq], _dp)
+        n = C.c_longlong(0)
+        ptr = {k: (_ptr(out[k], _dp) if k in out else None) for k in ("time", "p", "lon", "lat")}
+        self._chk(self.L.mphip_select_atm(self.h, C.byref(s), cap, C.byref(n), _ptr(index, C.POINTER(C.c_int)), ptr["time"],
+                                          ptr["p"], ptr["lon"], ptr["lat"], qp if q is not None else None))
+        res = {"n": n.value}
+        if n.value > cap:
+            res.update({k: None for k in ("index", *out)})
+            if q is not None:
+                res["q"] = None
+            return res
+        res["index"] = index[:n.value].copy()
+        for k, v in out.items():
+            res[k] = v[:n.value].copy()
+        if q is not None:
+            res["q"] = q[:, :n.value].copy()
+        return res
 
     def set_radio_decay(self, quantities, on=True):
         """module_radio_decay (mphip_set_radio_decay).  `quantities`: the quantity names of the particles (in quantity

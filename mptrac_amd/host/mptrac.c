@@ -381,7 +381,8 @@ static const char *unsupported_qnt[] = {
   I(hip_met_prep, "HIP_MET_PREP", "0") \
   I(hip_device_analysis, "HIP_DEVICE_ANALYSIS", "1") \
   I(hip_device_intpol, "HIP_DEVICE_INTPOL", "0") \
-  I(hip_met_ingest, "HIP_MET_INGEST", "0")
+  I(hip_met_ingest, "HIP_MET_INGEST", "0") \
+  I(hip_device_select, "HIP_DEVICE_SELECT", "0")
 
 void mptrac_read_ctl(const char *filename, int argc, char *argv[], ctl_t *ctl) {
   LOG(1, "\nMassive-Parallel Trajectory Calculations (MPTRAC), MI355X build (%s)\n", mphip_version());
@@ -466,6 +467,7 @@ void mptrac_read_ctl(const char *filename, int argc, char *argv[], ctl_t *ctl) {
   REQUIRE(ctl->hip_met_packed == 0 || ctl->hip_met_packed == 1, "Set HIP_MET_PACKED to 0 or 1!");
   REQUIRE(ctl->hip_device_intpol == 0 || ctl->hip_device_intpol == 1, "Set HIP_DEVICE_INTPOL to 0 or 1!");
   REQUIRE(ctl->hip_met_ingest == 0 || ctl->hip_met_ingest == 1, "Set HIP_MET_INGEST to 0 or 1!");
+  REQUIRE(ctl->hip_device_select == 0 || ctl->hip_device_select == 1, "Set HIP_DEVICE_SELECT to 0 or 1!");
   if (ctl->met_type == 0) {
     /* netCDF input is taken as stored: no hybrid-coefficient levels (mptrac.c:7770-7830) ... */
     static const struct {
@@ -1299,7 +1301,7 @@ int mptrac_read_atm(const char *filename, const ctl_t *ctl, atm_t *atm) {
 
 /* ASCII table as the reference writes it: numbered column legend, blank line, one particle per line;
  * ATM_FILTER 1 blanks (NaN), 2 drops the particles whose time is not within half a step of t */
-static void write_atm_asc(const char *filename, const ctl_t *ctl, const atm_t *atm, const double t) {
+static void write_atm_asc_rows(const char *filename, const ctl_t *ctl, const atm_rows_t *rows, const double t) {
   FILE *out = fopen(filename, "w");
   REQUIRE(out, "Cannot create file!");
   const int cartesian = ctl->met_coord_type != 0;
@@ -1311,18 +1313,37 @@ static void write_atm_asc(const char *filename, const ctl_t *ctl, const atm_t *a
     fprintf(out, "# $%i = %s [%s]\n", iq + 5, ctl->qnt_name[iq], ctl->qnt_unit[iq]);
   fputc('\n', out);
   const char *position = cartesian ? "%.2f %g %.2f %.2f" : "%.2f %g %g %g";
-  for (int ip = 0; ip < atm->np; ip += ctl->atm_stride) {
-    const int outside = atm->time[ip] < t - 0.5 * ctl->dt_mod || atm->time[ip] > t + 0.5 * ctl->dt_mod;
+  for (int k = 0; k < rows->n; k++) {
+    const int ip = ATM_ROW(rows, k);
+    const int outside = rows->time[ip] < t - 0.5 * ctl->dt_mod || rows->time[ip] > t + 0.5 * ctl->dt_mod;
     if (outside && ctl->atm_filter == 2)
       continue;
-    fprintf(out, position, atm->time[ip], Z(atm->p[ip]), atm->lon[ip], atm->lat[ip]);
+    fprintf(out, position, rows->time[ip], Z(rows->p[ip]), rows->lon[ip], rows->lat[ip]);
     for (int iq = 0; iq < ctl->nq; iq++) {
       fputc(' ', out);
-      fprintf(out, ctl->qnt_format[iq], (outside && ctl->atm_filter == 1) ? NAN : atm->q[iq][ip]);
+      fprintf(out, ctl->qnt_format[iq], (outside && ctl->atm_filter == 1) ? NAN : rows->q[iq][ip]);
     }
     fputc('\n', out);
   }
   fclose(out);
+}
+
+/* ... every ATM_STRIDE-th of the host's particles */
+static void write_atm_asc(const char *filename, const ctl_t *ctl, const atm_t *atm, const double t) {
+  const int stride = ctl->atm_stride > 0 ? ctl->atm_stride : 1;
+  atm_rows_t rows = { atm->np > 0 ? (atm->np - 1) / stride + 1 : 0, NULL, stride, atm->time, atm->p, atm->lon, atm->lat, { NULL } };
+  for (int iq = 0; iq < ctl->nq; iq++)
+    rows.q[iq] = atm->q[iq];
+  write_atm_asc_rows(filename, ctl, &rows, t);
+}
+
+/* ... and of the particles the device holds (HIP_DEVICE_SELECT 1): the stride, and for ATM_FILTER 2 the window of the
+ * time step, in one mphip_select_atm call; filters 0 and 1 take the stride alone and blank by the returned time */
+static void write_atm_asc_device(const char *filename, const ctl_t *ctl, const int np, const double t) {
+  LOG(1, "Write atmospheric data: %s", filename);
+  atm_rows_t rows;
+  mptrac_amd_device_select_atm(np, ctl->atm_stride > 0 ? ctl->atm_stride : 1, ctl->atm_filter == 2, t - 0.5 * ctl->dt_mod, t + 0.5 * ctl->dt_mod, &rows);
+  write_atm_asc_rows(filename, ctl, &rows, t);
 }
 
 static void write_atm_bin(const char *filename, const ctl_t *ctl, const atm_t *atm) {
@@ -3395,6 +3416,39 @@ int mptrac_amd_device_station_hits(double t, double lon, double lat, double r, d
   return nhit;
 }
 
+void mptrac_amd_device_select_atm(int np, int stride, int use_window, double t0, double t1, atm_rows_t *rows) {
+  static double *buf;
+  static size_t buf_len;
+  const long long cap = np > 0 ? ((long long) np - 1) / stride + 1 : 0;   /* the candidates: always enough */
+  const size_t need = (size_t) (cap > 0 ? cap : 1) * (size_t) (4 + g_nq);
+  if (need > buf_len) {
+    free(buf);
+    ALLOC(buf, double, need);
+    buf_len = need;
+  }
+  mphip_select_t sel;
+  memset(&sel, 0, sizeof(sel));
+  sel.last = -1;
+  sel.stride = stride;
+  sel.use_time = use_window;
+  sel.t0 = t0;
+  sel.t1 = t1;
+  double *col[4 + MPHIP_NQ_MAX] = { 0 };
+  for (int k = 0; k < 4 + g_nq; k++)
+    col[k] = buf + (size_t) k * (size_t) cap;
+  long long nsel = 0;
+  HIP(mphip_select_atm(g_ctx, &sel, cap, &nsel, NULL, col[0], col[1], col[2], col[3], col + 4));
+  memset(rows, 0, sizeof(*rows));
+  rows->n = (int) nsel;
+  rows->step = 1;
+  rows->time = col[0];
+  rows->p = col[1];
+  rows->lon = col[2];
+  rows->lat = col[3];
+  for (int iq = 0; iq < g_nq && iq < NQ; iq++)
+    rows->q[iq] = col[4 + iq];
+}
+
 void mptrac_write_output(const char *dirname, const ctl_t *ctl, met_t *met0, met_t *met1, atm_t *atm,
                          depo_t *depo, const double t) {
   /* mptrac.c:8230-8330 without the radioactive deposition output */
@@ -3419,7 +3473,13 @@ void mptrac_write_output(const char *dirname, const ctl_t *ctl, met_t *met0, met
   atm_t *const loop_atm = on_device ? NULL : atm;
   if (t == ctl->t_start)
     g_output_downloads = 0;
-  if (atm_due || ens_due || vtk_due || (every_step && !on_device)) {
+  /* HIP_DEVICE_SELECT 1: the strided or filtered ASCII particle file and the VTK output are written from the rows the
+   * device selects -- when nothing else in this call needs all particles (the ensemble output, host analysis loops, a
+   * particle file of another kind); that is no download, and `atm` stays stale */
+  const int atm_by_rows = ctl->atm_type_out == 0 && (ctl->atm_stride > 1 || ctl->atm_filter == 2);
+  const int selected = g_ctx != NULL && ctl->hip_device_select && (atm_due || vtk_due) && !ens_due
+    && !(every_step && !on_device) && (!atm_due || atm_by_rows);
+  if (!selected && (atm_due || ens_due || vtk_due || (every_step && !on_device))) {
     mptrac_update_host(NULL, NULL, NULL, NULL, NULL, atm);
     if (g_ctx)
       g_output_downloads++;
@@ -3429,7 +3489,10 @@ void mptrac_write_output(const char *dirname, const ctl_t *ctl, met_t *met0, met
             ctl->atm_type_out == 0 ? "tab" : ctl->atm_type_out == 1 ? "bin" : "nc");
     if (g_world > 1)   /* every rank writes its index range: <name>.rank<k> */
       sprintf(filename + strlen(filename), ".rank%d", g_rank);
-    mptrac_write_atm(filename, ctl, atm, t);
+    if (selected)
+      write_atm_asc_device(filename, ctl, atm->np, t);
+    else
+      mptrac_write_atm(filename, ctl, atm, t);
   }
   if (grid_due) {
     sprintf(filename, "%s/%s_%s.%s", dirname, ctl->grid_basename, stamp, ctl->grid_type == 0 ? "tab" : "nc");
@@ -3465,7 +3528,10 @@ void mptrac_write_output(const char *dirname, const ctl_t *ctl, met_t *met0, met
     if (t == ctl->t_start)
       nvtk = 0;
     sprintf(filename, "%s/%s_%05d.vtk", dirname, ctl->vtk_basename, ++nvtk);
-    write_vtk(filename, ctl, atm, t);
+    if (selected)
+      write_vtk_device(filename, ctl, atm->np, t);
+    else
+      write_vtk(filename, ctl, atm, t);
   }
 }
 

@@ -245,6 +245,11 @@ typedef struct {
                              the unit scales, the re-ordering into met_t, the extrapolation below the lowest valid level,
                              the polar winds and the periodic column happen on the device (mphip_ingest_met; the same
                              bits, so the same files); 0: in the reader's own loops; other values are refused */
+  int hip_device_select;  /* HIP_DEVICE_SELECT (default 0): 1: an ASCII particle file with ATM_STRIDE > 1 or ATM_FILTER 2 and
+                             the VTK output are written from the rows one mphip_select_atm call returns (the same bytes)
+                             when nothing else in the same mptrac_write_output call needs all particles; such an output
+                             is no particle download and leaves the host's atm_t stale; 0: from downloaded particles;
+                             other values are refused */
 } ctl_t;
 
 /* air parcels, as the reference (mptrac.h:3563-3583) */
@@ -415,6 +420,23 @@ void mptrac_amd_device_sample_obs(double t0, double t1, int nobs, const double *
                                   double dx, double dz, int nk, const double *kz, const double *kw, int *count, double *mass);
 int mptrac_amd_device_station_hits(double t, double lon, double lat, double r, double stat_t0, double stat_t1, int qnt_stat,
                                    int cap, int *index, double *rows);
+/* Rows of particles as write_atm_asc and write_vtk format them, so that the host's particles and the rows of a selection
+ * made on the device share every fprintf: row k is element ATM_ROW(rows, k) of the columns -- pick[k] where a list is
+ * given, else k * step (the host's particles with the writer's stride; 1 for selected rows). */
+typedef struct {
+  int n;
+  const int *pick;
+  int step;
+  const double *time, *p, *lon, *lat;
+  const double *q[NQ];
+} atm_rows_t;
+#define ATM_ROW(rows, k) ((rows)->pick ? (rows)->pick[k] : (k) * (rows)->step)
+/* The particles 0, stride, 2 stride, ... of the np the device holds (this rank's), with use_window those whose time is not
+ * outside [t0, t1] (a NaN time passes), in ascending index: one mphip_select_atm call, no download.  The columns belong
+ * to the call (grow-only) and hold until the next one. */
+void mptrac_amd_device_select_atm(int np, int stride, int use_window, double t0, double t1, atm_rows_t *rows);
+/* write_vtk on such rows (HIP_DEVICE_SELECT 1): the same file without the host's particles */
+void write_vtk_device(const char *filename, const ctl_t *ctl, const int np, const double t);
 /* particle downloads mptrac_write_output has made since the last mptrac_init (the driver's closing summary) */
 long mptrac_amd_output_downloads(void);
 /* a level field (selected by its offset in met_t) at a point, both snapshots blended in time: what

@@ -10,7 +10,8 @@
  * HIP_DEVICE_ANALYSIS 0), and the same loop on the device (atm == NULL: mphip_box_sums, mphip_sample_obs,
  * mphip_station_hits through the mptrac_amd_device_* calls of mptrac.c), which returns the loop's bits without a
  * download.  File handling, observation tables, box post-processing, statistics and the printed lines are shared.
- * write_ens and write_vtk are periodic and run on downloaded particles only.
+ * write_ens and write_vtk are periodic: write_ens runs on downloaded particles only, write_vtk on those or -- with
+ * HIP_DEVICE_SELECT 1 -- on the rows of a selection made on the device (write_vtk_device).
  *
  * The implementation is this repository's own: one regular lon / lat / z box grid type serves the CSI and
  * profile binning, one observation table type with a cursor serves the three observation-driven writers, and
@@ -892,35 +893,63 @@ void write_station(const char *filename, const ctl_t *ctl, atm_t *atm, const dou
 /* ---------------------------------------------------------------------------------------------------------- */
 
 /* every VTK_STRIDE-th particle of this time step as a legacy-VTK point cloud (lon / lat / scaled height, or on
- * a sphere) with the quantities as point data */
-void write_vtk(const char *filename, const ctl_t *ctl, const atm_t *atm, const double t) {
-  latlon_only(ctl);
-  LOG(1, "Write VTK data: %s", filename);
-  const step_window now = window_around(ctl, t);
-  const double t0 = now.t0, t1 = now.t1;
-  const int stride = ctl->vtk_stride > 0 ? ctl->vtk_stride : 1;
-  int *pick, n = 0;
-  ALLOC(pick, int, atm->np / stride + 1);
-  for (int ip = 0; ip < atm->np; ip += stride)
-    if (atm->time[ip] >= t0 && atm->time[ip] <= t1)
-      pick[n++] = ip;
+ * a sphere) with the quantities as point data: the rows of a view, from the host's particles (write_vtk) or from a
+ * selection on the device (write_vtk_device) */
+static void write_vtk_rows(const char *filename, const ctl_t *ctl, const atm_rows_t *rows) {
+  const int n = rows->n;
   FILE *out = create_text_file(filename);
   fprintf(out, "# vtk DataFile Version 3.0\nvtk output\nASCII\nDATASET POLYDATA\nPOINTS %d float\n", n);
   for (int k = 0; k < n; k++) {
-    const int ip = pick[k];
-    const double height = Z(atm->p[ip]) * ctl->vtk_scale + ctl->vtk_offset;
+    const int ip = ATM_ROW(rows, k);
+    const double height = Z(rows->p[ip]) * ctl->vtk_scale + ctl->vtk_offset;
     if (ctl->vtk_sphere) {
-      const double r = (RE + height) / RE, phi = DEG2RAD(atm->lat[ip]), lam = DEG2RAD(atm->lon[ip]);
+      const double r = (RE + height) / RE, phi = DEG2RAD(rows->lat[ip]), lam = DEG2RAD(rows->lon[ip]);
       fprintf(out, "%g %g %g\n", r * cos(phi) * cos(lam), r * cos(phi) * sin(lam), r * sin(phi));
     } else
-      fprintf(out, "%g %g %g\n", atm->lon[ip], atm->lat[ip], height);
+      fprintf(out, "%g %g %g\n", rows->lon[ip], rows->lat[ip], height);
   }
   fprintf(out, "POINT_DATA %d\n", n);
   for (int iq = 0; iq < ctl->nq; iq++) {
     fprintf(out, "SCALARS %s float 1\nLOOKUP_TABLE default\n", ctl->qnt_name[iq]);
     for (int k = 0; k < n; k++)
-      fprintf(out, "%g\n", atm->q[iq][pick[k]]);
+      fprintf(out, "%g\n", rows->q[iq][ATM_ROW(rows, k)]);
   }
   fclose(out);
+}
+
+/* the elements `first`, `first + stride`, ... of the columns whose time lies in the time step: the test of the
+ * reference's loop (`>= && <=`: a NaN time is not written) */
+static void write_vtk_picked(const char *filename, const ctl_t *ctl, atm_rows_t *rows, int count, int stride, const double t) {
+  const step_window now = window_around(ctl, t);
+  const double t0 = now.t0, t1 = now.t1;
+  int *pick, n = 0;
+  ALLOC(pick, int, count / stride + 1);
+  for (int ip = 0; ip < count; ip += stride)
+    if (rows->time[ip] >= t0 && rows->time[ip] <= t1)
+      pick[n++] = ip;
+  rows->n = n;
+  rows->pick = pick;
+  write_vtk_rows(filename, ctl, rows);
   free(pick);
+}
+
+void write_vtk(const char *filename, const ctl_t *ctl, const atm_t *atm, const double t) {
+  latlon_only(ctl);
+  LOG(1, "Write VTK data: %s", filename);
+  atm_rows_t rows = { 0, NULL, 1, atm->time, atm->p, atm->lon, atm->lat, { NULL } };
+  for (int iq = 0; iq < ctl->nq; iq++)
+    rows.q[iq] = atm->q[iq];
+  write_vtk_picked(filename, ctl, &rows, atm->np, ctl->vtk_stride > 0 ? ctl->vtk_stride : 1, t);
+}
+
+/* ... on the particles the device holds (HIP_DEVICE_SELECT 1): one mphip_select_atm call with the stride and the time
+ * step's window returns the rows; the window's negated-or test lets a NaN time through, which the loop's own test
+ * then drops */
+void write_vtk_device(const char *filename, const ctl_t *ctl, const int np, const double t) {
+  latlon_only(ctl);
+  LOG(1, "Write VTK data: %s", filename);
+  const step_window now = window_around(ctl, t);
+  atm_rows_t rows;
+  mptrac_amd_device_select_atm(np, ctl->vtk_stride > 0 ? ctl->vtk_stride : 1, 1, now.t0, now.t1, &rows);
+  write_vtk_picked(filename, ctl, &rows, rows.n, 1, t);
 }
